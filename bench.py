@@ -6,9 +6,20 @@ u8 page -> LUT normalise + tiling -> ResNet-50-U-Net forward (HIP, MFMA) -> soft
 margin-crop stitch -> u8 label map in HBM, page after page.
 
 N = 1 (default): BASELINE.json configs[1] -- 3500x2500 pages, textline model (2 classes), margin 0.1 -> 70 tiles
-of 448x448 per page; a step is `--pages-per-step` (16) such pages back to back, so that the timed region lasts
-seconds, not a fraction of one (the clocks settle).  value = tiles / time, the median of `--repeats` (3) timed
-regions of exactly K steps each (all repeats are reported).
+of 448x448 per page; a step is `--pages-per-step` (32) such pages back to back, so that the timed region lasts
+seconds, not a fraction of one (the clocks settle).  value = tiles / time over one timed region of exactly K steps
+(`--steps`) after W warm-up steps (`--warmup`); `--repeats R` times R such regions and reports their median (all
+repeats are listed; `--full` defaults to 3).
+
+Plain run vs `--full`.  A plain `bench.py --gpus 1 --steps K --warmup W` does only what the headline needs: set up, warm
+up, time the K steps, write `--dump-outputs DIR` if given, print the line.  Every side measurement and check -- the
+roofline pass, the CPU baseline, the other arithmetic mode and the label check against the fp32 oracle, the host-memory
+path, the one-page / pipeline3 / batch64 side workloads, the N > 1 exchange and per-rank figures -- runs with `--full`
+only (and its `--no-*` switches trim it); the keys they fill are null otherwise.
+
+`--dump-outputs DIR`: after the timed steps, the label maps the last step wrote (what a caller of the path receives) go to
+DIR as .npy files (`dump_outputs`: the first page whole, a seeded sample of every page, per-page label counts; float32 /
+float64, at most 64 MB).  Inputs are seeded: the same arguments give the same inputs on every run and build.
 
 N > 1 (round 4: like for like with N = 1): the SAME page workload on every rank -- 16 such pages per GPU per step -- plus one RCCL
 all-gather of the u8 masks per step (the "stitch" exchange north_star names); `scaling` = "weak" at every N, so value(N) / value(1)
@@ -29,8 +40,8 @@ Arithmetic modes.  `value` is the mode `--precision` names -- by default "f16x3"
 north_star's "argmax label map bit-exact" bar against the fp32 oracle.  The fast plain-fp16 mode ("f16", BASELINE
 configs[4]) is measured in the same run and reported under `modes` with its own roofline and label agreement.
 
-Prints ONE JSON line on rank 0.  Extra objects: `roofline` (dominant conv launch, HIP-event timed per launch on
-the library's stream) and `cpu_baseline` (torch-CPU fp32 proxy of the Keras/TF CPU path on the host cores;
+Prints ONE JSON line on rank 0.  Extra objects with `--full`: `roofline` (dominant conv launch, HIP-event timed per launch
+on the library's stream) and `cpu_baseline` (torch-CPU fp32 proxy of the Keras/TF CPU path on the host cores;
 the oracle port is kept beside it), rank 0, N = 1.
 """
 import argparse
@@ -66,6 +77,41 @@ def csrc_sha():
         with open(os.path.join(ROOT, "sbb_textline_detection_amd", "csrc", name), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:12]
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE = 1 << 20
+
+
+def dump_outputs(out_dir, outputs, seed=0):
+    """`--dump-outputs`: write what the timed path's last step left in its output buffers, at most DUMP_BUDGET_BYTES in all.
+    `outputs` = {name: uint8 label tensor [pages, H, W] or [H, W]}.  Per output: `<name>_counts` (float64 [pages, labels]: every
+    page's label histogram), `<name>_sample` (float32: the labels at DUMP_SAMPLE flat positions of the whole tensor, drawn with
+    numpy PCG64(seed) and sorted) with `<name>_sample_index` (float64: those positions), then, while the budget allows,
+    `<name>_page0` (float32 [H, W]: the first page whole).  Returns the file names written."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    left, written, pages = DUMP_BUDGET_BYTES, [], []
+
+    def save(name, arr):
+        nonlocal left
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        left -= arr.nbytes + 128                                    # + the .npy header
+        written.append(name + ".npy")
+
+    for name, t in outputs.items():
+        t = t.reshape(-1, t.shape[-2], t.shape[-1])
+        flat = t.reshape(-1)
+        idx = np.sort(np.random.Generator(np.random.PCG64(seed)).integers(0, flat.numel(), min(DUMP_SAMPLE, flat.numel())))
+        n_labels = int(t.max()) + 1
+        save(name + "_counts", torch.stack([torch.bincount(p.reshape(-1), minlength=n_labels) for p in t]).cpu().numpy().astype(np.float64))
+        save(name + "_sample", flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().astype(np.float32))
+        save(name + "_sample_index", idx.astype(np.float64))
+        pages.append((name, t[0]))
+    for name, p in pages:
+        if p.numel() * 4 + 128 <= left:
+            save(name + "_page0", p.cpu().numpy().astype(np.float32))
+    return written
 
 
 def _free_port():
@@ -159,7 +205,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of exactly --steps steps each; value = their median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of exactly --steps steps each; value = their median (default 1; 3 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (roofline, CPU baseline, second mode + label check, host path, "
+                         "side workloads, N > 1 exchange); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the label maps of the last timed step to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--precision", default=os.environ.get("SBBSEG_BENCH_PRECISION", "f16x3"), choices=["f16", "bf16", "f16x3"],
                     help="arithmetic mode of `value`: f16x3 = label-exact split-fp16 (default), f16 = fast plain fp16")
     ap.add_argument("--max-batch", type=int, default=int(os.environ.get("SBBSEG_MAX_BATCH", "0")),
@@ -168,17 +220,19 @@ def main():
                     help="A/B knob of the conv kernel (see sbbseg.h sbbseg_debug_set_conv_variant)")
     ap.add_argument("--workload", default="auto", choices=["auto", "page", "pipeline3", "batch64"],
                     help="auto = page at every N (BASELINE configs[1], the metric's config; weak scaling), with configs[3] (64 pages of "
-                         "4000x3000 sharded over the ranks, strong scaling) measured beside it under `batch64`; batch64 = configs[3] as the "
+                         "4000x3000 sharded over the ranks, strong scaling) measured beside it under `batch64` by --full; batch64 = configs[3] as the "
                          "headline; pipeline3 = configs[2] (border + layout + textline)")
     ap.add_argument("--pages-per-step", type=int, default=32, help="page workload: pages segmented back to back per step (32 x 70 tiles = 7 chunks of 320)")
     ap.add_argument("--batch-pages", type=int, default=64, help="batch64 workload: pages in the batch (64 = BASELINE configs[3])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-second-mode", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the one-page and pipeline3 side measurements of the default line")
-    ap.add_argument("--cpu-patches", type=int, default=8)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (and with it the label check)")
+    ap.add_argument("--no-second-mode", action="store_true", help="--full: skip the other arithmetic mode and the host-memory path")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the one-page, pipeline3 and batch64 side measurements")
+    ap.add_argument("--cpu-patches", type=int, default=8, help="--full: tiles sampled for the CPU baseline and the label check")
     ap.add_argument("--plumbing-check", action="store_true",
                     help="launcher / rendezvous / all-gather only, gloo on CPU, no model (CPU tests of the N > 1 launch path)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_self_launch(args.gpus))           # plain `python bench.py --gpus N`: become the launcher
@@ -276,7 +330,12 @@ def main():
     # ---- workloads: build(model) -> (step(), tiles per step, description, scaling, gather() or None, bytes gathered)
     def build_page(m):
         P = max(1, args.pages_per_step)
-        pages = [torch.from_numpy(page0 if k == 0 else synthetic_page(PAGE_H, PAGE_W, seed=rank * 1000 + k)).cuda() for k in range(P)]
+        # the pages are drawn on a few host threads (numpy's generators and array ops release the GIL for most of the work): one
+        # 3500x2500 page costs a third of a second on one core, 32 of them serially would dwarf a short timed region
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=max(1, min(16, P - 1, os.cpu_count() or 1))) as ex:
+            drawn = ex.map(lambda k: synthetic_page(PAGE_H, PAGE_W, seed=rank * 1000 + k), range(1, P))
+            pages = [torch.from_numpy(page0).cuda()] + [torch.from_numpy(p_).cuda() for p_ in drawn]
         labels = torch.empty((P, PAGE_H, PAGE_W), dtype=torch.uint8, device="cuda")
         d_all = torch.empty((world, P, PAGE_H, PAGE_W), dtype=torch.uint8, device="cuda") if world > 1 else None
         page_state[id(m)] = labels                  # the buffer the timed steps write: label_match reads it back afterwards
@@ -294,6 +353,7 @@ def main():
         def step_local():
             m.ctx.segment_pages_dev(page_ptrs, PAGE_H, PAGE_W, label_ptrs)
         step.ctxs = step_local.ctxs = [m.ctx]
+        step.outputs = {"labels": labels}
         return step, tiles_per_page * P * world, desc, "weak", (gather if world > 1 else None), P * PAGE_H * PAGE_W * world, step_local, tiles_per_page * P
 
     def build_batch64(m, distinct=None):
@@ -328,6 +388,7 @@ def main():
             if count:
                 m.ctx.segment_pages_dev(page_ptrs, BH, BW, label_ptrs)
         step.ctxs = step_local.ctxs = [m.ctx]
+        step.outputs = {"labels": d_mine[:count]}
         return step, tpp * NPAGES, desc, "strong", (gather if world > 1 else None), world * block * BH * BW, step_local, tpp * count
 
     def build_pipeline3(m):
@@ -377,6 +438,7 @@ def main():
             "textline_stage_ms": lambda: m_text.ctx.segment_crop_dev(d_page.data_ptr(), PAGE_H, PAGE_W, Hs, Ws, box, False, d_lines.data_ptr()),
         }
         step.ctxs = [m_border.ctx, m_layout.ctx] + ([m_text.ctx] if m_text is not m_layout else [])
+        step.outputs = {"text_regions": d_clean, "textlines": d_lines}
         desc = f"BASELINE configs[2]: border + layout + textline on one {PAGE_H}x{PAGE_W} page ({Hs}x{Ws} upscaled, box {box}, {tiles_crop} tiles per patch stage)"
         return step, (1 + 2 * tiles_crop) * world, desc, "weak", None, 0, None, 1 + 2 * tiles_crop
 
@@ -409,20 +471,24 @@ def main():
         """Forwards the handles REALLY run in one step (sbbseg_debug_counter 1 = patches through the plan), summed over the ranks.  The
         fused page paths compute a repeated clamped tile once (sbbseg_set_dedupe, default on): on page sizes with extent % 360 in (0, 88]
         this is less than the reference's call count (4000 x 3000: 99 forwards for 108 calls) -- rates are quoted on what ran."""
-        ctxs = list({id(c): c for c in step_fn.ctxs}.values())
-        before = sum(c.forwards() for c in ctxs)
+        before = forwards_now(step_fn)
         step_fn()
         torch.cuda.synchronize()
-        n = sum(c.forwards() for c in ctxs) - before
-        if whole_job and world > 1:
+        n = forwards_now(step_fn) - before
+        return summed_over_ranks(n) if whole_job else int(n)
+
+    def forwards_now(step_fn):
+        """the handles' forward counters (host-side: bumped as the calls enqueue work)"""
+        return sum(c.forwards() for c in {id(c): c for c in step_fn.ctxs}.values())
+
+    def summed_over_ranks(n):
+        if world > 1:
             t = torch.tensor([n], dtype=torch.int64, device="cuda" if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
             n = int(t.item())
         return int(n)
 
     step, reference_calls_per_step, workload_desc, scaling, gather, gathered_bytes, step_local, local_calls = builders[workload](model)
-    tiles_per_step = forwards_of(step)                              # what `value` counts: forwards executed, whole job
-    local_tiles = forwards_of(step_local, whole_job=False) if step_local is not None else tiles_per_step // world
 
     def executed_flops_per_patch(ctx):
         """FLOPs (reference formulation, per op) the handle EXECUTED per forward since its last profile_reset: owned-region launches
@@ -431,16 +497,21 @@ def main():
         fw = max(o["exec_patches"] for o in prof)
         return sum(o["flops"] * o["exec_patches"] for o in prof) / fw if fw else 0.0
     model.ctx.profile_reset()
+    before = forwards_now(step)
     dts = timed(step, args.steps, args.warmup, max(1, args.repeats))
+    # what `value` counts: forwards executed per step, whole job, read off the counters over the warm-up and timed steps
+    tiles_per_step = summed_over_ranks(forwards_now(step) - before) // (args.warmup + args.steps * max(1, args.repeats))
     exec_flops = executed_flops_per_patch(model.ctx) if workload != "pipeline3" else 2 * model.plan.macs_per_patch()
     dt = statistics.median(dts)
     value = tiles_per_step * args.steps / dt
     rates = [tiles_per_step * args.steps / t for t in dts]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step.outputs)
     # what the timed steps themselves wrote: page 0's mask out of the pooled label buffer, read back before any other call
-    timed_labels0 = page_state[id(model)][0].cpu().numpy() if (rank == 0 and workload == "page") else None
+    timed_labels0 = page_state[id(model)][0].cpu().numpy() if (args.full and rank == 0 and workload == "page") else None
 
     exchange, per_rank = None, None
-    if gather is not None:                                          # the exchange alone: all-gather GB/s over xGMI
+    if gather is not None and args.full:                            # the exchange alone: all-gather GB/s over xGMI
         for _ in range(2):
             gather()
         fence()
@@ -457,6 +528,7 @@ def main():
         # every rank's rate on its own shard with NO collective and no barrier inside the loop (what the exchange and the
         # slowest-rank wait cost is value vs the sum of these)
         local_step = step_local if step_local is not None else step
+        local_tiles = forwards_of(step_local, whole_job=False) if step_local is not None else tiles_per_step // world
         n_loc = max(2, args.steps // 4)
         fence()
         t0 = time.perf_counter()
@@ -476,7 +548,7 @@ def main():
 
     # ---- BASELINE configs[3] beside the headline, at EVERY N (N = 1 = the base of its strong-scaling curve) --------------
     batch64 = None
-    if workload == "page" and not args.no_extras:
+    if args.full and workload == "page" and not args.no_extras:
         try:
             stepb, callsb, descb, scalb, gatherb, bytesb = build_batch64(model, distinct=8)[:6]
             tilesb = forwards_of(stepb)                                 # forwards executed (4000 x 3000: 99 per page, the reference calls 108)
@@ -633,11 +705,11 @@ def main():
                   for o in prof if o["launches"]]
         return r, per_op
 
-    roofline, per_op = (roofline_of(model) if rank == 0 else (None, []))
+    roofline, per_op = (roofline_of(model) if args.full and rank == 0 else (None, []))
 
     # ---- the same pages starting (and ending) in HOST memory: never `value`, reported beside it -------------------------
     host_path = None
-    if rank == 0 and world == 1 and workload == "page" and not args.no_second_mode:
+    if args.full and rank == 0 and world == 1 and workload == "page" and not args.no_second_mode:
         hp_pages = [page0 if k == 0 else synthetic_page(PAGE_H, PAGE_W, seed=k) for k in range(max(1, args.pages_per_step))]
         model.ctx.segment_pages(hp_pages[:4])                                  # allocates the pinned staging
         t0 = time.perf_counter()
@@ -654,7 +726,7 @@ def main():
 
     # ---- the other arithmetic mode + live label agreement of both modes with the fp32 oracle ------
     modes, label_match, cpu_baseline, cpu_port = None, None, None, None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         xy = _capi.tile_grid(PAGE_H, PAGE_W, MODEL_HW, MODEL_HW)[0]
         pick = np.linspace(0, len(xy) - 1, args.cpu_patches).astype(int)
         patches = np.stack([page0[y0:y0 + MODEL_HW, x0:x0 + MODEL_HW] for (x0, y0) in xy[pick]])
@@ -789,7 +861,7 @@ def main():
 
     exit_code = 0
     extras = None
-    if rank == 0 and world == 1 and workload == "page" and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and workload == "page" and not args.no_extras:
         extras = {}
         # one page per step (BASELINE configs[1] literally: ONE 3500x2500 page = 70 tiles per call)
         keep = args.pages_per_step
@@ -871,7 +943,7 @@ def main():
                         f.write(json.dumps({key: side}) + "\n")
                 line = json.dumps(out, separators=(",", ":"))
         print(line)
-        if os.environ.get("SBBSEG_BENCH_OPS"):
+        if os.environ.get("SBBSEG_BENCH_OPS") and args.full:
             with open(os.environ["SBBSEG_BENCH_OPS"], "w") as f:
                 json.dump(per_op, f, indent=1)
     if world > 1:

@@ -1416,7 +1416,7 @@ def test_bench_batch64_workload_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "batch64", "--batch-pages", "2", "--steps", "2",
-                          "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--no-second-mode", "--no-extras"],
+                          "--warmup", "1", "--repeats", "1", "--full", "--no-cpu-baseline", "--no-second-mode", "--no-extras"],
                          capture_output=True, text=True, env=env, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -1441,7 +1441,7 @@ def test_bench_label_match_reads_the_timed_buffer():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--pages-per-step", "4", "--steps", "2", "--warmup", "1",
-                          "--repeats", "1", "--cpu-patches", "2", "--no-second-mode", "--no-extras"],
+                          "--repeats", "1", "--full", "--cpu-patches", "2", "--no-second-mode", "--no-extras"],
                          capture_output=True, text=True, env=env, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -1457,6 +1457,48 @@ def test_bench_label_match_reads_the_timed_buffer():
     cfgd = d["config"]
     assert 0.7 < cfgd["executed_share"] < 0.95 and abs(cfgd["executed_flops_per_patch"] - cfgd["executed_share"] * cfgd["flops_per_patch"]) < 1e-3 * cfgd["flops_per_patch"]
     assert d["achieved_tflops_end_to_end"] < d["reference_formulation_tflops_end_to_end"]
+
+
+def test_bench_plain_run_dumps_the_timed_output(tmp_path):
+    """A plain bench run (no --full) times the headline only: ONE region of exactly --steps steps, the side measurements' keys null,
+    and `--dump-outputs` writes what the last timed step computed: page 0 whole equals the same page through the library's
+    page-by-page device entry, and the seeded sample and the label counts agree with it.  Cut down: 2 pages per step."""
+    import subprocess
+    import sys
+    import torch
+    from sbb_textline_detection_amd.model import SegModel
+    from tools.synth_model import calibrated_model
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = str(tmp_path / "outputs")
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--pages-per-step", "2", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", out], capture_output=True, text=True, env=env, timeout=900, cwd=root)
+    assert res.returncode == 0, res.stderr[-2000:]
+    d = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["unit"] == "patches/s" and d["higher_is_better"] is True and d["dtype"] == "f16x3" and d["value"] > 0
+    assert d["steps"] == 3 and len(d["repeats"]["timed_region_s"]) == 1
+    assert abs(d["ms_per_step"] * 3 / 1e3 - d["repeats"]["timed_region_s"][0]) < 2e-3
+    assert d["config"]["forwards_per_step"] == 2 * 70
+    assert all(d[k] is None for k in ("roofline", "cpu_baseline", "label_match", "modes", "host_path", "extras", "batch64", "exchange"))
+    names = sorted(os.listdir(out))
+    assert names == ["labels_counts.npy", "labels_page0.npy", "labels_sample.npy", "labels_sample_index.npy"]
+    assert sum(os.path.getsize(os.path.join(out, n)) for n in names) <= 64 * 10 ** 6
+    arr = {n[:-4]: np.load(os.path.join(out, n)) for n in names}
+    page0, counts = arr["labels_page0"], arr["labels_counts"]
+    assert page0.dtype == np.float32 and page0.shape == (3500, 2500) and counts.dtype == np.float64 and counts.shape[0] == 2
+    assert np.array_equal(counts[0], np.bincount(page0.astype(np.int64).ravel(), minlength=counts.shape[1]))
+    idx = arr["labels_sample_index"].astype(np.int64)
+    on0 = idx < page0.size
+    assert arr["labels_sample"].dtype == np.float32 and 0 < on0.sum() < len(idx)
+    assert np.array_equal(arr["labels_sample"][on0], page0.ravel()[idx[on0]])
+    cfg, w = calibrated_model(2, 448, 448, seed=0)
+    m = SegModel(cfg, w, device=0, max_batch=320, precision="f16x3")
+    d_page = torch.from_numpy(synthetic_page(3500, 2500, seed=0)).cuda()
+    single = torch.full((3500, 2500), 7, dtype=torch.uint8, device="cuda")
+    m.ctx.segment_page_dev(d_page.data_ptr(), 3500, 2500, single.data_ptr())
+    torch.cuda.synchronize()
+    assert np.array_equal(single.cpu().numpy(), page0)
+    m.release()
 
 
 def test_extract_page_box_dev_equals_host_entry(torch_cuda, stitch_model):

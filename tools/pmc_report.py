@@ -7,7 +7,7 @@ from collections import defaultdict
 
 # usage: tools/pmc_report.py <tag> [ops.json from SBBSEG_BENCH_OPS] [summary.json to write] [precision] [patches per launch]
 tag = sys.argv[1] if len(sys.argv) > 1 else "pmc1"
-root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
+root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "results")         # where tools/pmc_run.sh writes
 ops_json = sys.argv[2] if len(sys.argv) > 2 else None
 summary_out = sys.argv[3] if len(sys.argv) > 3 else None
 precision = sys.argv[4] if len(sys.argv) > 4 else "f16"
@@ -80,7 +80,7 @@ for k, (d, df, dw) in enumerate(zip(ids, idf, idw)):
     summary[nm] = {"us": round(us, 1), "shader_clock_mhz": round(mhz), "mfma_busy_pct": round(mfma, 1), "fetch_bytes": round(fetch * 1e6), "write_bytes": round(write * 1e6),
                    "hbm_gbps": round(gbps), "l2_hit_pct": round(hit / (hit + miss + 1e-9) * 100, 1), "lds_conflict_pct": round(c.get('SQ_LDS_BANK_CONFLICT', 0) / busy * 100, 2)}
 if summary_out:
-    json.dump({"source": "rocprofv3 --pmc passes over `python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-second-mode` (tools/pmc_run.sh: SQ_*, "
+    json.dump({"source": "rocprofv3 --pmc passes over `python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-second-mode` (tools/pmc_run.sh: SQ_*, "
                          "FETCH_SIZE+GRBM_GUI_ACTIVE, WRITE_SIZE+TCC_HIT/MISS in separate runs); last launch of every op = the bench's roofline pass "
                          "(one whole chunk per launch on one lane); FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 counts half of wide coalesced reads); "
                          "duplicate op names keep the last launch; mfma_busy_pct = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE x 32 CUs x 4 SIMDs) "
