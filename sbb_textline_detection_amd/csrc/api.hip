@@ -212,17 +212,6 @@ struct sbbseg_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int lanes = 2, lane1_batch = 0;
     int lane_prio = 0, prio_least = 0, prio_greatest = 0;      // priority class of lane_stream (never the own stream's class: see sbbseg_create)
-    // CU-partitioned lanes (round 4, opt-in: SBBSEG_CU_SPLIT=1): two private streams, each confined to HALF of the chip's CUs (hipExtStreamCreateWithCUMask: the
-    // mask's bits are dealt round-robin over the eight XCDs, so each half = 16 CUs of every XCD).  The chip is power-capped under
-    // dense MFMA (1 350 TFLOP/s at 1.65 GHz on 256 CUs, 910 at 2.2 GHz on 128) and its HBM fabric saturates from half the CUs
-    // (4.2 of 4.4 TB/s): an MFMA-bound kernel on one half beside an HBM-bound kernel on the other half get 0.52x + 0.91x of their
-    // whole-chip rates AT THE SAME TIME (tools/probes/cu_mask_probe.hip, profiles/r04_cu_mask_probe.txt).  The lanes walk their
-    // tile units half a network apart (tile_range_impl), so that one lane's decoder (MFMA) runs beside the other's encoder (HBM).
-    hipStream_t half_stream[2] = {nullptr, nullptr};
-    hipEvent_t ev_half[2] = {nullptr, nullptr};
-    int half_cus[2] = {0, 0};
-    bool cu_split = false;           // both masked streams exist
-    int stagger_min_tiles = 64;      // tile ranges from this size on take the CU-partitioned, staggered schedule (SBBSEG_STAGGER_MIN_TILES)
     int in_H = 0, in_W = 0, in_C = 0;
     std::vector<Tensor> tensors;
     std::vector<Op> ops;
@@ -671,17 +660,12 @@ int fill_ingest(sbbseg_ctx* c, IngestParams& ip)
 constexpr int kMinLaneTiles = 8;      // a lane gets at least this many tiles, else the chunk runs whole on lane 0
 
 // activation buffers and stream of lane L become the ones run_plan / fill_ingest see
-// (halves = true: the lane's CU-masked stream, persistent grids sized for its half of the chip)
 struct LaneScope {
-    sbbseg_ctx* c; hipStream_t saved; int saved_cus;
-    LaneScope(sbbseg_ctx* c_, int lane, bool halves = false) : c(c_), saved(c_->stream), saved_cus(c_->num_cus)
+    sbbseg_ctx* c; hipStream_t saved;
+    LaneScope(sbbseg_ctx* c_, int lane) : c(c_), saved(c_->stream)
     {
-        if (lane == 1)
+        if (lane == 1) {
             for (auto& t : c->tensors) t.buf = t.lane_buf[1];
-        if (halves) {
-            c->stream = c->half_stream[lane];
-            c->num_cus = c->half_cus[lane];
-        } else if (lane == 1) {
             c->stream = c->lane_stream;
         }
     }
@@ -689,7 +673,6 @@ struct LaneScope {
     {
         for (auto& t : c->tensors) t.buf = t.lane_buf[0];
         c->stream = saved;
-        c->num_cus = saved_cus;
     }
 };
 
@@ -905,37 +888,9 @@ int sbbseg_create(int device, int precision, sbbseg_ctx** out)
         sbbseg_destroy(c);
         return fail("lane stream/event creation failed: %s", hipGetErrorString(e));
     }
-    // CU-partitioned lanes: OPT-IN (SBBSEG_CU_SPLIT=1).  Measured (profiles/r04_experiments.md): the conv kernels of this library need
-    // all 256 CUs to fill the HBM fabric -- on half the chip every op takes 1.5-1.8x as long (the streaming probe: 1.06x) -- so the
-    // staggered halves come out 2 % (f16x3) to 5 % (f16) BEHIND the shared-chip lanes; kept for A/B, off by default
-    const char* split_env = getenv("SBBSEG_CU_SPLIT");
-    if (split_env && split_env[0] == '1' && c->num_cus >= 16) {
-        const int words = (c->num_cus + 31) / 32, half = c->num_cus / 2;
-        std::vector<uint32_t> lo(words, 0u), hi(words, 0u);
-        for (int i = 0; i < c->num_cus; ++i) (i < half ? lo : hi)[i / 32] |= 1u << (i % 32);
-        hipError_t e0 = hipExtStreamCreateWithCUMask(&c->half_stream[0], (uint32_t)words, lo.data());
-        hipError_t e1 = e0 == hipSuccess ? hipExtStreamCreateWithCUMask(&c->half_stream[1], (uint32_t)words, hi.data()) : e0;
-        if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&c->ev_half[0], hipEventDisableTiming);
-        if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&c->ev_half[1], hipEventDisableTiming);
-        if (e1 == hipSuccess) {
-            c->cu_split = true;
-            c->half_cus[0] = half; c->half_cus[1] = c->num_cus - half;
-        } else {
-            (void)hipGetLastError();
-            for (int k = 0; k < 2; ++k) {
-                if (c->half_stream[k]) (void)hipStreamDestroy(c->half_stream[k]);
-                if (c->ev_half[k]) (void)hipEventDestroy(c->ev_half[k]);
-                c->half_stream[k] = nullptr; c->ev_half[k] = nullptr;
-            }
-        }
-    }
-    if (const char* v = getenv("SBBSEG_STAGGER_MIN_TILES")) c->stagger_min_tiles = atoi(v);
     if (const char* v = getenv("SBBSEG_DEDUPE")) c->dedupe = v[0] != '0';
     if (const char* v = getenv("SBBSEG_KSPLIT")) c->ksplit = v[0] != '0';
     if (const char* v = getenv("SBBSEG_OWNED_REGIONS")) c->owned_mode = v[0] == '0' ? 0 : (v[0] == '2' ? 2 : 1);
-    // experiment (round 6): persistent grids sized for this many CUs instead of the device's -- with two lanes, grids of half the chip let both
-    // lanes' kernels run side by side for their whole duration (no CU masks: the dispatcher places the blocks)
-    if (const char* v = getenv("SBBSEG_GRID_CUS")) { const int n = atoi(v); if (n >= 8 && n <= c->num_cus) c->num_cus = n & ~7; }
     *out = c;
     return 0;
     API_END
@@ -948,8 +903,6 @@ int sbbseg_destroy(sbbseg_ctx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->lane_stream) (void)hipStreamSynchronize(c->lane_stream);
-    for (int k = 0; k < 2; ++k)
-        if (c->half_stream[k]) (void)hipStreamSynchronize(c->half_stream[k]);
     for (auto& t : c->tensors) {
         (void)hipFree(t.lane_buf[0]);
         (void)hipFree(t.lane_buf[1]);
@@ -998,10 +951,6 @@ int sbbseg_destroy(sbbseg_ctx* c)
     for (auto e : c->free_events) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->lane_stream) (void)hipStreamDestroy(c->lane_stream);
-    for (int k = 0; k < 2; ++k) {
-        if (c->half_stream[k]) (void)hipStreamDestroy(c->half_stream[k]);
-        if (c->ev_half[k]) (void)hipEventDestroy(c->ev_half[k]);
-    }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     delete c;
@@ -1479,9 +1428,8 @@ int sbbseg_add_conv(sbbseg_ctx* c, const sbbseg_conv_desc* d, const float* w_src
     {
         const sbbseg_conv_src& cs = d->src[0];
         const Tensor& st = c->tensors[cs.tensor];
-        const char* env = getenv("SBBSEG_STEM_KERNEL");
         const bool plain16 = c->precision == kF16 || c->precision == kBF16;     // the dedicated kernels read the one-plane layout
-        if ((plain16 || split) && !(env && env[0] == '0') && d->n_src == 1 && st.is_input_form && st.form == SBBSEG_INPUT_PAIRS &&
+        if ((plain16 || split) && d->n_src == 1 && st.is_input_form && st.form == SBBSEG_INPUT_PAIRS &&
             cs.channels == 8 && cs.kh == 7 && cs.kw == 4 && cs.stride_y == 2 && cs.stride_x == 1 && cs.pad_top == 0 && cs.pad_left == 0 &&
             cs.up_shift == 0 && cs.off_y == 0 && cs.off_x == 0 && d->cout == 64 && d->out_h % 16 == 0 && d->out_w % 16 == 0 &&
             st.H >= 2 * d->out_h + 5 && st.W >= d->out_w + 3 &&
@@ -1511,8 +1459,7 @@ int sbbseg_add_conv(sbbseg_ctx* c, const sbbseg_conv_desc* d, const float* w_src
             op.name = "stem_" + op.name;
         }
         // 3x3 / stride 1 / pad 1, 64 -> 64 channels: direct conv on an LDS halo tile, weights in registers
-        const char* env2 = getenv("SBBSEG_DIRECT64_KERNEL");
-        if ((plain16 || split) && !(env2 && env2[0] == '0') && d->n_src == 1 && !st.is_input_form && st.C == 64 && cs.channels == 64 &&
+        if ((plain16 || split) && d->n_src == 1 && !st.is_input_form && st.C == 64 && cs.channels == 64 &&
             cs.kh == 3 && cs.kw == 3 && cs.stride_y == 1 && cs.stride_x == 1 && cs.pad_top == 1 && cs.pad_left == 1 && cs.up_shift == 0 &&
             cs.off_y == 0 && cs.off_x == 0 && d->cout == 64 && d->out_h == st.H && d->out_w == st.W && d->residual_tensor < 0 &&
             d->raw_out_tensor < 0 && d->head_classes == 0 && d->out_tensor >= 0 && d->out_stride_y == 1 && d->out_stride_x == 1 &&
@@ -1995,13 +1942,12 @@ int sbbseg_finalize(sbbseg_ctx* c, int max_batch)
     if (build_fast_gather_tables(c)) return 1;
     // split mode: the decoder conv at 224 x 224 -- four merged parity classes of  conv3x3([up2(128 ch @ 112 x 112), 64 ch @ 224 x 224]) -> 64 ch
     // -- runs dec_halo_x3 (source halos resident in LDS, dec_halo_x3.hip) on the classes' OWN packed weights and K-step order:
-    // the rows of every class matrix are read back and re-laid as MFMA A fragments.  SBBSEG_DEC_HALO=0 keeps the generic kernel.
+    // the rows of every class matrix are read back and re-laid as MFMA A fragments.  Conv-variant bit 23 keeps the generic kernel.
     {
-        const char* env = getenv("SBBSEG_DEC_HALO");
         // (plain fp16 mode: dec_halo_f16.hip -- K-steps of 64 channels: 2 x 4 + 9 of them, fragments of the two k-halves in place of hi | lo)
         const bool x3 = c->precision == kF16X3;
         const int n0 = x3 ? 16 : 8, n1 = x3 ? 18 : 9, nsteps = n0 + n1;
-        for (size_t i = 0; (x3 || c->precision == kF16) && !(env && env[0] == '0') && i < c->ops.size(); ++i) {
+        for (size_t i = 0; (x3 || c->precision == kF16) && i < c->ops.size(); ++i) {
             Op& op = c->ops[i];
             if (op.type != kConv) continue;
             ConvOp& co = op.conv;
@@ -2051,9 +1997,8 @@ int sbbseg_finalize(sbbseg_ctx* c, int max_batch)
     }
     // split and plain fp16 modes, encoder stages 3 / 4: an identity block's last 1x1 conv (C -> 4C, + residual, ReLU) directly followed by the next block's
     // first 1x1 conv (4C -> C, stride 1, ReLU) -> one launch writes both outputs (expand_reduce_x3.hip: y is contracted from LDS instead
-    // of being read back).  Both matrices are read back and re-laid as MFMA A fragments.  SBBSEG_EXPAND_REDUCE=0 keeps two launches.
+    // of being read back).  Both matrices are read back and re-laid as MFMA A fragments.  Conv-variant bit 24 keeps two launches.
     {
-        const char* env = getenv("SBBSEG_EXPAND_REDUCE");
         const bool x3 = c->precision == kF16X3;
         const int kch = x3 ? 32 : 64;                                  // channels per K-step (plain fp16: two k-halves in place of hi | lo)
         auto pointwise = [&](const ConvOp& co, int cin, int cout) -> bool {
@@ -2072,7 +2017,7 @@ int sbbseg_finalize(sbbseg_ctx* c, int max_batch)
             }
             return true;
         };
-        for (size_t i = 0; (x3 || c->precision == kF16) && !(env && env[0] == '0') && i + 1 < c->ops.size(); ++i) {
+        for (size_t i = 0; (x3 || c->precision == kF16) && i + 1 < c->ops.size(); ++i) {
             if (c->ops[i].type != kConv || c->ops[i + 1].type != kConv) continue;
             ConvOp& e = c->ops[i].conv;
             ConvOp& r = c->ops[i + 1].conv;
@@ -2114,10 +2059,9 @@ int sbbseg_finalize(sbbseg_ctx* c, int max_batch)
         }
         // Round 6, stage 3 (C = 128; H, W multiples of 8): the identity block's 3x3 conv in front of such a pair joins the launch
         // (conv3_expand_reduce.hip: b stays in LDS).  The conv's packed rows are re-laid as A fragments in ITS K-step order, the taps and
-        // channel groups of the K-steps go along as a table.  SBBSEG_C3ER=0 keeps the 3x3 conv's own launch.
-        const char* env3 = getenv("SBBSEG_C3ER");
+        // channel groups of the K-steps go along as a table.  Conv-variant bit 25 keeps the 3x3 conv's own launch.
         const char* envfb = getenv("SBBSEG_FUSE_BLOCKS");          // (= 0: "keep every plan tensor materialised" -- the per-layer tests; b would not be)
-        if (envfb && envfb[0] == '0') env3 = "0";
+        const bool c3er = !(envfb && envfb[0] == '0');
         auto readers_of = [&](int tensor) {
             int nrd = 0;
             for (const Op& o : c->ops) {
@@ -2131,7 +2075,7 @@ int sbbseg_finalize(sbbseg_ctx* c, int max_batch)
             }
             return nrd;
         };
-        for (size_t i = 1; (x3 || c->precision == kF16) && !(env && env[0] == '0') && !(env3 && env3[0] == '0') && i < c->ops.size(); ++i) {
+        for (size_t i = 1; (x3 || c->precision == kF16) && c3er && i < c->ops.size(); ++i) {
             if (c->ops[i].type != kConv || c->ops[i - 1].type != kConv) continue;
             ConvOp& e = c->ops[i].conv;
             ConvOp& k3 = c->ops[i - 1].conv;
@@ -2177,14 +2121,13 @@ int sbbseg_finalize(sbbseg_ctx* c, int max_batch)
         }
     }
     // split and plain fp16 modes: the stem (dedicated kernel, raw output only) directly followed by the 3x3 / stride-2 max-pool of that tensor with an
-    // affine on every tap (bn_conv1 + ReLU) -> one launch writes both tensors (stem_pool_x3.hip); SBBSEG_STEM_POOL=0 keeps two launches
+    // affine on every tap (bn_conv1 + ReLU) -> one launch writes both tensors (stem_pool_x3.hip); conv-variant bit 22 keeps two launches
     {
-        const char* env = getenv("SBBSEG_STEM_POOL");
         // (plain fp16 mode: the one-plane form stem_pool<false> is bit-identical too but no faster than the two launches -- 0.53 against
         // 0.26 + 0.29 ms per 140 patches: with one MFMA per product the pool stage is most of the kernel -- so it is opt-in: SBBSEG_STEM_POOL_F16=1)
         const char* env16 = getenv("SBBSEG_STEM_POOL_F16");
         const bool on = c->precision == kF16X3 || (c->precision == kF16 && env16 && env16[0] == '1');
-        for (size_t i = 0; on && !(env && env[0] == '0') && i + 1 < c->ops.size(); ++i) {
+        for (size_t i = 0; on && i + 1 < c->ops.size(); ++i) {
             Op& a = c->ops[i];
             Op& b = c->ops[i + 1];
             if (a.type != kConv || !a.conv.d_stem_wfrag || b.type != kPool) continue;
@@ -2459,8 +2402,8 @@ static int tile_range_impl(sbbseg_ctx* c, const void* const* d_pages, int n_page
         return 0;
     };
     struct RegionOff { sbbseg_ctx* c; ~RegionOff() { c->rr.on = false; } };
-    auto run_chunk = [&](int lane, int first, int nb, bool halves = false) -> int {
-        LaneScope scope(c, lane, halves);
+    auto run_chunk = [&](int lane, int first, int nb) -> int {
+        LaneScope scope(c, lane);
         RegionOff roff{c};
         if (regions && setup_regions(lane, first_tile + first, nb)) return 1;
         IngestParams lp = ip;
@@ -2484,35 +2427,6 @@ static int tile_range_impl(sbbseg_ctx* c, const void* const* d_pages, int n_page
         }
         return run_plan(c, nb, (uint8_t*)d_tile_labels + first * per, nullptr);
     };
-    // CU-partitioned, staggered lanes (see sbbseg_ctx::half_stream): lane 0 takes the first half of the tile range in units of
-    // u = max_batch / 2 tiles, lane 1 the second half as [u / 2, u, u, ..., rest] -- its short first unit puts it half a network
-    // behind lane 0, so that from then on one lane's decoder (MFMA-bound, power-capped) runs beside the other lane's encoder
-    // (HBM-bound) on disjoint halves of the chip; no join before the end of the range.  Results do not depend on the schedule:
-    // every tile is computed by the same kernels from the same operands (test_two_lanes_equal_one_lane, the chunking tests).
-    if (c->cu_split && c->lane1_batch > 0 && c->lanes == 2 && !c->profiling && n_tiles >= c->stagger_min_tiles && n_tiles >= 4 * kMinLaneTiles) {
-        const int u = c->lane1_batch;                              // <= the second lane's buffers (and lane 0's hold max_batch >= u)
-        const int n0 = (n_tiles + 1) / 2, n1 = n_tiles - n0;
-        std::vector<std::pair<int, int>> units[2];                 // (first tile, count)
-        for (int o = 0; o < n0; o += u) units[0].push_back({o, n0 - o < u ? n0 - o : u});
-        int o1 = 0;
-        static const int head_pct = getenv("SBBSEG_STAGGER_HEAD_PCT") ? atoi(getenv("SBBSEG_STAGGER_HEAD_PCT")) : 50;      // probe knob
-        const int head_u = head_pct > 0 ? u * head_pct / 100 : u;
-        const int head = n1 > u ? (head_u > kMinLaneTiles ? head_u : kMinLaneTiles) : n1;
-        units[1].push_back({n0, head < n1 ? head : n1});
-        o1 = units[1][0].second;
-        for (; o1 < n1; o1 += u) units[1].push_back({n0 + o1, n1 - o1 < u ? n1 - o1 : u});
-        HIPCHK(hipEventRecord(c->ev_fork, c->stream));             // pages / thresholds / earlier ranges are ordered before both lanes
-        HIPCHK(hipStreamWaitEvent(c->half_stream[0], c->ev_fork, 0));
-        HIPCHK(hipStreamWaitEvent(c->half_stream[1], c->ev_fork, 0));
-        for (size_t i = 0; i < units[0].size() || i < units[1].size(); ++i)     // enqueue alternately: neither lane waits for the host
-            for (int lane = 0; lane < 2; ++lane)
-                if (i < units[lane].size() && run_chunk(lane, units[lane][i].first, units[lane][i].second, true)) return 1;
-        for (int lane = 0; lane < 2; ++lane) {
-            HIPCHK(hipEventRecord(c->ev_half[lane], c->half_stream[lane]));
-            HIPCHK(hipStreamWaitEvent(c->stream, c->ev_half[lane], 0));
-        }
-        return 0;
-    }
     // chunks of equal size (108 tiles at max_batch 70 -> 54 + 54, not 70 + 38): launches shrink evenly.
     // (Profiling runs every launch alone on one lane: its chunks are capped at the size a LANE's launch has in normal operation -- half a
     // chunk -- so that the per-op times describe the launches the product runs, partial last rounds of the persistent grids included.)
@@ -2529,16 +2443,6 @@ static int tile_range_impl(sbbseg_ctx* c, const void* const* d_pages, int n_page
                 HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
                 forked = false;
             }
-            // (probe knob SBBSEG_PROFILE_HALF=1: the profiling pass runs on lane 0's HALF of the chip, the other half idle)
-            static const bool prof_half = getenv("SBBSEG_PROFILE_HALF") && getenv("SBBSEG_PROFILE_HALF")[0] == '1';
-            if (c->profiling && prof_half && c->cu_split) {
-                HIPCHK(hipEventRecord(c->ev_fork, c->stream));
-                HIPCHK(hipStreamWaitEvent(c->half_stream[0], c->ev_fork, 0));
-                if (run_chunk(0, done, nb, true)) return 1;
-                HIPCHK(hipEventRecord(c->ev_half[0], c->half_stream[0]));
-                HIPCHK(hipStreamWaitEvent(c->stream, c->ev_half[0], 0));
-                continue;
-            }
             if (run_chunk(0, done, nb)) return 1;               // (not forked here: a fork in front was joined above)
             continue;
         }
@@ -2546,9 +2450,8 @@ static int tile_range_impl(sbbseg_ctx* c, const void* const* d_pages, int n_page
         // The lanes fork ONCE per tile range and join once behind its last chunk (round 5): a lane's halves of consecutive chunks follow each
         // other on the lane's own stream and buffers, nothing of one lane depends on the other.  (Up to round 4 every chunk forked and joined:
         // the lane that finished its half first waited for the other one -- 7-10 % of the timed region had ONE kernel in flight,
-        // profiles/r05_timeline_gaps.txt.  SBBSEG_JOIN_PER_CHUNK=1 restores that for A/B.)
-        static const bool join_per_chunk = getenv("SBBSEG_JOIN_PER_CHUNK") && getenv("SBBSEG_JOIN_PER_CHUNK")[0] == '1';
-        if (!forked || join_per_chunk) {
+        // profiles/r05_timeline_gaps.txt.)
+        if (!forked) {
             HIPCHK(hipEventRecord(c->ev_fork, c->stream));     // page / threshold / earlier ranges are ordered before
             HIPCHK(hipStreamWaitEvent(c->lane_stream, c->ev_fork, 0));
             forked = true;
@@ -2563,11 +2466,6 @@ static int tile_range_impl(sbbseg_ctx* c, const void* const* d_pages, int n_page
         };
         if (run_chunk(0, done, na)) return join_on_error();
         if (run_chunk(1, done + na, nb2)) return join_on_error();           // (starting lane 1 later -- after lane 0's op k -- measured 3-14 % slower)
-        if (join_per_chunk) {
-            HIPCHK(hipEventRecord(c->ev_join, c->lane_stream));
-            HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-            forked = false;
-        }
     }
     if (forked) {
         HIPCHK(hipEventRecord(c->ev_join, c->lane_stream));
@@ -2661,11 +2559,6 @@ int sbbseg_segment_pages_dev(sbbseg_ctx* c, int n_pages, const void* const* d_pa
     while (b) { const size_t t = a % b; a = b; b = t; }                 // a = gcd
     size_t G = (size_t)c->max_batch / a;                                 // pages per group with G * tpp = lcm
     if (G > 32) G = (8 * (size_t)c->max_batch + tpp - 1) / tpp;
-    if (c->cu_split && c->lanes == 2 && c->lane1_batch > 0) {
-        // the staggered lanes run a whole group without a join: groups of about eight chunks (four units per lane and more)
-        const size_t want = (8 * (size_t)c->max_batch + tpp - 1) / tpp;
-        if (G < want) G = want;
-    }
     if (G < 1) G = 1;
     if (G > (size_t)n_pages) G = (size_t)n_pages;
     REQUIRE(tpp * G < (size_t)1 << 30, "page group of %zu tiles is too large", tpp * G);

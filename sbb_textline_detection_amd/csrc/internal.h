@@ -97,8 +97,6 @@ struct ConvParams {
     float* probs;             // [n][TH][TW][classes] or null
     uint32_t howo_magic, howo_shift, wo_magic, wo_shift, nct_magic, nct_shift;   // FastDiv pairs for Ho * Wo, Wo and the number of
                                                            // channel tiles, filled by the launcher (kernels.hip)
-    int tile2d, tpr;                  // 1: pixel indices are cut into 16 x 16 blocks (tpr = Wo / 16 blocks per row), see decode_yx in conv_igemm_mfma
-    uint32_t tpr_magic, tpr_shift;    //    (filled by the launcher)
     const FgStepRec* fgstep_cls[4];   // fast gather: per-class tables read in place of kstep / kstep_cls (class 0 = entry 0)
     int fast_gather;          // every K-step regular, each source's taps within a 4 x 4 window, no upsampling source, buffers < 2 GiB:
                               // run the FG form of conv_igemm_mfma (kernels.hip)

@@ -298,21 +298,10 @@ void conv_igemm_mfma(const ConvParams p)
     const int lswz = GS == 8 ? lrow : ((0x78 >> (2 * ((lrow >> 2) & 3))) & 3);
     const int gsrc = (lane % GS) ^ lswz;                // source granule (within the stage) this lane fetches
     const int HoWo = p.Ho * p.Wo;
-    // output-grid pixel index inside one patch -> (oy, ox).  Linear: row-major, a pixel tile = a strip of BP consecutive pixels.
-    // tile2d (round 4; Ho, Wo multiples of 16): the index space is cut into 16 x 16 BLOCKS (256 consecutive indices = one block, blocks
-    // row-major), so a pixel tile is one or two square blocks: the taps of a 3x3 / 2x2 conv re-read an 18 x 18 halo INSIDE the tile's
-    // own K loop (L2 hits a few microseconds apart) instead of rows that the tiles above / below fetch at other times on other CUs.
-    // Which pixels share a tile changes, what is computed for a pixel does not: results are bit-identical.
+    // output-grid pixel index inside one patch -> (oy, ox): row-major, a pixel tile = a strip of BP consecutive pixels
     auto decode_yx = [&](int rem, int& oy, int& ox) __attribute__((always_inline)) {
-        if (p.tile2d) {
-            const int t = rem >> 8, r = rem & 255;
-            const int ty = fast_div(t, p.tpr_magic, p.tpr_shift);
-            oy = (ty << 4) + (r >> 4);
-            ox = ((t - ty * p.tpr) << 4) + (r & 15);
-        } else {
-            oy = fast_div(rem, p.wo_magic, p.wo_shift);
-            ox = rem - oy * p.Wo;
-        }
+        oy = fast_div(rem, p.wo_magic, p.wo_shift);
+        ox = rem - oy * p.Wo;
     };
     // pixel index m of class `cls` -> (patch, oy, ox) on the op's output grid.  Owned-region launches (ConvParams::rmap, region.h) look the
     // triple up in the launch's table -- the grid is walked only where the page stitch keeps the result (plus the later levels' halo);
@@ -1322,25 +1311,11 @@ static hipError_t launch_conv_impl(const ConvParams& p, hipStream_t s)
     // the 8-wave ones); p.persist_blocks == 0 -> one block per tile (A/B)
     const int resident = p.persist_blocks > 0 ? p.persist_blocks * T::kBlocksPerCU : n_tiles;
     int grid = n_tiles < resident ? n_tiles : resident;
-    // Balanced rounds (round 6, SBBSEG_BALANCED_GRID=1, off by default: an experiment): a launch of R = ceil(tiles / resident) rounds runs on
-    // ceil(tiles / R) blocks instead of all resident ones -- every block walks R tiles (+- 1), no CU idles through a last partial round
-    // while its neighbours finish it, and the CUs the launch does not occupy are free for the other lane's kernel from the start.
-    static const bool balanced = getenv("SBBSEG_BALANCED_GRID") && getenv("SBBSEG_BALANCED_GRID")[0] == '1';
-    if (balanced && p.persist_blocks > 0 && n_tiles > resident) {
-        const int rounds = (n_tiles + resident - 1) / resident;
-        grid = (n_tiles + rounds - 1) / rounds;
-    }
     if (p.tile_map >= 1) grid = (grid + 7) & ~7;          // the XCD-grouped walk needs a multiple of 8 blocks
     ConvParams q = p;
     make_fast_div((uint32_t)(p.Ho * p.Wo), &q.howo_magic, &q.howo_shift);
     make_fast_div((uint32_t)p.Wo, &q.wo_magic, &q.wo_shift);
     make_fast_div((uint32_t)n_ct, &q.nct_magic, &q.nct_shift);
-    // 2D pixel tiles for convs with real taps on the fast gather: an experiment (SBBSEG_TILE2D=1), off by default -- it measured neutral
-    // (profiles/r04_experiments.md section 3) and one plan shape (a k = 2 Conv2DTranspose decoder at 32 x 48) came out wrong with it
-    static const bool tile2d_on = getenv("SBBSEG_TILE2D") && getenv("SBBSEG_TILE2D")[0] == '1';
-    q.tile2d = (tile2d_on && p.fast_gather == 1 && p.Ho % 16 == 0 && p.Wo % 16 == 0) ? 1 : 0;
-    q.tpr = p.Wo / 16;
-    make_fast_div((uint32_t)(q.tpr > 0 ? q.tpr : 1), &q.tpr_magic, &q.tpr_shift);
     hipLaunchKernelGGL((conv_igemm_mfma<BP, BC, WP, WC, NS, F16, GS, PH8, X3, FG, KS>), dim3(grid), dim3(T::kThreads), T::kLdsBytes, s, q);
     return hipGetLastError();
 }

@@ -98,6 +98,12 @@ def test_shipped_library_has_no_wrong_answer_probes(lib):
     blob = open(_capi.LIB_PATH, "rb").read()
     for name in (b"SBBSEG_CONV_PROBE_LOCAL", b"SBBSEG_CONV_PROBE_WHOT", b"SBBSEG_BLOCK_DBG", b"SBBSEG_ER_DBG", b"SBBSEG_PROBES"):
         assert name not in blob, name.decode()
+    # switches removed from the library: lost experiments (one of them, TILE2D, wrong on a plan), and finalize-time copies of
+    # conv-variant bits (sbbseg_debug_set_conv_variant).  STEM_POOL is a prefix of STEM_POOL_F16, which stays: match it with its NUL.
+    for name in (b"SBBSEG_CU_SPLIT", b"SBBSEG_STAGGER_MIN_TILES", b"SBBSEG_STAGGER_HEAD_PCT", b"SBBSEG_PROFILE_HALF", b"SBBSEG_JOIN_PER_CHUNK",
+                 b"SBBSEG_BALANCED_GRID", b"SBBSEG_GRID_CUS", b"SBBSEG_TILE2D", b"SBBSEG_DEC_HALO", b"SBBSEG_EXPAND_REDUCE", b"SBBSEG_C3ER",
+                 b"SBBSEG_STEM_POOL\0", b"SBBSEG_STEM_KERNEL", b"SBBSEG_DIRECT64_KERNEL"):
+        assert name not in blob, name.decode()
     for src in ("api.hip", "kernels.hip", "block_x3.hip", "expand_reduce_x3.hip"):
         text = open(os.path.join(ROOT, "sbb_textline_detection_amd", "csrc", src)).read()
         # every use of the probe bits in device code goes through SBBSEG_PROBE(...) (constant false in the shipped build) ...
