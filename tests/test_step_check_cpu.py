@@ -1,0 +1,334 @@
+"""tests/step_check.py is tight enough and not too tight -- no GPU.
+
+A numpy stand-in for the device runs small plans step by step: operands quantised as the host code quantises them, products
+accumulated in FLOAT32 in K-chunks of 16 or 32 walked in a shuffled (seeded) order, epilogue in float32, outputs rounded to the
+storage format.  (1) Correct arithmetic stays inside the derived bound in all four precisions; (2) each of ten one-line kernel
+defects, injected into the stand-in, puts the step it was injected into over the bound in f16 and f16x3 -- and the range-relative
+criterion of the per-layer tests (``TOL_LAYER_REL``) is evaluated on the same tensor to show what it lets through."""
+import copy
+import functools
+import zlib
+
+import numpy as np
+import pytest
+
+import step_check as sc
+from plan_interp import make_input_forms
+from sbb_textline_detection_amd.keras_graph import parse_model_config
+from sbb_textline_detection_amd.planner import build_plan
+from sbb_textline_detection_amd.synthetic import synthetic_page
+from tools.synth_model import calibrated_model
+
+TOL_LAYER_REL = {"bf16": 0.25, "f16": 0.04, "f32": 2e-4, "f16x3": 2e-4}      # tests/gpu_common.py (its import needs the built library)
+PRECISIONS = ["f16", "f16x3", "bf16", "f32"]
+# (classes, H, W, planner switches beyond what SegModel derives from the precision).  The second net keeps the decoder convs
+# whole (SBBSEG_PARITY_SPLIT=0: two-source 3x3 convs over an upsampled source, `shift`) and the head in a conv's epilogue.
+MODELS = {"c2_64x96": (2, 64, 96, {}), "c4_64x64": (4, 64, 64, dict(parity_split=False, fuse_tail=False))}
+PIXEL_TILE = 64          # the stand-in's pixel tile (defect 8)
+
+
+@functools.lru_cache(maxsize=None)
+def _net(model):
+    classes, h, w, _ = MODELS[model]
+    cfg, weights = calibrated_model(classes, h, w, seed=3, calib_hw=64)
+    page = synthetic_page(300, 400, 7)
+    x = np.stack([page[10:10 + h, 20:20 + w], page[120:120 + h, 210:210 + w]]).astype(np.float32) / 255
+    return parse_model_config(cfg), weights, x
+
+
+@functools.lru_cache(maxsize=None)
+def _plan(model, precision):
+    graph, weights, _ = _net(model)
+    args = dict(fuse_head=precision != "f32", fuse_tail=precision != "f32")        # model.py SegModel._plan_args
+    args.update(MODELS[model][3])
+    return build_plan(graph, weights, **args)
+
+
+# ------------------------------------------------------------------------------------------------ the stand-in
+def _im2col(vals, g, out_h, out_w, edge_left=False):
+    a = sc.source_input(vals, g, np.float32)
+    n, h, w, c = a.shape
+    need_h = (out_h - 1) * g.stride_y - g.pad_top + g.kh
+    need_w = (out_w - 1) * g.stride_x - g.pad_left + g.kw
+    P = np.zeros((n, need_h + g.pad_top, need_w + g.pad_left, c), np.float32)
+    y0, x0 = g.pad_top + g.off_y, g.pad_left + g.off_x
+    hh, ww = min(h, P.shape[1] - y0), min(w, P.shape[2] - x0)
+    P[:, y0:y0 + hh, x0:x0 + ww] = a[:, :hh, :ww]
+    if edge_left and x0 > 0:
+        P[:, :, :x0] = P[:, :, x0:x0 + 1]                                # defect 6: edge replication instead of zeros, left side
+    cols = [P[:, ky:ky + (out_h - 1) * g.stride_y + 1:g.stride_y, kx:kx + (out_w - 1) * g.stride_x + 1:g.stride_x]
+            for ky in range(g.kh) for kx in range(g.kw)]
+    return np.stack(cols, axis=3).reshape(n * out_h * out_w, g.kh * g.kw * c)
+
+
+class StandIn:
+    """The device, in numpy.  `defect` (None or a key of DEFECTS) is applied to the one step it is passed to."""
+
+    def __init__(self, precision, seed=0):
+        self.precision, self.seed = precision, seed
+
+    def _accumulate(self, A, W, rng, drop=None):
+        """float32 sum over K in shuffled chunks; A, W lists of operand planes multiplied pairwise (split: hi*hi, hi*lo, lo*hi)."""
+        K = A[0].shape[1]
+        size = 16 if rng.randint(2) else 32
+        chunks = [(k, min(k + size, K)) for k in range(0, K, size)]
+        acc = np.zeros((A[0].shape[0], W[0].shape[1]), np.float32)
+        for i in rng.permutation(len(chunks)):
+            k0, k1 = chunks[i]
+            for a, w in zip(A, W):
+                wc = w[k0:k1]
+                if drop is not None and i == len(chunks) - 1:
+                    wc = wc.copy()
+                    wc[:, drop] = 0                                      # defect 10: the last K-chunk dropped for one channel
+                acc += a[:, k0:k1] @ wc
+        return acc
+
+    def conv(self, s, vals, ws, defect=None):
+        """-> dict of fp32 outputs on the step's grid: "out", "raw_out", "probs"."""
+        prec = self.precision
+        rng = np.random.RandomState(self.seed + (zlib.crc32(s.name.encode()) & 0xFFFF))
+        n = vals[s.srcs[0].tensor].shape[0]
+        A = np.concatenate([_im2col(vals, g, s.out_h, s.out_w, edge_left=defect == 6) for g in s.srcs], axis=1)
+        pre = 1.0
+        if prec == "f16x3":
+            halves, pre = sc.split_weights(ws)
+            Wh = np.concatenate([h.reshape(-1, s.cout) for h, _ in halves])
+            Wl = np.concatenate([l.reshape(-1, s.cout) for _, l in halves])
+            Wp = [Wh, Wl, Wh]
+        else:
+            Wp = [np.concatenate([sc.quantise_weights(prec, w).astype(np.float32).reshape(-1, s.cout) for w in ws])]
+        g0 = s.srcs[0]
+        tap = ((g0.kh // 2) * g0.kw + g0.kw // 2) * g0.channels           # the centre tap of source 0
+        px = np.arange(A.shape[0])
+        ox, oy, on = px % s.out_w, (px // s.out_w) % s.out_h, px // (s.out_w * s.out_h)
+        if defect == 1:
+            A = A.copy()
+            A[ox == s.out_w - 1, tap:tap + g0.channels] = 0              # one tap skipped, last output column
+        if defect == 2:
+            A = A.copy()
+            A[(oy == 0) & (on == 1), tap:tap + g0.channels] = 0          # one tap skipped, first output row of the second patch
+        if defect == 7:
+            Wp = [w.copy() for w in Wp]
+            for w in Wp:
+                w[0:8], w[8:16] = w[8:16].copy(), w[0:8].copy()          # two 8-channel K groups swapped on the weight side
+        if prec == "f16x3":
+            Ah = A.astype(np.float16).astype(np.float32)
+            Ap = [Ah, Ah, A - Ah]
+        else:
+            Ap = [A]
+        acc = self._accumulate(Ap, Wp, rng, drop=5 if defect == 10 else None)
+        f32 = lambda v: np.asarray(v, np.float32)
+        scale, shift = f32(s.scale) / np.float32(pre), f32(s.shift).copy()
+        if defect == 5:
+            shift[3] = shift[2]                                          # shift of one channel taken from its neighbour
+        out = {}
+        shape = (n, s.out_h, s.out_w, s.cout)
+        if s.raw_out >= 0:
+            out["raw_out"] = sc.round_storage(prec, acc * (f32(s.raw_scale) / np.float32(pre)) + f32(s.raw_shift)).reshape(shape)
+        res = f32(sc.placed(vals[s.residual], s)).reshape(-1, s.cout) if s.residual >= 0 else None
+        if defect == 3:
+            z = (acc + res * np.float32(pre)) * scale + shift            # residual added before `* scale`
+        else:
+            z = acc * scale + shift
+            if res is not None:
+                z = z + res
+        if s.relu:
+            keep = z[:, 1].copy()
+            z = np.maximum(z, 0)
+            if defect == 4:
+                z[:, 1] = keep                                           # ReLU not applied to one channel
+        z = f32(z)
+        if s.out >= 0 or s.head is None:
+            o = sc.round_storage(prec, z)
+            if defect == 8:                                              # channels 16..31 of the ragged last pixel tile from the tile before
+                m0 = (o.shape[0] // PIXEL_TILE) * PIXEL_TILE
+                o = o.copy()
+                o[m0:, 16:32] = o[m0 - PIXEL_TILE:m0 - PIXEL_TILE + (o.shape[0] - m0), 16:32]
+            out["out"] = o.reshape(shape)
+        if s.head is not None:
+            hd = s.head
+            lg = f32(f32(z @ f32(hd.w)) * f32(hd.scale) + f32(hd.shift))
+            ex = np.exp(lg - lg.max(-1, keepdims=True), dtype=np.float32)
+            out["probs"] = (ex / ex.sum(-1, keepdims=True)).reshape(n, s.out_h, s.out_w, hd.classes)
+        return out
+
+    def pool(self, s, vals, defect=None):
+        x = np.asarray(vals[s.src], np.float32)
+        if s.pre_scale is not None:
+            x = x * np.asarray(s.pre_scale, np.float32) + np.asarray(s.pre_shift, np.float32)
+            if s.pre_relu:
+                x = np.maximum(x, 0)
+        oh, ow = (x.shape[1] - s.k) // s.stride + 1, (x.shape[2] - s.k) // s.stride + 1
+        win = lambda k: np.max([x[:, dy:dy + (oh - 1) * s.stride + 1:s.stride, dx:dx + (ow - 1) * s.stride + 1:s.stride]
+                                for dy in range(k) for dx in range(k)], axis=0)
+        o = win(s.k)
+        if defect == 9:
+            o[:, -1] = win(s.k - 1)[:, -1]                               # 2 x 2 window instead of 3 x 3 on the last row
+        return sc.round_storage(self.precision, o) if s.pre_scale is not None else o
+
+    def run_step(self, plan, s, vals, probs, defect=None):
+        """Run one step on the stored inputs in `vals`; writes its outputs into `vals` / `probs` (fp32 images of the stored values)."""
+        n = next(iter(vals.values())).shape[0]
+
+        def tensor(tid):
+            if tid not in vals:
+                t = plan.tensors[tid]
+                vals[tid] = np.zeros((n, t.H, t.W, t.C), np.float32)
+            return vals[tid]
+        if s.kind == "conv":
+            o = self.conv(s, vals, [g.w for g in s.srcs], defect)
+            if s.out >= 0:
+                sc.placed(tensor(s.out), s)[...] = o["out"]
+            if s.raw_out >= 0:
+                sc.placed(tensor(s.raw_out), s)[...] = o["raw_out"]
+            if "probs" in o:
+                sc.placed(probs, s)[...] = o["probs"]
+        elif s.kind == "tail":
+            for c in sc.tail_class_steps(s):
+                o = self._tail_class(c, s, vals)
+                sc.placed(probs, c)[...] = o["probs"]
+        elif s.kind == "maxpool":
+            vals[s.dst] = self.pool(s, vals, defect)
+        elif s.kind == "head":
+            z = np.asarray(vals[s.src], np.float32)
+            lg = (z.reshape(-1, s.cin) @ np.asarray(s.w, np.float32)) * np.asarray(s.scale, np.float32) + np.asarray(s.shift, np.float32)
+            ex = np.exp(lg - lg.max(-1, keepdims=True), dtype=np.float32)
+            probs[...] = (ex / ex.sum(-1, keepdims=True)).reshape(probs.shape)
+
+    def _tail_class(self, c, tail, vals):
+        if self.precision != "f16x3":
+            return self.conv(c, vals, [g.w for g in c.srcs])
+        # split mode: ONE pre-scale over the four classes' pre-summed weights and the image taps
+        allw = [k.srcs[0].w for k in sc.tail_class_steps(tail)] + [c.srcs[1].w]
+        pre = sc.split_prescale(allw)
+        own = sc.split_prescale([g.w for g in c.srcs])
+        # scaling both the weights and (inversely) the BN scale by the same power of two leaves the class's own prescale rule at `pre`
+        k = np.float32(pre / own)
+        c2 = copy.copy(c)
+        c2.srcs = [copy.copy(g) for g in c.srcs]
+        for g in c2.srcs:
+            g.w = np.asarray(g.w, np.float32) * k
+        c2.scale = np.asarray(c.scale, np.float32) / k
+        return self.conv(c2, vals, [g.w for g in c2.srcs])
+
+
+def _fresh(plan, precision, x):
+    vals = {tid: sc.round_storage(precision, a) for tid, a in make_input_forms(plan, x).items()}
+    probs = np.zeros(x.shape[:3] + (plan.classes,), np.float32)
+    return vals, probs
+
+
+@functools.lru_cache(maxsize=None)
+def _clean_run(model, precision):
+    """The stand-in over the whole plan: (vals, probs, [report per step])."""
+    plan, x = _plan(model, precision), _net(model)[2]
+    dev = StandIn(precision, seed=11)
+    vals, probs = _fresh(plan, precision, x)
+    reports = []
+    for s in plan.steps:
+        dev.run_step(plan, s, vals, probs)
+    for s in plan.steps:
+        reports.append(sc.check_step(plan, s, vals, precision, probs=probs))
+    return vals, probs, reports
+
+
+def _step_kind(plan, s):
+    if s.kind != "conv":
+        return s.kind
+    g = s.srcs[0]
+    tags = [f"conv{g.kh}x{g.kw}", f"s{g.stride_y}"]
+    if plan.tensors[g.tensor].kind == "input_pairs":
+        tags.append("stem")
+    if len(s.srcs) == 2:
+        tags.append("cat")
+    if any(q.shift for q in s.srcs):
+        tags.append("up")
+    if s.residual >= 0:
+        tags.append("res")
+    if s.out_stride != (1, 1):
+        tags.append("par")
+    if s.head is not None:
+        tags.append("head")
+    return "_".join(tags)
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("model", list(MODELS))
+def test_correct_arithmetic_stays_inside_the_bound(model, precision):
+    plan = _plan(model, precision)
+    _, _, reports = _clean_run(model, precision)
+    worst = {}
+    for s, r in zip(plan.steps, reports):
+        k = _step_kind(plan, s)
+        worst[k] = max(worst.get(k, 0.0), r["worst"])
+    print(f"\n[stand-in {model} {precision}] worst err / bound per step kind: " + ", ".join(f"{k} {v:.3f}" for k, v in sorted(worst.items())))
+    for s, r in zip(plan.steps, reports):
+        assert not sc.failed(r), (s.name, r)
+    kinds = set(worst)
+    if model == "c2_64x96":
+        assert any("stem" in k for k in kinds) and "maxpool" in kinds
+        assert any((g.kh, g.kw, g.stride_y, g.stride_x) == (3, 3, 2, 2) for s in plan.steps if s.kind == "conv" for g in s.srcs)
+        assert any("res" in k for k in kinds) and any("cat" in k and "conv1x1" in k for k in kinds)       # identity / projection blocks
+        assert ("head" if precision == "f32" else "tail") in kinds
+    else:
+        assert any("up" in k and "cat" in k for k in kinds)                 # two-source decoder conv with `shift`
+        assert "head" in kinds if precision == "f32" else any(k.endswith("head") for k in kinds)
+    assert plan.steps[1].kind == "maxpool" and plan.steps[1].pre_scale is not None
+
+
+# ------------------------------------------------------------------------------------------------ defects
+DEFECTS = {
+    1: "one spatial tap skipped for the last output column only",
+    2: "one spatial tap skipped for the first output row of the second patch only",
+    3: "residual added before * scale instead of after",
+    4: "ReLU not applied to one output channel",
+    5: "shift of one channel taken from its neighbour",
+    6: "zero padding replaced by edge replication on one side",
+    7: "two 8-channel groups of K swapped on the weight side only",
+    8: "output channels 16..31 of a ragged last tile written from the tile before",
+    9: "max-pool window 2 x 2 instead of 3 x 3 on the last row",
+    10: "the last K-chunk dropped for one output channel",
+}
+
+
+def _applies(plan, s, defect, n):
+    """The step a defect is injected into is the FIRST step of the plan (in order) it can occur in -- fixed by this rule, not by outcome."""
+    if defect == 9:
+        return s.kind == "maxpool"
+    if s.kind != "conv" or s.out < 0:
+        return False
+    g = s.srcs[0]
+    M = n * s.out_h * s.out_w
+    return {1: g.kh * g.kw > 1, 2: g.kh * g.kw > 1, 3: s.residual >= 0, 4: s.relu, 5: True,
+            6: any(q.pad_left + q.off_x > 0 for q in s.srcs), 7: sc.step_K(s) >= 16,
+            8: s.cout >= 32 and M % PIXEL_TILE != 0 and M > PIXEL_TILE, 10: True}[defect]
+
+
+# Findings about the bound, not about the checker's code: on conv2d_2:p00 (K = 13312) the accumulation term n_add * 2^-23 * S is
+# 1.6e-3 S (4.8e-3 S in the split mode), and these two defects stay below it.  Worst err / bound measured on the stand-in:
+_INVISIBLE = {(5, "longest_k", "f16"): "0.107", (5, "longest_k", "f16x3"): "0.0356",
+              (10, "longest_k", "f16"): "0.0234 (the dropped chunk multiplies activations that are zero behind the ReLU: error 0 on that channel)",
+              (10, "longest_k", "f16x3"): "2.2e-05 (the same: error 0 on that channel)"}
+_CASES = [pytest.param(d, w, p, marks=[pytest.mark.xfail(strict=True, reason=f"worst err / bound {_INVISIBLE[(d, w, p)]}: below the bound at K = 13312")]
+                       if (d, w, p) in _INVISIBLE else [])
+          for d in sorted(DEFECTS) for w in ("first", "longest_k") for p in ("f16", "f16x3")]
+
+
+@pytest.mark.parametrize("defect,where,precision", _CASES)
+def test_injected_defect_is_reported(defect, where, precision):
+    """`where`: the first step of the plan the defect can occur in, or the one among them with the longest contraction (first of
+    equals) -- there the accumulation term of the bound is largest and one dropped product smallest against it."""
+    model = "c2_64x96"
+    plan = _plan(model, precision)
+    clean_vals, clean_probs, _ = _clean_run(model, precision)
+    n = clean_probs.shape[0]
+    cand = [s for s in plan.steps if _applies(plan, s, defect, n)]
+    step = cand[0] if where == "first" else max(cand, key=sc.step_K)
+    vals = {k: v.copy() for k, v in clean_vals.items()}
+    StandIn(precision, seed=11).run_step(plan, step, vals, clean_probs.copy(), defect=defect)
+    rep = sc.check_step(plan, step, vals, precision)
+    old_caught = not rep["old_rel"] < TOL_LAYER_REL[precision]
+    print(f"\n[defect {defect:2d} {where} {precision}] {DEFECTS[defect]} -> step {step.name} (K {rep['K']}): worst err / bound {rep['worst']:.3g} at {rep['index']}, "
+          f"{rep['n_over']} elements over; caught-by-new {sc.failed(rep)}; caught-by-old {old_caught} "
+          f"(max|err| / max|ref| {rep['old_rel']:.3g} vs {TOL_LAYER_REL[precision]})")
+    assert sc.failed(rep) and rep["n_over"] > 0, (DEFECTS[defect], step.name, rep)
