@@ -298,8 +298,20 @@ int sbbseg_extract_page_box_dev(sbbseg_ctx* c, const void* d_page_hwc, int Hp, i
  * the textline model at all (main.py:2083-2096): pixels == label -> 255, cv2.morphologyEx MORPH_OPEN then MORPH_CLOSE with the 5x5
  * kernel, cv2.findContours(RETR_TREE), keep parentless contours whose polygon area >= min_area * H * W (the reference: min_area =
  * 0.00001, max_area = 1).  *present = 1 when at least one contour is kept.  Decided from the largest outer-contour area of the
- * opened / closed plane (the ranking of sbbseg_page_box_dev); the polygons themselves are not produced.  Synchronises the stream. */
+ * opened / closed plane (the ranking of sbbseg_page_box_dev); the polygons themselves are not produced (their boxes: sbbseg_text_region_boxes_dev below).  Synchronises the stream. */
 int sbbseg_text_regions_present_dev(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, double min_area, int* present);
+
+/* The boxes of those contours (main.py:474-478, `self.boxes`): the same class mask, MORPH_OPEN and MORPH_CLOSE, then cv2.boundingRect
+ * {x, y, w, h} of every component that has no parent (it is 4-adjacent to the background connected to the frame: an island inside
+ * another component's hole is dropped) and whose outer-contour area lies in [min_area, max_area] x H x W (the reference: 0.00001, 1).
+ * *n_boxes = the number found; at most `cap` boxes are written (cap = 0 and boxes_xywh = NULL: count only, then call again).
+ * Order [EXT, unpinned]: the component's first pixel in raster order, DESCENDING -- the reverse discovery order assumed for
+ * cv2.findContours' list; slopes are per box, nothing downstream depends on it.  The polygons are not produced.  Synchronises the
+ * stream.  The second form takes a HOST plane. */
+int sbbseg_text_region_boxes_dev(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, double min_area, double max_area,
+                                 int32_t* boxes_xywh, int cap, int* n_boxes);
+int sbbseg_text_region_boxes(sbbseg_ctx* c, const uint8_t* regions_hw, int H, int W, int label, double min_area, double max_area,
+                             int32_t* boxes_xywh, int cap, int* n_boxes);
 
 /* ---- device buffers for callers without a device runtime of their own.  The reference's environment is Keras/TF (requirements.txt),
  * not PyTorch: what run() keeps resident across its three stages (main.py:2056-2107: the stored page, the border mask, the region
@@ -353,6 +365,19 @@ int sbbseg_deskew_profiles_dev(sbbseg_ctx* c, const void* d_mask_hw, int H, int 
                                int n_angles, int32_t* counts);
 int sbbseg_deskew_profiles(sbbseg_ctx* c, const uint8_t* mask_hw, int H, int W, const double* matrices, const double* angles_deg,
                            int n_angles, int32_t* counts);
+
+/* The same rotate-and-project for ALL text-region boxes of a page in one call (do_work_of_slopes, main.py:1728-1738).  textline_hw: the
+ * u8 textline label plane [H][W]; boxes_xywh: n_boxes x {x, y, w, h} inside it.  Per box: crop (crop_image_inside_box), cv2.erode with
+ * the 5x5 kernel `erode_iterations` times ON THE CROP (the reference: 2; 0 = none), centre on the zero square of side
+ * S_r = int(1.4 * max(h_r, w_r)), rotate by every angle, binarise (!= 0), sum the rows -- bit for bit what sbbseg_deskew_profiles gives
+ * for the eroded crop.  counts is packed: region r starts at offsets[r] and holds [n_angles][S_r] int32; offsets has n_boxes + 1
+ * entries, the last one is the total.  counts = NULL: only offsets is filled (to size counts; needs no handle).  All regions and
+ * angles run in three launches whatever n_boxes is; one device-to-host copy.  A box that leaves the plane, w or h < 1, or
+ * S_r > 32767 is an error (status + sbbseg_last_error()).  Synchronises the stream. */
+int sbbseg_region_deskew_profiles_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
+                                      int erode_iterations, const double* angles_deg, int n_angles, int32_t* counts, int64_t* offsets);
+int sbbseg_region_deskew_profiles(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
+                                  int erode_iterations, const double* angles_deg, int n_angles, int32_t* counts, int64_t* offsets);
 
 /* ---- multi-GPU: one process per GPU, one handle per process; tiles (sbbseg_segment_tile_range_dev) or whole
  * pages (sbbseg_segment_pages_dev) are sharded by the caller, and the ONE data-path collective -- the all-gather of the u8

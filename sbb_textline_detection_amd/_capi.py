@@ -34,6 +34,7 @@ EXPORTS = [
     "sbbseg_debug_largest_contour_area2", "sbbseg_text_regions_present_dev", "sbbseg_run_page", "sbbseg_device_alloc", "sbbseg_device_free", "sbbseg_upload", "sbbseg_download", "sbbseg_download_labels",
     "sbbseg_set_owned_regions", "sbbseg_owned_region_info", "sbbseg_op_executed", "sbbseg_debug_owned_range", "sbbseg_debug_region_rows",
     "sbbseg_debug_poison_activations",
+    "sbbseg_text_region_boxes_dev", "sbbseg_text_region_boxes", "sbbseg_region_deskew_profiles_dev", "sbbseg_region_deskew_profiles",
 ]
 
 
@@ -154,6 +155,10 @@ def load_library(path: Optional[str] = None):
         "sbbseg_debug_owned_range": [i32, i32, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)],
         "sbbseg_debug_region_rows": [i32, i32, i32, i32, i32, i32, vp, vp],
         "sbbseg_debug_poison_activations": [vp, i32],
+        "sbbseg_text_region_boxes_dev": [vp, vp, i32, i32, i32, C.c_double, C.c_double, vp, i32, C.POINTER(C.c_int)],
+        "sbbseg_text_region_boxes": [vp, vp, i32, i32, i32, C.c_double, C.c_double, vp, i32, C.POINTER(C.c_int)],
+        "sbbseg_region_deskew_profiles_dev": [vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp],
+        "sbbseg_region_deskew_profiles": [vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -534,14 +539,67 @@ class Context:
 
     def text_regions_present(self, regions: np.ndarray, label: int = 1, min_area: float = 0.00001) -> bool:
         plane = np.ascontiguousarray(regions[:, :, 0] if regions.ndim == 3 else regions, np.uint8)
-        # staging buffer cached on the Context (grown on demand, released with the handle): sbbseg_device_free synchronises the device
+        return self.text_regions_present_dev(self.stage(plane), plane.shape[0], plane.shape[1], label, min_area)
+
+    def stage(self, plane: np.ndarray) -> int:
+        """Upload a host plane into the staging buffer cached on the Context (grown on demand, released with the handle:
+        sbbseg_device_free synchronises the device); returns the device pointer, valid until the next stage()."""
         cap = getattr(self, "_gate_cap", 0)
-        if cap < plane.size:
+        if cap < plane.nbytes:
             if cap:
                 self.device_free(self._gate_buf)
-            self._gate_buf, self._gate_cap = self.device_alloc(plane.size), plane.size
+            self._gate_buf, self._gate_cap = self.device_alloc(plane.nbytes), plane.nbytes
         self.upload(self._gate_buf, plane)
-        return self.text_regions_present_dev(self._gate_buf, plane.shape[0], plane.shape[1], label, min_area)
+        return self._gate_buf
+
+    def text_region_boxes_dev(self, d_regions: int, H: int, W: int, label: int = 1, min_area: float = 0.00001, max_area: float = 1.0):
+        """get_text_region_contours_and_boxes' ``self.boxes`` (main.py:456-480) from a device label plane: a list of [x, y, w, h].
+        Order [EXT, unpinned]: first pixel in raster order, descending (see sbbseg.h)."""
+        return self._boxes_call(self.lib.sbbseg_text_region_boxes_dev, C.c_void_p(d_regions), H, W, label, min_area, max_area)
+
+    def text_region_boxes(self, regions: np.ndarray, label: int = 1, min_area: float = 0.00001, max_area: float = 1.0):
+        """The same from a host label map ([H, W] or [H, W, 3]: all channels must equal ``label``, main.py:458)."""
+        regions = np.asarray(regions)
+        if regions.ndim == 3:
+            plane = np.where(np.all(regions == label, axis=-1), label, (label + 1) & 255).astype(np.uint8)      # any value but the label
+        else:
+            plane = np.ascontiguousarray(regions, np.uint8)
+        return self._boxes_call(self.lib.sbbseg_text_region_boxes, _ptr(plane), plane.shape[0], plane.shape[1], label, min_area, max_area)
+
+    def _boxes_call(self, fn, src, H, W, label, min_area, max_area):
+        n = C.c_int(0)
+        cap = 64
+        while True:                                             # a second call only when there are more boxes than the first guess
+            boxes = np.zeros((cap, 4), np.int32)
+            check(fn(self.h, src, int(H), int(W), int(label), float(min_area), float(max_area), _ptr(boxes), cap, C.byref(n)), "sbbseg_text_region_boxes")
+            if n.value <= cap:
+                return [[int(v) for v in b] for b in boxes[:n.value]]
+            cap = n.value
+
+    def _region_profiles_call(self, fn, src, H, W, boxes, angles_deg, erode_iterations):
+        boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        angles_deg = np.ascontiguousarray(angles_deg, np.float64).reshape(-1)
+        n, na = boxes.shape[0], angles_deg.shape[0]
+        offsets = region_deskew_offsets(boxes, na, H, W)
+        if n == 0:
+            return []
+        counts = np.empty(int(offsets[-1]), np.int32)
+        check(fn(self.h, src, int(H), int(W), _ptr(boxes), n, int(erode_iterations), _ptr(angles_deg), na, _ptr(counts), _ptr(offsets)),
+              "sbbseg_region_deskew_profiles")
+        return [counts[offsets[r]:offsets[r + 1]].reshape(na, -1) for r in range(n)]
+
+    def region_deskew_profiles_dev(self, d_textlines: int, H: int, W: int, boxes, angles_deg, erode_iterations: int = 2):
+        """Row profiles of the deskew sweep for every box of a device textline plane, one call: a list of int32 [n_angles][S_r]."""
+        return self._region_profiles_call(self.lib.sbbseg_region_deskew_profiles_dev, C.c_void_p(d_textlines), H, W, boxes, angles_deg, erode_iterations)
+
+    def region_deskew_profiles(self, textlines: np.ndarray, boxes, angles_deg, erode_iterations: int = 2):
+        """The same from a host textline map uint8 [H, W] (uploaded once per call): per box, bit for bit
+        ``deskew_profiles(cv2.erode(crop, 5x5, iterations), angles)``."""
+        plane = np.ascontiguousarray(textlines, np.uint8)
+        if plane.ndim != 2:
+            raise ValueError("region_deskew_profiles expects a uint8 plane [H, W]")
+        return self._region_profiles_call(self.lib.sbbseg_region_deskew_profiles, _ptr(plane), plane.shape[0], plane.shape[1], boxes, angles_deg,
+                                          erode_iterations)
 
     def page_box_dev(self, d_mask: int, H: int, W: int):
         """((x, y, w, h), pixels) of the largest component of the dilated mask (main.py:394-404); pixels == 0: empty mask."""
@@ -710,6 +768,16 @@ def deskew_side(H: int, W: int) -> int:
     side = C.c_int(0)
     check(load_library().sbbseg_deskew_side(int(H), int(W), C.byref(side)), "sbbseg_deskew_side")
     return int(side.value)
+
+
+def region_deskew_offsets(boxes, n_angles: int, H: int, W: int) -> np.ndarray:
+    """int64 [n_boxes + 1]: where region r's [n_angles][S_r] counts start in the packed buffer of sbbseg_region_deskew_profiles (the
+    last entry is the total).  Validates the boxes against the H x W plane; no GPU and no handle needed."""
+    boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+    offsets = np.zeros(boxes.shape[0] + 1, np.int64)
+    check(load_library().sbbseg_region_deskew_profiles_dev(None, None, int(H), int(W), _ptr(boxes), boxes.shape[0], 0, None, int(n_angles), None,
+                                                           _ptr(offsets)), "sbbseg_region_deskew_profiles")
+    return offsets
 
 
 def rotation_matrix(cx: float, cy: float, angle_deg: float) -> np.ndarray:

@@ -269,6 +269,9 @@ struct sbbseg_ctx {
     int* d_cc_list = nullptr;             // [6 + kCcMaxRivals]: launch_largest_contour's result record
     int* d_cc_aux = nullptr; size_t cc_aux_cap = 0;      // five int planes: doubled cell area + bounding boxes per root (sbbseg_page_box_dev)
     unsigned long long* d_cc_small = nullptr;      // [0] best key, [1..2] box (4 ints)
+    int* d_cc_bg = nullptr; size_t cc_bg_cap = 0;        // two int planes: labels of the complement, border flags (sbbseg_text_region_boxes_dev)
+    int* d_cc_roots = nullptr; size_t cc_roots_cap = 0;  // parentless roots, 6 ints each
+    void* d_rdk = nullptr; size_t rdk_cap = 0;           // sbbseg_region_deskew_profiles_dev: maps | table | geometry | crops | counts
     // profiling
     bool profiling = false;
     int conv_variant = 0;
@@ -932,6 +935,7 @@ int sbbseg_destroy(sbbseg_ctx* c)
     (void)hipFree(c->d_page); (void)hipFree(c->d_page_labels); (void)hipFree(c->d_page_labels3); (void)hipFree(c->d_tile_labels);
     (void)hipFree(c->d_own_x); (void)hipFree(c->d_own_y); (void)hipFree(c->d_map); (void)hipFree(c->d_wmap);
     (void)hipFree(c->d_deskew);
+    (void)hipFree(c->d_cc_bg); (void)hipFree(c->d_cc_roots); (void)hipFree(c->d_rdk);
     for (int lane = 0; lane < 2; ++lane)
         for (int L = 0; L < kRegionMaxLevels; ++L) (void)hipFree(c->d_rtab[lane][L]);
     (void)hipFree(c->d_run_page); (void)hipFree(c->d_run_mask); (void)hipFree(c->d_run_a); (void)hipFree(c->d_run_b);
@@ -3029,7 +3033,7 @@ int sbbseg_page_box_dev(sbbseg_ctx* c, const void* d_mask_hw, int H, int W, int3
 // component and every hole is a union of 5x5 squares, so no contour has fewer than three points (the `jv` bookkeeping of
 // filter_contours_area_of_image, main.py:81-91, never drifts), and the largest outer contour of the plane is always a parentless one
 // (a component nested in a hole is smaller than the component around it): contours exist <=> the largest outer-contour area
-// reaches min_area * H * W.  The contours themselves (polygons, boxes) are out of scope.
+// reaches min_area * H * W.  The boxes: sbbseg_text_region_boxes_dev below; the polygons are out of scope.
 int sbbseg_text_regions_present_dev(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, double min_area, int* present)
 {
     API_BEGIN
@@ -3051,6 +3055,102 @@ int sbbseg_text_regions_present_dev(sbbseg_ctx* c, const void* d_regions_hw, int
     if (rank_contours(c, H, W, false, box, &any, &area2, &traced, 2.0 * need)) return 1;
     *present = (any && (double)area2 * 0.5 >= need) ? 1 : 0;
     return 0;
+    API_END
+}
+
+// get_text_region_contours_and_boxes' BOXES (main.py:456-480, `self.boxes`): the same front end as the existence test above, then
+// cv2.boundingRect of every contour that filter_contours_area_of_image keeps -- a component without a parent (launch_parentless_roots)
+// whose outer-contour area lies in [min_area, max_area] x H x W.  The device has a lower bound of that area per root (cells of the
+// component as it is) and the bounding-box upper bound (w - 1)(h - 1); only a component the two bounds leave undecided is traced on the
+// host (trace_outer_area2 on the label plane, as rank_contours does).  Order [EXT, unpinned]: the component's first pixel in raster order,
+// DESCENDING -- the reverse discovery order that OpenCV's contour list is assumed to have (see host_largest_contour).  Nothing downstream
+// of the boxes depends on it: slopes are per box.
+int sbbseg_text_region_boxes_dev(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, double min_area, double max_area,
+                                 int32_t* boxes_xywh, int cap, int* n_boxes)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    REQUIRE(d_regions_hw && n_boxes && H > 0 && W > 0 && label >= 0 && label <= 255 && min_area >= 0.0 && max_area >= min_area && cap >= 0 &&
+                (boxes_xywh || cap == 0), "bad arguments");
+    REQUIRE((size_t)H * W < ((size_t)1 << 31), "plane too large for 32-bit pixel indices");
+    const size_t pix = (size_t)H * W;
+    if (ensure(c, (void**)&c->d_morph_a, &c->morph_a_cap, pix) || ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
+    if (ensure(c, (void**)&c->d_cc_parent, &c->cc_parent_cap, pix * sizeof(int)) || ensure(c, (void**)&c->d_cc_count, &c->cc_count_cap, pix * sizeof(int))) return 1;
+    if (ensure(c, (void**)&c->d_cc_aux, &c->cc_aux_cap, 5 * pix * sizeof(int)) || ensure(c, (void**)&c->d_cc_bg, &c->cc_bg_cap, 2 * pix * sizeof(int))) return 1;
+    if (!c->d_cc_small && dmalloc(c, (void**)&c->d_cc_small, 4 * sizeof(unsigned long long))) return 1;
+    if (!c->d_cc_list && dmalloc(c, (void**)&c->d_cc_list, (6 + kCcMaxRivals) * sizeof(int))) return 1;
+    // after OPEN + CLOSE a component holds a whole 5x5 square (planes narrower than the kernel: no such bound)
+    const size_t list_cap = (H >= 5 && W >= 5) ? pix / 25 + 16 : pix;
+    if (ensure(c, (void**)&c->d_cc_roots, &c->cc_roots_cap, list_cap * 6 * sizeof(int))) return 1;
+    HIPCHK(launch_morph((const uint8_t*)d_regions_hw, c->d_morph_a, c->d_morph_b, H, W, 2, 0, 0x100 | label, c->stream));
+    HIPCHK(launch_morph(c->d_morph_b, c->d_morph_a, c->d_morph_b, H, W, 4, 1, 0, c->stream));
+    HIPCHK(launch_morph(c->d_morph_b, c->d_morph_a, c->d_morph_b, H, W, 2, 0, 0, c->stream));
+    int* aux = c->d_cc_aux;
+    HIPCHK(launch_largest_contour(c->d_morph_b, H, W, c->d_cc_parent, c->d_cc_count, aux, aux + pix, aux + 2 * pix, aux + 3 * pix, aux + 4 * pix,
+                                  c->d_cc_small, c->d_cc_list, c->stream));
+    int* d_n = (int*)(c->d_cc_small + 2);
+    HIPCHK(launch_parentless_roots(c->d_morph_b, c->d_morph_a, H, W, c->d_cc_parent, c->d_cc_bg, c->d_cc_count, aux, aux + pix, aux + 2 * pix,
+                                   aux + 3 * pix, aux + 4 * pix, d_n, c->d_cc_roots, (int)list_cap, c->stream));
+    int found = 0;
+    HIPCHK(hipMemcpyAsync(&found, d_n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    REQUIRE(found >= 0 && (size_t)found <= list_cap, "internal error: %d parentless components, room for %zu", found, list_cap);
+    alloc_check();
+    struct Root { int root, x0, y0, x1, y1, lower2; };
+    std::vector<Root> roots((size_t)found);
+    if (found) HIPCHK(hipMemcpy(roots.data(), c->d_cc_roots, (size_t)found * sizeof(Root), hipMemcpyDeviceToHost));
+    std::sort(roots.begin(), roots.end(), [](const Root& a, const Root& b) { return a.root > b.root; });
+    // main.py:87: area >= min_area * np.prod(image.shape[:2]) and area <= max_area * np.prod(image.shape[:2])
+    const double lo = min_area * (double)((long long)H * W), hi = max_area * (double)((long long)H * W);
+    std::vector<int> state((size_t)found);                     // 1 keep, 0 drop, 2 undecided
+    bool trace = false;
+    for (int k = 0; k < found; ++k) {
+        const Root& r = roots[k];
+        const double lower = (double)r.lower2 * 0.5, upper = (double)(r.x1 - r.x0) * (double)(r.y1 - r.y0);
+        if (c->force_host_contours) state[k] = 2;
+        else if (upper < lo || lower > hi) state[k] = 0;
+        else if (lower >= lo && upper <= hi) state[k] = 1;
+        else state[k] = 2;
+        trace = trace || state[k] == 2;
+    }
+    if (trace) {
+        std::vector<int> lab(pix);
+        HIPCHK(hipMemcpy(lab.data(), c->d_cc_parent, pix * sizeof(int), hipMemcpyDeviceToHost));
+        for (int k = 0; k < found; ++k) {
+            if (state[k] != 2) continue;
+            const int root = roots[k].root;
+            auto inside = [&](int y, int x) { return (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W && lab[(size_t)y * W + x] == root; };
+            int tb[4];
+            const double area = (double)trace_outer_area2(inside, root / W, root % W, (long)pix, tb) * 0.5;
+            state[k] = (area >= lo && area <= hi) ? 1 : 0;
+        }
+        c->host_contour_calls += 1;
+    }
+    int kept = 0;
+    for (int k = 0; k < found; ++k) {
+        if (state[k] != 1) continue;
+        if (kept < cap) {
+            const Root& r = roots[k];
+            int32_t* o = boxes_xywh + (size_t)kept * 4;
+            o[0] = r.x0; o[1] = r.y0; o[2] = r.x1 - r.x0 + 1; o[3] = r.y1 - r.y0 + 1;                  // cv2.boundingRect
+        }
+        ++kept;
+    }
+    *n_boxes = kept;
+    return 0;
+    API_END
+}
+
+int sbbseg_text_region_boxes(sbbseg_ctx* c, const uint8_t* regions_hw, int H, int W, int label, double min_area, double max_area,
+                             int32_t* boxes_xywh, int cap, int* n_boxes)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    REQUIRE(regions_hw && H > 0 && W > 0, "bad arguments");
+    const size_t pix = (size_t)H * W;
+    if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
+    HIPCHK(hipMemcpyAsync(c->d_morph_b, regions_hw, pix, hipMemcpyHostToDevice, c->stream));
+    return sbbseg_text_region_boxes_dev(c, c->d_morph_b, H, W, label, min_area, max_area, boxes_xywh, cap, n_boxes);
     API_END
 }
 
@@ -3329,6 +3429,91 @@ int sbbseg_deskew_profiles(sbbseg_ctx* c, const uint8_t* mask_hw, int H, int W, 
     if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
     HIPCHK(hipMemcpyAsync(c->d_morph_b, mask_hw, pix, hipMemcpyHostToDevice, c->stream));
     return sbbseg_deskew_profiles_dev(c, c->d_morph_b, H, W, matrices, angles_deg, n_angles, counts);
+    API_END
+}
+
+// The same sweep for every text-region box of a page in one call (do_work_of_slopes, main.py:1728-1738): crop_image_inside_box,
+// cv2.erode(crop, 5x5, iterations) on the CROP, return_deskew_slope's square and rotations.  offsets[r] = first int of region r in
+// `counts` ([n_angles][S_r]), offsets[n_boxes] = the total; counts == NULL: only the offsets are computed (to size the buffer).
+int sbbseg_region_deskew_profiles_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
+                                      int erode_iterations, const double* angles_deg, int n_angles, int32_t* counts, int64_t* offsets)
+{
+    API_BEGIN
+    REQUIRE(H > 0 && W > 0 && n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && offsets && n_angles >= 1 && n_angles <= 4096 &&
+                erode_iterations >= 0 && erode_iterations <= 64, "bad arguments");
+    alloc_check();
+    std::vector<DeskewRegion> geom((size_t)n_boxes);
+    long long total_pix = 0, total_counts = 0, total_blocks = 0;
+    for (int r = 0; r < n_boxes; ++r) {
+        const int32_t* b = boxes_xywh + (size_t)r * 4;
+        REQUIRE(b[2] >= 1 && b[3] >= 1, "box %d: width %d, height %d (both must be at least 1)", r, b[2], b[3]);
+        REQUIRE(b[0] >= 0 && b[1] >= 0 && (long long)b[0] + b[2] <= W && (long long)b[1] + b[3] <= H, "box %d (%d, %d, %d, %d) leaves the %d x %d plane",
+                r, b[0], b[1], b[2], b[3], W, H);
+        DeskewRegion& g = geom[r];
+        g.x = b[0]; g.y = b[1]; g.w = b[2]; g.h = b[3];
+        g.S = (int)((double)(g.h > g.w ? g.h : g.w) * 1.4);                               // main.py:1613
+        REQUIRE(g.S >= 1 && g.S <= 32767, "box %d: deskew square side %d out of range", r, g.S);
+        const int cp = (int)(g.S / 2.0);
+        g.top = cp - (int)(g.h / 2.0); g.left = cp - (int)(g.w / 2.0);                    // main.py:1615-1619
+        g.clip = (g.top >= 1 && g.left >= 1 && g.top + g.h <= g.S - 1 && g.left + g.w <= g.S - 1) ? 1 : 0;
+        g.crop_off = total_pix; g.count_off = total_counts;
+        g.row_groups = (g.S + kRegionDeskewRows - 1) / kRegionDeskewRows;
+        g.block0 = (int)total_blocks;
+        offsets[r] = total_counts;
+        total_pix += (long long)g.w * g.h;
+        total_counts += (long long)n_angles * g.S;
+        total_blocks += (long long)n_angles * g.row_groups;
+        REQUIRE(total_counts < (1ll << 31) && total_blocks < (1ll << 31), "too much work for one sweep (%d boxes, %d angles): split the boxes", n_boxes, n_angles);
+    }
+    offsets[n_boxes] = total_counts;
+    if (!counts || n_boxes == 0) return 0;                         // (the size query needs no handle)
+    if (check_ready(c)) return 1;
+    REQUIRE(d_textline_hw && angles_deg, "bad arguments");
+    // head of the device buffer, built on the host and copied in one piece: inverse maps | bicubic table | geometry
+    const size_t minv_bytes = (size_t)n_boxes * n_angles * 6 * sizeof(double), tab_bytes = 128 * sizeof(float);
+    const size_t geom_off = minv_bytes + tab_bytes, head_bytes = (geom_off + (size_t)n_boxes * sizeof(DeskewRegion) + 15) & ~(size_t)15;
+    const size_t pix_bytes = ((size_t)total_pix + 15) & ~(size_t)15;
+    std::vector<unsigned char> head(head_bytes);
+    double* minv = (double*)head.data();
+    for (int r = 0; r < n_boxes; ++r)
+        for (int a = 0; a < n_angles; ++a) {
+            double M[6];
+            if (sbbseg_rotation_matrix((double)(geom[r].S / 2), (double)(geom[r].S / 2), angles_deg[a], M)) return 1;     // main.py:161
+            invert_affine(M, minv + ((size_t)r * n_angles + a) * 6);
+        }
+    cubic_table((float*)(head.data() + minv_bytes));
+    memcpy(head.data() + geom_off, geom.data(), (size_t)n_boxes * sizeof(DeskewRegion));
+    if (ensure(c, &c->d_rdk, &c->rdk_cap, head_bytes + 2 * pix_bytes + (size_t)total_counts * sizeof(int))) return 1;
+    unsigned char* d = (unsigned char*)c->d_rdk;
+    RegionDeskewParams p;
+    p.plane = (const uint8_t*)d_textline_hw; p.H = H; p.W = W;
+    p.geom = (const DeskewRegion*)(d + geom_off); p.n_regions = n_boxes; p.n_angles = n_angles; p.radius = 2 * erode_iterations;
+    p.total_pix = total_pix;
+    p.minv = (const double*)d; p.cubic = (const float*)(d + minv_bytes);
+    p.tmp = d + head_bytes; p.crops = d + head_bytes + pix_bytes; p.counts = (int*)(d + head_bytes + 2 * pix_bytes);
+    p.total_blocks = (int)total_blocks;
+    HIPCHK(hipMemcpyAsync(d, head.data(), head_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_region_deskew_crops(p, c->stream));
+    HIPCHK(launch_region_deskew_profiles(p, c->stream));
+    HIPCHK(hipMemcpyAsync(counts, p.counts, (size_t)total_counts * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffer lives until here)
+    return 0;
+    API_END
+}
+
+int sbbseg_region_deskew_profiles(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
+                                  int erode_iterations, const double* angles_deg, int n_angles, int32_t* counts, int64_t* offsets)
+{
+    API_BEGIN
+    REQUIRE(H > 0 && W > 0, "bad arguments");
+    if (counts && n_boxes > 0) {
+        if (check_ready(c)) return 1;
+        REQUIRE(textline_hw, "bad arguments");
+        const size_t pix = (size_t)H * W;
+        if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
+        HIPCHK(hipMemcpyAsync(c->d_morph_b, textline_hw, pix, hipMemcpyHostToDevice, c->stream));
+    }
+    return sbbseg_region_deskew_profiles_dev(c, (counts && n_boxes > 0) ? c->d_morph_b : nullptr, H, W, boxes_xywh, n_boxes, erode_iterations, angles_deg, n_angles, counts, offsets);
     API_END
 }
 

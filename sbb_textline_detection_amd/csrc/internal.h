@@ -343,6 +343,36 @@ hipError_t launch_morph(const uint8_t* src, uint8_t* tmp, uint8_t* dst, int H, i
 constexpr int kCcMaxRivals = 250;    // rival roots sbbseg_page_box_dev gets back from the device (more: the host scans the label plane)
 hipError_t launch_largest_contour(const uint8_t* mask, int H, int W, int* parent, int* count, int* area2, int* bx0, int* by0, int* bx1,
                                   int* by1, unsigned long long* d_best, int* d_out, hipStream_t s);
+// the roots of the components without a parent (RETR_TREE), after launch_largest_contour on the same plane (kernels.hip)
+hipError_t launch_parentless_roots(const uint8_t* mask, uint8_t* inv, int H, int W, const int* parent, int* bg, int* touch, const int* area2,
+                                   const int* bx0, const int* by0, const int* bx1, const int* by1, int* d_n, int* list, int cap, hipStream_t s);
+// batched per-region deskew profiles (region_deskew.hip): crop + erode every box of a label plane, then rotate-and-project all
+// (region, angle, row) of a sweep in one launch
+struct DeskewRegion {
+    int x, y, w, h;           // the box on the plane
+    int S, top, left;         // side of the zero square (int(1.4 * max(h, w))), placement of the crop inside it (main.py:1613-1619)
+    int clip;                 // 1: the crop keeps a margin of at least one pixel to the square's edges (the analytic x span is valid)
+    long long crop_off;       // first byte of the eroded crop in the packed crop buffer
+    long long count_off;      // first int of the region's [n_angles][S] counts
+    int block0;               // first block of the region in the profile launch
+    int row_groups;           // blocks per angle: ceil(S / kRegionDeskewRows)
+};
+constexpr int kRegionDeskewRows = 8;      // destination rows per block of region_deskew_profile_kernel (a wave per row, two rounds)
+struct RegionDeskewParams {
+    const uint8_t* plane;     // [H][W] label plane (device)
+    int H, W;
+    const DeskewRegion* geom; // [n_regions]
+    int n_regions, n_angles, radius;
+    long long total_pix;      // sum of w * h
+    const double* minv;       // [n_regions][n_angles][6] inverse affine maps
+    const float* cubic;       // [32][4]
+    uint8_t* tmp;             // [total_pix] row pass of the erosion
+    uint8_t* crops;           // [total_pix] eroded crops, packed
+    int* counts;              // packed row counts
+    int total_blocks;
+};
+hipError_t launch_region_deskew_crops(const RegionDeskewParams& p, hipStream_t s);
+hipError_t launch_region_deskew_profiles(const RegionDeskewParams& p, hipStream_t s);
 hipError_t launch_replicate3(const uint8_t* src, uint8_t* dst, size_t n, hipStream_t s);
 hipError_t launch_to_f32(const void* src, float* dst, size_t n, int precision, hipStream_t s);
 hipError_t launch_deskew_profiles(const uint8_t* mask, int H, int W, int S, int top, int left, const double* minv, const float* cubic,

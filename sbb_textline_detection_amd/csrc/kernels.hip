@@ -4126,6 +4126,94 @@ hipError_t launch_largest_contour(const uint8_t* mask, int H, int W, int* parent
     return hipGetLastError();
 }
 
+// ---- the PARENTLESS components of a labelled plane (cv2.findContours(RETR_TREE): hierarchy[..][3] == -1, main.py:88).  An
+// 8-connected component has no parent when it is 4-adjacent to the background that is 4-connected to the frame around the image;
+// an island inside another component's hole is not.  So: label the COMPLEMENT with 4-connectivity (the same union-find), flag the
+// background components that reach the image border, and mark every foreground root one of whose pixels lies on the border or
+// next to flagged background.  The marked roots are then compacted into a list of {root, x0, y0, x1, y1, area2 lower bound}.
+__global__ __launch_bounds__(256) void cc_invert_kernel(const uint8_t* mask, uint8_t* inv, long n)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) inv[i] = mask[i] ? 0 : 255;
+}
+__global__ __launch_bounds__(256) void cc_link4_kernel(const uint8_t* mask, int* parent, int H, int W)
+{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)H * W) return;
+    const int y = (int)(idx / W), x = (int)(idx - (long)y * W);
+    if (y == 0 || !mask[idx] || !mask[idx - W]) return;
+    // only the left end of a contact between two row runs makes the union (see cc_link_kernel)
+    if (x > 0 && mask[idx - 1] && mask[idx - W - 1]) return;
+    cc_union(parent, (int)idx, (int)(idx - W));
+}
+// flag[root] = 1 for every background component with a pixel on the image border (flag[] is zero on entry)
+__global__ __launch_bounds__(256) void cc_frame_flag_kernel(const int* bg_parent, int* flag, int H, int W)
+{
+    const long k = (long)blockIdx.x * 256 + threadIdx.x;
+    long i;
+    if (k < W) i = k;                                                  // top row
+    else if (k < 2L * W) i = (long)(H - 1) * W + (k - W);              // bottom row
+    else if (k < 2L * W + H) i = (k - 2L * W) * W;                     // left column
+    else if (k < 2L * W + 2L * H) i = (k - 2L * W - H) * W + (W - 1);  // right column
+    else return;
+    const int r = bg_parent[i];
+    if (r >= 0) flag[r] = 1;
+}
+// touch[root] = 1 for every foreground component that is 4-adjacent to the frame or to flagged background (touch[] is zero on entry;
+// all writers store the same value)
+__global__ __launch_bounds__(256) void cc_touch_kernel(const int* parent, const int* bg_parent, const int* flag, int* touch, int H, int W)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)H * W) return;
+    const int r = parent[i];
+    if (r < 0) return;
+    const int y = (int)(i / W), x = (int)(i - (long)y * W);
+    bool t = x == 0 || y == 0 || x == W - 1 || y == H - 1;
+    if (!t) {
+        const long nb[4] = {i - 1, i + 1, i - W, i + W};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int b = bg_parent[nb[q]];
+            if (b >= 0 && flag[b]) t = true;
+        }
+    }
+    if (t) touch[r] = 1;
+}
+__global__ __launch_bounds__(256) void cc_collect_roots_kernel(const int* parent, const int* touch, const int* area2, const int* bx0, const int* by0,
+                                                               const int* bx1, const int* by1, long n, int* n_found, int* list, int cap)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || parent[i] != (int)i || !touch[i]) return;
+    const int k = atomicAdd(n_found, 1);                       // the list's order is arbitrary: the host sorts it by root
+    if (k >= cap) return;
+    int* rec = list + (size_t)k * 6;
+    rec[0] = (int)i; rec[1] = bx0[i]; rec[2] = by0[i]; rec[3] = bx1[i]; rec[4] = by1[i]; rec[5] = area2[i];
+}
+
+// After launch_largest_contour on the same plane (parent flat; area2 / boxes per root in place).  inv: u8 scratch plane; bg: two int
+// planes of H * W (labels of the complement, border flags); touch: an int plane of H * W (launch_largest_contour's `count` may be
+// given: the pixel counts are lost).  d_n: the number of parentless roots, list: the first `cap` of them, 6 ints each.
+hipError_t launch_parentless_roots(const uint8_t* mask, uint8_t* inv, int H, int W, const int* parent, int* bg, int* touch, const int* area2,
+                                   const int* bx0, const int* by0, const int* bx1, const int* by1, int* d_n, int* list, int cap, hipStream_t s)
+{
+    const long n = (long)H * W;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    int* bg_parent = bg;
+    int* flag = bg + n;
+    hipError_t e = hipMemsetAsync(d_n, 0, sizeof(int), s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(touch, 0, (size_t)n * sizeof(int), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cc_invert_kernel, dim3(grid), dim3(256), 0, s, mask, inv, n);
+    hipLaunchKernelGGL(cc_rows_kernel, dim3((unsigned)H), dim3(64), 0, s, (const uint8_t*)inv, bg_parent, flag, H, W);      // (zeroes flag[])
+    hipLaunchKernelGGL(cc_link4_kernel, dim3(grid), dim3(256), 0, s, (const uint8_t*)inv, bg_parent, H, W);
+    hipLaunchKernelGGL(cc_flatten_kernel, dim3(grid), dim3(256), 0, s, bg_parent, n);
+    hipLaunchKernelGGL(cc_frame_flag_kernel, dim3((unsigned)((2L * W + 2L * H + 255) / 256)), dim3(256), 0, s, (const int*)bg_parent, flag, H, W);
+    hipLaunchKernelGGL(cc_touch_kernel, dim3(grid), dim3(256), 0, s, parent, (const int*)bg_parent, (const int*)flag, touch, H, W);
+    hipLaunchKernelGGL(cc_collect_roots_kernel, dim3(grid), dim3(256), 0, s, parent, (const int*)touch, area2, bx0, by0, bx1, by1, n, d_n, list, cap);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // deskew_profile_kernel -- the rotate-and-project of the deskew search (main.py:1601-1718): for every angle of a sweep,
 // the region mask (centred on a zero square of side S, main.py:1613-1621) is rotated as rotate_image does (main.py:159-163:

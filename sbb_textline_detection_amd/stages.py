@@ -13,7 +13,12 @@ it that section 8(f) ranks next, with the reference's names and call pattern:
     return_deskew_slope             main.py:1601-1718 the per-region deskew search: rotate-and-project on the device (one launch
                                                       per sweep), the 1-D peak logic on the host with the reference's own scipy calls
 
-The rest of the cv2 contour post-processing (text-region contours, line separation, ...) is out of scope.
+    get_text_region_contours_and_boxes  main.py:456-480   the BOXES of the text regions (``self.boxes``), on the device
+    do_work_of_slopes (slope half)  main.py:1721-1748 one deskew slope per box: crop, erode x 2 and the rotate-and-project of ALL boxes in
+                                                      one batched sweep on the device (``get_slopes``), peak logic per region on the host
+
+Out of scope: textline_contours_postprocessing, the polygons, the reading order and PAGE-XML; a device-side Gaussian / find_peaks /
+std (the host half of the deskew search stays the reference's own scipy calls).
 """
 from __future__ import annotations
 
@@ -108,6 +113,35 @@ def host_text_regions_present(regions: np.ndarray, label: int = 1, min_area: flo
     return _capi.host_largest_contour_area2(p) * 0.5 >= min_area * float(p.shape[0] * p.shape[1])
 
 
+def host_text_region_boxes(regions: np.ndarray, label: int = 1, min_area: float = 0.00001, max_area: float = 1.0):
+    """Host mirror of sbbseg_text_region_boxes_dev (foreign model objects, CPU-only checks; main.py:456-480): class mask -> OPEN -> CLOSE ->
+    [x, y, w, h] of every 8-connected component that is 4-adjacent to the background connected to the frame (no parent) and whose
+    outer-contour area (the library's host tracer, no GPU) lies in [min_area, max_area] x H x W.  Order [EXT, unpinned]: first pixel in
+    raster order, descending -- the reverse discovery order assumed for cv2.findContours' list."""
+    from scipy import ndimage
+    from . import _capi
+    a = np.asarray(regions)
+    m = np.all(a == label, axis=-1) if a.ndim == 3 else a == label
+    p = np.where(m, 255, 0).astype(np.uint8)
+    p = host_morph(host_morph(p, False, 5, 1), True, 5, 2)             # OPEN's erode + dilate, CLOSE's dilate ...
+    p = host_morph(p, False, 5, 1)                                     # ... and erode
+    lab, n = ndimage.label(p > 0, structure=np.ones((3, 3), int))      # numbered by first pixel in raster order
+    back, _ = ndimage.label(np.pad(p == 0, 1, constant_values=True))   # 4-connected background, with the frame around the image
+    outer = back == back[0, 0]
+    beside = outer[1:-1, :-2] | outer[1:-1, 2:] | outer[:-2, 1:-1] | outer[2:, 1:-1]
+    parentless = np.zeros(n + 1, bool)
+    parentless[np.unique(lab[beside & (lab > 0)])] = True
+    lo, hi = min_area * float(p.shape[0] * p.shape[1]), max_area * float(p.shape[0] * p.shape[1])
+    boxes = []
+    for k, sl in reversed(list(enumerate(ndimage.find_objects(lab), start=1))):
+        if not parentless[k]:
+            continue
+        area = _capi.host_largest_contour_area2(np.where(lab[sl] == k, 255, 0).astype(np.uint8)) * 0.5
+        if lo <= area <= hi:
+            boxes.append([sl[1].start, sl[0].start, sl[1].stop - sl[1].start, sl[0].stop - sl[0].start])
+    return boxes
+
+
 def _profile_statistics(y: np.ndarray, sigma: float, multiplier: float):
     """get_standard_deviation_of_summed_textline_patch_along_width (main.py:1545-1599) from the row sums on: smoothed profile z,
     its maxima and the minima of the padded, negated profile (scipy, as the reference), the "deep" minima below
@@ -161,6 +195,36 @@ def return_deskew_slope(img_patch: np.ndarray, sigma_des: float, ctx=None) -> fl
         angles = np.linspace(-90, -50, 30)
         ang = _deskew_sweep(ctx.deskew_profiles(mask, angles), angles, sigma_des)
     return ang
+
+
+def get_slopes(textline_mask: np.ndarray, boxes, ctx=None, sigma_des: float = 2):
+    """The slope half of ``do_work_of_slopes`` (main.py:1728-1748) for all boxes of a page: a list of float, one per box.  The textline
+    map is uploaded once; crop, ``cv2.erode(crop, kernel, iterations=2)`` and the 80 rotations of every box run as ONE batched sweep on the
+    device (``sbbseg_region_deskew_profiles_dev``), a second batched sweep of 30 angles covers only the boxes whose first answer is steeper
+    than 15 degrees (main.py:1669-1670); the peak logic runs per region on the host (``_deskew_sweep``).  Then the reference's clean-up:
+    a failed search (its 999) and |slope| > 120.5 become 0 (main.py:1744-1747).  ``ctx``: a ``_capi.Context`` (any finalized handle)."""
+    if ctx is None:
+        raise RuntimeError("get_slopes needs a library handle (SegModel.ctx): there is no CPU fallback")
+    plane = np.ascontiguousarray(textline_mask, np.uint8)
+    boxes = [[int(v) for v in b] for b in boxes]
+    if not boxes:
+        return []
+    d_plane = ctx.stage(plane)
+
+    def sweep(which, angles):
+        found = {}
+        profiles = ctx.region_deskew_profiles_dev(d_plane, plane.shape[0], plane.shape[1], [boxes[r] for r in which], angles, 2)
+        for r, prof in zip(which, profiles):
+            try:
+                found[r] = _deskew_sweep(prof, angles, sigma_des)
+            except Exception:                                       # main.py:1739-1740
+                found[r] = 999
+        return found
+    slopes = sweep(list(range(len(boxes))), np.linspace(-25, 25, 80))                          # main.py:1622
+    steep = [r for r, ang in slopes.items() if ang != 999 and abs(ang) > 15]                   # main.py:1669-1670
+    if steep:
+        slopes.update(sweep(steep, np.linspace(-90, -50, 30)))
+    return [0 if (ang == 999 or abs(ang) > 120.5) else ang for ang in (slopes[r] for r in range(len(boxes)))]
 
 
 class InferenceStages:
@@ -315,6 +379,38 @@ class InferenceStages:
             return host_text_regions_present(regions)
         finally:
             session.close()
+
+    def get_text_region_boxes(self, regions: np.ndarray):
+        """get_text_region_contours_and_boxes' ``self.boxes`` (main.py:456-480) for the cleaned layout map: a list of [x, y, w, h].  On the
+        device for a SegModel (``sbbseg_text_region_boxes``); foreign model objects get the host mirror."""
+        model, session = start_new_session_and_model(self.model_region_dir, **self.kw)
+        try:
+            if isinstance(model, SegModel):
+                return model.ctx.text_region_boxes(regions, 1, 0.00001, 1.0)
+            return host_text_region_boxes(regions)
+        finally:
+            session.close()
+
+    def get_slopes(self, textlines: np.ndarray, boxes):
+        """One deskew slope per box (``get_slopes``: main.py:1728-1748) on the textline model's handle."""
+        model, session = start_new_session_and_model(self.model_textline_dir, **self.kw)
+        try:
+            if not isinstance(model, SegModel):
+                raise RuntimeError("get_slopes needs a library handle (SegModel.ctx): there is no CPU fallback")
+            return get_slopes(textlines, boxes, model.ctx)
+        finally:
+            session.close()
+
+    def run_with_slopes(self, image_u8: np.ndarray):
+        """``run()`` and the step the reference takes next (main.py:2080, 2111): the text-region boxes and one deskew slope per box.
+        Returns run()'s four values plus (boxes, slopes), also kept as ``self.boxes`` / ``self.slopes`` like the reference; both are []
+        when the textline model did not run."""
+        page_mask, regions, textlines, page_coord = self.run(image_u8)
+        self.boxes, self.slopes = [], []
+        if textlines is not None:
+            self.boxes = self.get_text_region_boxes(regions)
+            self.slopes = self.get_slopes(textlines, self.boxes)
+        return page_mask, regions, textlines, page_coord, self.boxes, self.slopes
 
     def _run_resident(self):
         """run()'s three stages with the stored page uploaded ONCE and kept in device memory for all of them (run() hands the same
