@@ -355,8 +355,9 @@ int sbbseg_run_page(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline
  * cv2.getRotationMatrix2D((S/2, S/2), angle, 1.0) + cv2.warpAffine INTER_CUBIC / BORDER_REPLICATE), binarised (!= 0,
  * main.py:1642) and summed along its rows (main.py:1546).  counts: host int32 [n_angles][S].  One launch for the sweep.
  * matrices (optional, [n_angles][6] forward 2 x 3 maps) overrides angles_deg; otherwise sbbseg_rotation_matrix is used.
- * The 1-D peak logic on the profiles (scipy gaussian_filter1d / find_peaks, main.py:1545-1599) stays on the host
- * (stages.return_deskew_slope).  [EXT, unpinned]: OpenCV 4.5.1's warpAffine arithmetic is restated (fixed-point source
+ * The 1-D peak logic on the profiles (scipy gaussian_filter1d / find_peaks, main.py:1545-1599) of this ONE-region call stays on the
+ * host (stages.return_deskew_slope); for all boxes of a page it runs on the device (sbbseg_profile_statistics_dev,
+ * sbbseg_region_deskew_slopes below).  [EXT, unpinned]: OpenCV 4.5.1's warpAffine arithmetic is restated (fixed-point source
  * coordinates with 5 fractional bits, float bicubic table with A = -0.75, replicated borders); cv2 is not available to
  * pin it against. */
 int sbbseg_deskew_side(int H, int W, int* side);
@@ -378,6 +379,46 @@ int sbbseg_region_deskew_profiles_dev(sbbseg_ctx* c, const void* d_textline_hw, 
                                       int erode_iterations, const double* angles_deg, int n_angles, int32_t* counts, int64_t* offsets);
 int sbbseg_region_deskew_profiles(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
                                   int erode_iterations, const double* angles_deg, int n_angles, int32_t* counts, int64_t* offsets);
+
+/* ---- stage glue: the 1-D statistic of the deskew search and the angle selection (get_standard_deviation_of_summed_textline_patch_along_width,
+ * main.py:1545-1599; the angle loops of return_deskew_slope, main.py:1630-1716).  Per row profile y (n samples): z = gaussian_filter1d(y),
+ * the maxima of z and the minima of the padded, flipped profile (y between 10 zeros, max - that between 10 more zeros, smoothed,
+ * find_peaks(height = 0), positions - 20 with numpy's indexing: a negative one wraps, one >= n is the reference's IndexError), the "deep"
+ * minima z < L - L / multiplier with L = mean(maxima > 10), and np.std(z).  Every float64 value equals scipy's / numpy's BIT FOR BIT
+ * (multiplies and adds rounded one by one in correlate1d's order, numpy's pairwise sums, correctly rounded divide and sqrt), because the
+ * winner is an arg max in which equal maxima occur and find_peaks compares exactly.
+ *   counts / offsets    packed as sbbseg_region_deskew_profiles packs them: region r holds [n_angles][S_r] int32 from offsets[r]; offsets
+ *                       has n_regions + 1 entries; S_r = 1 .. 32767
+ *   weights, radius     the half Gaussian kernel weights[0 .. radius], weights[j] = normalised weight at distance j, computed by the CALLER
+ *                       as scipy.ndimage does (numpy's exp: libm's differs in the last bit for some sigma).  weights = NULL: the built-in
+ *                       table of sigma = 2 (radius 8), the only sigma the reference uses (main.py:1737); `radius` is then ignored
+ *   multiplier          the reference passes 20.3 (main.py:1644)
+ *   spread  [n_regions][n_angles]   np.std(z) where state is 0, else 0
+ *   state   [n_regions][n_angles]   0 appended; 1 skipped (no deep minimum: NOT appended); 2 exception (the IndexError: appended, spread 0)
+ *   winner  [n_regions]             index into the angle array: the first maximum of the appended spreads, whose POSITION in the shortened
+ *                                   list indexes the full angle array (main.py:1655-1665); -1: nothing appended (the slope is then 0)
+ *   smooth  (host entry, optional)  z of every profile, packed like counts
+ * sbbseg_profile_statistics_host runs serially on the CPU and needs no handle (it is what holds the arithmetic to scipy on a machine
+ * without a GPU); sbbseg_profile_statistics_dev takes the counts in DEVICE memory (offsets, weights and the outputs are host arrays; NULL
+ * outputs are skipped) and runs all profiles in one launch (a second one for S_r > 2048, whose smoothed profiles do not fit in LDS) plus the
+ * selection.  Both give the same bits.  n_angles < 1, radius < 0, bad offsets, a null handle: status + sbbseg_last_error(). */
+int sbbseg_profile_statistics_host(const int32_t* counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights, int radius,
+                                   double multiplier, double* spread, uint8_t* state, int32_t* winner, double* smooth);
+int sbbseg_profile_statistics_dev(sbbseg_ctx* c, const void* d_counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights,
+                                  int radius, double multiplier, double* spread, uint8_t* state, int32_t* winner);
+/* The angles of return_deskew_slope's two sweeps, bit for bit numpy's: sweep 0 = np.linspace(-25, 25, 80) (main.py:1622), sweep 1 =
+ * np.linspace(-90, -50, 30) (main.py:1670).  capacity = 0: only *n_angles is set.  Host only. */
+int sbbseg_deskew_sweep_angles(int sweep, double* angles_deg, int capacity, int* n_angles);
+/* The whole slope half of do_work_of_slopes (main.py:1728-1748) for a page: crop, erode and the sweep of 80 angles for every box
+ * (sbbseg_region_deskew_profiles' launches), statistic and selection on the device, ONE small copy of the winners; then the same with the 30
+ * angles of the second sweep for the boxes whose first answer is steeper than 15 degrees only (main.py:1669-1670); then the reference's
+ * clean-up (|slope| > 120.5 -> 0; nothing appended -> 0).  slopes: host double [n_boxes].  The row counts never leave the device.
+ * weights / radius as above (NULL: sigma = 2).  Errors as sbbseg_region_deskew_profiles (the message names the box); n_boxes = 0 is
+ * success.  Synchronises the stream. */
+int sbbseg_region_deskew_slopes_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
+                                    int erode_iterations, const double* weights, int radius, double* slopes);
+int sbbseg_region_deskew_slopes(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
+                                int erode_iterations, const double* weights, int radius, double* slopes);
 
 /* ---- multi-GPU: one process per GPU, one handle per process; tiles (sbbseg_segment_tile_range_dev) or whole
  * pages (sbbseg_segment_pages_dev) are sharded by the caller, and the ONE data-path collective -- the all-gather of the u8

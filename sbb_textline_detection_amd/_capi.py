@@ -35,6 +35,7 @@ EXPORTS = [
     "sbbseg_set_owned_regions", "sbbseg_owned_region_info", "sbbseg_op_executed", "sbbseg_debug_owned_range", "sbbseg_debug_region_rows",
     "sbbseg_debug_poison_activations",
     "sbbseg_text_region_boxes_dev", "sbbseg_text_region_boxes", "sbbseg_region_deskew_profiles_dev", "sbbseg_region_deskew_profiles",
+    "sbbseg_profile_statistics_host", "sbbseg_profile_statistics_dev", "sbbseg_deskew_sweep_angles", "sbbseg_region_deskew_slopes_dev", "sbbseg_region_deskew_slopes",
 ]
 
 
@@ -159,6 +160,11 @@ def load_library(path: Optional[str] = None):
         "sbbseg_text_region_boxes": [vp, vp, i32, i32, i32, C.c_double, C.c_double, vp, i32, C.POINTER(C.c_int)],
         "sbbseg_region_deskew_profiles_dev": [vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp],
         "sbbseg_region_deskew_profiles": [vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp],
+        "sbbseg_profile_statistics_host": [vp, vp, i32, i32, vp, i32, C.c_double, vp, vp, vp, vp],
+        "sbbseg_profile_statistics_dev": [vp, vp, vp, i32, i32, vp, i32, C.c_double, vp, vp, vp],
+        "sbbseg_deskew_sweep_angles": [i32, vp, i32, C.POINTER(C.c_int)],
+        "sbbseg_region_deskew_slopes_dev": [vp, vp, i32, i32, vp, i32, i32, vp, i32, vp],
+        "sbbseg_region_deskew_slopes": [vp, vp, i32, i32, vp, i32, i32, vp, i32, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -601,6 +607,38 @@ class Context:
         return self._region_profiles_call(self.lib.sbbseg_region_deskew_profiles, _ptr(plane), plane.shape[0], plane.shape[1], boxes, angles_deg,
                                           erode_iterations)
 
+    def profile_statistics_dev(self, d_counts: int, offsets, n_angles: int, weights=None, multiplier: float = 20.3):
+        """The 1-D statistic of the deskew search for every (region, angle) profile of a sweep whose packed int32 counts are in device memory,
+        and the winner per region: (spread float64 [n_regions, n_angles], state uint8 [n_regions, n_angles], winner int32 [n_regions]) --
+        see sbbseg.h.  ``weights``: ``gaussian_weights(sigma)``; None = the library's table for sigma = 2."""
+        offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        n = offsets.shape[0] - 1
+        w = None if weights is None else np.ascontiguousarray(weights, np.float64).reshape(-1)
+        spread, state, winner = np.zeros((n, n_angles), np.float64), np.zeros((n, n_angles), np.uint8), np.zeros(n, np.int32)
+        check(self.lib.sbbseg_profile_statistics_dev(self.h, C.c_void_p(d_counts), _ptr(offsets), n, int(n_angles), _ptr(w), 0 if w is None else w.shape[0] - 1,
+                                                     float(multiplier), _ptr(spread), _ptr(state), _ptr(winner)), "sbbseg_profile_statistics_dev")
+        return spread, state, winner
+
+    def _slopes_call(self, fn, src, H, W, boxes, erode_iterations, weights):
+        boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        w = None if weights is None else np.ascontiguousarray(weights, np.float64).reshape(-1)
+        slopes = np.zeros(boxes.shape[0], np.float64)
+        check(fn(self.h, src, int(H), int(W), _ptr(boxes), boxes.shape[0], int(erode_iterations), _ptr(w), 0 if w is None else w.shape[0] - 1, _ptr(slopes)),
+              "sbbseg_region_deskew_slopes")
+        return [float(v) for v in slopes]
+
+    def region_deskew_slopes_dev(self, d_textlines: int, H: int, W: int, boxes, erode_iterations: int = 2, weights=None):
+        """The slope half of do_work_of_slopes (main.py:1728-1748) for every box of a device textline plane: a list of float.  Sweeps,
+        statistic and angle selection run on the device; only the winners are copied back (sbbseg.h)."""
+        return self._slopes_call(self.lib.sbbseg_region_deskew_slopes_dev, C.c_void_p(d_textlines), H, W, boxes, erode_iterations, weights)
+
+    def region_deskew_slopes(self, textlines: np.ndarray, boxes, erode_iterations: int = 2, weights=None):
+        """The same from a host textline map uint8 [H, W] (uploaded once per call)."""
+        plane = np.ascontiguousarray(textlines, np.uint8)
+        if plane.ndim != 2:
+            raise ValueError("region_deskew_slopes expects a uint8 plane [H, W]")
+        return self._slopes_call(self.lib.sbbseg_region_deskew_slopes, _ptr(plane), plane.shape[0], plane.shape[1], boxes, erode_iterations, weights)
+
     def page_box_dev(self, d_mask: int, H: int, W: int):
         """((x, y, w, h), pixels) of the largest component of the dilated mask (main.py:394-404); pixels == 0: empty mask."""
         box = np.zeros(4, np.int32)
@@ -778,6 +816,40 @@ def region_deskew_offsets(boxes, n_angles: int, H: int, W: int) -> np.ndarray:
     check(load_library().sbbseg_region_deskew_profiles_dev(None, None, int(H), int(W), _ptr(boxes), boxes.shape[0], 0, None, int(n_angles), None,
                                                            _ptr(offsets)), "sbbseg_region_deskew_profiles")
     return offsets
+
+
+def gaussian_weights(sigma: float, truncate: float = 4.0) -> np.ndarray:
+    """The half kernel weights[0 .. radius] of ``scipy.ndimage.gaussian_filter1d(., sigma)``, computed exactly as scipy's
+    ``_gaussian_kernel1d`` does (numpy's exp, divided by its numpy sum): what the library's profile statistic takes from its caller."""
+    sd = float(sigma)
+    radius = int(truncate * sd + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sd * sd) * x ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[radius:], np.float64)
+
+
+def profile_statistics_host(counts, offsets, n_angles: int, weights=None, multiplier: float = 20.3, want_smooth: bool = False):
+    """``Context.profile_statistics_dev`` on the CPU (serial, no handle, no GPU): the same bits.  ``counts``: packed int32 host array.
+    With ``want_smooth`` a fourth value: the smoothed profiles, packed like ``counts``."""
+    counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+    offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+    n = offsets.shape[0] - 1
+    w = None if weights is None else np.ascontiguousarray(weights, np.float64).reshape(-1)
+    spread, state, winner = np.zeros((n, n_angles), np.float64), np.zeros((n, n_angles), np.uint8), np.zeros(n, np.int32)
+    smooth = np.zeros(counts.shape[0], np.float64) if want_smooth else None
+    check(load_library().sbbseg_profile_statistics_host(_ptr(counts), _ptr(offsets), n, int(n_angles), _ptr(w), 0 if w is None else w.shape[0] - 1,
+                                                        float(multiplier), _ptr(spread), _ptr(state), _ptr(winner), _ptr(smooth)),
+          "sbbseg_profile_statistics_host")
+    return (spread, state, winner, smooth) if want_smooth else (spread, state, winner)
+
+
+def deskew_sweep_angles(sweep: int) -> np.ndarray:
+    """The library's angles of return_deskew_slope's sweep 0 (80 in [-25, 25]) or 1 (30 in [-90, -50]): np.linspace's values."""
+    n = C.c_int(0)
+    out = np.zeros(80, np.float64)
+    check(load_library().sbbseg_deskew_sweep_angles(int(sweep), _ptr(out), 80, C.byref(n)), "sbbseg_deskew_sweep_angles")
+    return out[:n.value].copy()
 
 
 def rotation_matrix(cx: float, cy: float, angle_deg: float) -> np.ndarray:

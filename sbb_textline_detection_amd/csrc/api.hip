@@ -24,6 +24,7 @@
 
 #include "internal.h"
 #include "region.h"
+#include "profile_stat.h"
 
 using namespace sbbseg;
 
@@ -272,6 +273,7 @@ struct sbbseg_ctx {
     int* d_cc_bg = nullptr; size_t cc_bg_cap = 0;        // two int planes: labels of the complement, border flags (sbbseg_text_region_boxes_dev)
     int* d_cc_roots = nullptr; size_t cc_roots_cap = 0;  // parentless roots, 6 ints each
     void* d_rdk = nullptr; size_t rdk_cap = 0;           // sbbseg_region_deskew_profiles_dev: maps | table | geometry | crops | counts
+    void* d_pstat = nullptr; size_t pstat_cap = 0;       // sbbseg_profile_statistics_dev: weights | regions | spread | winner | state | workspace
     // profiling
     bool profiling = false;
     int conv_variant = 0;
@@ -935,7 +937,7 @@ int sbbseg_destroy(sbbseg_ctx* c)
     (void)hipFree(c->d_page); (void)hipFree(c->d_page_labels); (void)hipFree(c->d_page_labels3); (void)hipFree(c->d_tile_labels);
     (void)hipFree(c->d_own_x); (void)hipFree(c->d_own_y); (void)hipFree(c->d_map); (void)hipFree(c->d_wmap);
     (void)hipFree(c->d_deskew);
-    (void)hipFree(c->d_cc_bg); (void)hipFree(c->d_cc_roots); (void)hipFree(c->d_rdk);
+    (void)hipFree(c->d_cc_bg); (void)hipFree(c->d_cc_roots); (void)hipFree(c->d_rdk); (void)hipFree(c->d_pstat);
     for (int lane = 0; lane < 2; ++lane)
         for (int L = 0; L < kRegionMaxLevels; ++L) (void)hipFree(c->d_rtab[lane][L]);
     (void)hipFree(c->d_run_page); (void)hipFree(c->d_run_mask); (void)hipFree(c->d_run_a); (void)hipFree(c->d_run_b);
@@ -3432,13 +3434,16 @@ int sbbseg_deskew_profiles(sbbseg_ctx* c, const uint8_t* mask_hw, int H, int W, 
     API_END
 }
 
-// The same sweep for every text-region box of a page in one call (do_work_of_slopes, main.py:1728-1738): crop_image_inside_box,
-// cv2.erode(crop, 5x5, iterations) on the CROP, return_deskew_slope's square and rotations.  offsets[r] = first int of region r in
-// `counts` ([n_angles][S_r]), offsets[n_boxes] = the total; counts == NULL: only the offsets are computed (to size the buffer).
-int sbbseg_region_deskew_profiles_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
-                                      int erode_iterations, const double* angles_deg, int n_angles, int32_t* counts, int64_t* offsets)
+// The same sweep for every text-region box of a page (do_work_of_slopes, main.py:1728-1738): crop_image_inside_box, cv2.erode(crop, 5x5,
+// iterations) on the CROP, return_deskew_slope's square and rotations.  offsets[r] = first int of region r in the packed counts
+// ([n_angles][S_r]), offsets[n_boxes] = the total.  size_only: only the offsets are computed (needs no handle).  Otherwise the sweep is
+// queued on the stream and *d_counts points at the packed counts in the handle's buffer: they STAY on the device.  `head` is the host
+// staging buffer of the tables: the caller keeps it alive until it has synchronised the stream.
+static int region_sweep(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                        const double* angles_deg, int n_angles, int64_t* offsets, bool size_only, std::vector<unsigned char>& head,
+                        const int32_t** d_counts)
 {
-    API_BEGIN
+    *d_counts = nullptr;
     REQUIRE(H > 0 && W > 0 && n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && offsets && n_angles >= 1 && n_angles <= 4096 &&
                 erode_iterations >= 0 && erode_iterations <= 64, "bad arguments");
     alloc_check();
@@ -3466,14 +3471,14 @@ int sbbseg_region_deskew_profiles_dev(sbbseg_ctx* c, const void* d_textline_hw, 
         REQUIRE(total_counts < (1ll << 31) && total_blocks < (1ll << 31), "too much work for one sweep (%d boxes, %d angles): split the boxes", n_boxes, n_angles);
     }
     offsets[n_boxes] = total_counts;
-    if (!counts || n_boxes == 0) return 0;                         // (the size query needs no handle)
+    if (size_only || n_boxes == 0) return 0;                       // (the size query needs no handle)
     if (check_ready(c)) return 1;
     REQUIRE(d_textline_hw && angles_deg, "bad arguments");
     // head of the device buffer, built on the host and copied in one piece: inverse maps | bicubic table | geometry
     const size_t minv_bytes = (size_t)n_boxes * n_angles * 6 * sizeof(double), tab_bytes = 128 * sizeof(float);
     const size_t geom_off = minv_bytes + tab_bytes, head_bytes = (geom_off + (size_t)n_boxes * sizeof(DeskewRegion) + 15) & ~(size_t)15;
     const size_t pix_bytes = ((size_t)total_pix + 15) & ~(size_t)15;
-    std::vector<unsigned char> head(head_bytes);
+    head.assign(head_bytes, 0);
     double* minv = (double*)head.data();
     for (int r = 0; r < n_boxes; ++r)
         for (int a = 0; a < n_angles; ++a) {
@@ -3495,7 +3500,20 @@ int sbbseg_region_deskew_profiles_dev(sbbseg_ctx* c, const void* d_textline_hw, 
     HIPCHK(hipMemcpyAsync(d, head.data(), head_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(launch_region_deskew_crops(p, c->stream));
     HIPCHK(launch_region_deskew_profiles(p, c->stream));
-    HIPCHK(hipMemcpyAsync(counts, p.counts, (size_t)total_counts * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    *d_counts = p.counts;
+    return 0;
+}
+
+// counts == NULL: only the offsets are computed (to size the buffer).
+int sbbseg_region_deskew_profiles_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
+                                      int erode_iterations, const double* angles_deg, int n_angles, int32_t* counts, int64_t* offsets)
+{
+    API_BEGIN
+    std::vector<unsigned char> head;
+    const int32_t* d_counts = nullptr;
+    if (region_sweep(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, angles_deg, n_angles, offsets, !counts, head, &d_counts)) return 1;
+    if (!d_counts) return 0;
+    HIPCHK(hipMemcpyAsync(counts, d_counts, (size_t)offsets[n_boxes] * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffer lives until here)
     return 0;
     API_END
@@ -3514,6 +3532,191 @@ int sbbseg_region_deskew_profiles(sbbseg_ctx* c, const uint8_t* textline_hw, int
         HIPCHK(hipMemcpyAsync(c->d_morph_b, textline_hw, pix, hipMemcpyHostToDevice, c->stream));
     }
     return sbbseg_region_deskew_profiles_dev(c, (counts && n_boxes > 0) ? c->d_morph_b : nullptr, H, W, boxes_xywh, n_boxes, erode_iterations, angles_deg, n_angles, counts, offsets);
+    API_END
+}
+
+// ---- stage glue: the 1-D statistic of the deskew search and the angle selection (main.py:1545-1599, 1630-1716; profile_stat.h) ----
+static const double kSigma2Weights[kSigma2Radius + 1] = SBBSEG_SIGMA2_WEIGHTS;
+
+// np.linspace(start, stop, num) bit for bit: i * ((stop - start) / (num - 1)) + start, the last one = stop
+static void linspace(double start, double stop, int num, double* out)
+{
+#pragma clang fp contract(off)
+    const double step = (stop - start) / (double)(num - 1);
+    for (int i = 0; i < num; ++i) {
+        const double t = (double)i * step;
+        out[i] = t + start;
+    }
+    out[num - 1] = stop;
+}
+
+int sbbseg_deskew_sweep_angles(int sweep, double* angles_deg, int capacity, int* n_angles)
+{
+    API_BEGIN
+    REQUIRE((sweep == 0 || sweep == 1) && n_angles && (angles_deg || capacity == 0) && capacity >= 0, "bad arguments");
+    const int n = sweep == 0 ? 80 : 30;                             // main.py:1622, 1670
+    *n_angles = n;
+    if (capacity == 0) return 0;
+    REQUIRE(capacity >= n, "room for %d angles, the sweep has %d", capacity, n);
+    if (sweep == 0) linspace(-25.0, 25.0, n, angles_deg);
+    else linspace(-90.0, -50.0, n, angles_deg);
+    return 0;
+    API_END
+}
+
+static int check_profile_tables(const int64_t* offsets, int n_regions, int n_angles, const double* weights, int radius)
+{
+    REQUIRE(n_regions >= 0 && n_regions <= (1 << 20) && (offsets || n_regions == 0), "bad arguments");
+    REQUIRE(n_angles >= 1 && n_angles <= 4096, "n_angles %d out of range (1 .. 4096)", n_angles);
+    REQUIRE(radius >= 0 && radius <= (1 << 16), "radius %d out of range (0 .. 65536)", radius);
+    for (int r = 0; r < n_regions; ++r) {
+        const int64_t len = offsets[r + 1] - offsets[r];
+        REQUIRE(offsets[r] >= 0 && len >= n_angles && len % n_angles == 0 && len / n_angles <= 32767 && offsets[r + 1] < (1ll << 31),
+                "region %d: offsets %lld .. %lld do not hold %d profiles of 1 .. 32767 samples", r, (long long)offsets[r], (long long)offsets[r + 1], n_angles);
+    }
+    (void)weights;
+    return 0;
+}
+
+int sbbseg_profile_statistics_host(const int32_t* counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights, int radius,
+                                   double multiplier, double* spread, uint8_t* state, int32_t* winner, double* smooth)
+{
+    API_BEGIN
+    if (check_profile_tables(offsets, n_regions, n_angles, weights, radius)) return 1;
+    REQUIRE((counts && spread && state && winner) || n_regions == 0, "bad arguments");
+    alloc_check();
+    if (!weights) { weights = kSigma2Weights; radius = kSigma2Radius; }
+    std::vector<double> z, g;
+    PairwiseStack stack;
+    for (int r = 0; r < n_regions; ++r) {
+        const int S = (int)((offsets[r + 1] - offsets[r]) / n_angles);
+        z.resize((size_t)S); g.resize((size_t)S + kProfileFlipExtra);
+        for (int a = 0; a < n_angles; ++a) {
+            const size_t k = (size_t)r * n_angles + a;
+            const size_t at = (size_t)offsets[r] + (size_t)a * S;
+            state[k] = (uint8_t)profile_statistic_serial(counts + at, S, weights, radius, multiplier, z.data(), g.data(), &stack, &spread[k]);
+            if (smooth) memcpy(smooth + at, z.data(), (size_t)S * sizeof(double));
+        }
+        winner[r] = sweep_winner(spread + (size_t)r * n_angles, state + (size_t)r * n_angles, n_angles);
+    }
+    return 0;
+    API_END
+}
+
+// queues the statistic of a sweep whose counts are in device memory; *out holds the device pointers of the results (in c->d_pstat)
+static int profile_stats_queue(sbbseg_ctx* c, const int32_t* d_counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights,
+                               int radius, double multiplier, std::vector<unsigned char>& head, ProfileStatParams* out)
+{
+    if (!weights) { weights = kSigma2Weights; radius = kSigma2Radius; }
+    const size_t np = (size_t)n_regions * n_angles;
+    const size_t w_bytes = (size_t)(radius + 1) * sizeof(double), head_bytes = w_bytes + (size_t)n_regions * sizeof(ProfileRegion);
+    head.assign(head_bytes, 0);
+    memcpy(head.data(), weights, w_bytes);
+    ProfileRegion* reg = (ProfileRegion*)(head.data() + w_bytes);
+    long long ws_doubles = 0;
+    for (int r = 0; r < n_regions; ++r) {
+        reg[r].count_off = offsets[r];
+        reg[r].S = (int)((offsets[r + 1] - offsets[r]) / n_angles);
+        reg[r].ws_off = ws_doubles;
+        if (reg[r].S > kProfileLdsSamples) ws_doubles += (long long)n_angles * (2ll * reg[r].S + kProfileFlipExtra);
+    }
+    const size_t spread_off = head_bytes, winner_off = spread_off + np * sizeof(double), state_off = winner_off + (size_t)n_regions * sizeof(int32_t);
+    const size_t ws_off = (state_off + np + 15) & ~(size_t)15;
+    if (ensure(c, &c->d_pstat, &c->pstat_cap, ws_off + (size_t)ws_doubles * sizeof(double))) return 1;
+    unsigned char* d = (unsigned char*)c->d_pstat;
+    ProfileStatParams p;
+    p.counts = d_counts; p.regions = (const ProfileRegion*)(d + w_bytes); p.n_regions = n_regions; p.n_angles = n_angles;
+    p.weights = (const double*)d; p.radius = radius; p.multiplier = multiplier;
+    p.workspace = (double*)(d + ws_off); p.spread = (double*)(d + spread_off); p.state = d + state_off; p.winner = (int32_t*)(d + winner_off);
+    HIPCHK(hipMemcpyAsync(d, head.data(), head_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_profile_statistics(p, ws_doubles > 0, c->stream));
+    *out = p;
+    return 0;
+}
+
+int sbbseg_profile_statistics_dev(sbbseg_ctx* c, const void* d_counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights,
+                                  int radius, double multiplier, double* spread, uint8_t* state, int32_t* winner)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    if (check_profile_tables(offsets, n_regions, n_angles, weights, radius)) return 1;
+    if (n_regions == 0) return 0;
+    REQUIRE(d_counts, "bad arguments");
+    alloc_check();
+    std::vector<unsigned char> head;
+    ProfileStatParams p;
+    if (profile_stats_queue(c, (const int32_t*)d_counts, offsets, n_regions, n_angles, weights, radius, multiplier, head, &p)) return 1;
+    const size_t np = (size_t)n_regions * n_angles;
+    if (spread) HIPCHK(hipMemcpyAsync(spread, p.spread, np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (state) HIPCHK(hipMemcpyAsync(state, p.state, np, hipMemcpyDeviceToHost, c->stream));
+    if (winner) HIPCHK(hipMemcpyAsync(winner, p.winner, (size_t)n_regions * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffer lives until here)
+    return 0;
+    API_END
+}
+
+// one sweep of all `boxes`: rotate-and-project, statistic, selection; the winners come back, the counts do not
+static int slopes_sweep(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                        const double* angles, int n_angles, const double* weights, int radius, std::vector<int32_t>& winner)
+{
+    std::vector<int64_t> offsets((size_t)n_boxes + 1);
+    std::vector<unsigned char> head_sweep, head_stat;
+    const int32_t* d_counts = nullptr;
+    if (region_sweep(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, angles, n_angles, offsets.data(), false, head_sweep, &d_counts)) return 1;
+    ProfileStatParams p;
+    if (profile_stats_queue(c, d_counts, offsets.data(), n_boxes, n_angles, weights, radius, 20.3, head_stat, &p)) return 1;      // main.py:1644
+    winner.resize((size_t)n_boxes);
+    HIPCHK(hipMemcpyAsync(winner.data(), p.winner, (size_t)n_boxes * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffers live until here)
+    return 0;
+}
+
+int sbbseg_region_deskew_slopes_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
+                                    int erode_iterations, const double* weights, int radius, double* slopes)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    REQUIRE(H > 0 && W > 0 && n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && (slopes || n_boxes == 0), "bad arguments");
+    REQUIRE(radius >= 0 && radius <= (1 << 16), "radius %d out of range (0 .. 65536)", radius);
+    if (n_boxes == 0) return 0;
+    REQUIRE(d_textline_hw, "bad arguments");
+    alloc_check();
+    double first[80], second[30];
+    linspace(-25.0, 25.0, 80, first);                               // main.py:1622
+    linspace(-90.0, -50.0, 30, second);                             // main.py:1670
+    std::vector<int32_t> winner;
+    if (slopes_sweep(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, first, 80, weights, radius, winner)) return 1;
+    std::vector<int32_t> steep, steep_boxes;
+    for (int r = 0; r < n_boxes; ++r) {
+        slopes[r] = winner[r] < 0 ? 0.0 : first[winner[r]];
+        if (std::fabs(slopes[r]) > 15.0) {                          // main.py:1669-1670
+            steep.push_back(r);
+            steep_boxes.insert(steep_boxes.end(), boxes_xywh + (size_t)r * 4, boxes_xywh + (size_t)r * 4 + 4);
+        }
+    }
+    if (!steep.empty()) {
+        if (slopes_sweep(c, d_textline_hw, H, W, steep_boxes.data(), (int)steep.size(), erode_iterations, second, 30, weights, radius, winner)) return 1;
+        for (size_t k = 0; k < steep.size(); ++k) slopes[steep[k]] = winner[k] < 0 ? 0.0 : second[winner[k]];
+    }
+    for (int r = 0; r < n_boxes; ++r)
+        if (std::fabs(slopes[r]) > 120.5) slopes[r] = 0.0;          // main.py:1746-1747
+    return 0;
+    API_END
+}
+
+int sbbseg_region_deskew_slopes(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
+                                int erode_iterations, const double* weights, int radius, double* slopes)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    REQUIRE(H > 0 && W > 0 && n_boxes >= 0, "bad arguments");
+    if (n_boxes > 0) {
+        REQUIRE(textline_hw, "bad arguments");
+        const size_t pix = (size_t)H * W;
+        if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
+        HIPCHK(hipMemcpyAsync(c->d_morph_b, textline_hw, pix, hipMemcpyHostToDevice, c->stream));
+    }
+    return sbbseg_region_deskew_slopes_dev(c, n_boxes > 0 ? c->d_morph_b : nullptr, H, W, boxes_xywh, n_boxes, erode_iterations, weights, radius, slopes);
     API_END
 }
 

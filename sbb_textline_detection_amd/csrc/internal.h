@@ -373,6 +373,26 @@ struct RegionDeskewParams {
 };
 hipError_t launch_region_deskew_crops(const RegionDeskewParams& p, hipStream_t s);
 hipError_t launch_region_deskew_profiles(const RegionDeskewParams& p, hipStream_t s);
+// the 1-D statistic of every (region, angle) profile of a sweep and the winner per region (profile_stats.hip, profile_stat.h)
+constexpr int kProfileLdsSamples = 2048;  // longest profile whose smoothed forms stay in LDS; longer ones use ProfileStatParams::workspace
+struct ProfileRegion {
+    long long count_off;      // first int of the region's [n_angles][S] counts
+    long long ws_off;         // S > kProfileLdsSamples: first double of the region's [n_angles][2 S + 40] workspace
+    int S, pad;
+};
+struct ProfileStatParams {
+    const int32_t* counts;    // packed row counts (device)
+    const ProfileRegion* regions;
+    int n_regions, n_angles;
+    const double* weights;    // [radius + 1] half Gaussian kernel
+    int radius;
+    double multiplier;
+    double* workspace;
+    double* spread;           // [n_regions][n_angles]
+    uint8_t* state;           // [n_regions][n_angles]: 0 appended, 1 skipped, 2 exception
+    int32_t* winner;          // [n_regions]
+};
+hipError_t launch_profile_statistics(const ProfileStatParams& p, bool any_long, hipStream_t s);
 hipError_t launch_replicate3(const uint8_t* src, uint8_t* dst, size_t n, hipStream_t s);
 hipError_t launch_to_f32(const void* src, float* dst, size_t n, int precision, hipStream_t s);
 hipError_t launch_deskew_profiles(const uint8_t* mask, int H, int W, int S, int top, int left, const double* minv, const float* cubic,

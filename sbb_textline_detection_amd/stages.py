@@ -10,15 +10,15 @@ it that section 8(f) ranks next, with the reference's names and call pattern:
     extract_page   (glue part)      main.py:394-426   border mask -> dilate x 6 -> largest blob -> box -> crop (device)
     erode x 3 / dilate x 4          main.py:2074-2075 on the layout map (device)
 
-    return_deskew_slope             main.py:1601-1718 the per-region deskew search: rotate-and-project on the device (one launch
+    return_deskew_slope             main.py:1601-1718 the deskew search of ONE region: rotate-and-project on the device (one launch
                                                       per sweep), the 1-D peak logic on the host with the reference's own scipy calls
 
     get_text_region_contours_and_boxes  main.py:456-480   the BOXES of the text regions (``self.boxes``), on the device
     do_work_of_slopes (slope half)  main.py:1721-1748 one deskew slope per box: crop, erode x 2 and the rotate-and-project of ALL boxes in
-                                                      one batched sweep on the device (``get_slopes``), peak logic per region on the host
+                                                      one batched sweep on the device (``get_slopes``), the peak logic (Gaussian, find_peaks,
+                                                      std) and the angle selection on the device too (``statistics="host"``: scipy)
 
-Out of scope: textline_contours_postprocessing, the polygons, the reading order and PAGE-XML; a device-side Gaussian / find_peaks /
-std (the host half of the deskew search stays the reference's own scipy calls).
+Out of scope: textline_contours_postprocessing, the polygons, the reading order and PAGE-XML.
 """
 from __future__ import annotations
 
@@ -197,12 +197,18 @@ def return_deskew_slope(img_patch: np.ndarray, sigma_des: float, ctx=None) -> fl
     return ang
 
 
-def get_slopes(textline_mask: np.ndarray, boxes, ctx=None, sigma_des: float = 2):
+def get_slopes(textline_mask: np.ndarray, boxes, ctx=None, sigma_des: float = 2, statistics: str = "device"):
     """The slope half of ``do_work_of_slopes`` (main.py:1728-1748) for all boxes of a page: a list of float, one per box.  The textline
     map is uploaded once; crop, ``cv2.erode(crop, kernel, iterations=2)`` and the 80 rotations of every box run as ONE batched sweep on the
-    device (``sbbseg_region_deskew_profiles_dev``), a second batched sweep of 30 angles covers only the boxes whose first answer is steeper
-    than 15 degrees (main.py:1669-1670); the peak logic runs per region on the host (``_deskew_sweep``).  Then the reference's clean-up:
-    a failed search (its 999) and |slope| > 120.5 become 0 (main.py:1744-1747).  ``ctx``: a ``_capi.Context`` (any finalized handle)."""
+    device, a second batched sweep of 30 angles covers only the boxes whose first answer is steeper than 15 degrees (main.py:1669-1670).
+    Then the reference's clean-up: a failed search (its 999) and |slope| > 120.5 become 0 (main.py:1744-1747).
+    ``statistics="device"`` (default): the peak logic and the angle selection run on the device too (``sbbseg_region_deskew_slopes_dev``:
+    the row counts never leave it, only the winners come back), with float64 results equal bit for bit to scipy's.  ``statistics="host"``:
+    the row counts are copied back (``sbbseg_region_deskew_profiles_dev``) and the peak logic runs per region on the host with the
+    reference's own scipy calls (``_deskew_sweep``) -- the A/B path and the tests' yardstick; same slopes.
+    ``ctx``: a ``_capi.Context`` (any finalized handle)."""
+    if statistics not in ("device", "host"):
+        raise ValueError("statistics must be 'device' or 'host', not %r" % (statistics,))
     if ctx is None:
         raise RuntimeError("get_slopes needs a library handle (SegModel.ctx): there is no CPU fallback")
     plane = np.ascontiguousarray(textline_mask, np.uint8)
@@ -210,6 +216,10 @@ def get_slopes(textline_mask: np.ndarray, boxes, ctx=None, sigma_des: float = 2)
     if not boxes:
         return []
     d_plane = ctx.stage(plane)
+    if statistics == "device":
+        from . import _capi
+        weights = None if sigma_des == 2 else _capi.gaussian_weights(sigma_des)          # (the library carries the table of sigma = 2)
+        return ctx.region_deskew_slopes_dev(d_plane, plane.shape[0], plane.shape[1], boxes, 2, weights)
 
     def sweep(which, angles):
         found = {}
@@ -391,17 +401,17 @@ class InferenceStages:
         finally:
             session.close()
 
-    def get_slopes(self, textlines: np.ndarray, boxes):
+    def get_slopes(self, textlines: np.ndarray, boxes, statistics: str = "device"):
         """One deskew slope per box (``get_slopes``: main.py:1728-1748) on the textline model's handle."""
         model, session = start_new_session_and_model(self.model_textline_dir, **self.kw)
         try:
             if not isinstance(model, SegModel):
                 raise RuntimeError("get_slopes needs a library handle (SegModel.ctx): there is no CPU fallback")
-            return get_slopes(textlines, boxes, model.ctx)
+            return get_slopes(textlines, boxes, model.ctx, statistics=statistics)
         finally:
             session.close()
 
-    def run_with_slopes(self, image_u8: np.ndarray):
+    def run_with_slopes(self, image_u8: np.ndarray, statistics: str = "device"):
         """``run()`` and the step the reference takes next (main.py:2080, 2111): the text-region boxes and one deskew slope per box.
         Returns run()'s four values plus (boxes, slopes), also kept as ``self.boxes`` / ``self.slopes`` like the reference; both are []
         when the textline model did not run."""
@@ -409,7 +419,7 @@ class InferenceStages:
         self.boxes, self.slopes = [], []
         if textlines is not None:
             self.boxes = self.get_text_region_boxes(regions)
-            self.slopes = self.get_slopes(textlines, self.boxes)
+            self.slopes = self.get_slopes(textlines, self.boxes, statistics=statistics)
         return page_mask, regions, textlines, page_coord, self.boxes, self.slopes
 
     def _run_resident(self):
