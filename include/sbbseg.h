@@ -420,6 +420,42 @@ int sbbseg_region_deskew_slopes_dev(sbbseg_ctx* c, const void* d_textline_hw, in
 int sbbseg_region_deskew_slopes(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
                                 int erode_iterations, const double* weights, int radius, double* slopes);
 
+/* ---- stage glue: the deskewed text-line mask of every text region and the two projections the line splitters open on
+ * (textline_contours_postprocessing, main.py:1472-1487, called by do_work_of_slopes at main.py:1750 with the ERODED crop and the region's
+ * cleaned slope; seperate_lines' row sums, main.py:539; seperate_lines_vertical's column sums, main.py:1020).  Per box [x, y, w, h] of
+ * the u8 textline plane, with slopes[r] in degrees (as sbbseg_region_deskew_slopes returns them):
+ *   a. crop, cv2.erode with the 5x5 kernel `erode_iterations` times on the crop (the reference: 2) -- sbbseg_region_deskew_profiles' crops;
+ *   b. * 255 in uint8, MORPH_OPEN then MORPH_CLOSE with the 5x5 kernel on the crop (erode, dilate, dilate, erode; default border: outside
+ *      pixels never win), computed as one clipped separable min(5) / max(9) / min(5);
+ *   c. rotate_image(mask, slope) (main.py:159-163): getRotationMatrix2D((w / 2, h / 2), slope, 1.0) (integer halves), warpAffine onto the
+ *      crop's own (w, h), INTER_CUBIC, BORDER_REPLICATE.  The source is uint8, so this is OpenCV's FIXED-POINT bicubic path, not the float
+ *      path of the deskew sweep above.  [EXT, unpinned: OpenCV 4.5.1 imgwarp.cpp (initInterTab2D, remapBicubic) restated from memory; cv2 is
+ *      not available to pin it against.]  Source coordinates and table indices: as the deskew sweep (5 fractional bits).  Weights: for every
+ *      (ay, ax) the 16 entries i[r][c] = saturate_cast<short>(float(tab[ay][r] * tab[ax][c]) * 32768), tab = the float bicubic table
+ *      (A = -0.75), rounded to nearest even, clamped to int16; if they do not sum to 32768 the difference is removed from one entry of the
+ *      2 x 2 block at rows / columns {2, 3}: scanned row-major with both candidates starting at (2, 2), a strictly smaller entry replaces
+ *      the minimum candidate, otherwise a strictly larger entry replaces the maximum candidate; a negative difference raises the maximum, a
+ *      positive one lowers the minimum.  Pixel: v = clamp((sum over the 16 taps of src * i + 16384) >> 15, 0, 255) in int32 (arithmetic
+ *      shift), the taps clamped to the crop.  The builder knows of no difference between this and the OpenCV text;
+ *   d. dst = (v != 0) as 0 / 1; rows = dst.sum(axis = 1); cols = dst.sum(axis = 0).  Both projections are returned: the caller picks by
+ *      |slope| > 45 as main.py:1514 does.
+ * Outputs are HOST buffers packed in box order: masks u8 (region r from mask_off[r], h_r x w_r; NULL: the masks stay on the device),
+ * rows int32 (from row_off[r], h_r values), cols int32 (from col_off[r], w_r values).  The three offset arrays have n_boxes + 1 entries
+ * (prefix sums of w * h, h and w; the last entry is the total); the caller sizes the buffers from the same sums.  All boxes run in ten launches whatever n_boxes is (crop + erode 2, morphology
+ * 6, warp + row sums 1, column sums 1).  n_boxes = 0 is success.  A box that leaves the plane, w or h < 1: status + sbbseg_last_error()
+ * (the message names the box).  Shares the deskew sweep's workspace: call order with sbbseg_region_deskew_slopes does not matter.
+ * Synchronises the stream.
+ * sbbseg_region_line_masks_host: no GPU, no handle -- ONE crop (the textline plane cut to the box, h x w), the same statements on the
+ * CPU (csrc/line_mask.h is shared by both); mask may be NULL.  sbbseg_region_line_table: the int16 [32][32][16] weights (host only). */
+int sbbseg_region_line_masks_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                                 const double* slopes, uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off, int64_t* row_off,
+                                 int64_t* col_off);
+int sbbseg_region_line_masks(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                             const double* slopes, uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off, int64_t* row_off, int64_t* col_off);
+int sbbseg_region_line_masks_host(const uint8_t* crop_hw, int h, int w, int erode_iterations, double slope, uint8_t* mask, int32_t* rows,
+                                  int32_t* cols);
+int sbbseg_region_line_table(int16_t* itab, int capacity);
+
 /* ---- multi-GPU: one process per GPU, one handle per process; tiles (sbbseg_segment_tile_range_dev) or whole
  * pages (sbbseg_segment_pages_dev) are sharded by the caller, and the ONE data-path collective -- the all-gather of the u8
  * label maps -- runs on RCCL inside the library, on the handle's stream, so an integrator needs neither PyTorch nor an MPI:
@@ -488,7 +524,7 @@ int sbbseg_debug_region_rows(int extent, int tile, int margin, int n_tiles, int 
  * launch did not write then shows; 0xFF = NaN in every 16-bit format) */
 int sbbseg_debug_poison_activations(sbbseg_ctx* c, int byte_value);
 /* counters: which 0 = how often sbbseg_page_box_dev had to fall back to the host ranking on this handle */
-int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value);      /* which: 0 = exact host contour rankings, 1 = patches run through the plan */
+int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value);      /* which: 0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by sbbseg_region_line_masks(_dev) */
 /* Test hook for the no-abort guarantee: the nth_check-th next internal host-allocation checkpoint throws
  * std::bad_alloc, which every entry point turns into a non-zero status + sbbseg_last_error() instead of
  * terminating the process (main.py:2061-2157 relies on ordinary exceptions).  0 disarms.  Process-global. */

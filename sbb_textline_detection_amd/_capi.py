@@ -36,6 +36,7 @@ EXPORTS = [
     "sbbseg_debug_poison_activations",
     "sbbseg_text_region_boxes_dev", "sbbseg_text_region_boxes", "sbbseg_region_deskew_profiles_dev", "sbbseg_region_deskew_profiles",
     "sbbseg_profile_statistics_host", "sbbseg_profile_statistics_dev", "sbbseg_deskew_sweep_angles", "sbbseg_region_deskew_slopes_dev", "sbbseg_region_deskew_slopes",
+    "sbbseg_region_line_masks_dev", "sbbseg_region_line_masks", "sbbseg_region_line_masks_host", "sbbseg_region_line_table",
 ]
 
 
@@ -165,6 +166,10 @@ def load_library(path: Optional[str] = None):
         "sbbseg_deskew_sweep_angles": [i32, vp, i32, C.POINTER(C.c_int)],
         "sbbseg_region_deskew_slopes_dev": [vp, vp, i32, i32, vp, i32, i32, vp, i32, vp],
         "sbbseg_region_deskew_slopes": [vp, vp, i32, i32, vp, i32, i32, vp, i32, vp],
+        "sbbseg_region_line_masks_dev": [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+        "sbbseg_region_line_masks": [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+        "sbbseg_region_line_masks_host": [vp, i32, i32, i32, C.c_double, vp, vp, vp],
+        "sbbseg_region_line_table": [vp, i32],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -639,6 +644,42 @@ class Context:
             raise ValueError("region_deskew_slopes expects a uint8 plane [H, W]")
         return self._slopes_call(self.lib.sbbseg_region_deskew_slopes, _ptr(plane), plane.shape[0], plane.shape[1], boxes, erode_iterations, weights)
 
+    def _line_masks_call(self, fn, src, H, W, boxes, slopes, erode_iterations, masks):
+        boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        slopes = np.ascontiguousarray(slopes, np.float64).reshape(-1)
+        n = boxes.shape[0]
+        if slopes.shape[0] != n:
+            raise ValueError("one slope per box: %d boxes, %d slopes" % (n, slopes.shape[0]))
+        if n == 0:
+            return []
+        w, h = boxes[:, 2].astype(np.int64).clip(0), boxes[:, 3].astype(np.int64).clip(0)
+        out_masks = np.empty(int((w * h).sum()), np.uint8) if masks else None
+        rows, cols = np.empty(int(h.sum()), np.int32), np.empty(int(w.sum()), np.int32)
+        mo, ro, co = (np.zeros(n + 1, np.int64) for _ in range(3))
+        check(fn(self.h, src, int(H), int(W), _ptr(boxes), n, int(erode_iterations), _ptr(slopes), _ptr(out_masks), _ptr(rows), _ptr(cols),
+                 _ptr(mo), _ptr(ro), _ptr(co)), "sbbseg_region_line_masks")
+        return [(out_masks[mo[r]:mo[r + 1]].reshape(int(h[r]), int(w[r])) if masks else None,
+                 rows[ro[r]:ro[r + 1]].astype(np.int64), cols[co[r]:co[r + 1]].astype(np.int64)) for r in range(n)]
+
+    def region_line_masks_dev(self, d_textlines: int, H: int, W: int, boxes, slopes, erode_iterations: int = 2, masks: bool = True):
+        """The deskewed text-line mask of every box of a device textline plane (textline_contours_postprocessing up to ``dst``,
+        main.py:1472-1487) and its projections, one call: a list of (dst uint8 [h, w] of 0 / 1, or None with ``masks=False``; row sums
+        int64 [h]; column sums int64 [w]) -- see sbbseg.h."""
+        return self._line_masks_call(self.lib.sbbseg_region_line_masks_dev, C.c_void_p(d_textlines), H, W, boxes, slopes, erode_iterations, masks)
+
+    def region_line_masks(self, textlines: np.ndarray, boxes, slopes, erode_iterations: int = 2, masks: bool = True):
+        """The same from a host textline map uint8 [H, W] (uploaded once per call)."""
+        plane = np.ascontiguousarray(textlines, np.uint8)
+        if plane.ndim != 2:
+            raise ValueError("region_line_masks expects a uint8 plane [H, W]")
+        return self._line_masks_call(self.lib.sbbseg_region_line_masks, _ptr(plane), plane.shape[0], plane.shape[1], boxes, slopes, erode_iterations, masks)
+
+    def line_mask_launches(self) -> int:
+        """Kernels the line-mask calls have queued on this handle so far (sbbseg_debug_counter 2)."""
+        v = C.c_int64(0)
+        check(self.lib.sbbseg_debug_counter(self.h, 2, C.byref(v)), "sbbseg_debug_counter")
+        return int(v.value)
+
     def page_box_dev(self, d_mask: int, H: int, W: int):
         """((x, y, w, h), pixels) of the largest component of the dilated mask (main.py:394-404); pixels == 0: empty mask."""
         box = np.zeros(4, np.int32)
@@ -842,6 +883,27 @@ def profile_statistics_host(counts, offsets, n_angles: int, weights=None, multip
                                                         float(multiplier), _ptr(spread), _ptr(state), _ptr(winner), _ptr(smooth)),
           "sbbseg_profile_statistics_host")
     return (spread, state, winner, smooth) if want_smooth else (spread, state, winner)
+
+
+def host_region_line_mask(crop: np.ndarray, slope: float, erode_iterations: int = 2, mask: bool = True):
+    """``Context.region_line_masks_dev`` for ONE box on the CPU (no handle, no GPU; the same statements, csrc/line_mask.h): ``crop`` is the
+    textline plane cut to the box.  Returns (dst uint8 [h, w] or None, row sums int64 [h], column sums int64 [w])."""
+    crop = np.ascontiguousarray(crop, np.uint8)
+    if crop.ndim != 2:
+        raise ValueError("host_region_line_mask expects a uint8 crop [h, w]")
+    h, w = crop.shape
+    dst = np.empty((h, w), np.uint8) if mask else None
+    rows, cols = np.empty(h, np.int32), np.empty(w, np.int32)
+    check(load_library().sbbseg_region_line_masks_host(_ptr(crop), h, w, int(erode_iterations), float(slope), _ptr(dst), _ptr(rows), _ptr(cols)),
+          "sbbseg_region_line_masks_host")
+    return dst, rows.astype(np.int64), cols.astype(np.int64)
+
+
+def region_line_table() -> np.ndarray:
+    """int16 [32][32][4][4]: the fixed-point bicubic weights of the line-mask rotation, indexed [ay][ax][row][column] (sbbseg.h)."""
+    out = np.empty(32 * 32 * 16, np.int16)
+    check(load_library().sbbseg_region_line_table(_ptr(out), out.shape[0]), "sbbseg_region_line_table")
+    return out.reshape(32, 32, 4, 4)
 
 
 def deskew_sweep_angles(sweep: int) -> np.ndarray:

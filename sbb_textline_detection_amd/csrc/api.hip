@@ -25,6 +25,7 @@
 #include "internal.h"
 #include "region.h"
 #include "profile_stat.h"
+#include "line_mask.h"
 
 using namespace sbbseg;
 
@@ -274,6 +275,8 @@ struct sbbseg_ctx {
     int* d_cc_roots = nullptr; size_t cc_roots_cap = 0;  // parentless roots, 6 ints each
     void* d_rdk = nullptr; size_t rdk_cap = 0;           // sbbseg_region_deskew_profiles_dev: maps | table | geometry | crops | counts
     void* d_pstat = nullptr; size_t pstat_cap = 0;       // sbbseg_profile_statistics_dev: weights | regions | spread | winner | state | workspace
+    long long line_launches = 0;                         // kernels queued by sbbseg_region_line_masks_dev (sbbseg_debug_counter 2)
+    int16_t* d_line_tab = nullptr;                       // sbbseg_region_line_masks_dev: the fixed-point bicubic table, built on first use
     // profiling
     bool profiling = false;
     int conv_variant = 0;
@@ -937,7 +940,7 @@ int sbbseg_destroy(sbbseg_ctx* c)
     (void)hipFree(c->d_page); (void)hipFree(c->d_page_labels); (void)hipFree(c->d_page_labels3); (void)hipFree(c->d_tile_labels);
     (void)hipFree(c->d_own_x); (void)hipFree(c->d_own_y); (void)hipFree(c->d_map); (void)hipFree(c->d_wmap);
     (void)hipFree(c->d_deskew);
-    (void)hipFree(c->d_cc_bg); (void)hipFree(c->d_cc_roots); (void)hipFree(c->d_rdk); (void)hipFree(c->d_pstat);
+    (void)hipFree(c->d_cc_bg); (void)hipFree(c->d_cc_roots); (void)hipFree(c->d_rdk); (void)hipFree(c->d_pstat); (void)hipFree(c->d_line_tab);
     for (int lane = 0; lane < 2; ++lane)
         for (int L = 0; L < kRegionMaxLevels; ++L) (void)hipFree(c->d_rtab[lane][L]);
     (void)hipFree(c->d_run_page); (void)hipFree(c->d_run_mask); (void)hipFree(c->d_run_a); (void)hipFree(c->d_run_b);
@@ -3720,6 +3723,167 @@ int sbbseg_region_deskew_slopes(sbbseg_ctx* c, const uint8_t* textline_hw, int H
     API_END
 }
 
+// ---- stage glue: deskewed text-line masks and line profiles per region (textline_contours_postprocessing, main.py:1472-1487; line_mask.h) ----
+static void line_table(std::vector<int16_t>& itab)
+{
+    float tab[128];
+    cubic_table(tab);
+    itab.resize((size_t)kLineTabEntries);
+    for (int ay = 0; ay < 32; ++ay)
+        for (int ax = 0; ax < 32; ++ax) line_mask_weights(tab, ay, ax, itab.data() + (size_t)(ay * 32 + ax) * 16);
+}
+
+// rotate_image's inverse map for an h x w crop (main.py:159-163: center = (w // 2, h // 2))
+static int line_inverse_map(int h, int w, double slope, double* minv6)
+{
+    double M[6];
+    if (sbbseg_rotation_matrix((double)(w / 2), (double)(h / 2), slope, M)) return 1;
+    invert_affine(M, minv6);
+    return 0;
+}
+
+int sbbseg_region_line_table(int16_t* itab, int capacity)
+{
+    API_BEGIN
+    REQUIRE(itab && capacity >= kLineTabEntries, "room for %d weights, the table has %d", capacity, kLineTabEntries);
+    alloc_check();
+    std::vector<int16_t> t;
+    line_table(t);
+    memcpy(itab, t.data(), t.size() * sizeof(int16_t));
+    return 0;
+    API_END
+}
+
+// one clipped separable min / max of the given radius, in place (tmp: h * w bytes)
+static void host_line_morph(uint8_t* img, uint8_t* tmp, int h, int w, int radius, int is_max, int scale)
+{
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) tmp[(size_t)y * w + x] = (uint8_t)line_mask_morph_1d(img + (size_t)y * w, 1, x, w, radius, is_max, scale);
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) img[(size_t)y * w + x] = (uint8_t)line_mask_morph_1d(tmp + x, (size_t)w, y, h, radius, is_max, 1);
+}
+
+int sbbseg_region_line_masks_host(const uint8_t* crop_hw, int h, int w, int erode_iterations, double slope, uint8_t* mask, int32_t* rows, int32_t* cols)
+{
+    API_BEGIN
+    REQUIRE(crop_hw && rows && cols && erode_iterations >= 0 && erode_iterations <= 64, "bad arguments");
+    REQUIRE(h >= 1 && w >= 1, "crop: width %d, height %d (both must be at least 1)", w, h);
+    REQUIRE((long long)h * w < (1ll << 31), "crop of %d x %d is too large", w, h);
+    alloc_check();
+    const size_t pix = (size_t)h * w;
+    std::vector<uint8_t> img(crop_hw, crop_hw + pix), tmp(pix);
+    std::vector<int16_t> itab;
+    line_table(itab);
+    host_line_morph(img.data(), tmp.data(), h, w, 2 * erode_iterations, 0, 1);        // cv2.erode(crop, 5x5, iterations) (main.py:1734)
+    host_line_morph(img.data(), tmp.data(), h, w, 2, 0, 255);                         // * 255, then OPEN's erode ...
+    host_line_morph(img.data(), tmp.data(), h, w, 4, 1, 1);                           // ... OPEN's dilate + CLOSE's dilate ...
+    host_line_morph(img.data(), tmp.data(), h, w, 2, 0, 1);                           // ... and CLOSE's erode
+    double m[6];
+    if (line_inverse_map(h, w, slope, m)) return 1;
+    for (int x = 0; x < w; ++x) cols[x] = 0;
+    for (int y = 0; y < h; ++y) {
+        long long X0, Y0;
+        line_mask_row_origin(m, y, &X0, &Y0);
+        int cnt = 0;
+        for (int x = 0; x < w; ++x) {
+            const int d = line_mask_pixel(img.data(), w, h, m[0], m[3], X0, Y0, x, itab.data()) != 0;
+            if (mask) mask[(size_t)y * w + x] = (uint8_t)d;
+            cnt += d;
+            cols[x] += d;
+        }
+        rows[y] = cnt;
+    }
+    return 0;
+    API_END
+}
+
+int sbbseg_region_line_masks_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                                 const double* slopes, uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off, int64_t* row_off, int64_t* col_off)
+{
+    API_BEGIN
+    REQUIRE(H > 0 && W > 0 && n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && mask_off && row_off && col_off &&
+                erode_iterations >= 0 && erode_iterations <= 64, "bad arguments");
+    alloc_check();
+    std::vector<DeskewRegion> crop_geom((size_t)n_boxes);
+    std::vector<LineRegion> geom((size_t)n_boxes);
+    long long total_pix = 0, total_rows = 0, total_cols = 0, total_blocks = 0;
+    for (int r = 0; r < n_boxes; ++r) {
+        const int32_t* b = boxes_xywh + (size_t)r * 4;
+        REQUIRE(b[2] >= 1 && b[3] >= 1, "box %d: width %d, height %d (both must be at least 1)", r, b[2], b[3]);
+        REQUIRE(b[0] >= 0 && b[1] >= 0 && (long long)b[0] + b[2] <= W && (long long)b[1] + b[3] <= H, "box %d (%d, %d, %d, %d) leaves the %d x %d plane",
+                r, b[0], b[1], b[2], b[3], W, H);
+        DeskewRegion& cg = crop_geom[r];
+        memset(&cg, 0, sizeof(cg));
+        cg.x = b[0]; cg.y = b[1]; cg.w = b[2]; cg.h = b[3]; cg.crop_off = total_pix;
+        LineRegion& g = geom[r];
+        g.w = b[2]; g.h = b[3]; g.crop_off = total_pix; g.row_off = (int)total_rows; g.col_off = (int)total_cols; g.block0 = (int)total_blocks; g.pad = 0;
+        mask_off[r] = total_pix; row_off[r] = total_rows; col_off[r] = total_cols;
+        total_pix += (long long)g.w * g.h;
+        total_rows += g.h;
+        total_cols += g.w;
+        total_blocks += (g.h + kRegionLineRows - 1) / kRegionLineRows;
+        REQUIRE(total_pix < (1ll << 31) && total_rows < (1ll << 30) && total_cols < (1ll << 30), "too much work for one call (%d boxes): split the boxes", n_boxes);
+    }
+    mask_off[n_boxes] = total_pix; row_off[n_boxes] = total_rows; col_off[n_boxes] = total_cols;
+    if (n_boxes == 0) return 0;
+    if (check_ready(c)) return 1;
+    REQUIRE(d_textline_hw && slopes && rows && cols, "bad arguments");
+    if (!c->d_line_tab) {
+        std::vector<int16_t> itab;
+        line_table(itab);
+        if (upload(c, &c->d_line_tab, itab.data(), itab.size())) return 1;
+    }
+    // head of the device buffer, built on the host and copied in one piece: inverse maps | crop geometry | line geometry
+    const size_t minv_bytes = (size_t)n_boxes * 6 * sizeof(double), cgeom_bytes = (size_t)n_boxes * sizeof(DeskewRegion);
+    const size_t lgeom_off = minv_bytes + cgeom_bytes, head_bytes = (lgeom_off + (size_t)n_boxes * sizeof(LineRegion) + 15) & ~(size_t)15;
+    const size_t pix_bytes = ((size_t)total_pix + 15) & ~(size_t)15;
+    std::vector<unsigned char> head(head_bytes, 0);
+    for (int r = 0; r < n_boxes; ++r)
+        if (line_inverse_map(geom[r].h, geom[r].w, slopes[r], (double*)head.data() + (size_t)r * 6)) return 1;
+    memcpy(head.data() + minv_bytes, crop_geom.data(), cgeom_bytes);
+    memcpy(head.data() + lgeom_off, geom.data(), (size_t)n_boxes * sizeof(LineRegion));
+    if (ensure(c, &c->d_rdk, &c->rdk_cap, head_bytes + 3 * pix_bytes + (size_t)(total_rows + total_cols) * sizeof(int))) return 1;
+    unsigned char* d = (unsigned char*)c->d_rdk;
+    RegionDeskewParams cp;
+    memset(&cp, 0, sizeof(cp));
+    cp.plane = (const uint8_t*)d_textline_hw; cp.H = H; cp.W = W;
+    cp.geom = (const DeskewRegion*)(d + minv_bytes); cp.n_regions = n_boxes; cp.radius = 2 * erode_iterations; cp.total_pix = total_pix;
+    cp.tmp = d + head_bytes; cp.crops = d + head_bytes + pix_bytes;
+    RegionLinesParams p;
+    p.geom = (const LineRegion*)(d + lgeom_off); p.n_regions = n_boxes; p.total_pix = total_pix; p.total_cols = (int)total_cols;
+    p.total_blocks = (int)total_blocks; p.minv = (const double*)d; p.itab = c->d_line_tab;
+    p.a = cp.tmp; p.b = cp.crops; p.mask = d + head_bytes + 2 * pix_bytes;
+    p.rows = (int*)(d + head_bytes + 3 * pix_bytes); p.cols = p.rows + total_rows;
+    HIPCHK(hipMemcpyAsync(d, head.data(), head_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_region_deskew_crops(cp, c->stream));
+    HIPCHK(launch_region_line_morph(p, c->stream));
+    HIPCHK(launch_region_line_masks(p, c->stream));
+    c->line_launches += 2 + kRegionLineLaunches;
+    if (masks) HIPCHK(hipMemcpyAsync(masks, p.mask, (size_t)total_pix, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(rows, p.rows, (size_t)total_rows * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(cols, p.cols, (size_t)total_cols * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffer lives until here)
+    return 0;
+    API_END
+}
+
+int sbbseg_region_line_masks(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                             const double* slopes, uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off, int64_t* row_off, int64_t* col_off)
+{
+    API_BEGIN
+    REQUIRE(H > 0 && W > 0 && n_boxes >= 0, "bad arguments");
+    if (n_boxes > 0) {
+        if (check_ready(c)) return 1;
+        REQUIRE(textline_hw, "bad arguments");
+        const size_t pix = (size_t)H * W;
+        if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
+        HIPCHK(hipMemcpyAsync(c->d_morph_b, textline_hw, pix, hipMemcpyHostToDevice, c->stream));
+    }
+    return sbbseg_region_line_masks_dev(c, n_boxes > 0 ? c->d_morph_b : nullptr, H, W, boxes_xywh, n_boxes, erode_iterations, slopes, masks, rows, cols,
+                                        mask_off, row_off, col_off);
+    API_END
+}
+
 // ----------------------------------------------------------------------------------------- debug
 int sbbseg_debug_ingest(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, int Wp, const int32_t* tile_xy, int n_tiles,
                         int form, float* out, size_t out_floats)
@@ -3877,8 +4041,8 @@ int sbbseg_debug_largest_contour_area2(const uint8_t* mask_hw, int H, int W, int
 int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value)
 {
     API_BEGIN
-    REQUIRE(c && value && (which == 0 || which == 1), "unknown counter %d (0 = exact host contour rankings, 1 = patches run through the plan)", which);
-    *value = which == 0 ? (int64_t)c->host_contour_calls : c->forwards;
+    REQUIRE(c && value && which >= 0 && which <= 2, "unknown counter %d (0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by the line-mask calls)", which);
+    *value = which == 0 ? (int64_t)c->host_contour_calls : which == 1 ? (int64_t)c->forwards : (int64_t)c->line_launches;
     return 0;
     API_END
 }

@@ -373,6 +373,33 @@ struct RegionDeskewParams {
 };
 hipError_t launch_region_deskew_crops(const RegionDeskewParams& p, hipStream_t s);
 hipError_t launch_region_deskew_profiles(const RegionDeskewParams& p, hipStream_t s);
+// deskewed text-line masks and their projections for every box of a page (region_lines.hip, line_mask.h): OPEN / CLOSE of the packed
+// eroded crops * 255, the fixed-point bicubic rotation by the region's own slope onto the crop's own h x w, != 0, row and column sums
+struct LineRegion {
+    int w, h;
+    long long crop_off;       // first byte of the region in the packed crop / mask buffers
+    int row_off, col_off;     // first int of the region's row sums / column sums
+    int block0;               // first block of the region in the warp launch
+    int pad;
+};
+constexpr int kRegionLineRows = 8;        // destination rows per block of region_line_warp_kernel (a wave per row, two rounds)
+struct RegionLinesParams {
+    const LineRegion* geom;   // [n_regions]
+    int n_regions;
+    long long total_pix;      // sum of w * h
+    int total_cols;           // sum of w
+    int total_blocks;
+    const double* minv;       // [n_regions][6] inverse affine maps
+    const int16_t* itab;      // [32][32][16] fixed-point bicubic weights (line_mask_weights)
+    uint8_t* a;               // packed scratch
+    uint8_t* b;               // packed: the eroded crops on entry, the opened / closed crops (0 / 255) after the morphology
+    uint8_t* mask;            // packed dst (0 / 1)
+    int* rows;                // packed row sums
+    int* cols;                // packed column sums
+};
+hipError_t launch_region_line_morph(const RegionLinesParams& p, hipStream_t s);      // 6 launches: b -> ... -> b
+hipError_t launch_region_line_masks(const RegionLinesParams& p, hipStream_t s);      // 2 launches: warp + row sums, column sums
+constexpr int kRegionLineLaunches = 8;    // of the two calls above, whatever n_regions is
 // the 1-D statistic of every (region, angle) profile of a sweep and the winner per region (profile_stats.hip, profile_stat.h)
 constexpr int kProfileLdsSamples = 2048;  // longest profile whose smoothed forms stay in LDS; longer ones use ProfileStatParams::workspace
 struct ProfileRegion {

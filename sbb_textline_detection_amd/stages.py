@@ -17,8 +17,12 @@ it that section 8(f) ranks next, with the reference's names and call pattern:
     do_work_of_slopes (slope half)  main.py:1721-1748 one deskew slope per box: crop, erode x 2 and the rotate-and-project of ALL boxes in
                                                       one batched sweep on the device (``get_slopes``), the peak logic (Gaussian, find_peaks,
                                                       std) and the angle selection on the device too (``statistics="host"``: scipy)
+    textline_contours_postprocessing (mask half)  main.py:1472-1487 per box: crop * 255, OPEN, CLOSE, rotate_image by the box's slope, != 0
+                                                      -- ``dst``, and the row / column sums the line splitters open on (main.py:539, 1020), for
+                                                      ALL boxes in one batched pass on the device (``get_line_masks``)
 
-Out of scope: textline_contours_postprocessing, the polygons, the reading order and PAGE-XML.
+Out of scope: the contour half of textline_contours_postprocessing (main.py:1492-1511), seperate_lines / seperate_lines_vertical after
+their projection, the polygons, the reading order and PAGE-XML.
 """
 from __future__ import annotations
 
@@ -237,6 +241,43 @@ def get_slopes(textline_mask: np.ndarray, boxes, ctx=None, sigma_des: float = 2,
     return [0 if (ang == 999 or abs(ang) > 120.5) else ang for ang in (slopes[r] for r in range(len(boxes)))]
 
 
+def _line_masks_args(textline_mask, boxes, slopes, ctx, name):
+    if ctx is None:
+        raise RuntimeError(name + " needs a library handle (SegModel.ctx): there is no CPU fallback")
+    plane = np.ascontiguousarray(textline_mask, np.uint8)
+    boxes = [[int(v) for v in b] for b in boxes]
+    if slopes is not None and len(slopes) != len(boxes):
+        raise ValueError("one slope per box: %d boxes, %d slopes" % (len(boxes), len(slopes)))
+    return plane, boxes
+
+
+def get_line_masks(textline_mask: np.ndarray, boxes, slopes, ctx=None, masks: bool = True):
+    """The mask half of ``textline_contours_postprocessing`` (main.py:1472-1487) as ``do_work_of_slopes`` calls it (main.py:1750) for all
+    boxes of a page: a list, one entry per box, of ``(dst, rows, cols)``.  ``dst`` (uint8 [h, w] of 0 / 1; None with ``masks=False``) is
+    the box's textline crop, eroded x 2, * 255, opened and closed with the 5 x 5 kernel, rotated by the box's slope (``rotate_image``:
+    OpenCV's fixed-point bicubic on uint8) and binarised; ``rows`` = ``dst.sum(axis=1)`` (int64 [h]) is what ``seperate_lines`` opens on,
+    ``cols`` = ``dst.sum(axis=0)`` (int64 [w]) what ``seperate_lines_vertical`` opens on -- the caller picks by ``abs(slope) > 45``
+    (main.py:1514).  The textline map is uploaded once; all boxes run in a fixed number of launches (``sbbseg_region_line_masks_dev``).
+    ``slopes``: what ``get_slopes`` returned for these boxes.  ``ctx``: a ``_capi.Context`` (any finalized handle)."""
+    plane, boxes = _line_masks_args(textline_mask, boxes, slopes, ctx, "get_line_masks")
+    if not boxes:
+        return []
+    return ctx.region_line_masks_dev(ctx.stage(plane), plane.shape[0], plane.shape[1], boxes, [float(s) for s in slopes], 2, masks)
+
+
+def get_slopes_and_line_masks(textline_mask: np.ndarray, boxes, ctx=None, sigma_des: float = 2, masks: bool = True):
+    """``get_slopes`` (statistic on the device) and ``get_line_masks`` with the slopes it found, the textline map staged ONCE for both:
+    (slopes, line masks)."""
+    plane, boxes = _line_masks_args(textline_mask, boxes, None, ctx, "get_slopes_and_line_masks")
+    if not boxes:
+        return [], []
+    from . import _capi
+    d_plane = ctx.stage(plane)
+    weights = None if sigma_des == 2 else _capi.gaussian_weights(sigma_des)
+    slopes = ctx.region_deskew_slopes_dev(d_plane, plane.shape[0], plane.shape[1], boxes, 2, weights)
+    return slopes, ctx.region_line_masks_dev(d_plane, plane.shape[0], plane.shape[1], boxes, slopes, 2, masks)
+
+
 class InferenceStages:
     """The model-running part of ``textline_detector.run()`` (main.py:2056-2107)."""
 
@@ -421,6 +462,26 @@ class InferenceStages:
             self.boxes = self.get_text_region_boxes(regions)
             self.slopes = self.get_slopes(textlines, self.boxes, statistics=statistics)
         return page_mask, regions, textlines, page_coord, self.boxes, self.slopes
+
+    def get_line_masks(self, textlines: np.ndarray, boxes, slopes, masks: bool = True):
+        """Per box (dst, row sums, column sums) (``get_line_masks``: main.py:1472-1487) on the textline model's handle."""
+        model, session = start_new_session_and_model(self.model_textline_dir, **self.kw)
+        try:
+            if not isinstance(model, SegModel):
+                raise RuntimeError("get_line_masks needs a library handle (SegModel.ctx): there is no CPU fallback")
+            return get_line_masks(textlines, boxes, slopes, model.ctx, masks=masks)
+        finally:
+            session.close()
+
+    def run_with_lines(self, image_u8: np.ndarray, statistics: str = "device", masks: bool = True):
+        """``run_with_slopes`` and what the reference does with every slope in the same loop iteration (main.py:1750): the deskewed
+        text-line mask of every box and its projections.  Returns run_with_slopes' six values plus the list of ``get_line_masks``, also
+        kept as ``self.line_masks``; [] when the textline model did not run."""
+        page_mask, regions, textlines, page_coord, boxes, slopes = self.run_with_slopes(image_u8, statistics=statistics)
+        self.line_masks = []
+        if textlines is not None:
+            self.line_masks = self.get_line_masks(textlines, boxes, slopes, masks=masks)
+        return page_mask, regions, textlines, page_coord, boxes, slopes, self.line_masks
 
     def _run_resident(self):
         """run()'s three stages with the stored page uploaded ONCE and kept in device memory for all of them (run() hands the same
