@@ -456,6 +456,52 @@ int sbbseg_region_line_masks_host(const uint8_t* crop_hw, int h, int w, int erod
                                   int32_t* cols);
 int sbbseg_region_line_table(int16_t* itab, int capacity);
 
+/* ---- stage glue: text-line peaks and line boxes per region.  Everything seperate_lines (main.py:516-991) and seperate_lines_vertical
+ * (main.py:993-1457) compute from the projection of dst (the row sums, or the column sums for |slope| > 45, main.py:1514): the sigma
+ * estimate of the first `try` block (12 where it raises, at least 3), the second pass with that sigma, the merged peaks, their mean / std,
+ * the five branches and the corners of every line, unrotated and rotated.  One wave per region on the device, one launch for all regions
+ * (a second one when a profile is longer than 2048 samples), the profiles never leave the device between sbbseg_region_line_masks_dev's
+ * kernels and this step.  Every float64 result equals scipy's gaussian_filter1d / find_peaks and numpy's mean / std bit for bit, on the
+ * device and in the serial host twin (csrc/line_split.h is shared by both).
+ *   SCOPE: the contour enters the reference only through cv2.pointPolygonTest (x_min / x_max of the horizontal splitter; the vertical
+ *   splitter computes it and never uses it).  The contour half of textline_contours_postprocessing (main.py:1492-1511) is NOT built and
+ *   not approximated: every line gets the reference's own fallback extent x_min_cont = 0, x_max_cont = w (main.py:786-788).  The rotation
+ *   terms are inputs, so a caller that has the contour re-rotates with its own x extent.  return_contours_of_image /
+ *   filter_contours_area_of_image inside the first `try` (main.py:608-609) are treated as dead and non-raising [EXT] unpinned.
+ * Inputs per region r: geom[r] = {length of the profile, the other extent of dst, vertical (0 / 1)}; rot[r] = {cos, -sin, sin, cos, x_d,
+ * y_d}: numpy's cos / sin of thetha / 180. * np.pi (thetha = slope, + 90 first for the vertical splitter) and M[0, 2], M[1, 2] of
+ * getRotationMatrix2D((w // 2, h // 2), -thetha, 1.0) (sbbseg_rotation_matrix); libm is not reproduced by the library, so the caller
+ * passes them.  profiles: packed int32, region r from offsets[r] (n_regions + 1 entries, offsets[r + 1] - offsets[r] = length).
+ * weights / weight_off: the half kernels of gaussian_filter1d for sigma = 2 .. sigma_max one after the other (sigma s: 4 s + 1 doubles
+ * from weight_off[s - 2]; sigma_max - 2 + 2 offsets; sigma_max >= 12).  The device uses the table up to sigma 128.
+ * Outputs (host buffers).  info[r] = {status, sigma_gaus, 1 if the first estimate raised, branch, line count}; status SBBSEG_LINES_OK,
+ * SBBSEG_LINES_NONE (the second pass raised: textline_contours_postprocessing's bare except returns [], main.py:1520) or
+ * SBBSEG_LINES_SIGMA_TOO_LARGE (sigma_gaus is in neither table: nothing else was computed; finish the region with
+ * sbbseg_line_split_host and that sigma's half kernel as extra_weights / extra_sigma); branch 0 .. 4 = main.py:744, 822, 825, 864, 919
+ * in that order, -1 = not reached.  Lines are packed by CAPACITY: region r owns lines line_off[r] .. line_off[r + 1] with
+ * line_off[r + 1] - line_off[r] = (length + 40) / 2 (the maxima of the padded profile bound the peaks, and the merged list is never longer);
+ * line_off has n_regions + 1 entries and is written by the call, the caller sizes lines [total][3] = {peak, point_up, point_down},
+ * corners [total][4][2] (main.py:817-820) and corners_rot [total][4][2] (int(a * x + b * y + d), every operation rounded on its own,
+ * with the reference's four `< 0` clamps) from the same sums.  Only the first `count` lines of a region are written; the buffers need no
+ * fill.  sbbseg_line_split_host: serial, no handle, no GPU.  sbbseg_region_line_boxes(_dev): sbbseg_region_line_masks' steps a .. d on
+ * all boxes and then the split of each box's own profile, boxes and slopes in, line boxes out; rot as above with (w, h) of the box.
+ * Synchronise the stream. */
+#define SBBSEG_LINES_OK 0
+#define SBBSEG_LINES_NONE 1
+#define SBBSEG_LINES_SIGMA_TOO_LARGE 2
+int sbbseg_line_split_host(const int32_t* profiles, const int64_t* offsets, int n_regions, const int32_t* geom, const double* rot, const double* weights,
+                           const int64_t* weight_off, int sigma_max, const double* extra_weights, int extra_sigma, int32_t* info, int64_t* line_off,
+                           int32_t* lines, int32_t* corners, int32_t* corners_rot);
+int sbbseg_line_split_dev(sbbseg_ctx* c, const void* d_profiles, const int64_t* offsets, int n_regions, const int32_t* geom, const double* rot,
+                          const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info, int64_t* line_off, int32_t* lines,
+                          int32_t* corners, int32_t* corners_rot);
+int sbbseg_region_line_boxes_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                                 const double* slopes, const double* rot, const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info,
+                                 int64_t* line_off, int32_t* lines, int32_t* corners, int32_t* corners_rot);
+int sbbseg_region_line_boxes(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                             const double* slopes, const double* rot, const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info,
+                             int64_t* line_off, int32_t* lines, int32_t* corners, int32_t* corners_rot);
+
 /* ---- multi-GPU: one process per GPU, one handle per process; tiles (sbbseg_segment_tile_range_dev) or whole
  * pages (sbbseg_segment_pages_dev) are sharded by the caller, and the ONE data-path collective -- the all-gather of the u8
  * label maps -- runs on RCCL inside the library, on the handle's stream, so an integrator needs neither PyTorch nor an MPI:

@@ -37,6 +37,7 @@ EXPORTS = [
     "sbbseg_text_region_boxes_dev", "sbbseg_text_region_boxes", "sbbseg_region_deskew_profiles_dev", "sbbseg_region_deskew_profiles",
     "sbbseg_profile_statistics_host", "sbbseg_profile_statistics_dev", "sbbseg_deskew_sweep_angles", "sbbseg_region_deskew_slopes_dev", "sbbseg_region_deskew_slopes",
     "sbbseg_region_line_masks_dev", "sbbseg_region_line_masks", "sbbseg_region_line_masks_host", "sbbseg_region_line_table",
+    "sbbseg_line_split_host", "sbbseg_line_split_dev", "sbbseg_region_line_boxes_dev", "sbbseg_region_line_boxes",
 ]
 
 
@@ -170,6 +171,10 @@ def load_library(path: Optional[str] = None):
         "sbbseg_region_line_masks": [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
         "sbbseg_region_line_masks_host": [vp, i32, i32, i32, C.c_double, vp, vp, vp],
         "sbbseg_region_line_table": [vp, i32],
+        "sbbseg_line_split_host": [vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
+        "sbbseg_line_split_dev": [vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
+        "sbbseg_region_line_boxes_dev": [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
+        "sbbseg_region_line_boxes": [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -190,6 +195,10 @@ def check(rc: int, what: str = "libsbbseg"):
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+LINE_SIGMA_MAX = 128                                             # largest sigma of the line splitter's device table (csrc/line_split.h)
+LINES_OK, LINES_NONE, LINES_SIGMA_TOO_LARGE = 0, 1, 2
 
 
 class Context:
@@ -674,8 +683,66 @@ class Context:
             raise ValueError("region_line_masks expects a uint8 plane [H, W]")
         return self._line_masks_call(self.lib.sbbseg_region_line_masks, _ptr(plane), plane.shape[0], plane.shape[1], boxes, slopes, erode_iterations, masks)
 
+    def line_split_dev(self, d_profiles: int, offsets, others, verticals, rots, sigma_max: int = LINE_SIGMA_MAX):
+        """The text lines of every region from its projection (``seperate_lines`` / ``seperate_lines_vertical`` after ``img_patch.sum``,
+        main.py:516-1457) for packed int32 profiles in device memory, one call: a list of line records (``line_split_host``).  The x
+        extent of every line is the reference's fallback (0, w): the contour is not built (sbbseg.h).  A region whose sigma_gaus exceeds
+        the device's table is finished by the host twin with that sigma's weights."""
+        offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        n = offsets.shape[0] - 1
+        geom = _line_geom(np.diff(offsets), others, verticals)
+        rots = np.ascontiguousarray(rots, np.float64).reshape(n, 6)
+        w, w_off = line_weight_table(sigma_max)
+        out = _line_split_buffers(geom)
+        if n:
+            check(self.lib.sbbseg_line_split_dev(self.h, C.c_void_p(d_profiles), _ptr(offsets), n, _ptr(geom), _ptr(rots), _ptr(w), _ptr(w_off), int(sigma_max),
+                                                 *[_ptr(a) for a in out]), "sbbseg_line_split_dev")
+        records = _line_records(*out)
+        for r, rec in enumerate(records):
+            if rec["status"] == LINES_SIGMA_TOO_LARGE:
+                prof = self.download(d_profiles + 4 * int(offsets[r]), (int(geom[r, 0]),), np.int32)
+                records[r] = line_split_host([prof], [geom[r, 1]], [geom[r, 2]], [rots[r]], sigma_max)[0]
+        return records
+
+    def _line_boxes_call(self, fn, src, d_src, H, W, boxes, slopes, erode_iterations, sigma_max):
+        boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        slopes = np.ascontiguousarray(slopes, np.float64).reshape(-1)
+        n = boxes.shape[0]
+        if slopes.shape[0] != n:
+            raise ValueError("one slope per box: %d boxes, %d slopes" % (n, slopes.shape[0]))
+        if n == 0:
+            return []
+        vertical = np.abs(slopes) > 45
+        geom = _line_geom(np.where(vertical, boxes[:, 2], boxes[:, 3]).clip(1), np.where(vertical, boxes[:, 3], boxes[:, 2]), vertical)
+        rots = np.array([line_rotation_terms(int(b[2]), int(b[3]), float(s)) for b, s in zip(boxes, slopes)], np.float64).reshape(n, 6)
+        w, w_off = line_weight_table(sigma_max)
+        out = _line_split_buffers(geom)
+        check(fn(self.h, src, int(H), int(W), _ptr(boxes), n, int(erode_iterations), _ptr(slopes), _ptr(rots), _ptr(w), _ptr(w_off), int(sigma_max),
+                 *[_ptr(a) for a in out]), "sbbseg_region_line_boxes")
+        records = _line_records(*out)
+        for r, rec in enumerate(records):
+            if rec["status"] == LINES_SIGMA_TOO_LARGE:          # the profile of this one box, then the host twin with its sigma's weights
+                _m, rows, cols = self.region_line_masks_dev(d_src(), H, W, [boxes[r]], [slopes[r]], erode_iterations, False)[0]
+                records[r] = line_split_host([cols if vertical[r] else rows], [geom[r, 1]], [geom[r, 2]], [rots[r]], sigma_max)[0]
+        return records
+
+    def region_line_boxes_dev(self, d_textlines: int, H: int, W: int, boxes, slopes, erode_iterations: int = 2, sigma_max: int = LINE_SIGMA_MAX):
+        """``region_line_masks_dev`` and then the line splitter of every box on its own profile (row sums, or column sums for
+        ``abs(slope) > 45``, main.py:1514), the profiles staying on the device: a list of line records (``line_split_host``) -- see
+        sbbseg.h.  The x extent of every line is the reference's fallback (0, w): the contour half is not built."""
+        return self._line_boxes_call(self.lib.sbbseg_region_line_boxes_dev, C.c_void_p(d_textlines), lambda: d_textlines, H, W, boxes, slopes,
+                                     erode_iterations, sigma_max)
+
+    def region_line_boxes(self, textlines: np.ndarray, boxes, slopes, erode_iterations: int = 2, sigma_max: int = LINE_SIGMA_MAX):
+        """The same from a host textline map uint8 [H, W] (uploaded once per call)."""
+        plane = np.ascontiguousarray(textlines, np.uint8)
+        if plane.ndim != 2:
+            raise ValueError("region_line_boxes expects a uint8 plane [H, W]")
+        return self._line_boxes_call(self.lib.sbbseg_region_line_boxes, _ptr(plane), lambda: self.stage(plane), plane.shape[0], plane.shape[1], boxes,
+                                     slopes, erode_iterations, sigma_max)
+
     def line_mask_launches(self) -> int:
-        """Kernels the line-mask calls have queued on this handle so far (sbbseg_debug_counter 2)."""
+        """Kernels the line-mask and line-split calls have queued on this handle so far (sbbseg_debug_counter 2)."""
         v = C.c_int64(0)
         check(self.lib.sbbseg_debug_counter(self.h, 2, C.byref(v)), "sbbseg_debug_counter")
         return int(v.value)
@@ -883,6 +950,84 @@ def profile_statistics_host(counts, offsets, n_angles: int, weights=None, multip
                                                         float(multiplier), _ptr(spread), _ptr(state), _ptr(winner), _ptr(smooth)),
           "sbbseg_profile_statistics_host")
     return (spread, state, winner, smooth) if want_smooth else (spread, state, winner)
+
+
+_LINE_TABLES = {}
+
+
+def line_weight_table(sigma_max: int = LINE_SIGMA_MAX):
+    """(weights float64, offsets int64 [sigma_max]): ``gaussian_weights(sigma)`` for sigma = 2 .. sigma_max one after the other (4 sigma +
+    1 values each, from offsets[sigma - 2]): what the line splitter takes from its caller.  Built once per sigma_max."""
+    sigma_max = int(sigma_max)
+    if sigma_max not in _LINE_TABLES:
+        halves = [gaussian_weights(s) for s in range(2, sigma_max + 1)]
+        offsets = np.concatenate([[0], np.cumsum([h.shape[0] for h in halves])]).astype(np.int64)
+        _LINE_TABLES[sigma_max] = (np.ascontiguousarray(np.concatenate(halves), np.float64), offsets)
+    return _LINE_TABLES[sigma_max]
+
+
+def line_rotation_terms(w: int, h: int, slope: float):
+    """[cos, -sin, sin, cos, x_d, y_d] of seperate_lines (main.py:517-524) for a dst of h x w, or of seperate_lines_vertical
+    (main.py:996-1005: thetha + 90 first) when ``abs(slope) > 45``: numpy's cos / sin and the library's getRotationMatrix2D."""
+    thetha = float(slope) + 90 if abs(float(slope)) > 45 else float(slope)
+    M = rotation_matrix(w // 2, h // 2, -thetha)
+    t = thetha / 180. * np.pi
+    return [float(np.cos(t)), float(-np.sin(t)), float(np.sin(t)), float(np.cos(t)), float(M[0, 2]), float(M[1, 2])]
+
+
+def _line_geom(lengths, others, verticals) -> np.ndarray:
+    return np.ascontiguousarray(np.stack([np.asarray(lengths, np.int64), np.asarray(others, np.int64), np.asarray(verticals, np.int64)], axis=1)
+                                if len(lengths) else np.zeros((0, 3)), np.int32)
+
+
+def _line_split_buffers(geom: np.ndarray):
+    """(info, line_off, lines, corners, corners_rot) sized by the capacities sbbseg.h documents."""
+    total = int(((geom[:, 0].astype(np.int64) + 40) // 2).sum())
+    return (np.zeros((geom.shape[0], 5), np.int32), np.zeros(geom.shape[0] + 1, np.int64), np.zeros((total, 3), np.int32),
+            np.zeros((total, 4, 2), np.int32), np.zeros((total, 4, 2), np.int32))
+
+
+def _line_records(info, line_off, lines, corners, corners_rot):
+    out = []
+    for r in range(info.shape[0]):
+        at, n = int(line_off[r]), int(info[r, 4])
+        out.append({"status": int(info[r, 0]), "sigma": int(info[r, 1]), "raised": bool(info[r, 2]), "branch": int(info[r, 3]),
+                    "peaks": lines[at:at + n, 0].copy(), "point_up": lines[at:at + n, 1].copy(), "point_down": lines[at:at + n, 2].copy(),
+                    "boxes": corners[at:at + n].copy(), "boxes_rot": corners_rot[at:at + n].copy()})
+    return out
+
+
+def line_split_host_raw(profiles, others, verticals, rots, sigma_max: int = LINE_SIGMA_MAX, extra_sigma: int = 0):
+    """``sbbseg_line_split_host`` as the library packs it: (info int32 [n, 5], line_off int64 [n + 1], lines [total, 3], corners
+    [total, 4, 2], corners_rot [total, 4, 2]).  ``extra_sigma``: one further sigma whose weights are computed on the spot."""
+    profiles = [np.ascontiguousarray(p, np.int32).reshape(-1) for p in profiles]
+    n = len(profiles)
+    offsets = np.concatenate([[0], np.cumsum([p.shape[0] for p in profiles])]).astype(np.int64)
+    packed = np.ascontiguousarray(np.concatenate(profiles) if n else np.zeros(0), np.int32)
+    geom = _line_geom([p.shape[0] for p in profiles], others, verticals)
+    rots = np.ascontiguousarray(rots, np.float64).reshape(n, 6)
+    w, w_off = line_weight_table(sigma_max)
+    extra = gaussian_weights(extra_sigma) if extra_sigma else None
+    out = _line_split_buffers(geom)
+    check(load_library().sbbseg_line_split_host(_ptr(packed), _ptr(offsets), n, _ptr(geom), _ptr(rots), _ptr(w), _ptr(w_off), int(sigma_max), _ptr(extra),
+                                                int(extra_sigma), *[_ptr(a) for a in out]), "sbbseg_line_split_host")
+    return out
+
+
+def line_split_host(profiles, others, verticals, rots, sigma_max: int = LINE_SIGMA_MAX):
+    """``Context.line_split_dev`` on the CPU (serial, no handle, no GPU): the same bits.  ``profiles``: one int array per region (row sums
+    of dst, or column sums for the vertical splitter); ``others``: the other extent of dst; ``rots``: ``line_rotation_terms``.  Returns
+    one record per region: status (LINES_OK, or LINES_NONE where the reference returns []), sigma (sigma_gaus), raised (the first
+    estimate's ``try`` raised), branch (0 .. 4: main.py:744, 822, 825, 864, 919; -1 not reached), peaks, point_up, point_down (int32
+    [lines]), boxes and boxes_rot (int32 [lines, 4, 2]: main.py:817-820 and 812-815).  The x extent is the reference's fallback (0, w):
+    the contour is not built.  A region whose sigma_gaus is beyond the table is run again with that sigma's weights."""
+    raw = line_split_host_raw(profiles, others, verticals, rots, sigma_max)
+    records = _line_records(*raw)
+    for r, rec in enumerate(records):
+        if rec["status"] == LINES_SIGMA_TOO_LARGE:
+            one = line_split_host_raw([profiles[r]], [others[r]], [verticals[r]], [np.asarray(rots, np.float64).reshape(-1, 6)[r]], sigma_max, rec["sigma"])
+            records[r] = _line_records(*one)[0]
+    return records
 
 
 def host_region_line_mask(crop: np.ndarray, slope: float, erode_iterations: int = 2, mask: bool = True):

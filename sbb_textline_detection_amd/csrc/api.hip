@@ -26,6 +26,7 @@
 #include "region.h"
 #include "profile_stat.h"
 #include "line_mask.h"
+#include "line_split.h"
 
 using namespace sbbseg;
 
@@ -276,6 +277,9 @@ struct sbbseg_ctx {
     void* d_rdk = nullptr; size_t rdk_cap = 0;           // sbbseg_region_deskew_profiles_dev: maps | table | geometry | crops | counts
     void* d_pstat = nullptr; size_t pstat_cap = 0;       // sbbseg_profile_statistics_dev: weights | regions | spread | winner | state | workspace
     long long line_launches = 0;                         // kernels queued by sbbseg_region_line_masks_dev (sbbseg_debug_counter 2)
+    void* d_lsplit = nullptr; size_t lsplit_cap = 0;     // sbbseg_line_split_dev: regions | info | lines | corners | rotated corners | workspace
+    void* d_line_w = nullptr; size_t line_w_cap = 0;     // ... its table of half Gaussian kernels: offsets | weights, uploaded when it differs from
+    std::vector<double> line_w_host;                     // ... this copy of the last one
     int16_t* d_line_tab = nullptr;                       // sbbseg_region_line_masks_dev: the fixed-point bicubic table, built on first use
     // profiling
     bool profiling = false;
@@ -941,6 +945,7 @@ int sbbseg_destroy(sbbseg_ctx* c)
     (void)hipFree(c->d_own_x); (void)hipFree(c->d_own_y); (void)hipFree(c->d_map); (void)hipFree(c->d_wmap);
     (void)hipFree(c->d_deskew);
     (void)hipFree(c->d_cc_bg); (void)hipFree(c->d_cc_roots); (void)hipFree(c->d_rdk); (void)hipFree(c->d_pstat); (void)hipFree(c->d_line_tab);
+    (void)hipFree(c->d_lsplit); (void)hipFree(c->d_line_w);
     for (int lane = 0; lane < 2; ++lane)
         for (int L = 0; L < kRegionMaxLevels; ++L) (void)hipFree(c->d_rtab[lane][L]);
     (void)hipFree(c->d_run_page); (void)hipFree(c->d_run_mask); (void)hipFree(c->d_run_a); (void)hipFree(c->d_run_b);
@@ -3797,10 +3802,13 @@ int sbbseg_region_line_masks_host(const uint8_t* crop_hw, int h, int w, int erod
     API_END
 }
 
-int sbbseg_region_line_masks_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
-                                 const double* slopes, uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off, int64_t* row_off, int64_t* col_off)
+// queues crop / erode / OPEN / CLOSE / warp / sums of all boxes; *out holds the device pointers of the results (in c->d_rdk), out->n_regions
+// == 0 when there is nothing to do.  `need_sums`: what a caller that downloads rows and cols must have passed.
+static int region_line_masks_queue(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                                   const double* slopes, bool need_sums, int64_t* mask_off, int64_t* row_off, int64_t* col_off,
+                                   std::vector<unsigned char>& head, RegionLinesParams* out, long long* rows_total)
 {
-    API_BEGIN
+    out->n_regions = 0;
     REQUIRE(H > 0 && W > 0 && n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && mask_off && row_off && col_off &&
                 erode_iterations >= 0 && erode_iterations <= 64, "bad arguments");
     alloc_check();
@@ -3827,7 +3835,7 @@ int sbbseg_region_line_masks_dev(sbbseg_ctx* c, const void* d_textline_hw, int H
     mask_off[n_boxes] = total_pix; row_off[n_boxes] = total_rows; col_off[n_boxes] = total_cols;
     if (n_boxes == 0) return 0;
     if (check_ready(c)) return 1;
-    REQUIRE(d_textline_hw && slopes && rows && cols, "bad arguments");
+    REQUIRE(d_textline_hw && slopes && need_sums, "bad arguments");
     if (!c->d_line_tab) {
         std::vector<int16_t> itab;
         line_table(itab);
@@ -3837,7 +3845,7 @@ int sbbseg_region_line_masks_dev(sbbseg_ctx* c, const void* d_textline_hw, int H
     const size_t minv_bytes = (size_t)n_boxes * 6 * sizeof(double), cgeom_bytes = (size_t)n_boxes * sizeof(DeskewRegion);
     const size_t lgeom_off = minv_bytes + cgeom_bytes, head_bytes = (lgeom_off + (size_t)n_boxes * sizeof(LineRegion) + 15) & ~(size_t)15;
     const size_t pix_bytes = ((size_t)total_pix + 15) & ~(size_t)15;
-    std::vector<unsigned char> head(head_bytes, 0);
+    head.assign(head_bytes, 0);
     for (int r = 0; r < n_boxes; ++r)
         if (line_inverse_map(geom[r].h, geom[r].w, slopes[r], (double*)head.data() + (size_t)r * 6)) return 1;
     memcpy(head.data() + minv_bytes, crop_geom.data(), cgeom_bytes);
@@ -3859,9 +3867,24 @@ int sbbseg_region_line_masks_dev(sbbseg_ctx* c, const void* d_textline_hw, int H
     HIPCHK(launch_region_line_morph(p, c->stream));
     HIPCHK(launch_region_line_masks(p, c->stream));
     c->line_launches += 2 + kRegionLineLaunches;
-    if (masks) HIPCHK(hipMemcpyAsync(masks, p.mask, (size_t)total_pix, hipMemcpyDeviceToHost, c->stream));
+    *out = p;
+    *rows_total = total_rows;
+    return 0;
+}
+
+int sbbseg_region_line_masks_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                                 const double* slopes, uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off, int64_t* row_off, int64_t* col_off)
+{
+    API_BEGIN
+    std::vector<unsigned char> head;
+    RegionLinesParams p;
+    long long total_rows = 0;
+    if (region_line_masks_queue(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, slopes, rows && cols, mask_off, row_off, col_off, head, &p,
+                                &total_rows)) return 1;
+    if (p.n_regions == 0) return 0;
+    if (masks) HIPCHK(hipMemcpyAsync(masks, p.mask, (size_t)p.total_pix, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(rows, p.rows, (size_t)total_rows * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(cols, p.cols, (size_t)total_cols * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(cols, p.cols, (size_t)p.total_cols * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffer lives until here)
     return 0;
     API_END
@@ -3881,6 +3904,198 @@ int sbbseg_region_line_masks(sbbseg_ctx* c, const uint8_t* textline_hw, int H, i
     }
     return sbbseg_region_line_masks_dev(c, n_boxes > 0 ? c->d_morph_b : nullptr, H, W, boxes_xywh, n_boxes, erode_iterations, slopes, masks, rows, cols,
                                         mask_off, row_off, col_off);
+    API_END
+}
+
+// ---- stage glue: text-line peaks and line boxes per region (seperate_lines / seperate_lines_vertical after the projection; line_split.h) ----
+static int check_line_split_tables(const int64_t* offsets, int n_regions, const int32_t* geom, const double* rot, const double* weights,
+                                   const int64_t* weight_off, int sigma_max, int64_t* line_off)
+{
+    REQUIRE(n_regions >= 0 && n_regions <= (1 << 20) && line_off && ((offsets && geom && rot) || n_regions == 0), "bad arguments");
+    REQUIRE(weights && weight_off && sigma_max >= kLineSigmaRaised && sigma_max <= 4096, "the weight table must hold sigma = 2 .. sigma_max, sigma_max in 12 .. 4096");
+    for (int s = kLineSigmaMin; s <= sigma_max; ++s)
+        REQUIRE(weight_off[s - kLineSigmaMin] >= 0 && weight_off[s - kLineSigmaMin + 1] - weight_off[s - kLineSigmaMin] == 4 * s + 1,
+                "weight table: sigma %d does not have 4 * sigma + 1 weights", s);
+    long long lines = 0;
+    for (int r = 0; r < n_regions; ++r) {
+        const int32_t* g = geom + (size_t)r * 3;
+        REQUIRE(g[0] >= 1 && g[0] <= 32767 && g[1] >= 1 && g[1] <= (1 << 24) && (g[2] == 0 || g[2] == 1),
+                "region %d: length %d (1 .. 32767), other extent %d (1 .. 2^24), vertical %d (0, 1)", r, g[0], g[1], g[2]);
+        REQUIRE(offsets[r] >= 0 && offsets[r + 1] - offsets[r] == g[0] && offsets[r + 1] < (1ll << 31), "region %d: offsets %lld .. %lld do not hold %d samples", r,
+                (long long)offsets[r], (long long)offsets[r + 1], g[0]);
+        line_off[r] = lines;
+        lines += line_capacity(g[0]);
+    }
+    line_off[n_regions] = lines;
+    REQUIRE(lines < (1ll << 27), "too much work for one call (%d regions): split the regions", n_regions);
+    return 0;
+}
+
+static LineGeom line_geom(const int32_t* g, const double* rot)
+{
+    LineGeom out;
+    out.n = g[0]; out.other = g[1]; out.vertical = g[2];
+    out.r00 = rot[0]; out.r01 = rot[1]; out.r10 = rot[2]; out.r11 = rot[3]; out.xd = rot[4]; out.yd = rot[5];
+    return out;
+}
+
+int sbbseg_line_split_host(const int32_t* profiles, const int64_t* offsets, int n_regions, const int32_t* geom, const double* rot, const double* weights,
+                           const int64_t* weight_off, int sigma_max, const double* extra_weights, int extra_sigma, int32_t* info, int64_t* line_off,
+                           int32_t* lines, int32_t* corners, int32_t* corners_rot)
+{
+    API_BEGIN
+    if (check_line_split_tables(offsets, n_regions, geom, rot, weights, weight_off, sigma_max, line_off)) return 1;
+    REQUIRE((profiles && info && lines && corners && corners_rot) || n_regions == 0, "bad arguments");
+    REQUIRE(!extra_weights || extra_sigma >= 1, "extra_sigma %d", extra_sigma);
+    alloc_check();
+    const LineWeights w{weights, weight_off, sigma_max, extra_weights, extra_sigma};
+    std::vector<unsigned char> work;
+    PairwiseStack stack;
+    for (int r = 0; r < n_regions; ++r) {
+        const LineGeom g = line_geom(geom + (size_t)r * 3, rot + (size_t)r * 6);
+        work.resize(line_work_bytes(g.n));
+        const size_t at = (size_t)line_off[r];
+        line_split_serial(profiles + offsets[r], g, w, LineWork{work.data(), g.n, &stack}, info + (size_t)r * kLineInfoInts, lines + at * 3, corners + at * 8,
+                          corners_rot + at * 8);
+    }
+    return 0;
+    API_END
+}
+
+// queues the split of regions whose profiles are in device memory (region r: n ints from d_profiles + prof_off[r]); *out holds the device
+// pointers of the results (in c->d_lsplit)
+static int line_split_queue(sbbseg_ctx* c, const int32_t* d_profiles, const int64_t* prof_off, int n_regions, const int32_t* geom, const double* rot,
+                            const double* weights, const int64_t* weight_off, int sigma_max, const int64_t* line_off, std::vector<unsigned char>& head,
+                            LineSplitParams* out)
+{
+    if (sigma_max > kLineSigmaMax) sigma_max = kLineSigmaMax;      // the device's table ends there; larger sigmas are reported, not computed
+    const size_t n_off = (size_t)(sigma_max - kLineSigmaMin + 2), n_w = (size_t)weight_off[n_off - 1];
+    const size_t off_bytes = (n_off * sizeof(long long) + 15) & ~(size_t)15;
+    if (c->line_w_host.size() != n_w || !c->d_line_w || memcmp(c->line_w_host.data(), weights, n_w * sizeof(double)) != 0) {
+        std::vector<unsigned char> tab(off_bytes + n_w * sizeof(double));
+        for (size_t i = 0; i < n_off; ++i) ((long long*)tab.data())[i] = (long long)weight_off[i];
+        memcpy(tab.data() + off_bytes, weights, n_w * sizeof(double));
+        c->line_w_host.clear();
+        if (ensure(c, &c->d_line_w, &c->line_w_cap, tab.size())) return 1;
+        HIPCHK(hipMemcpyAsync(c->d_line_w, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->line_w_host.assign(weights, weights + n_w);
+    }
+    const size_t lines = (size_t)line_off[n_regions];
+    const size_t info_off = ((size_t)n_regions * sizeof(LineSplitRegion) + 15) & ~(size_t)15;
+    const size_t pts_off = (info_off + (size_t)n_regions * kLineInfoInts * sizeof(int32_t) + 15) & ~(size_t)15;
+    const size_t box_off = (pts_off + lines * 3 * sizeof(int32_t) + 15) & ~(size_t)15, rot_off = box_off + lines * 8 * sizeof(int32_t);
+    const size_t ws_off = rot_off + lines * 8 * sizeof(int32_t);
+    head.assign(info_off, 0);
+    LineSplitRegion* reg = (LineSplitRegion*)head.data();
+    size_t ws_bytes = 0;
+    for (int r = 0; r < n_regions; ++r) {
+        const int32_t* g = geom + (size_t)r * 3;
+        reg[r].prof_off = prof_off[r]; reg[r].ws_off = (long long)ws_bytes;
+        reg[r].n = g[0]; reg[r].other = g[1]; reg[r].vertical = g[2]; reg[r].line_off = (int)line_off[r];
+        memcpy(reg[r].rot, rot + (size_t)r * 6, 6 * sizeof(double));
+        if (g[0] > kProfileLdsSamples) ws_bytes += line_work_bytes(g[0]);
+    }
+    if (ensure(c, &c->d_lsplit, &c->lsplit_cap, ws_off + ws_bytes)) return 1;
+    unsigned char* d = (unsigned char*)c->d_lsplit;
+    LineSplitParams p;
+    p.profiles = d_profiles; p.regions = (const LineSplitRegion*)d; p.n_regions = n_regions; p.sigma_max = sigma_max;
+    p.weights = (const double*)((unsigned char*)c->d_line_w + off_bytes); p.weight_off = (const long long*)c->d_line_w;
+    p.workspace = d + ws_off; p.info = (int32_t*)(d + info_off); p.pts = (int32_t*)(d + pts_off); p.box = (int32_t*)(d + box_off);
+    p.rot = (int32_t*)(d + rot_off);
+    HIPCHK(hipMemcpyAsync(d, head.data(), info_off, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_line_split(p, ws_bytes > 0, c->stream));
+    c->line_launches += ws_bytes > 0 ? 2 : 1;
+    *out = p;
+    return 0;
+}
+
+// copies info and, per region, its first `count` lines back: nothing beyond a region's count is written on the host
+static int line_split_download(sbbseg_ctx* c, const LineSplitParams& p, const int64_t* line_off, int32_t* info, int32_t* lines, int32_t* corners,
+                               int32_t* corners_rot)
+{
+    const size_t total = (size_t)line_off[p.n_regions];
+    std::vector<int32_t> stage(total * 19);
+    HIPCHK(hipMemcpyAsync(info, p.info, (size_t)p.n_regions * kLineInfoInts * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(stage.data(), p.pts, total * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(stage.data() + total * 3, p.box, total * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(stage.data() + total * 11, p.rot, total * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffers live until here)
+    for (int r = 0; r < p.n_regions; ++r) {
+        const size_t at = (size_t)line_off[r], n = (size_t)info[(size_t)r * kLineInfoInts + kLineInfoCount];
+        memcpy(lines + at * 3, stage.data() + at * 3, n * 3 * sizeof(int32_t));
+        memcpy(corners + at * 8, stage.data() + total * 3 + at * 8, n * 8 * sizeof(int32_t));
+        memcpy(corners_rot + at * 8, stage.data() + total * 11 + at * 8, n * 8 * sizeof(int32_t));
+    }
+    return 0;
+}
+
+int sbbseg_line_split_dev(sbbseg_ctx* c, const void* d_profiles, const int64_t* offsets, int n_regions, const int32_t* geom, const double* rot,
+                          const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info, int64_t* line_off, int32_t* lines,
+                          int32_t* corners, int32_t* corners_rot)
+{
+    API_BEGIN
+    if (check_line_split_tables(offsets, n_regions, geom, rot, weights, weight_off, sigma_max, line_off)) return 1;
+    if (n_regions == 0) return 0;
+    if (check_ready(c)) return 1;
+    REQUIRE(d_profiles && info && lines && corners && corners_rot, "bad arguments");
+    alloc_check();
+    std::vector<unsigned char> head;
+    LineSplitParams p;
+    if (line_split_queue(c, (const int32_t*)d_profiles, offsets, n_regions, geom, rot, weights, weight_off, sigma_max, line_off, head, &p)) return 1;
+    return line_split_download(c, p, line_off, info, lines, corners, corners_rot);
+    API_END
+}
+
+int sbbseg_region_line_boxes_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                                 const double* slopes, const double* rot, const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info,
+                                 int64_t* line_off, int32_t* lines, int32_t* corners, int32_t* corners_rot)
+{
+    API_BEGIN
+    REQUIRE(n_boxes >= 0 && n_boxes <= (1 << 20) && line_off && ((boxes_xywh && slopes && rot) || n_boxes == 0), "bad arguments");
+    alloc_check();
+    std::vector<int64_t> mask_off((size_t)n_boxes + 1), row_off((size_t)n_boxes + 1), col_off((size_t)n_boxes + 1), prof_off((size_t)n_boxes + 1);
+    std::vector<int32_t> geom((size_t)n_boxes * 3);
+    std::vector<unsigned char> head_masks, head_split;
+    RegionLinesParams lp;
+    long long total_rows = 0;
+    if (region_line_masks_queue(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, slopes, true, mask_off.data(), row_off.data(), col_off.data(),
+                                head_masks, &lp, &total_rows)) return 1;
+    // rows and cols are one device array (cols behind rows): a region's profile is its row sums, or its column sums beyond 45 degrees
+    // (main.py:1514)
+    int64_t at = 0;
+    for (int r = 0; r < n_boxes; ++r) {
+        const int w = boxes_xywh[(size_t)r * 4 + 2], h = boxes_xywh[(size_t)r * 4 + 3], vertical = std::fabs(slopes[r]) > 45.0;
+        geom[(size_t)r * 3] = vertical ? w : h; geom[(size_t)r * 3 + 1] = vertical ? h : w; geom[(size_t)r * 3 + 2] = vertical;
+        prof_off[r] = at;
+        at += geom[(size_t)r * 3];
+    }
+    prof_off[n_boxes] = at;
+    if (check_line_split_tables(prof_off.data(), n_boxes, geom.data(), rot, weights, weight_off, sigma_max, line_off)) return 1;
+    if (n_boxes == 0) return 0;
+    REQUIRE(info && lines && corners && corners_rot, "bad arguments");
+    for (int r = 0; r < n_boxes; ++r) prof_off[r] = geom[(size_t)r * 3 + 2] ? total_rows + col_off[r] : row_off[r];
+    LineSplitParams p;
+    if (line_split_queue(c, lp.rows, prof_off.data(), n_boxes, geom.data(), rot, weights, weight_off, sigma_max, line_off, head_split, &p)) return 1;
+    return line_split_download(c, p, line_off, info, lines, corners, corners_rot);
+    API_END
+}
+
+int sbbseg_region_line_boxes(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                             const double* slopes, const double* rot, const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info,
+                             int64_t* line_off, int32_t* lines, int32_t* corners, int32_t* corners_rot)
+{
+    API_BEGIN
+    REQUIRE(H > 0 && W > 0 && n_boxes >= 0, "bad arguments");
+    if (n_boxes > 0) {
+        if (check_ready(c)) return 1;
+        REQUIRE(textline_hw, "bad arguments");
+        const size_t pix = (size_t)H * W;
+        if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
+        HIPCHK(hipMemcpyAsync(c->d_morph_b, textline_hw, pix, hipMemcpyHostToDevice, c->stream));
+    }
+    return sbbseg_region_line_boxes_dev(c, n_boxes > 0 ? c->d_morph_b : nullptr, H, W, boxes_xywh, n_boxes, erode_iterations, slopes, rot, weights,
+                                        weight_off, sigma_max, info, line_off, lines, corners, corners_rot);
     API_END
 }
 

@@ -420,6 +420,27 @@ struct ProfileStatParams {
     int32_t* winner;          // [n_regions]
 };
 hipError_t launch_profile_statistics(const ProfileStatParams& p, bool any_long, hipStream_t s);
+// the text lines of every region from its row or column sums (line_split.hip, line_split.h): one wave per region
+struct LineSplitRegion {
+    long long prof_off;       // first int of the region's profile
+    long long ws_off;         // n > kProfileLdsSamples: first byte of the region's line_work_bytes(n) workspace
+    int n, other, vertical;   // samples of the profile, the other extent of dst, 1 = seperate_lines_vertical
+    int line_off;             // first line of the region in the packed outputs
+    double rot[6];            // cos, -sin, sin, cos (main.py:524), M[0, 2], M[1, 2] (main.py:519-521)
+};
+struct LineSplitParams {
+    const int32_t* profiles;  // packed profiles (device)
+    const LineSplitRegion* regions;
+    int n_regions, sigma_max;
+    const double* weights;    // half kernels of sigma = 2 .. sigma_max
+    const long long* weight_off;
+    unsigned char* workspace;
+    int32_t* info;            // [n_regions][kLineInfoInts]
+    int32_t* pts;             // [lines][3] peak, point_up, point_down
+    int32_t* box;             // [lines][4][2]
+    int32_t* rot;             // [lines][4][2]
+};
+hipError_t launch_line_split(const LineSplitParams& p, bool any_long, hipStream_t s);      // 1 launch, 2 with a profile beyond kProfileLdsSamples
 hipError_t launch_replicate3(const uint8_t* src, uint8_t* dst, size_t n, hipStream_t s);
 hipError_t launch_to_f32(const void* src, float* dst, size_t n, int precision, hipStream_t s);
 hipError_t launch_deskew_profiles(const uint8_t* mask, int H, int W, int S, int top, int left, const double* minv, const float* cubic,

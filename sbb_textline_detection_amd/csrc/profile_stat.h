@@ -127,6 +127,31 @@ struct FlippedSamples {
     }
 };
 
+// The same two arrays for any pad (line_split.h: pad 20, main.py:544-556): y between `pad` zeros, n + 2 * pad samples ...
+struct PaddedSamplesP {
+    const int32_t* y;
+    int n, pad;
+    SBB_HD double operator()(int k) const
+    {
+        const int j = k - pad;
+        return ((unsigned)j < (unsigned)n) ? (double)y[j] : 0.0;
+    }
+};
+
+// ... and max(padded) - padded between another `pad` zeros on either side, n + 4 * pad samples
+struct FlippedSamplesP {
+    const int32_t* y;
+    int n, pad;
+    double top;                                                     // max(padded) = max(0, max(y))
+    SBB_HD double operator()(int k) const
+    {
+#pragma clang fp contract(off)
+        if (k < pad || k >= n + 3 * pad) return 0.0;
+        const int j = k - 2 * pad;
+        return top - (((unsigned)j < (unsigned)n) ? (double)y[j] : 0.0);
+    }
+};
+
 // one sample of scipy.ndimage.gaussian_filter1d(e, sigma) (correlate1d's symmetric branch): w[j] = the normalised weight at distance j
 template <class Samples>
 SBB_HD double smooth_sample(const Samples& e, int n, const double* w, int radius, int c)

@@ -278,6 +278,31 @@ def get_slopes_and_line_masks(textline_mask: np.ndarray, boxes, ctx=None, sigma_
     return slopes, ctx.region_line_masks_dev(d_plane, plane.shape[0], plane.shape[1], boxes, slopes, 2, masks)
 
 
+def get_line_boxes(textline_mask: np.ndarray, boxes, slopes, ctx=None):
+    """What ``textline_contours_postprocessing`` (main.py:1472-1524) gets from ``seperate_lines`` / ``seperate_lines_vertical`` for all
+    boxes of a page: ``get_line_masks``' steps and then the splitter of every box on its own projection, the projections staying on the
+    device (``sbbseg_region_line_boxes_dev``).  One record per box (``_capi.line_split_host``): status, sigma, raised, branch, peaks,
+    point_up, point_down, boxes, boxes_rot; ``boxes_rot`` is the reference's ``textline_boxes_rot``, [] where it returns [].
+    CAVEAT: the contour half (main.py:1492-1511) is not built, so every line has the reference's fallback x extent 0 .. w
+    (main.py:786-788), not the extent of the region's contour at the peak row; nothing approximates the contour."""
+    plane, boxes = _line_masks_args(textline_mask, boxes, slopes, ctx, "get_line_boxes")
+    if not boxes:
+        return []
+    return ctx.region_line_boxes_dev(ctx.stage(plane), plane.shape[0], plane.shape[1], boxes, [float(s) for s in slopes], 2)
+
+
+def get_slopes_and_line_boxes(textline_mask: np.ndarray, boxes, ctx=None, sigma_des: float = 2):
+    """``get_slopes`` and ``get_line_boxes`` with the slopes it found, the textline map staged ONCE for both: (slopes, line records)."""
+    plane, boxes = _line_masks_args(textline_mask, boxes, None, ctx, "get_slopes_and_line_boxes")
+    if not boxes:
+        return [], []
+    from . import _capi
+    d_plane = ctx.stage(plane)
+    weights = None if sigma_des == 2 else _capi.gaussian_weights(sigma_des)
+    slopes = ctx.region_deskew_slopes_dev(d_plane, plane.shape[0], plane.shape[1], boxes, 2, weights)
+    return slopes, ctx.region_line_boxes_dev(d_plane, plane.shape[0], plane.shape[1], boxes, slopes, 2)
+
+
 class InferenceStages:
     """The model-running part of ``textline_detector.run()`` (main.py:2056-2107)."""
 
@@ -482,6 +507,26 @@ class InferenceStages:
         if textlines is not None:
             self.line_masks = self.get_line_masks(textlines, boxes, slopes, masks=masks)
         return page_mask, regions, textlines, page_coord, boxes, slopes, self.line_masks
+
+    def get_line_boxes(self, textlines: np.ndarray, boxes, slopes):
+        """Per box the line record of ``get_line_boxes`` (main.py:516-1457 after the projection) on the textline model's handle."""
+        model, session = start_new_session_and_model(self.model_textline_dir, **self.kw)
+        try:
+            if not isinstance(model, SegModel):
+                raise RuntimeError("get_line_boxes needs a library handle (SegModel.ctx): there is no CPU fallback")
+            return get_line_boxes(textlines, boxes, slopes, model.ctx)
+        finally:
+            session.close()
+
+    def run_with_line_boxes(self, image_u8: np.ndarray, statistics: str = "device", masks: bool = True):
+        """``run_with_lines`` and the text lines of every box (``get_line_boxes``; x extent: the reference's fallback 0 .. w, the contour
+        is not built).  Returns run_with_lines' seven values plus the list of line records, also kept as ``self.line_boxes``; [] when
+        the textline model did not run."""
+        out = self.run_with_lines(image_u8, statistics=statistics, masks=masks)
+        self.line_boxes = []
+        if out[2] is not None:
+            self.line_boxes = self.get_line_boxes(out[2], out[4], out[5])
+        return out + (self.line_boxes,)
 
     def _run_resident(self):
         """run()'s three stages with the stored page uploaded ONCE and kept in device memory for all of them (run() hands the same
