@@ -1,4 +1,4 @@
-// api.hip -- host side of libsbbseg: the C ABI declared in include/sbbseg.h.
+// api.hip -- host side of libsbbseg: the C ABI declared in include/sbbseg.h, less its stage glue (stage_glue.hip; both sit on ctx.h).
 //
 // Holds the execution plan the Python planner builds (tensors + fused ops), owns all device
 // memory, packs weights into the kernels' contraction order, and drives the per-page pipeline
@@ -11,73 +11,20 @@
 
 #include <algorithm>
 #include <cmath>
-#include <new>
-#include <stdexcept>
-#include <string>
-#include <utility>
-#include <vector>
-
-#include "../../include/sbbseg.h"
-#include <dlfcn.h>
-
 #include <mutex>
 
-#include "internal.h"
-#include "region.h"
-#include "profile_stat.h"
-#include "line_mask.h"
-#include "line_split.h"
+#include <dlfcn.h>
+
+#include "ctx.h"
 
 using namespace sbbseg;
 
-namespace {
+namespace sbbseg {
 
 thread_local std::string g_err;
-
-int fail(const char* fmt, ...)
-{
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return 1;
-}
-
-#define HIPCHK(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);   \
-    } while (0)
-
-#define REQUIRE(cond, ...)                    \
-    do {                                      \
-        if (!(cond)) return fail(__VA_ARGS__); \
-    } while (0)
-
-// Every extern "C" body runs inside API_BEGIN / API_END: a C++ exception (std::bad_alloc from a std::vector, ...)
-// becomes a non-zero status + sbbseg_last_error() instead of terminating the caller's process -- the reference's
-// callers rely on ordinary Python exceptions (main.py:2061-2157).
-#define API_BEGIN try {
-#define API_END                                                                                     \
-    }                                                                                               \
-    catch (const std::bad_alloc&) { return fail("out of host memory (std::bad_alloc)"); }           \
-    catch (const std::exception& e_) { return fail("internal error: %s", e_.what()); }              \
-    catch (...) { return fail("unknown internal error"); }
-
-// test hook (sbbseg_debug_inject_alloc_failure): the n-th next alloc_check() throws std::bad_alloc
 int g_alloc_fail_countdown = 0;
-inline void alloc_check()
-{
-    if (g_alloc_fail_countdown > 0 && --g_alloc_fail_countdown == 0) throw std::bad_alloc();
-}
 
-}  // namespace
-
-namespace sbbseg {
-int set_error(const char* fmt, ...)                     // for the other translation units of the library (loader.cpp)
+int set_error(const char* fmt, ...)
 {
     char buf[1024];
     va_list ap;
@@ -87,246 +34,11 @@ int set_error(const char* fmt, ...)                     // for the other transla
     g_err = buf;
     return 1;
 }
-}  // namespace sbbseg
-
-namespace {
-
-struct Tensor {
-    int H = 0, W = 0, C = 0;
-    size_t elems_per_patch = 0;
-    char* buf = nullptr;          // zero header + data (of the lane in use)
-    char* lane_buf[2] = {nullptr, nullptr};
-    bool is_input_form = false;
-    int form = -1, pad = 0;
-    char* data() const { return buf + kZeroHeaderBytes; }
-};
-
-enum OpType { kConv = 0, kPool = 1, kHead = 2, kTail = 3, kBlock = 4 };
-
-struct ConvOp {
-    sbbseg_conv_desc d;
-    int Ho = 0, Wo = 0, TH = 0, TW = 0;
-    int cout_pad = 0, Ktot = 0, total_ksteps = 0, ksteps[2] = {0, 0};
-    KTabEntry* d_ktab = nullptr;
-    KStepRec* d_kstep = nullptr;
-    void* d_w = nullptr;
-    float *d_scale = nullptr, *d_shift = nullptr, *d_rscale = nullptr, *d_rshift = nullptr;
-    float *d_head_w = nullptr, *d_head_scale = nullptr, *d_head_shift = nullptr;
-    // further placement classes merged into this op (parity siblings); class 0 = the fields above
-    int n_cls = 1;
-    void* d_w_cls[4] = {nullptr, nullptr, nullptr, nullptr};
-    KStepRec* d_kstep_cls[4] = {nullptr, nullptr, nullptr, nullptr};
-    KTabEntry* d_ktab_cls[4] = {nullptr, nullptr, nullptr, nullptr};
-    int ooy_cls[4] = {0, 0, 0, 0}, oox_cls[4] = {0, 0, 0, 0};
-    float wmul_cls[4] = {1.f, 1.f, 1.f, 1.f};   // split mode: 2^-s of the class's power-of-two weight pre-scale
-    std::vector<float> h_epi;             // host copy of scale | shift | head_w | head_scale | head_shift: parity siblings are
-                                          // only merged into one launch when these are identical (they share class 0's)
-    uint16_t* d_stem_wfrag = nullptr;     // non-null: the op is the network stem and runs stem_conv_pairs
-    int fused_pool = -1;                  // split mode: index of the max-pool op this stem also computes (sbbseg_finalize), or -1
-    uint16_t* d_halo_wfrag = nullptr;     // split mode, the 224 x 224 decoder conv: the four classes' weights as MFMA A fragments (dec_halo_x3.hip)
-    int* d_halo_taps = nullptr;           //   ... and their taps in K-step order (sbbseg_finalize)
-    uint16_t* d_d64_wfrag = nullptr;      // non-null: 3x3 s1 64->64 conv, runs conv3x3_c64_direct
-    int fused_reduce = -1;                // split mode: index of the NEXT block's first 1x1 conv, computed by this (expand) conv's launch too
-                                          // (expand_reduce_x3.hip; sbbseg_finalize), or -1
-    uint16_t *d_er_w3 = nullptr, *d_er_w1 = nullptr;      //   ... the two convs' packed rows as MFMA A fragments
-    bool fused_into_expand = false;       // split mode: this op's output is written by the launch of the op before it; it launches nothing
-    int fused_conv3 = -1;                 // on an expand conv with fused_reduce: index of the block's 3x3 conv, which the same launch computes too
-                                          // (conv3_expand_reduce.hip; sbbseg_finalize), or -1
-    uint16_t* d_c3_w2 = nullptr;          //   ... the 3x3 conv's packed rows as MFMA A fragments, and its K-steps (taps / channel groups) in order
-    int* d_c3_k0 = nullptr;
-    bool fused_into_c3 = false;           // the 3x3 conv of such a block: its output tensor lives in LDS only, the op launches nothing
-    std::vector<float> h_w[2];            // host copy of a small 1x1 conv's weights ([cin][cout] per source): bottleneck fusion
-                                          // (sbbseg_finalize) repacks them as MFMA A fragments
-    bool fg_ok = true;                    // every K-step (of every class) regular: the fast gather of conv_igemm_mfma applies
-                                          // (ConvParams::fast_gather) if each source's taps also span at most 4 x 4 offsets
-    int tap_lo[2][2] = {{127, 127}, {127, 127}}, tap_hi[2][2] = {{-127, -127}, {-127, -127}};   // [source][y|x] over all classes
-    std::vector<KStepRec> h_ksteps_cls[4];   // host copies: sbbseg_finalize builds the fast gather's tables from them
-    FgStepRec* d_fgstep_cls[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool fg_pointwise = false;            // all taps (0, 0) in bounds: ConvParams::fast_gather = 2 (no masks)
-};
-
-struct PoolOp {
-    int src, dst, k, stride, Ho, Wo; float *d_pre_scale = nullptr, *d_pre_shift = nullptr; int pre_relu = 0;
-    bool fused_into_stem = false;         // split mode: the stem op before it writes this pool's output too (stem_pool_x3); the op then launches nothing
-};
-
-struct HeadOp {
-    int src, cin, classes;
-    float *d_w = nullptr, *d_scale = nullptr, *d_shift = nullptr;
-};
-
-struct TailOp {
-    int src0 = -1, img = -1, classes = 0;
-    void* d_wfrag = nullptr;
-    float *d_scale = nullptr, *d_shift = nullptr, *d_head_w = nullptr, *d_head_scale = nullptr, *d_head_shift = nullptr;
-};
-
-// a fused ResNet bottleneck block (bottleneck_fused): the three convs it replaces stay alive as `parts` of the op
-// (they own the scale / shift arrays and the 3x3 fragments the fused kernel reads, and they are what runs when the
-// fusion is switched off at run time, conv variant bit 18)
-struct BlockOp {
-    int x_tensor = -1, out_tensor = -1, cin = 0, proj = 0, H = 0, W = 0;
-    uint16_t *d_w1 = nullptr, *d_w3 = nullptr;
-    float wmul[3] = {1.f, 1.f, 1.f};      // split mode: 2^-s of the three convs' weight pre-scales
-};
-
-struct Op {
-    OpType type;
-    std::string name;
-    double flops = 0, min_bytes = 0;
-    double issued_flops = 0;      // MFMA work the kernel really issues per patch (K padding, pre-summed taps, 3x in split mode)
-    ConvOp conv;
-    PoolOp pool;
-    HeadOp head;
-    TailOp tail;
-    BlockOp block;
-    std::vector<Op> parts;        // kBlock: the convs it fuses
-    double prof_ms = 0;
-    int64_t prof_launches = 0, prof_patches = 0;
-    int region_level = -1;        // >= 0: a decoder level of the owned-region chain (sbbseg_finalize: region_chain; region.h)
-    double exec_patches = 0;      // work executed since sbbseg_profile_reset, in whole-patch equivalents: a launch of n patches adds n, an
-                                  // owned-region launch n x (pixels walked / pixels of the whole grid)
-    double prof_exec_patches = 0; // the same, over the launches the profiling events timed (prof_ms)
-};
-
-struct PendingEvent { int op; hipEvent_t a, b; int patches; double exec; };
-
-// owned-region launches (region.h): tables of the chunk a lane is running
-struct RegionRun {
-    bool on = false;
-    int kind[kRegionMaxLevels] = {0};            // 0 = tile table, 1 = pixel map (what the level's kernel takes: dec_halo_* / tail vs conv_igemm_mfma)
-    int total[kRegionMaxLevels] = {0};           // entries (per class)
-    double frac[kRegionMaxLevels] = {0};         // pixels walked / pixels of the whole grid, over the chunk
-    uint32_t* tab[kRegionMaxLevels] = {nullptr};
-};
-
-}  // namespace
-
-struct sbbseg_ctx {
-    int device = 0;
-    int precision = kBF16;
-    int elem = 2;                 // bytes per stored half-element (weights, one activation plane)
-    int planes = 1;               // 16-bit planes per activation element: 2 in the split mode (hi, lo), else 1
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    // second lane: its own activation buffers and stream; a chunk of tiles is split over the two lanes so
-    // that one half's launch tails (few tiles left, most CUs idle) are filled by the other half's kernels
-    hipStream_t lane_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int lanes = 2, lane1_batch = 0;
-    int lane_prio = 0, prio_least = 0, prio_greatest = 0;      // priority class of lane_stream (never the own stream's class: see sbbseg_create)
-    int in_H = 0, in_W = 0, in_C = 0;
-    std::vector<Tensor> tensors;
-    std::vector<Op> ops;
-    int form_tensor[2] = {-1, -1};
-    int classes = 0, max_batch = 0;
-    bool finalized = false;
-    size_t device_bytes = 0;
-    // run-time buffers
-    float* d_lut = nullptr;
-    unsigned* d_hist = nullptr;   // [256] channel-0 histogram + [1] Otsu threshold (int) behind it
-    int* d_tile_xy = nullptr;          // [max_batch][2]
-    uint8_t* d_batch_labels = nullptr; // [max_batch][H][W] (predict / whole-image path)
-    float* d_probs = nullptr;          // [max_batch][H][W][classes], lazily allocated
-    float* d_xin = nullptr;            // predict(): staged float input, lazily allocated
-    float* d_ks_ws = nullptr; size_t ks_ws_cap = 0;      // split-K partial sums (whole-image branch)
-    bool ksplit = true, ksplit_now = false;              // SBBSEG_KSPLIT=0 switches it off; _now: inside the whole-image branch's run_plan
-    uint8_t* d_page = nullptr; size_t page_cap = 0;
-    uint8_t* d_page_labels = nullptr; size_t page_labels_cap = 0;
-    uint8_t* d_page_labels3 = nullptr; size_t page_labels3_cap = 0;   // 3-channel copy for label_channels == 3
-    int label_channels = 1;
-    uint8_t* d_tile_labels = nullptr; size_t tile_labels_cap = 0;
-    int *d_own_x = nullptr, *d_own_y = nullptr; size_t own_cap = 0;
-    int own_Hp = -1, own_Wp = -1, own_nyf = 0;
-    bool own_dedupe = false;          // the cached owner tables index the deduplicated grid (see fused_grid)
-    // Duplicate clamped tiles: when extent % mid lies in (0, tile - mid] the inward clamp (main.py:276-281) gives the LAST
-    // TWO tiles of an axis the same origin -- the reference runs the same forward twice and pastes the same labels twice.  The fused
-    // page paths skip the repeat (same label map, 1 / n of the forwards of that axis saved); the tile-indexed entry points
-    // (sbbseg_tile_grid, _segment_tile_range_dev, _stitch_dev: the multi-rank protocol) keep the reference's call list.
-    bool dedupe = true;               // sbbseg_set_dedupe / SBBSEG_DEDUPE=0
-    int64_t forwards = 0;             // patches run through the plan so far (sbbseg_debug_counter 1)
-    int *d_map = nullptr; size_t map_cap = 0;
-    int *d_wmap = nullptr; size_t wmap_cap = 0;      // gather tables of the whole-image branch, cached per geometry
-    int wmap_key[6] = {0, 0, 0, 0, 0, 0};            // {Hp, Wp, Hs, Ws, out_h, out_w} (0 = none)
-    int map_key[4] = {0, 0, 0, 0};     // {Hs, Ws, Hp, Wp} the nearest maps in d_map were built for (sbbseg_segment_crop_dev; 0 = none)
-    // stage glue scratch (morphology planes, union-find arrays, result words)
-    uint8_t *d_morph_a = nullptr, *d_morph_b = nullptr; size_t morph_a_cap = 0, morph_b_cap = 0;
-    // pipelined multi-page host path (sbbseg_segment_pages): copy streams, two slots of pinned staging + device buffers
-    hipStream_t copy_in = nullptr, copy_out = nullptr;
-    hipEvent_t pp_in[2] = {nullptr, nullptr}, pp_comp[2] = {nullptr, nullptr}, pp_out[2] = {nullptr, nullptr};
-    uint8_t *pp_h_in[2] = {nullptr, nullptr}, *pp_h_out[2] = {nullptr, nullptr}, *pp_d_in[2] = {nullptr, nullptr}, *pp_d_out[2] = {nullptr, nullptr},
-            *pp_d_out3[2] = {nullptr, nullptr};
-    size_t pp_in_cap = 0, pp_out_cap = 0, pp_out3_cap = 0;        // device buffers (bytes each)
-    size_t pp_hin_cap = 0, pp_hout_cap = 0;                       // pinned host staging (bytes each)
-    bool pp_ready = false;                                        // streams + events of the page pipeline exist
-    // RCCL communicator of the sharded path (sbbseg_comm_init; librccl is dlopen'ed on first use)
-    void* comm = nullptr;
-    int comm_rank = 0, comm_world = 1;
-    void* d_deskew = nullptr; size_t deskew_cap = 0;      // inverse maps | bicubic table | row counts of sbbseg_deskew_profiles
-    // sbbseg_run_page's resident buffers (owned by the handle passed as `border` / `layout` / `textline` respectively)
-    uint8_t *d_run_page = nullptr, *d_run_mask = nullptr, *d_run_a = nullptr, *d_run_b = nullptr;
-    size_t run_page_cap = 0, run_mask_cap = 0, run_a_cap = 0, run_b_cap = 0;
-    int *d_cc_parent = nullptr, *d_cc_count = nullptr; size_t cc_parent_cap = 0, cc_count_cap = 0;
-    bool force_host_contours = false;     // test hook (conv variant bit 21): always take the exact host ranking
-    int host_contour_calls = 0;           // how often the exact host ranking ran (sbbseg_debug_counter)
-    int* d_cc_list = nullptr;             // [6 + kCcMaxRivals]: launch_largest_contour's result record
-    int* d_cc_aux = nullptr; size_t cc_aux_cap = 0;      // five int planes: doubled cell area + bounding boxes per root (sbbseg_page_box_dev)
-    unsigned long long* d_cc_small = nullptr;      // [0] best key, [1..2] box (4 ints)
-    int* d_cc_bg = nullptr; size_t cc_bg_cap = 0;        // two int planes: labels of the complement, border flags (sbbseg_text_region_boxes_dev)
-    int* d_cc_roots = nullptr; size_t cc_roots_cap = 0;  // parentless roots, 6 ints each
-    void* d_rdk = nullptr; size_t rdk_cap = 0;           // sbbseg_region_deskew_profiles_dev: maps | table | geometry | crops | counts
-    void* d_pstat = nullptr; size_t pstat_cap = 0;       // sbbseg_profile_statistics_dev: weights | regions | spread | winner | state | workspace
-    long long line_launches = 0;                         // kernels queued by sbbseg_region_line_masks_dev (sbbseg_debug_counter 2)
-    void* d_lsplit = nullptr; size_t lsplit_cap = 0;     // sbbseg_line_split_dev: regions | info | lines | corners | rotated corners | workspace
-    void* d_line_w = nullptr; size_t line_w_cap = 0;     // ... its table of half Gaussian kernels: offsets | weights, uploaded when it differs from
-    std::vector<double> line_w_host;                     // ... this copy of the last one
-    int16_t* d_line_tab = nullptr;                       // sbbseg_region_line_masks_dev: the fixed-point bicubic table, built on first use
-    // profiling
-    bool profiling = false;
-    int conv_variant = 0;
-    bool ph8 = false;            // 8-phase schedule on the 256x256 tile (opt-in, conv variant bit 16)
-    int fg_min_ksteps = 9;             // convs with real taps take the fast gather from this many K-steps on (SBBSEG_FG_MIN)
-    int fg_pointwise_min_ksteps = 4;   // pointwise convs take the fast gather from this many K-steps on (SBBSEG_FG_POINTWISE_MIN)
-    bool ranged_walk = false;    // A/B: grouped launches walk XCD-contiguous tile ranges (conv variant bit 19)
-    bool block_pq = true;        // fused bottleneck blocks run the producer / consumer form (conv variant bit 20: the one-group form)
-    bool unfuse_blocks = false;  // A/B: run a fused bottleneck block as its three convs (conv variant bit 18)
-    bool unfuse_stem_pool = false;     // A/B: stem and max-pool as two launches (conv variant bit 22)
-    bool no_dec_halo = false;          // A/B: the 224 x 224 decoder conv on the generic kernel (conv variant bit 23)
-    bool no_expand_reduce = false;     // A/B: expand + next reduce 1x1 convs as two launches (conv variant bit 24)
-    bool no_c3er = false;              // A/B: the 3x3 conv of a stage-3 identity block as its own launch in front of expand_reduce (conv variant bit 25)
-    bool plain_gather = false;   // A/B: per-load address arithmetic instead of the fast gather (conv variant bit 17)
-    int contig_max_k = 0;        // short-K layers up to this K walk their tiles in per-block contiguous runs (tile map 2)
-    int fused_heads = 0;
-    int num_cus = 256;
-    std::vector<PendingEvent> pending;
-    std::vector<hipEvent_t> free_events;
-    // owned-region launches of the decoder (region.h; sbbseg_set_owned_regions): 0 = off, 1 = the fused page paths (default), 2 = the
-    // tile-range entry points of the multi-rank protocol too (their tile labels are then defined on the owned regions only)
-    int owned_mode = 1;
-    int region_levels = 0;                        // decoder levels of the chain found by sbbseg_finalize (0: the plan has none)
-    int region_op[kRegionMaxLevels] = {0};        // op index per level (level 0 = the tail)
-    uint32_t* d_rtab[2][kRegionMaxLevels] = {{nullptr}, {nullptr}};     // per lane and level: the chunk's table (allocated on first use)
-    size_t rtab_cap[2][kRegionMaxLevels] = {{0}, {0}};
-    RegionRun rr;                                 // the chunk run_plan is launching (set by tile_range_impl around run_plan)
-    double last_exec_frac = 1.0;                  // share of its output grid the op being launched walks (run_plan's accounting; launch_op resets
-                                                  // it to 1 when an A/B knob takes a level off its owned-region form)
-    std::vector<std::pair<void*, size_t>> user_bufs;      // sbbseg_device_alloc's buffers still alive (freed by sbbseg_destroy)
-};
-
-namespace {
 
 int dmalloc(sbbseg_ctx* c, void** p, size_t bytes)
 {
     HIPCHK(hipMalloc(p, bytes));
     c->device_bytes += bytes;
-    return 0;
-}
-
-template <typename T>
-int upload(sbbseg_ctx* c, T** dptr, const T* host, size_t n)
-{
-    if (dmalloc(c, (void**)dptr, n * sizeof(T))) return 1;
-    HIPCHK(hipMemcpy(*dptr, host, n * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -337,13 +49,24 @@ int ensure(sbbseg_ctx* c, void** p, size_t* cap, size_t bytes)
         HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(hipFree(*p));
         c->device_bytes -= *cap;
-        *p = nullptr;
-        *cap = 0;
+        *p = nullptr; *cap = 0;
     }
     if (dmalloc(c, p, bytes)) return 1;
     *cap = bytes;
     return 0;
 }
+
+int check_ready(sbbseg_ctx* c)
+{
+    REQUIRE(c != nullptr, "null handle");
+    REQUIRE(c->finalized, "plan not finalized");
+    HIPCHK(hipSetDevice(c->device));
+    return 0;
+}
+
+}  // namespace sbbseg
+
+namespace {
 
 int margin_of(int W) { return (int)(0.1 * (double)W); }   // main.py:233  int(0.1 * img_width_model)
 
@@ -731,7 +454,7 @@ int rccl_load()
     a.GetErrorString = (const char* (*)(int))dlsym(h, "ncclGetErrorString");
     if (!a.GetUniqueId || !a.CommInitRank || !a.CommDestroy || !a.AllGather || !a.GetErrorString) {
         dlclose(h);
-        return fail("librccl lacks an expected symbol (ncclGetUniqueId / ncclCommInitRank / ncclCommDestroy / ncclAllGather)");
+        return set_error("librccl lacks an expected symbol (ncclGetUniqueId / ncclCommInitRank / ncclCommDestroy / ncclAllGather)");
     }
     a.lib = h;
     g_rccl = a;
@@ -740,101 +463,13 @@ int rccl_load()
 #define RCCLCHK(expr)                                                                              \
     do {                                                                                           \
         const int r_ = (expr);                                                                     \
-        if (r_ != 0) return fail("%s failed: %s", #expr, g_rccl.GetErrorString(r_));              \
+        if (r_ != 0) return set_error("%s failed: %s", #expr, g_rccl.GetErrorString(r_));          \
     } while (0)
 
 void comm_release(sbbseg_ctx* c)
 {
     if (c->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(c->comm);
     c->comm = nullptr; c->comm_rank = 0; c->comm_world = 1;
-}
-
-// ---- extract_page's ranking, exact, on the host (main.py:398-404): cv2.findContours(RETR_TREE) + cv2.contourArea + np.argmax.
-// Only the OUTER contour of a component can win (a hole's contour lies inside it), so: label the 8-connected components, trace
-// each one's outer border through its boundary pixels (Moore neighbour tracing from the first pixel in raster order, whose
-// west / north neighbours are background; stop when the start pixel is re-entered in the start direction), shoelace area of
-// that closed chain (CHAIN_APPROX_SIMPLE drops collinear points only: same area).  Ties: the LAST component in raster order of
-// first pixels (round 4) [EXT, restated from OpenCV's contours.cpp, unpinned: the border-following scanner discovers outer borders
-// in raster order and cvInsertNodeIntoTree puts each new contour at the HEAD of its parent's child list, so the list findContours
-// returns runs in REVERSE discovery order and np.argmax's "first maximum" (main.py:400-401) is the last one discovered].
-// Returns {x0, y0, x1, y1, pixels}; false for an empty mask.
-// Doubled shoelace area of the outer border of the component `inside` describes, walked from its first pixel in raster order
-// (sy, sx) -- whose west / north neighbours are background -- by Moore neighbour tracing, clockwise with y pointing down; stops
-// when the start pixel is left again in the first direction.  box = {x0, y0, x1, y1} of the border (= of the component).
-template <typename Inside>
-long long trace_outer_area2(Inside inside, int sy, int sx, long n_pixels, int (&box)[4])
-{
-    static const int dx8[8] = {1, 1, 0, -1, -1, -1, 0, 1}, dy8[8] = {0, 1, 1, 1, 0, -1, -1, -1};      // E, SE, S, SW, W, NW, N, NE
-    long long area2 = 0;
-    int cy = sy, cx = sx, back = 4, first_dir = -1;              // back: direction of the background pixel the search resumes after (W)
-    box[0] = box[2] = sx; box[1] = box[3] = sy;
-    for (long guard = 0; guard < 4 * n_pixels + 8; ++guard) {
-        int d = -1;
-        for (int k = 1; k <= 8; ++k) {                           // clockwise from the backtrack direction
-            const int dd = (back + k) & 7;
-            if (inside(cy + dy8[dd], cx + dx8[dd])) { d = dd; break; }
-        }
-        if (d < 0) break;                                        // isolated pixel: area 0
-        if (cy == sy && cx == sx) {
-            if (first_dir < 0) first_dir = d;
-            else if (d == first_dir) break;                      // back at the start, leaving the same way: closed
-        }
-        const int ny = cy + dy8[d], nx = cx + dx8[d];
-        area2 += (long long)cx * ny - (long long)nx * cy;
-        cy = ny; cx = nx;
-        box[0] = cx < box[0] ? cx : box[0]; box[2] = cx > box[2] ? cx : box[2];
-        box[1] = cy < box[1] ? cy : box[1]; box[3] = cy > box[3] ? cy : box[3];
-        // the neighbour examined just before (direction d - 1 from the old pixel) is background; seen from the new pixel it
-        // lies in direction d + 6 (axis step) or d + 5 (diagonal step): the next search resumes right after it
-        back = (d + ((d & 1) ? 5 : 6)) & 7;
-    }
-    return area2 < 0 ? -area2 : area2;
-}
-
-bool host_largest_contour(const uint8_t* m, int H, int W, int (&out)[5], long long* area2_out = nullptr)
-{
-    const long n = (long)H * W;
-    std::vector<int> lab(n, -1);
-    std::vector<long> stack;
-    static const int dx8[8] = {1, 1, 0, -1, -1, -1, 0, 1}, dy8[8] = {0, 1, 1, 1, 0, -1, -1, -1};
-    long long best_area2 = -1;
-    int n_comp = 0;
-    for (long s = 0; s < n; ++s) {
-        if (!m[s] || lab[s] >= 0) continue;
-        // flood the component; box and pixel count on the way
-        const int id = n_comp++;
-        int x0 = W, y0 = H, x1 = -1, y1 = -1, cnt = 0;
-        stack.clear();
-        stack.push_back(s);
-        lab[s] = id;
-        while (!stack.empty()) {
-            const long i = stack.back();
-            stack.pop_back();
-            const int y = (int)(i / W), x = (int)(i - (long)y * W);
-            ++cnt;
-            x0 = x < x0 ? x : x0; x1 = x > x1 ? x : x1; y0 = y < y0 ? y : y0; y1 = y > y1 ? y : y1;
-            for (int d = 0; d < 8; ++d) {
-                const int yy = y + dy8[d], xx = x + dx8[d];
-                if ((unsigned)yy >= (unsigned)H || (unsigned)xx >= (unsigned)W) continue;
-                const long j = (long)yy * W + xx;
-                if (m[j] && lab[j] < 0) { lab[j] = id; stack.push_back(j); }
-            }
-        }
-        auto inside = [&](int y, int x) { return (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W && lab[(long)y * W + x] == id; };
-        int tb[4];
-        const long long area2 = trace_outer_area2(inside, (int)(s / W), (int)(s - (long)(s / W) * W), n, tb);
-        if (area2 >= best_area2) { best_area2 = area2; out[0] = x0; out[1] = y0; out[2] = x1; out[3] = y1; out[4] = cnt; }   // ties: the later one
-    }
-    if (area2_out) *area2_out = best_area2 < 0 ? 0 : best_area2;
-    return n_comp > 0;
-}
-
-int check_ready(sbbseg_ctx* c)
-{
-    REQUIRE(c != nullptr, "null handle");
-    REQUIRE(c->finalized, "plan not finalized");
-    HIPCHK(hipSetDevice(c->device));
-    return 0;
 }
 
 }  // namespace
@@ -877,7 +512,7 @@ int sbbseg_create(int device, int precision, sbbseg_ctx** out)
     hipError_t e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
-        return fail("hipStreamCreate failed: %s", hipGetErrorString(e));
+        return set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
     }
     c->stream = c->own_stream;
     // The second lane's stream is created in ANOTHER PRIORITY CLASS than the handle's own stream.  HIP multiplexes streams onto a few
@@ -898,7 +533,7 @@ int sbbseg_create(int device, int precision, sbbseg_ctx** out)
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming);
     if (e != hipSuccess) {
         sbbseg_destroy(c);
-        return fail("lane stream/event creation failed: %s", hipGetErrorString(e));
+        return set_error("lane stream/event creation failed: %s", hipGetErrorString(e));
     }
     if (const char* v = getenv("SBBSEG_DEDUPE")) c->dedupe = v[0] != '0';
     if (const char* v = getenv("SBBSEG_KSPLIT")) c->ksplit = v[0] != '0';
@@ -2925,245 +2560,6 @@ int sbbseg_segment_whole_scaled(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, 
     API_END
 }
 
-// ------------------------------------------------------------------------------ stage glue (8f-3)
-int sbbseg_morph_dev(sbbseg_ctx* c, const void* d_src_hw, int H, int W, int op, int ksize, int iterations, void* d_dst_hw)
-{
-    API_BEGIN
-    if (check_ready(c)) return 1;
-    REQUIRE(d_src_hw && d_dst_hw && H > 0 && W > 0, "bad arguments");
-    REQUIRE((op == SBBSEG_MORPH_ERODE || op == SBBSEG_MORPH_DILATE) && ksize >= 1 && (ksize & 1) && iterations >= 1, "morph: op 0|1, odd kernel, iterations >= 1");
-    const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_morph_a, &c->morph_a_cap, pix)) return 1;
-    HIPCHK(launch_morph((const uint8_t*)d_src_hw, c->d_morph_a, (uint8_t*)d_dst_hw, H, W, (ksize - 1) / 2 * iterations, op == SBBSEG_MORPH_DILATE, 0, c->stream));
-    return 0;
-    API_END
-}
-
-int sbbseg_morph(sbbseg_ctx* c, const uint8_t* src_hw, int H, int W, int op, int ksize, int iterations, uint8_t* dst_hw)
-{
-    API_BEGIN
-    if (check_ready(c)) return 1;
-    REQUIRE(src_hw && dst_hw && H > 0 && W > 0, "bad arguments");
-    const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
-    HIPCHK(hipMemcpyAsync(c->d_morph_b, src_hw, pix, hipMemcpyHostToDevice, c->stream));
-    if (sbbseg_morph_dev(c, c->d_morph_b, H, W, op, ksize, iterations, c->d_morph_b)) return 1;
-    HIPCHK(hipMemcpyAsync(dst_hw, c->d_morph_b, pix, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-    API_END
-}
-
-// The contour ranking behind sbbseg_page_box_dev and sbbseg_text_regions_present_dev: 8-connected components of the 0 / 255 plane in
-// c->d_morph_b, ranked by the area of their outer contour (cv2.contourArea of cv2.findContours' outer borders).  The device ranks by a
-// lower bound of that area and checks the winner against every other component's bounding-box bound (launch_largest_contour); when
-// that leaves the ranking open -- or when the caller needs the winner's EXACT area (`exact`) -- the host walks the outer borders of
-// the candidates on the device's label plane (parent[i] = root = the component's first pixel in raster order): 4 bytes per pixel of
-// D2H + the candidates' perimeters.  box = {x0, y0, x1, y1, pixels} of the winner; *any = false for an empty plane; *area2 = twice the
-// winner's contour area (exact when traced, else the device's lower bound; *traced says which).
-// exact_below2: trace on the host (exact area) also when the device's lower bound of TWICE the winner's area is below this -- the caller's
-// threshold: one labelling pass and one copy of the label plane decide "too small", not two
-static int rank_contours(sbbseg_ctx* c, int H, int W, bool exact, int (&box)[5], bool* any, long long* area2, bool* traced, double exact_below2 = -1.0)
-{
-    const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_cc_parent, &c->cc_parent_cap, pix * sizeof(int)) || ensure(c, (void**)&c->d_cc_count, &c->cc_count_cap, pix * sizeof(int))) return 1;
-    if (ensure(c, (void**)&c->d_cc_aux, &c->cc_aux_cap, 5 * pix * sizeof(int))) return 1;
-    if (!c->d_cc_small && dmalloc(c, (void**)&c->d_cc_small, 4 * sizeof(unsigned long long))) return 1;
-    if (!c->d_cc_list && dmalloc(c, (void**)&c->d_cc_list, (6 + kCcMaxRivals) * sizeof(int))) return 1;
-    int* d_out = c->d_cc_list;
-    int* aux = c->d_cc_aux;
-    HIPCHK(launch_largest_contour(c->d_morph_b, H, W, c->d_cc_parent, c->d_cc_count, aux, aux + pix, aux + 2 * pix, aux + 3 * pix, aux + 4 * pix,
-                                  c->d_cc_small, d_out, c->stream));
-    int out[6 + kCcMaxRivals];
-    unsigned long long key = 0;
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&key, c->d_cc_small, sizeof(key), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int q = 0; q < 5; ++q) box[q] = out[q];
-    *any = out[2] >= 0;
-    *area2 = (long long)(key >> 32);
-    *traced = false;
-    if (*any && (out[5] > 0 || exact || c->force_host_contours || (double)*area2 < exact_below2)) {
-        alloc_check();
-        std::vector<int> lab(pix);
-        HIPCHK(hipMemcpy(lab.data(), c->d_cc_parent, pix * sizeof(int), hipMemcpyDeviceToHost));
-        std::vector<int> cand;
-        cand.push_back((int)((unsigned)(key & 0xffffffffu) - 1u));
-        if (out[5] <= kCcMaxRivals && !c->force_host_contours) cand.insert(cand.end(), out + 6, out + 6 + out[5]);
-        else
-            for (size_t i = 0; i < pix; ++i)
-                if (lab[i] == (int)i && (int)i != cand[0]) cand.push_back((int)i);          // every root
-        long long best_area2 = -1;
-        int best_root = -1;
-        for (int root : cand) {
-            auto inside = [&](int y, int x) { return (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W && lab[(size_t)y * W + x] == root; };
-            int tb[4];
-            const long long a2 = trace_outer_area2(inside, root / W, root % W, (long)pix, tb);
-            if (a2 > best_area2 || (a2 == best_area2 && root > best_root)) {           // ties: the later root (see host_largest_contour)
-                best_area2 = a2; best_root = root;
-                box[0] = tb[0]; box[1] = tb[1]; box[2] = tb[2]; box[3] = tb[3];
-            }
-        }
-        HIPCHK(hipMemcpy(&box[4], c->d_cc_count + best_root, sizeof(int), hipMemcpyDeviceToHost));
-        c->host_contour_calls += 1;
-        *area2 = best_area2;
-        *traced = true;
-    }
-    return 0;
-}
-
-int sbbseg_page_box_dev(sbbseg_ctx* c, const void* d_mask_hw, int H, int W, int32_t* box_xywh, int64_t* pixels)
-{
-    API_BEGIN
-    if (check_ready(c)) return 1;
-    REQUIRE(d_mask_hw && box_xywh && H > 0 && W > 0, "bad arguments");
-    REQUIRE((size_t)H * W < ((size_t)1 << 31), "mask too large for 32-bit pixel indices");
-    const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_morph_a, &c->morph_a_cap, pix) || ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
-    // main.py:394-398: gray > 0 -> 255, dilate with the 5x5 kernel of ones, 6 iterations (= one clipped 25x25 maximum)
-    HIPCHK(launch_morph((const uint8_t*)d_mask_hw, c->d_morph_a, c->d_morph_b, H, W, 12, 1, 1, c->stream));
-    // main.py:398-404: the contour with the largest cv2.contourArea
-    int box[5];
-    bool any = false, traced = false;
-    long long area2 = 0;
-    if (rank_contours(c, H, W, false, box, &any, &area2, &traced)) return 1;
-    if (pixels) *pixels = any ? (int64_t)box[4] : 0;
-    if (!any) {                                        // empty mask: the reference's np.argmax of an empty list raises (main.py:399-401)
-        box_xywh[0] = box_xywh[1] = box_xywh[2] = box_xywh[3] = 0;
-        return 0;
-    }
-    box_xywh[0] = box[0]; box_xywh[1] = box[1]; box_xywh[2] = box[2] - box[0] + 1; box_xywh[3] = box[3] - box[1] + 1;   // cv2.boundingRect
-    return 0;
-    API_END
-}
-
-// get_text_region_contours_and_boxes' EXISTENCE test (main.py:456-480, the `if len(contours) > 0` that gates the textline model,
-// main.py:2083-2096): class mask (all channels == label -> 255), MORPH_OPEN, MORPH_CLOSE with the 5x5 kernel, findContours(RETR_TREE),
-// keep the contours without a parent whose polygon area lies in [min_area, max_area = 1] x H x W.  After OPEN and CLOSE every
-// component and every hole is a union of 5x5 squares, so no contour has fewer than three points (the `jv` bookkeeping of
-// filter_contours_area_of_image, main.py:81-91, never drifts), and the largest outer contour of the plane is always a parentless one
-// (a component nested in a hole is smaller than the component around it): contours exist <=> the largest outer-contour area
-// reaches min_area * H * W.  The boxes: sbbseg_text_region_boxes_dev below; the polygons are out of scope.
-int sbbseg_text_regions_present_dev(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, double min_area, int* present)
-{
-    API_BEGIN
-    if (check_ready(c)) return 1;
-    REQUIRE(d_regions_hw && present && H > 0 && W > 0 && label >= 0 && label <= 255 && min_area >= 0.0, "bad arguments");
-    REQUIRE((size_t)H * W < ((size_t)1 << 31), "plane too large for 32-bit pixel indices");
-    const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_morph_a, &c->morph_a_cap, pix) || ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
-    // OPEN = erode, dilate; CLOSE = dilate, erode (cv2.morphologyEx, one iteration each, default border: outside pixels never win);
-    // the two dilations in a row are one clipped 9x9 maximum
-    HIPCHK(launch_morph((const uint8_t*)d_regions_hw, c->d_morph_a, c->d_morph_b, H, W, 2, 0, 0x100 | label, c->stream));
-    HIPCHK(launch_morph(c->d_morph_b, c->d_morph_a, c->d_morph_b, H, W, 4, 1, 0, c->stream));
-    HIPCHK(launch_morph(c->d_morph_b, c->d_morph_a, c->d_morph_b, H, W, 2, 0, 0, c->stream));
-    const double need = min_area * (double)((long long)H * W);            // main.py:87: area >= min_area * np.prod(image.shape[:2])
-    int box[5];
-    bool any = false, traced = false;
-    long long area2 = 0;
-    // the device's figure is a lower bound (holes not filled): only the exact area can say "too small" -- traced in the same pass
-    if (rank_contours(c, H, W, false, box, &any, &area2, &traced, 2.0 * need)) return 1;
-    *present = (any && (double)area2 * 0.5 >= need) ? 1 : 0;
-    return 0;
-    API_END
-}
-
-// get_text_region_contours_and_boxes' BOXES (main.py:456-480, `self.boxes`): the same front end as the existence test above, then
-// cv2.boundingRect of every contour that filter_contours_area_of_image keeps -- a component without a parent (launch_parentless_roots)
-// whose outer-contour area lies in [min_area, max_area] x H x W.  The device has a lower bound of that area per root (cells of the
-// component as it is) and the bounding-box upper bound (w - 1)(h - 1); only a component the two bounds leave undecided is traced on the
-// host (trace_outer_area2 on the label plane, as rank_contours does).  Order [EXT, unpinned]: the component's first pixel in raster order,
-// DESCENDING -- the reverse discovery order that OpenCV's contour list is assumed to have (see host_largest_contour).  Nothing downstream
-// of the boxes depends on it: slopes are per box.
-int sbbseg_text_region_boxes_dev(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, double min_area, double max_area,
-                                 int32_t* boxes_xywh, int cap, int* n_boxes)
-{
-    API_BEGIN
-    if (check_ready(c)) return 1;
-    REQUIRE(d_regions_hw && n_boxes && H > 0 && W > 0 && label >= 0 && label <= 255 && min_area >= 0.0 && max_area >= min_area && cap >= 0 &&
-                (boxes_xywh || cap == 0), "bad arguments");
-    REQUIRE((size_t)H * W < ((size_t)1 << 31), "plane too large for 32-bit pixel indices");
-    const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_morph_a, &c->morph_a_cap, pix) || ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
-    if (ensure(c, (void**)&c->d_cc_parent, &c->cc_parent_cap, pix * sizeof(int)) || ensure(c, (void**)&c->d_cc_count, &c->cc_count_cap, pix * sizeof(int))) return 1;
-    if (ensure(c, (void**)&c->d_cc_aux, &c->cc_aux_cap, 5 * pix * sizeof(int)) || ensure(c, (void**)&c->d_cc_bg, &c->cc_bg_cap, 2 * pix * sizeof(int))) return 1;
-    if (!c->d_cc_small && dmalloc(c, (void**)&c->d_cc_small, 4 * sizeof(unsigned long long))) return 1;
-    if (!c->d_cc_list && dmalloc(c, (void**)&c->d_cc_list, (6 + kCcMaxRivals) * sizeof(int))) return 1;
-    // after OPEN + CLOSE a component holds a whole 5x5 square (planes narrower than the kernel: no such bound)
-    const size_t list_cap = (H >= 5 && W >= 5) ? pix / 25 + 16 : pix;
-    if (ensure(c, (void**)&c->d_cc_roots, &c->cc_roots_cap, list_cap * 6 * sizeof(int))) return 1;
-    HIPCHK(launch_morph((const uint8_t*)d_regions_hw, c->d_morph_a, c->d_morph_b, H, W, 2, 0, 0x100 | label, c->stream));
-    HIPCHK(launch_morph(c->d_morph_b, c->d_morph_a, c->d_morph_b, H, W, 4, 1, 0, c->stream));
-    HIPCHK(launch_morph(c->d_morph_b, c->d_morph_a, c->d_morph_b, H, W, 2, 0, 0, c->stream));
-    int* aux = c->d_cc_aux;
-    HIPCHK(launch_largest_contour(c->d_morph_b, H, W, c->d_cc_parent, c->d_cc_count, aux, aux + pix, aux + 2 * pix, aux + 3 * pix, aux + 4 * pix,
-                                  c->d_cc_small, c->d_cc_list, c->stream));
-    int* d_n = (int*)(c->d_cc_small + 2);
-    HIPCHK(launch_parentless_roots(c->d_morph_b, c->d_morph_a, H, W, c->d_cc_parent, c->d_cc_bg, c->d_cc_count, aux, aux + pix, aux + 2 * pix,
-                                   aux + 3 * pix, aux + 4 * pix, d_n, c->d_cc_roots, (int)list_cap, c->stream));
-    int found = 0;
-    HIPCHK(hipMemcpyAsync(&found, d_n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    REQUIRE(found >= 0 && (size_t)found <= list_cap, "internal error: %d parentless components, room for %zu", found, list_cap);
-    alloc_check();
-    struct Root { int root, x0, y0, x1, y1, lower2; };
-    std::vector<Root> roots((size_t)found);
-    if (found) HIPCHK(hipMemcpy(roots.data(), c->d_cc_roots, (size_t)found * sizeof(Root), hipMemcpyDeviceToHost));
-    std::sort(roots.begin(), roots.end(), [](const Root& a, const Root& b) { return a.root > b.root; });
-    // main.py:87: area >= min_area * np.prod(image.shape[:2]) and area <= max_area * np.prod(image.shape[:2])
-    const double lo = min_area * (double)((long long)H * W), hi = max_area * (double)((long long)H * W);
-    std::vector<int> state((size_t)found);                     // 1 keep, 0 drop, 2 undecided
-    bool trace = false;
-    for (int k = 0; k < found; ++k) {
-        const Root& r = roots[k];
-        const double lower = (double)r.lower2 * 0.5, upper = (double)(r.x1 - r.x0) * (double)(r.y1 - r.y0);
-        if (c->force_host_contours) state[k] = 2;
-        else if (upper < lo || lower > hi) state[k] = 0;
-        else if (lower >= lo && upper <= hi) state[k] = 1;
-        else state[k] = 2;
-        trace = trace || state[k] == 2;
-    }
-    if (trace) {
-        std::vector<int> lab(pix);
-        HIPCHK(hipMemcpy(lab.data(), c->d_cc_parent, pix * sizeof(int), hipMemcpyDeviceToHost));
-        for (int k = 0; k < found; ++k) {
-            if (state[k] != 2) continue;
-            const int root = roots[k].root;
-            auto inside = [&](int y, int x) { return (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W && lab[(size_t)y * W + x] == root; };
-            int tb[4];
-            const double area = (double)trace_outer_area2(inside, root / W, root % W, (long)pix, tb) * 0.5;
-            state[k] = (area >= lo && area <= hi) ? 1 : 0;
-        }
-        c->host_contour_calls += 1;
-    }
-    int kept = 0;
-    for (int k = 0; k < found; ++k) {
-        if (state[k] != 1) continue;
-        if (kept < cap) {
-            const Root& r = roots[k];
-            int32_t* o = boxes_xywh + (size_t)kept * 4;
-            o[0] = r.x0; o[1] = r.y0; o[2] = r.x1 - r.x0 + 1; o[3] = r.y1 - r.y0 + 1;                  // cv2.boundingRect
-        }
-        ++kept;
-    }
-    *n_boxes = kept;
-    return 0;
-    API_END
-}
-
-int sbbseg_text_region_boxes(sbbseg_ctx* c, const uint8_t* regions_hw, int H, int W, int label, double min_area, double max_area,
-                             int32_t* boxes_xywh, int cap, int* n_boxes)
-{
-    API_BEGIN
-    if (check_ready(c)) return 1;
-    REQUIRE(regions_hw && H > 0 && W > 0, "bad arguments");
-    const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
-    HIPCHK(hipMemcpyAsync(c->d_morph_b, regions_hw, pix, hipMemcpyHostToDevice, c->stream));
-    return sbbseg_text_region_boxes_dev(c, c->d_morph_b, H, W, label, min_area, max_area, boxes_xywh, cap, n_boxes);
-    API_END
-}
-
 // ---- device buffers for callers that have no device runtime of their own (the reference's environment is Keras/TF, not PyTorch):
 // what run() keeps resident across its three stages -- the stored page, the border mask, the region map, the textline map -- lives in
 // buffers the library hands out.  They belong to the handle that allocated them (sbbseg_destroy frees what is left) but any handle of
@@ -3198,7 +2594,7 @@ int sbbseg_device_free(sbbseg_ctx* c, void* d_ptr)
             c->user_bufs.erase(c->user_bufs.begin() + (long)i);
             return 0;
         }
-    return fail("sbbseg_device_free: %p was not allocated by this handle", d_ptr);
+    return set_error("sbbseg_device_free: %p was not allocated by this handle", d_ptr);
     API_END
 }
 
@@ -3342,763 +2738,6 @@ int sbbseg_run_page(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline
     API_END
 }
 
-// ---- stage glue: the rotate-and-project of the deskew search (main.py:1601-1718) ----------------------------------
-int sbbseg_deskew_side(int H, int W, int* side)
-{
-    API_BEGIN
-    REQUIRE(side && H > 0 && W > 0, "bad arguments");
-    *side = (int)((double)(H > W ? H : W) * 1.4);              // main.py:1613  int(max_x_y * (1.4))
-    return 0;
-    API_END
-}
-
-// cv2.getRotationMatrix2D(center, angle, 1.0) [EXT OpenCV 4.5.1]: positive angle = counter-clockwise
-int sbbseg_rotation_matrix(double cx, double cy, double angle_deg, double* m6)
-{
-    API_BEGIN
-    REQUIRE(m6, "bad arguments");
-    const double a = angle_deg * 3.14159265358979323846 / 180.0;
-    const double alpha = std::cos(a), beta = std::sin(a);
-    m6[0] = alpha; m6[1] = beta; m6[2] = (1 - alpha) * cx - beta * cy;
-    m6[3] = -beta; m6[4] = alpha; m6[5] = beta * cx + (1 - alpha) * cy;
-    return 0;
-    API_END
-}
-
-static void invert_affine(const double* M, double* o)
-{
-#pragma clang fp contract(off)
-    // the in-place inversion of cv::warpAffine (no WARP_INVERSE_MAP), same operation order
-    double m[6] = {M[0], M[1], M[2], M[3], M[4], M[5]};
-    double D = m[0] * m[4] - m[1] * m[3];
-    D = D != 0 ? 1.0 / D : 0.0;
-    const double A11 = m[4] * D, A22 = m[0] * D;
-    m[0] = A11; m[1] *= -D; m[3] *= -D; m[4] = A22;
-    const double b1 = -m[0] * m[2] - m[1] * m[5];
-    const double b2 = -m[3] * m[2] - m[4] * m[5];
-    m[2] = b1; m[5] = b2;
-    for (int i = 0; i < 6; ++i) o[i] = m[i];
-}
-
-static void cubic_table(float* tab)
-{
-#pragma clang fp contract(off)
-    // interpolateCubic of imgwarp.cpp, A = -0.75, float arithmetic
-    const float A = -0.75f;
-    for (int i = 0; i < 32; ++i) {
-        const float x = (float)i * (1.0f / 32);
-        float* c = tab + i * 4;
-        c[0] = ((A * (x + 1) - 5 * A) * (x + 1) + 8 * A) * (x + 1) - 4 * A;
-        c[1] = ((A + 2) * x - (A + 3)) * x * x + 1;
-        c[2] = ((A + 2) * (1 - x) - (A + 3)) * (1 - x) * (1 - x) + 1;
-        c[3] = 1.f - c[0] - c[1] - c[2];
-    }
-}
-
-int sbbseg_deskew_profiles_dev(sbbseg_ctx* c, const void* d_mask_hw, int H, int W, const double* matrices, const double* angles_deg,
-                               int n_angles, int32_t* counts)
-{
-    API_BEGIN
-    if (check_ready(c)) return 1;
-    REQUIRE(d_mask_hw && counts && H > 0 && W > 0 && n_angles >= 1 && n_angles <= 4096 && (matrices || angles_deg), "bad arguments");
-    const int S = (int)((double)(H > W ? H : W) * 1.4);
-    REQUIRE(S >= 1 && S <= 32767, "deskew square side %d out of range", S);
-    const int cp = (int)(S / 2.0), top = cp - (int)(H / 2.0), left = cp - (int)(W / 2.0);      // main.py:1615-1619
-    alloc_check();
-    std::vector<double> minv((size_t)n_angles * 6);
-    for (int a = 0; a < n_angles; ++a) {
-        double M[6];
-        if (matrices) memcpy(M, matrices + (size_t)a * 6, sizeof(M));
-        else if (sbbseg_rotation_matrix((double)(S / 2), (double)(S / 2), angles_deg[a], M)) return 1;     // main.py:161  center = (w // 2, h // 2)
-        invert_affine(M, &minv[(size_t)a * 6]);
-    }
-    float tab[128];
-    cubic_table(tab);
-    const size_t need = (size_t)n_angles * 6 * sizeof(double) + sizeof(tab) + (size_t)n_angles * S * sizeof(int);
-    if (ensure(c, (void**)&c->d_deskew, &c->deskew_cap, need)) return 1;
-    double* d_minv = (double*)c->d_deskew;
-    float* d_tab = (float*)(d_minv + (size_t)n_angles * 6);
-    int* d_counts = (int*)(d_tab + 128);
-    HIPCHK(hipMemcpyAsync(d_minv, minv.data(), minv.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_tab, tab, sizeof(tab), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));                       // (pageable host staging buffers die with this frame)
-    HIPCHK(launch_deskew_profiles((const uint8_t*)d_mask_hw, H, W, S, top, left, d_minv, d_tab, n_angles, d_counts, c->stream));
-    HIPCHK(hipMemcpyAsync(counts, d_counts, (size_t)n_angles * S * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-    API_END
-}
-
-int sbbseg_deskew_profiles(sbbseg_ctx* c, const uint8_t* mask_hw, int H, int W, const double* matrices, const double* angles_deg, int n_angles,
-                           int32_t* counts)
-{
-    API_BEGIN
-    if (check_ready(c)) return 1;
-    REQUIRE(mask_hw && H > 0 && W > 0, "bad arguments");
-    const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
-    HIPCHK(hipMemcpyAsync(c->d_morph_b, mask_hw, pix, hipMemcpyHostToDevice, c->stream));
-    return sbbseg_deskew_profiles_dev(c, c->d_morph_b, H, W, matrices, angles_deg, n_angles, counts);
-    API_END
-}
-
-// The same sweep for every text-region box of a page (do_work_of_slopes, main.py:1728-1738): crop_image_inside_box, cv2.erode(crop, 5x5,
-// iterations) on the CROP, return_deskew_slope's square and rotations.  offsets[r] = first int of region r in the packed counts
-// ([n_angles][S_r]), offsets[n_boxes] = the total.  size_only: only the offsets are computed (needs no handle).  Otherwise the sweep is
-// queued on the stream and *d_counts points at the packed counts in the handle's buffer: they STAY on the device.  `head` is the host
-// staging buffer of the tables: the caller keeps it alive until it has synchronised the stream.
-static int region_sweep(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
-                        const double* angles_deg, int n_angles, int64_t* offsets, bool size_only, std::vector<unsigned char>& head,
-                        const int32_t** d_counts)
-{
-    *d_counts = nullptr;
-    REQUIRE(H > 0 && W > 0 && n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && offsets && n_angles >= 1 && n_angles <= 4096 &&
-                erode_iterations >= 0 && erode_iterations <= 64, "bad arguments");
-    alloc_check();
-    std::vector<DeskewRegion> geom((size_t)n_boxes);
-    long long total_pix = 0, total_counts = 0, total_blocks = 0;
-    for (int r = 0; r < n_boxes; ++r) {
-        const int32_t* b = boxes_xywh + (size_t)r * 4;
-        REQUIRE(b[2] >= 1 && b[3] >= 1, "box %d: width %d, height %d (both must be at least 1)", r, b[2], b[3]);
-        REQUIRE(b[0] >= 0 && b[1] >= 0 && (long long)b[0] + b[2] <= W && (long long)b[1] + b[3] <= H, "box %d (%d, %d, %d, %d) leaves the %d x %d plane",
-                r, b[0], b[1], b[2], b[3], W, H);
-        DeskewRegion& g = geom[r];
-        g.x = b[0]; g.y = b[1]; g.w = b[2]; g.h = b[3];
-        g.S = (int)((double)(g.h > g.w ? g.h : g.w) * 1.4);                               // main.py:1613
-        REQUIRE(g.S >= 1 && g.S <= 32767, "box %d: deskew square side %d out of range", r, g.S);
-        const int cp = (int)(g.S / 2.0);
-        g.top = cp - (int)(g.h / 2.0); g.left = cp - (int)(g.w / 2.0);                    // main.py:1615-1619
-        g.clip = (g.top >= 1 && g.left >= 1 && g.top + g.h <= g.S - 1 && g.left + g.w <= g.S - 1) ? 1 : 0;
-        g.crop_off = total_pix; g.count_off = total_counts;
-        g.row_groups = (g.S + kRegionDeskewRows - 1) / kRegionDeskewRows;
-        g.block0 = (int)total_blocks;
-        offsets[r] = total_counts;
-        total_pix += (long long)g.w * g.h;
-        total_counts += (long long)n_angles * g.S;
-        total_blocks += (long long)n_angles * g.row_groups;
-        REQUIRE(total_counts < (1ll << 31) && total_blocks < (1ll << 31), "too much work for one sweep (%d boxes, %d angles): split the boxes", n_boxes, n_angles);
-    }
-    offsets[n_boxes] = total_counts;
-    if (size_only || n_boxes == 0) return 0;                       // (the size query needs no handle)
-    if (check_ready(c)) return 1;
-    REQUIRE(d_textline_hw && angles_deg, "bad arguments");
-    // head of the device buffer, built on the host and copied in one piece: inverse maps | bicubic table | geometry
-    const size_t minv_bytes = (size_t)n_boxes * n_angles * 6 * sizeof(double), tab_bytes = 128 * sizeof(float);
-    const size_t geom_off = minv_bytes + tab_bytes, head_bytes = (geom_off + (size_t)n_boxes * sizeof(DeskewRegion) + 15) & ~(size_t)15;
-    const size_t pix_bytes = ((size_t)total_pix + 15) & ~(size_t)15;
-    head.assign(head_bytes, 0);
-    double* minv = (double*)head.data();
-    for (int r = 0; r < n_boxes; ++r)
-        for (int a = 0; a < n_angles; ++a) {
-            double M[6];
-            if (sbbseg_rotation_matrix((double)(geom[r].S / 2), (double)(geom[r].S / 2), angles_deg[a], M)) return 1;     // main.py:161
-            invert_affine(M, minv + ((size_t)r * n_angles + a) * 6);
-        }
-    cubic_table((float*)(head.data() + minv_bytes));
-    memcpy(head.data() + geom_off, geom.data(), (size_t)n_boxes * sizeof(DeskewRegion));
-    if (ensure(c, &c->d_rdk, &c->rdk_cap, head_bytes + 2 * pix_bytes + (size_t)total_counts * sizeof(int))) return 1;
-    unsigned char* d = (unsigned char*)c->d_rdk;
-    RegionDeskewParams p;
-    p.plane = (const uint8_t*)d_textline_hw; p.H = H; p.W = W;
-    p.geom = (const DeskewRegion*)(d + geom_off); p.n_regions = n_boxes; p.n_angles = n_angles; p.radius = 2 * erode_iterations;
-    p.total_pix = total_pix;
-    p.minv = (const double*)d; p.cubic = (const float*)(d + minv_bytes);
-    p.tmp = d + head_bytes; p.crops = d + head_bytes + pix_bytes; p.counts = (int*)(d + head_bytes + 2 * pix_bytes);
-    p.total_blocks = (int)total_blocks;
-    HIPCHK(hipMemcpyAsync(d, head.data(), head_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_region_deskew_crops(p, c->stream));
-    HIPCHK(launch_region_deskew_profiles(p, c->stream));
-    *d_counts = p.counts;
-    return 0;
-}
-
-// counts == NULL: only the offsets are computed (to size the buffer).
-int sbbseg_region_deskew_profiles_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
-                                      int erode_iterations, const double* angles_deg, int n_angles, int32_t* counts, int64_t* offsets)
-{
-    API_BEGIN
-    std::vector<unsigned char> head;
-    const int32_t* d_counts = nullptr;
-    if (region_sweep(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, angles_deg, n_angles, offsets, !counts, head, &d_counts)) return 1;
-    if (!d_counts) return 0;
-    HIPCHK(hipMemcpyAsync(counts, d_counts, (size_t)offsets[n_boxes] * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffer lives until here)
-    return 0;
-    API_END
-}
-
-int sbbseg_region_deskew_profiles(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
-                                  int erode_iterations, const double* angles_deg, int n_angles, int32_t* counts, int64_t* offsets)
-{
-    API_BEGIN
-    REQUIRE(H > 0 && W > 0, "bad arguments");
-    if (counts && n_boxes > 0) {
-        if (check_ready(c)) return 1;
-        REQUIRE(textline_hw, "bad arguments");
-        const size_t pix = (size_t)H * W;
-        if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
-        HIPCHK(hipMemcpyAsync(c->d_morph_b, textline_hw, pix, hipMemcpyHostToDevice, c->stream));
-    }
-    return sbbseg_region_deskew_profiles_dev(c, (counts && n_boxes > 0) ? c->d_morph_b : nullptr, H, W, boxes_xywh, n_boxes, erode_iterations, angles_deg, n_angles, counts, offsets);
-    API_END
-}
-
-// ---- stage glue: the 1-D statistic of the deskew search and the angle selection (main.py:1545-1599, 1630-1716; profile_stat.h) ----
-static const double kSigma2Weights[kSigma2Radius + 1] = SBBSEG_SIGMA2_WEIGHTS;
-
-// np.linspace(start, stop, num) bit for bit: i * ((stop - start) / (num - 1)) + start, the last one = stop
-static void linspace(double start, double stop, int num, double* out)
-{
-#pragma clang fp contract(off)
-    const double step = (stop - start) / (double)(num - 1);
-    for (int i = 0; i < num; ++i) {
-        const double t = (double)i * step;
-        out[i] = t + start;
-    }
-    out[num - 1] = stop;
-}
-
-int sbbseg_deskew_sweep_angles(int sweep, double* angles_deg, int capacity, int* n_angles)
-{
-    API_BEGIN
-    REQUIRE((sweep == 0 || sweep == 1) && n_angles && (angles_deg || capacity == 0) && capacity >= 0, "bad arguments");
-    const int n = sweep == 0 ? 80 : 30;                             // main.py:1622, 1670
-    *n_angles = n;
-    if (capacity == 0) return 0;
-    REQUIRE(capacity >= n, "room for %d angles, the sweep has %d", capacity, n);
-    if (sweep == 0) linspace(-25.0, 25.0, n, angles_deg);
-    else linspace(-90.0, -50.0, n, angles_deg);
-    return 0;
-    API_END
-}
-
-static int check_profile_tables(const int64_t* offsets, int n_regions, int n_angles, const double* weights, int radius)
-{
-    REQUIRE(n_regions >= 0 && n_regions <= (1 << 20) && (offsets || n_regions == 0), "bad arguments");
-    REQUIRE(n_angles >= 1 && n_angles <= 4096, "n_angles %d out of range (1 .. 4096)", n_angles);
-    REQUIRE(radius >= 0 && radius <= (1 << 16), "radius %d out of range (0 .. 65536)", radius);
-    for (int r = 0; r < n_regions; ++r) {
-        const int64_t len = offsets[r + 1] - offsets[r];
-        REQUIRE(offsets[r] >= 0 && len >= n_angles && len % n_angles == 0 && len / n_angles <= 32767 && offsets[r + 1] < (1ll << 31),
-                "region %d: offsets %lld .. %lld do not hold %d profiles of 1 .. 32767 samples", r, (long long)offsets[r], (long long)offsets[r + 1], n_angles);
-    }
-    (void)weights;
-    return 0;
-}
-
-int sbbseg_profile_statistics_host(const int32_t* counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights, int radius,
-                                   double multiplier, double* spread, uint8_t* state, int32_t* winner, double* smooth)
-{
-    API_BEGIN
-    if (check_profile_tables(offsets, n_regions, n_angles, weights, radius)) return 1;
-    REQUIRE((counts && spread && state && winner) || n_regions == 0, "bad arguments");
-    alloc_check();
-    if (!weights) { weights = kSigma2Weights; radius = kSigma2Radius; }
-    std::vector<double> z, g;
-    PairwiseStack stack;
-    for (int r = 0; r < n_regions; ++r) {
-        const int S = (int)((offsets[r + 1] - offsets[r]) / n_angles);
-        z.resize((size_t)S); g.resize((size_t)S + kProfileFlipExtra);
-        for (int a = 0; a < n_angles; ++a) {
-            const size_t k = (size_t)r * n_angles + a;
-            const size_t at = (size_t)offsets[r] + (size_t)a * S;
-            state[k] = (uint8_t)profile_statistic_serial(counts + at, S, weights, radius, multiplier, z.data(), g.data(), &stack, &spread[k]);
-            if (smooth) memcpy(smooth + at, z.data(), (size_t)S * sizeof(double));
-        }
-        winner[r] = sweep_winner(spread + (size_t)r * n_angles, state + (size_t)r * n_angles, n_angles);
-    }
-    return 0;
-    API_END
-}
-
-// queues the statistic of a sweep whose counts are in device memory; *out holds the device pointers of the results (in c->d_pstat)
-static int profile_stats_queue(sbbseg_ctx* c, const int32_t* d_counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights,
-                               int radius, double multiplier, std::vector<unsigned char>& head, ProfileStatParams* out)
-{
-    if (!weights) { weights = kSigma2Weights; radius = kSigma2Radius; }
-    const size_t np = (size_t)n_regions * n_angles;
-    const size_t w_bytes = (size_t)(radius + 1) * sizeof(double), head_bytes = w_bytes + (size_t)n_regions * sizeof(ProfileRegion);
-    head.assign(head_bytes, 0);
-    memcpy(head.data(), weights, w_bytes);
-    ProfileRegion* reg = (ProfileRegion*)(head.data() + w_bytes);
-    long long ws_doubles = 0;
-    for (int r = 0; r < n_regions; ++r) {
-        reg[r].count_off = offsets[r];
-        reg[r].S = (int)((offsets[r + 1] - offsets[r]) / n_angles);
-        reg[r].ws_off = ws_doubles;
-        if (reg[r].S > kProfileLdsSamples) ws_doubles += (long long)n_angles * (2ll * reg[r].S + kProfileFlipExtra);
-    }
-    const size_t spread_off = head_bytes, winner_off = spread_off + np * sizeof(double), state_off = winner_off + (size_t)n_regions * sizeof(int32_t);
-    const size_t ws_off = (state_off + np + 15) & ~(size_t)15;
-    if (ensure(c, &c->d_pstat, &c->pstat_cap, ws_off + (size_t)ws_doubles * sizeof(double))) return 1;
-    unsigned char* d = (unsigned char*)c->d_pstat;
-    ProfileStatParams p;
-    p.counts = d_counts; p.regions = (const ProfileRegion*)(d + w_bytes); p.n_regions = n_regions; p.n_angles = n_angles;
-    p.weights = (const double*)d; p.radius = radius; p.multiplier = multiplier;
-    p.workspace = (double*)(d + ws_off); p.spread = (double*)(d + spread_off); p.state = d + state_off; p.winner = (int32_t*)(d + winner_off);
-    HIPCHK(hipMemcpyAsync(d, head.data(), head_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_profile_statistics(p, ws_doubles > 0, c->stream));
-    *out = p;
-    return 0;
-}
-
-int sbbseg_profile_statistics_dev(sbbseg_ctx* c, const void* d_counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights,
-                                  int radius, double multiplier, double* spread, uint8_t* state, int32_t* winner)
-{
-    API_BEGIN
-    if (check_ready(c)) return 1;
-    if (check_profile_tables(offsets, n_regions, n_angles, weights, radius)) return 1;
-    if (n_regions == 0) return 0;
-    REQUIRE(d_counts, "bad arguments");
-    alloc_check();
-    std::vector<unsigned char> head;
-    ProfileStatParams p;
-    if (profile_stats_queue(c, (const int32_t*)d_counts, offsets, n_regions, n_angles, weights, radius, multiplier, head, &p)) return 1;
-    const size_t np = (size_t)n_regions * n_angles;
-    if (spread) HIPCHK(hipMemcpyAsync(spread, p.spread, np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (state) HIPCHK(hipMemcpyAsync(state, p.state, np, hipMemcpyDeviceToHost, c->stream));
-    if (winner) HIPCHK(hipMemcpyAsync(winner, p.winner, (size_t)n_regions * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffer lives until here)
-    return 0;
-    API_END
-}
-
-// one sweep of all `boxes`: rotate-and-project, statistic, selection; the winners come back, the counts do not
-static int slopes_sweep(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
-                        const double* angles, int n_angles, const double* weights, int radius, std::vector<int32_t>& winner)
-{
-    std::vector<int64_t> offsets((size_t)n_boxes + 1);
-    std::vector<unsigned char> head_sweep, head_stat;
-    const int32_t* d_counts = nullptr;
-    if (region_sweep(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, angles, n_angles, offsets.data(), false, head_sweep, &d_counts)) return 1;
-    ProfileStatParams p;
-    if (profile_stats_queue(c, d_counts, offsets.data(), n_boxes, n_angles, weights, radius, 20.3, head_stat, &p)) return 1;      // main.py:1644
-    winner.resize((size_t)n_boxes);
-    HIPCHK(hipMemcpyAsync(winner.data(), p.winner, (size_t)n_boxes * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffers live until here)
-    return 0;
-}
-
-int sbbseg_region_deskew_slopes_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
-                                    int erode_iterations, const double* weights, int radius, double* slopes)
-{
-    API_BEGIN
-    if (check_ready(c)) return 1;
-    REQUIRE(H > 0 && W > 0 && n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && (slopes || n_boxes == 0), "bad arguments");
-    REQUIRE(radius >= 0 && radius <= (1 << 16), "radius %d out of range (0 .. 65536)", radius);
-    if (n_boxes == 0) return 0;
-    REQUIRE(d_textline_hw, "bad arguments");
-    alloc_check();
-    double first[80], second[30];
-    linspace(-25.0, 25.0, 80, first);                               // main.py:1622
-    linspace(-90.0, -50.0, 30, second);                             // main.py:1670
-    std::vector<int32_t> winner;
-    if (slopes_sweep(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, first, 80, weights, radius, winner)) return 1;
-    std::vector<int32_t> steep, steep_boxes;
-    for (int r = 0; r < n_boxes; ++r) {
-        slopes[r] = winner[r] < 0 ? 0.0 : first[winner[r]];
-        if (std::fabs(slopes[r]) > 15.0) {                          // main.py:1669-1670
-            steep.push_back(r);
-            steep_boxes.insert(steep_boxes.end(), boxes_xywh + (size_t)r * 4, boxes_xywh + (size_t)r * 4 + 4);
-        }
-    }
-    if (!steep.empty()) {
-        if (slopes_sweep(c, d_textline_hw, H, W, steep_boxes.data(), (int)steep.size(), erode_iterations, second, 30, weights, radius, winner)) return 1;
-        for (size_t k = 0; k < steep.size(); ++k) slopes[steep[k]] = winner[k] < 0 ? 0.0 : second[winner[k]];
-    }
-    for (int r = 0; r < n_boxes; ++r)
-        if (std::fabs(slopes[r]) > 120.5) slopes[r] = 0.0;          // main.py:1746-1747
-    return 0;
-    API_END
-}
-
-int sbbseg_region_deskew_slopes(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
-                                int erode_iterations, const double* weights, int radius, double* slopes)
-{
-    API_BEGIN
-    if (check_ready(c)) return 1;
-    REQUIRE(H > 0 && W > 0 && n_boxes >= 0, "bad arguments");
-    if (n_boxes > 0) {
-        REQUIRE(textline_hw, "bad arguments");
-        const size_t pix = (size_t)H * W;
-        if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
-        HIPCHK(hipMemcpyAsync(c->d_morph_b, textline_hw, pix, hipMemcpyHostToDevice, c->stream));
-    }
-    return sbbseg_region_deskew_slopes_dev(c, n_boxes > 0 ? c->d_morph_b : nullptr, H, W, boxes_xywh, n_boxes, erode_iterations, weights, radius, slopes);
-    API_END
-}
-
-// ---- stage glue: deskewed text-line masks and line profiles per region (textline_contours_postprocessing, main.py:1472-1487; line_mask.h) ----
-static void line_table(std::vector<int16_t>& itab)
-{
-    float tab[128];
-    cubic_table(tab);
-    itab.resize((size_t)kLineTabEntries);
-    for (int ay = 0; ay < 32; ++ay)
-        for (int ax = 0; ax < 32; ++ax) line_mask_weights(tab, ay, ax, itab.data() + (size_t)(ay * 32 + ax) * 16);
-}
-
-// rotate_image's inverse map for an h x w crop (main.py:159-163: center = (w // 2, h // 2))
-static int line_inverse_map(int h, int w, double slope, double* minv6)
-{
-    double M[6];
-    if (sbbseg_rotation_matrix((double)(w / 2), (double)(h / 2), slope, M)) return 1;
-    invert_affine(M, minv6);
-    return 0;
-}
-
-int sbbseg_region_line_table(int16_t* itab, int capacity)
-{
-    API_BEGIN
-    REQUIRE(itab && capacity >= kLineTabEntries, "room for %d weights, the table has %d", capacity, kLineTabEntries);
-    alloc_check();
-    std::vector<int16_t> t;
-    line_table(t);
-    memcpy(itab, t.data(), t.size() * sizeof(int16_t));
-    return 0;
-    API_END
-}
-
-// one clipped separable min / max of the given radius, in place (tmp: h * w bytes)
-static void host_line_morph(uint8_t* img, uint8_t* tmp, int h, int w, int radius, int is_max, int scale)
-{
-    for (int y = 0; y < h; ++y)
-        for (int x = 0; x < w; ++x) tmp[(size_t)y * w + x] = (uint8_t)line_mask_morph_1d(img + (size_t)y * w, 1, x, w, radius, is_max, scale);
-    for (int y = 0; y < h; ++y)
-        for (int x = 0; x < w; ++x) img[(size_t)y * w + x] = (uint8_t)line_mask_morph_1d(tmp + x, (size_t)w, y, h, radius, is_max, 1);
-}
-
-int sbbseg_region_line_masks_host(const uint8_t* crop_hw, int h, int w, int erode_iterations, double slope, uint8_t* mask, int32_t* rows, int32_t* cols)
-{
-    API_BEGIN
-    REQUIRE(crop_hw && rows && cols && erode_iterations >= 0 && erode_iterations <= 64, "bad arguments");
-    REQUIRE(h >= 1 && w >= 1, "crop: width %d, height %d (both must be at least 1)", w, h);
-    REQUIRE((long long)h * w < (1ll << 31), "crop of %d x %d is too large", w, h);
-    alloc_check();
-    const size_t pix = (size_t)h * w;
-    std::vector<uint8_t> img(crop_hw, crop_hw + pix), tmp(pix);
-    std::vector<int16_t> itab;
-    line_table(itab);
-    host_line_morph(img.data(), tmp.data(), h, w, 2 * erode_iterations, 0, 1);        // cv2.erode(crop, 5x5, iterations) (main.py:1734)
-    host_line_morph(img.data(), tmp.data(), h, w, 2, 0, 255);                         // * 255, then OPEN's erode ...
-    host_line_morph(img.data(), tmp.data(), h, w, 4, 1, 1);                           // ... OPEN's dilate + CLOSE's dilate ...
-    host_line_morph(img.data(), tmp.data(), h, w, 2, 0, 1);                           // ... and CLOSE's erode
-    double m[6];
-    if (line_inverse_map(h, w, slope, m)) return 1;
-    for (int x = 0; x < w; ++x) cols[x] = 0;
-    for (int y = 0; y < h; ++y) {
-        long long X0, Y0;
-        line_mask_row_origin(m, y, &X0, &Y0);
-        int cnt = 0;
-        for (int x = 0; x < w; ++x) {
-            const int d = line_mask_pixel(img.data(), w, h, m[0], m[3], X0, Y0, x, itab.data()) != 0;
-            if (mask) mask[(size_t)y * w + x] = (uint8_t)d;
-            cnt += d;
-            cols[x] += d;
-        }
-        rows[y] = cnt;
-    }
-    return 0;
-    API_END
-}
-
-// queues crop / erode / OPEN / CLOSE / warp / sums of all boxes; *out holds the device pointers of the results (in c->d_rdk), out->n_regions
-// == 0 when there is nothing to do.  `need_sums`: what a caller that downloads rows and cols must have passed.
-static int region_line_masks_queue(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
-                                   const double* slopes, bool need_sums, int64_t* mask_off, int64_t* row_off, int64_t* col_off,
-                                   std::vector<unsigned char>& head, RegionLinesParams* out, long long* rows_total)
-{
-    out->n_regions = 0;
-    REQUIRE(H > 0 && W > 0 && n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && mask_off && row_off && col_off &&
-                erode_iterations >= 0 && erode_iterations <= 64, "bad arguments");
-    alloc_check();
-    std::vector<DeskewRegion> crop_geom((size_t)n_boxes);
-    std::vector<LineRegion> geom((size_t)n_boxes);
-    long long total_pix = 0, total_rows = 0, total_cols = 0, total_blocks = 0;
-    for (int r = 0; r < n_boxes; ++r) {
-        const int32_t* b = boxes_xywh + (size_t)r * 4;
-        REQUIRE(b[2] >= 1 && b[3] >= 1, "box %d: width %d, height %d (both must be at least 1)", r, b[2], b[3]);
-        REQUIRE(b[0] >= 0 && b[1] >= 0 && (long long)b[0] + b[2] <= W && (long long)b[1] + b[3] <= H, "box %d (%d, %d, %d, %d) leaves the %d x %d plane",
-                r, b[0], b[1], b[2], b[3], W, H);
-        DeskewRegion& cg = crop_geom[r];
-        memset(&cg, 0, sizeof(cg));
-        cg.x = b[0]; cg.y = b[1]; cg.w = b[2]; cg.h = b[3]; cg.crop_off = total_pix;
-        LineRegion& g = geom[r];
-        g.w = b[2]; g.h = b[3]; g.crop_off = total_pix; g.row_off = (int)total_rows; g.col_off = (int)total_cols; g.block0 = (int)total_blocks; g.pad = 0;
-        mask_off[r] = total_pix; row_off[r] = total_rows; col_off[r] = total_cols;
-        total_pix += (long long)g.w * g.h;
-        total_rows += g.h;
-        total_cols += g.w;
-        total_blocks += (g.h + kRegionLineRows - 1) / kRegionLineRows;
-        REQUIRE(total_pix < (1ll << 31) && total_rows < (1ll << 30) && total_cols < (1ll << 30), "too much work for one call (%d boxes): split the boxes", n_boxes);
-    }
-    mask_off[n_boxes] = total_pix; row_off[n_boxes] = total_rows; col_off[n_boxes] = total_cols;
-    if (n_boxes == 0) return 0;
-    if (check_ready(c)) return 1;
-    REQUIRE(d_textline_hw && slopes && need_sums, "bad arguments");
-    if (!c->d_line_tab) {
-        std::vector<int16_t> itab;
-        line_table(itab);
-        if (upload(c, &c->d_line_tab, itab.data(), itab.size())) return 1;
-    }
-    // head of the device buffer, built on the host and copied in one piece: inverse maps | crop geometry | line geometry
-    const size_t minv_bytes = (size_t)n_boxes * 6 * sizeof(double), cgeom_bytes = (size_t)n_boxes * sizeof(DeskewRegion);
-    const size_t lgeom_off = minv_bytes + cgeom_bytes, head_bytes = (lgeom_off + (size_t)n_boxes * sizeof(LineRegion) + 15) & ~(size_t)15;
-    const size_t pix_bytes = ((size_t)total_pix + 15) & ~(size_t)15;
-    head.assign(head_bytes, 0);
-    for (int r = 0; r < n_boxes; ++r)
-        if (line_inverse_map(geom[r].h, geom[r].w, slopes[r], (double*)head.data() + (size_t)r * 6)) return 1;
-    memcpy(head.data() + minv_bytes, crop_geom.data(), cgeom_bytes);
-    memcpy(head.data() + lgeom_off, geom.data(), (size_t)n_boxes * sizeof(LineRegion));
-    if (ensure(c, &c->d_rdk, &c->rdk_cap, head_bytes + 3 * pix_bytes + (size_t)(total_rows + total_cols) * sizeof(int))) return 1;
-    unsigned char* d = (unsigned char*)c->d_rdk;
-    RegionDeskewParams cp;
-    memset(&cp, 0, sizeof(cp));
-    cp.plane = (const uint8_t*)d_textline_hw; cp.H = H; cp.W = W;
-    cp.geom = (const DeskewRegion*)(d + minv_bytes); cp.n_regions = n_boxes; cp.radius = 2 * erode_iterations; cp.total_pix = total_pix;
-    cp.tmp = d + head_bytes; cp.crops = d + head_bytes + pix_bytes;
-    RegionLinesParams p;
-    p.geom = (const LineRegion*)(d + lgeom_off); p.n_regions = n_boxes; p.total_pix = total_pix; p.total_cols = (int)total_cols;
-    p.total_blocks = (int)total_blocks; p.minv = (const double*)d; p.itab = c->d_line_tab;
-    p.a = cp.tmp; p.b = cp.crops; p.mask = d + head_bytes + 2 * pix_bytes;
-    p.rows = (int*)(d + head_bytes + 3 * pix_bytes); p.cols = p.rows + total_rows;
-    HIPCHK(hipMemcpyAsync(d, head.data(), head_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_region_deskew_crops(cp, c->stream));
-    HIPCHK(launch_region_line_morph(p, c->stream));
-    HIPCHK(launch_region_line_masks(p, c->stream));
-    c->line_launches += 2 + kRegionLineLaunches;
-    *out = p;
-    *rows_total = total_rows;
-    return 0;
-}
-
-int sbbseg_region_line_masks_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
-                                 const double* slopes, uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off, int64_t* row_off, int64_t* col_off)
-{
-    API_BEGIN
-    std::vector<unsigned char> head;
-    RegionLinesParams p;
-    long long total_rows = 0;
-    if (region_line_masks_queue(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, slopes, rows && cols, mask_off, row_off, col_off, head, &p,
-                                &total_rows)) return 1;
-    if (p.n_regions == 0) return 0;
-    if (masks) HIPCHK(hipMemcpyAsync(masks, p.mask, (size_t)p.total_pix, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(rows, p.rows, (size_t)total_rows * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(cols, p.cols, (size_t)p.total_cols * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffer lives until here)
-    return 0;
-    API_END
-}
-
-int sbbseg_region_line_masks(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
-                             const double* slopes, uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off, int64_t* row_off, int64_t* col_off)
-{
-    API_BEGIN
-    REQUIRE(H > 0 && W > 0 && n_boxes >= 0, "bad arguments");
-    if (n_boxes > 0) {
-        if (check_ready(c)) return 1;
-        REQUIRE(textline_hw, "bad arguments");
-        const size_t pix = (size_t)H * W;
-        if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
-        HIPCHK(hipMemcpyAsync(c->d_morph_b, textline_hw, pix, hipMemcpyHostToDevice, c->stream));
-    }
-    return sbbseg_region_line_masks_dev(c, n_boxes > 0 ? c->d_morph_b : nullptr, H, W, boxes_xywh, n_boxes, erode_iterations, slopes, masks, rows, cols,
-                                        mask_off, row_off, col_off);
-    API_END
-}
-
-// ---- stage glue: text-line peaks and line boxes per region (seperate_lines / seperate_lines_vertical after the projection; line_split.h) ----
-static int check_line_split_tables(const int64_t* offsets, int n_regions, const int32_t* geom, const double* rot, const double* weights,
-                                   const int64_t* weight_off, int sigma_max, int64_t* line_off)
-{
-    REQUIRE(n_regions >= 0 && n_regions <= (1 << 20) && line_off && ((offsets && geom && rot) || n_regions == 0), "bad arguments");
-    REQUIRE(weights && weight_off && sigma_max >= kLineSigmaRaised && sigma_max <= 4096, "the weight table must hold sigma = 2 .. sigma_max, sigma_max in 12 .. 4096");
-    for (int s = kLineSigmaMin; s <= sigma_max; ++s)
-        REQUIRE(weight_off[s - kLineSigmaMin] >= 0 && weight_off[s - kLineSigmaMin + 1] - weight_off[s - kLineSigmaMin] == 4 * s + 1,
-                "weight table: sigma %d does not have 4 * sigma + 1 weights", s);
-    long long lines = 0;
-    for (int r = 0; r < n_regions; ++r) {
-        const int32_t* g = geom + (size_t)r * 3;
-        REQUIRE(g[0] >= 1 && g[0] <= 32767 && g[1] >= 1 && g[1] <= (1 << 24) && (g[2] == 0 || g[2] == 1),
-                "region %d: length %d (1 .. 32767), other extent %d (1 .. 2^24), vertical %d (0, 1)", r, g[0], g[1], g[2]);
-        REQUIRE(offsets[r] >= 0 && offsets[r + 1] - offsets[r] == g[0] && offsets[r + 1] < (1ll << 31), "region %d: offsets %lld .. %lld do not hold %d samples", r,
-                (long long)offsets[r], (long long)offsets[r + 1], g[0]);
-        line_off[r] = lines;
-        lines += line_capacity(g[0]);
-    }
-    line_off[n_regions] = lines;
-    REQUIRE(lines < (1ll << 27), "too much work for one call (%d regions): split the regions", n_regions);
-    return 0;
-}
-
-static LineGeom line_geom(const int32_t* g, const double* rot)
-{
-    LineGeom out;
-    out.n = g[0]; out.other = g[1]; out.vertical = g[2];
-    out.r00 = rot[0]; out.r01 = rot[1]; out.r10 = rot[2]; out.r11 = rot[3]; out.xd = rot[4]; out.yd = rot[5];
-    return out;
-}
-
-int sbbseg_line_split_host(const int32_t* profiles, const int64_t* offsets, int n_regions, const int32_t* geom, const double* rot, const double* weights,
-                           const int64_t* weight_off, int sigma_max, const double* extra_weights, int extra_sigma, int32_t* info, int64_t* line_off,
-                           int32_t* lines, int32_t* corners, int32_t* corners_rot)
-{
-    API_BEGIN
-    if (check_line_split_tables(offsets, n_regions, geom, rot, weights, weight_off, sigma_max, line_off)) return 1;
-    REQUIRE((profiles && info && lines && corners && corners_rot) || n_regions == 0, "bad arguments");
-    REQUIRE(!extra_weights || extra_sigma >= 1, "extra_sigma %d", extra_sigma);
-    alloc_check();
-    const LineWeights w{weights, weight_off, sigma_max, extra_weights, extra_sigma};
-    std::vector<unsigned char> work;
-    PairwiseStack stack;
-    for (int r = 0; r < n_regions; ++r) {
-        const LineGeom g = line_geom(geom + (size_t)r * 3, rot + (size_t)r * 6);
-        work.resize(line_work_bytes(g.n));
-        const size_t at = (size_t)line_off[r];
-        line_split_serial(profiles + offsets[r], g, w, LineWork{work.data(), g.n, &stack}, info + (size_t)r * kLineInfoInts, lines + at * 3, corners + at * 8,
-                          corners_rot + at * 8);
-    }
-    return 0;
-    API_END
-}
-
-// queues the split of regions whose profiles are in device memory (region r: n ints from d_profiles + prof_off[r]); *out holds the device
-// pointers of the results (in c->d_lsplit)
-static int line_split_queue(sbbseg_ctx* c, const int32_t* d_profiles, const int64_t* prof_off, int n_regions, const int32_t* geom, const double* rot,
-                            const double* weights, const int64_t* weight_off, int sigma_max, const int64_t* line_off, std::vector<unsigned char>& head,
-                            LineSplitParams* out)
-{
-    if (sigma_max > kLineSigmaMax) sigma_max = kLineSigmaMax;      // the device's table ends there; larger sigmas are reported, not computed
-    const size_t n_off = (size_t)(sigma_max - kLineSigmaMin + 2), n_w = (size_t)weight_off[n_off - 1];
-    const size_t off_bytes = (n_off * sizeof(long long) + 15) & ~(size_t)15;
-    if (c->line_w_host.size() != n_w || !c->d_line_w || memcmp(c->line_w_host.data(), weights, n_w * sizeof(double)) != 0) {
-        std::vector<unsigned char> tab(off_bytes + n_w * sizeof(double));
-        for (size_t i = 0; i < n_off; ++i) ((long long*)tab.data())[i] = (long long)weight_off[i];
-        memcpy(tab.data() + off_bytes, weights, n_w * sizeof(double));
-        c->line_w_host.clear();
-        if (ensure(c, &c->d_line_w, &c->line_w_cap, tab.size())) return 1;
-        HIPCHK(hipMemcpyAsync(c->d_line_w, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->line_w_host.assign(weights, weights + n_w);
-    }
-    const size_t lines = (size_t)line_off[n_regions];
-    const size_t info_off = ((size_t)n_regions * sizeof(LineSplitRegion) + 15) & ~(size_t)15;
-    const size_t pts_off = (info_off + (size_t)n_regions * kLineInfoInts * sizeof(int32_t) + 15) & ~(size_t)15;
-    const size_t box_off = (pts_off + lines * 3 * sizeof(int32_t) + 15) & ~(size_t)15, rot_off = box_off + lines * 8 * sizeof(int32_t);
-    const size_t ws_off = rot_off + lines * 8 * sizeof(int32_t);
-    head.assign(info_off, 0);
-    LineSplitRegion* reg = (LineSplitRegion*)head.data();
-    size_t ws_bytes = 0;
-    for (int r = 0; r < n_regions; ++r) {
-        const int32_t* g = geom + (size_t)r * 3;
-        reg[r].prof_off = prof_off[r]; reg[r].ws_off = (long long)ws_bytes;
-        reg[r].n = g[0]; reg[r].other = g[1]; reg[r].vertical = g[2]; reg[r].line_off = (int)line_off[r];
-        memcpy(reg[r].rot, rot + (size_t)r * 6, 6 * sizeof(double));
-        if (g[0] > kProfileLdsSamples) ws_bytes += line_work_bytes(g[0]);
-    }
-    if (ensure(c, &c->d_lsplit, &c->lsplit_cap, ws_off + ws_bytes)) return 1;
-    unsigned char* d = (unsigned char*)c->d_lsplit;
-    LineSplitParams p;
-    p.profiles = d_profiles; p.regions = (const LineSplitRegion*)d; p.n_regions = n_regions; p.sigma_max = sigma_max;
-    p.weights = (const double*)((unsigned char*)c->d_line_w + off_bytes); p.weight_off = (const long long*)c->d_line_w;
-    p.workspace = d + ws_off; p.info = (int32_t*)(d + info_off); p.pts = (int32_t*)(d + pts_off); p.box = (int32_t*)(d + box_off);
-    p.rot = (int32_t*)(d + rot_off);
-    HIPCHK(hipMemcpyAsync(d, head.data(), info_off, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_line_split(p, ws_bytes > 0, c->stream));
-    c->line_launches += ws_bytes > 0 ? 2 : 1;
-    *out = p;
-    return 0;
-}
-
-// copies info and, per region, its first `count` lines back: nothing beyond a region's count is written on the host
-static int line_split_download(sbbseg_ctx* c, const LineSplitParams& p, const int64_t* line_off, int32_t* info, int32_t* lines, int32_t* corners,
-                               int32_t* corners_rot)
-{
-    const size_t total = (size_t)line_off[p.n_regions];
-    std::vector<int32_t> stage(total * 19);
-    HIPCHK(hipMemcpyAsync(info, p.info, (size_t)p.n_regions * kLineInfoInts * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(stage.data(), p.pts, total * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(stage.data() + total * 3, p.box, total * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(stage.data() + total * 11, p.rot, total * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffers live until here)
-    for (int r = 0; r < p.n_regions; ++r) {
-        const size_t at = (size_t)line_off[r], n = (size_t)info[(size_t)r * kLineInfoInts + kLineInfoCount];
-        memcpy(lines + at * 3, stage.data() + at * 3, n * 3 * sizeof(int32_t));
-        memcpy(corners + at * 8, stage.data() + total * 3 + at * 8, n * 8 * sizeof(int32_t));
-        memcpy(corners_rot + at * 8, stage.data() + total * 11 + at * 8, n * 8 * sizeof(int32_t));
-    }
-    return 0;
-}
-
-int sbbseg_line_split_dev(sbbseg_ctx* c, const void* d_profiles, const int64_t* offsets, int n_regions, const int32_t* geom, const double* rot,
-                          const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info, int64_t* line_off, int32_t* lines,
-                          int32_t* corners, int32_t* corners_rot)
-{
-    API_BEGIN
-    if (check_line_split_tables(offsets, n_regions, geom, rot, weights, weight_off, sigma_max, line_off)) return 1;
-    if (n_regions == 0) return 0;
-    if (check_ready(c)) return 1;
-    REQUIRE(d_profiles && info && lines && corners && corners_rot, "bad arguments");
-    alloc_check();
-    std::vector<unsigned char> head;
-    LineSplitParams p;
-    if (line_split_queue(c, (const int32_t*)d_profiles, offsets, n_regions, geom, rot, weights, weight_off, sigma_max, line_off, head, &p)) return 1;
-    return line_split_download(c, p, line_off, info, lines, corners, corners_rot);
-    API_END
-}
-
-int sbbseg_region_line_boxes_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
-                                 const double* slopes, const double* rot, const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info,
-                                 int64_t* line_off, int32_t* lines, int32_t* corners, int32_t* corners_rot)
-{
-    API_BEGIN
-    REQUIRE(n_boxes >= 0 && n_boxes <= (1 << 20) && line_off && ((boxes_xywh && slopes && rot) || n_boxes == 0), "bad arguments");
-    alloc_check();
-    std::vector<int64_t> mask_off((size_t)n_boxes + 1), row_off((size_t)n_boxes + 1), col_off((size_t)n_boxes + 1), prof_off((size_t)n_boxes + 1);
-    std::vector<int32_t> geom((size_t)n_boxes * 3);
-    std::vector<unsigned char> head_masks, head_split;
-    RegionLinesParams lp;
-    long long total_rows = 0;
-    if (region_line_masks_queue(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, slopes, true, mask_off.data(), row_off.data(), col_off.data(),
-                                head_masks, &lp, &total_rows)) return 1;
-    // rows and cols are one device array (cols behind rows): a region's profile is its row sums, or its column sums beyond 45 degrees
-    // (main.py:1514)
-    int64_t at = 0;
-    for (int r = 0; r < n_boxes; ++r) {
-        const int w = boxes_xywh[(size_t)r * 4 + 2], h = boxes_xywh[(size_t)r * 4 + 3], vertical = std::fabs(slopes[r]) > 45.0;
-        geom[(size_t)r * 3] = vertical ? w : h; geom[(size_t)r * 3 + 1] = vertical ? h : w; geom[(size_t)r * 3 + 2] = vertical;
-        prof_off[r] = at;
-        at += geom[(size_t)r * 3];
-    }
-    prof_off[n_boxes] = at;
-    if (check_line_split_tables(prof_off.data(), n_boxes, geom.data(), rot, weights, weight_off, sigma_max, line_off)) return 1;
-    if (n_boxes == 0) return 0;
-    REQUIRE(info && lines && corners && corners_rot, "bad arguments");
-    for (int r = 0; r < n_boxes; ++r) prof_off[r] = geom[(size_t)r * 3 + 2] ? total_rows + col_off[r] : row_off[r];
-    LineSplitParams p;
-    if (line_split_queue(c, lp.rows, prof_off.data(), n_boxes, geom.data(), rot, weights, weight_off, sigma_max, line_off, head_split, &p)) return 1;
-    return line_split_download(c, p, line_off, info, lines, corners, corners_rot);
-    API_END
-}
-
-int sbbseg_region_line_boxes(sbbseg_ctx* c, const uint8_t* textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
-                             const double* slopes, const double* rot, const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info,
-                             int64_t* line_off, int32_t* lines, int32_t* corners, int32_t* corners_rot)
-{
-    API_BEGIN
-    REQUIRE(H > 0 && W > 0 && n_boxes >= 0, "bad arguments");
-    if (n_boxes > 0) {
-        if (check_ready(c)) return 1;
-        REQUIRE(textline_hw, "bad arguments");
-        const size_t pix = (size_t)H * W;
-        if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
-        HIPCHK(hipMemcpyAsync(c->d_morph_b, textline_hw, pix, hipMemcpyHostToDevice, c->stream));
-    }
-    return sbbseg_region_line_boxes_dev(c, n_boxes > 0 ? c->d_morph_b : nullptr, H, W, boxes_xywh, n_boxes, erode_iterations, slopes, rot, weights,
-                                        weight_off, sigma_max, info, line_off, lines, corners, corners_rot);
-    API_END
-}
-
 // ----------------------------------------------------------------------------------------- debug
 int sbbseg_debug_ingest(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, int Wp, const int32_t* tile_xy, int n_tiles,
                         int form, float* out, size_t out_floats)
@@ -4222,33 +2861,6 @@ int sbbseg_allgather_labels_dev(sbbseg_ctx* c, const void* d_send, size_t bytes_
     HIPCHK(hipSetDevice(c->device));
     if (bytes_per_rank == 0) return 0;
     RCCLCHK(g_rccl.AllGather(d_send, d_recv, bytes_per_rank, /* ncclUint8 */ 1, c->comm, c->stream));
-    return 0;
-    API_END
-}
-
-int sbbseg_debug_largest_contour(const uint8_t* mask_hw, int H, int W, int32_t* box_xywh, int64_t* pixels)
-{
-    API_BEGIN
-    REQUIRE(mask_hw && box_xywh && H > 0 && W > 0 && (size_t)H * W < ((size_t)1 << 31), "bad arguments");
-    alloc_check();
-    int out[5] = {0, 0, 0, 0, 0};
-    const bool any = host_largest_contour(mask_hw, H, W, out);
-    if (pixels) *pixels = any ? out[4] : 0;
-    box_xywh[0] = any ? out[0] : 0; box_xywh[1] = any ? out[1] : 0;
-    box_xywh[2] = any ? out[2] - out[0] + 1 : 0; box_xywh[3] = any ? out[3] - out[1] + 1 : 0;
-    return 0;
-    API_END
-}
-
-int sbbseg_debug_largest_contour_area2(const uint8_t* mask_hw, int H, int W, int64_t* area2)
-{
-    API_BEGIN
-    REQUIRE(mask_hw && area2 && H > 0 && W > 0 && (size_t)H * W < ((size_t)1 << 31), "bad arguments");
-    alloc_check();
-    int out[5] = {0, 0, 0, 0, 0};
-    long long a2 = 0;
-    host_largest_contour(mask_hw, H, W, out, &a2);
-    *area2 = (int64_t)a2;
     return 0;
     API_END
 }

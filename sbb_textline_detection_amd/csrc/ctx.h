@@ -1,0 +1,273 @@
+// ctx.h -- private, host only: what the translation units behind the C ABI (api.hip, stage_glue.hip) share -- the error and
+// exception plumbing, the allocation helpers, and the handle (struct sbbseg_ctx) with the plan structs it embeds.
+#pragma once
+
+#include <new>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/sbbseg.h"
+#include "internal.h"
+#include "region.h"
+
+#define HIPCHK(expr)                                                                                                 \
+    do {                                                                                                             \
+        hipError_t e_ = (expr);                                                                                      \
+        if (e_ != hipSuccess)                                                                                        \
+            return sbbseg::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);     \
+    } while (0)
+
+#define REQUIRE(cond, ...) do { if (!(cond)) return sbbseg::set_error(__VA_ARGS__); } while (0)
+
+// Every extern "C" body runs inside API_BEGIN / API_END: a C++ exception (std::bad_alloc from a std::vector, ...)
+// becomes a non-zero status + sbbseg_last_error() instead of terminating the caller's process -- the reference's
+// callers rely on ordinary Python exceptions (main.py:2061-2157).
+#define API_BEGIN try {
+#define API_END                                                                                               \
+    }                                                                                                         \
+    catch (const std::bad_alloc&) { return sbbseg::set_error("out of host memory (std::bad_alloc)"); }        \
+    catch (const std::exception& e_) { return sbbseg::set_error("internal error: %s", e_.what()); }           \
+    catch (...) { return sbbseg::set_error("unknown internal error"); }
+
+namespace sbbseg {
+
+// Defined once in the library (api.hip): sbbseg_last_error() and sbbseg_debug_inject_alloc_failure() serve every unit.
+extern thread_local std::string g_err;          // written by set_error() (internal.h)
+extern int g_alloc_fail_countdown;              // test hook (sbbseg_debug_inject_alloc_failure): the n-th next alloc_check() throws std::bad_alloc
+inline void alloc_check() { if (g_alloc_fail_countdown > 0 && --g_alloc_fail_countdown == 0) throw std::bad_alloc(); }
+
+int dmalloc(sbbseg_ctx* c, void** p, size_t bytes);                    // hipMalloc, counted in c->device_bytes
+int ensure(sbbseg_ctx* c, void** p, size_t* cap, size_t bytes);        // grows *p to `bytes` (waits for the stream before it frees)
+int check_ready(sbbseg_ctx* c);                                        // a finalized handle; makes its device current
+
+template <typename T>
+int upload(sbbseg_ctx* c, T** dptr, const T* host, size_t n)
+{
+    if (dmalloc(c, (void**)dptr, n * sizeof(T))) return 1;
+    HIPCHK(hipMemcpy(*dptr, host, n * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+struct Tensor {
+    int H = 0, W = 0, C = 0;
+    size_t elems_per_patch = 0;
+    char* buf = nullptr;          // zero header + data (of the lane in use)
+    char* lane_buf[2] = {nullptr, nullptr};
+    bool is_input_form = false;
+    int form = -1, pad = 0;
+    char* data() const { return buf + kZeroHeaderBytes; }
+};
+
+enum OpType { kConv = 0, kPool = 1, kHead = 2, kTail = 3, kBlock = 4 };
+
+struct ConvOp {
+    sbbseg_conv_desc d;
+    int Ho = 0, Wo = 0, TH = 0, TW = 0;
+    int cout_pad = 0, Ktot = 0, total_ksteps = 0, ksteps[2] = {0, 0};
+    KTabEntry* d_ktab = nullptr;
+    KStepRec* d_kstep = nullptr;
+    void* d_w = nullptr;
+    float *d_scale = nullptr, *d_shift = nullptr, *d_rscale = nullptr, *d_rshift = nullptr;
+    float *d_head_w = nullptr, *d_head_scale = nullptr, *d_head_shift = nullptr;
+    // further placement classes merged into this op (parity siblings); class 0 = the fields above
+    int n_cls = 1;
+    void* d_w_cls[4] = {nullptr, nullptr, nullptr, nullptr};
+    KStepRec* d_kstep_cls[4] = {nullptr, nullptr, nullptr, nullptr};
+    KTabEntry* d_ktab_cls[4] = {nullptr, nullptr, nullptr, nullptr};
+    int ooy_cls[4] = {0, 0, 0, 0}, oox_cls[4] = {0, 0, 0, 0};
+    float wmul_cls[4] = {1.f, 1.f, 1.f, 1.f};   // split mode: 2^-s of the class's power-of-two weight pre-scale
+    std::vector<float> h_epi;             // host copy of scale | shift | head_w | head_scale | head_shift: parity siblings are
+                                          // only merged into one launch when these are identical (they share class 0's)
+    uint16_t* d_stem_wfrag = nullptr;     // non-null: the op is the network stem and runs stem_conv_pairs
+    int fused_pool = -1;                  // split mode: index of the max-pool op this stem also computes (sbbseg_finalize), or -1
+    uint16_t* d_halo_wfrag = nullptr;     // split mode, the 224 x 224 decoder conv: the four classes' weights as MFMA A fragments (dec_halo_x3.hip)
+    int* d_halo_taps = nullptr;           //   ... and their taps in K-step order (sbbseg_finalize)
+    uint16_t* d_d64_wfrag = nullptr;      // non-null: 3x3 s1 64->64 conv, runs conv3x3_c64_direct
+    int fused_reduce = -1;                // split mode: index of the NEXT block's first 1x1 conv, computed by this (expand) conv's launch too
+                                          // (expand_reduce_x3.hip; sbbseg_finalize), or -1
+    uint16_t *d_er_w3 = nullptr, *d_er_w1 = nullptr;      //   ... the two convs' packed rows as MFMA A fragments
+    bool fused_into_expand = false;       // split mode: this op's output is written by the launch of the op before it; it launches nothing
+    int fused_conv3 = -1;                 // on an expand conv with fused_reduce: index of the block's 3x3 conv, which the same launch computes too
+                                          // (conv3_expand_reduce.hip; sbbseg_finalize), or -1
+    uint16_t* d_c3_w2 = nullptr;          //   ... the 3x3 conv's packed rows as MFMA A fragments, and its K-steps (taps / channel groups) in order
+    int* d_c3_k0 = nullptr;
+    bool fused_into_c3 = false;           // the 3x3 conv of such a block: its output tensor lives in LDS only, the op launches nothing
+    std::vector<float> h_w[2];            // host copy of a small 1x1 conv's weights ([cin][cout] per source): bottleneck fusion
+                                          // (sbbseg_finalize) repacks them as MFMA A fragments
+    bool fg_ok = true;                    // every K-step (of every class) regular: the fast gather of conv_igemm_mfma applies
+                                          // (ConvParams::fast_gather) if each source's taps also span at most 4 x 4 offsets
+    int tap_lo[2][2] = {{127, 127}, {127, 127}}, tap_hi[2][2] = {{-127, -127}, {-127, -127}};   // [source][y|x] over all classes
+    std::vector<KStepRec> h_ksteps_cls[4];   // host copies: sbbseg_finalize builds the fast gather's tables from them
+    FgStepRec* d_fgstep_cls[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool fg_pointwise = false;            // all taps (0, 0) in bounds: ConvParams::fast_gather = 2 (no masks)
+};
+
+struct PoolOp {
+    int src, dst, k, stride, Ho, Wo; float *d_pre_scale = nullptr, *d_pre_shift = nullptr; int pre_relu = 0;
+    bool fused_into_stem = false;         // split mode: the stem op before it writes this pool's output too (stem_pool_x3); the op then launches nothing
+};
+
+struct HeadOp {
+    int src, cin, classes;
+    float *d_w = nullptr, *d_scale = nullptr, *d_shift = nullptr;
+};
+
+struct TailOp {
+    int src0 = -1, img = -1, classes = 0;
+    void* d_wfrag = nullptr;
+    float *d_scale = nullptr, *d_shift = nullptr, *d_head_w = nullptr, *d_head_scale = nullptr, *d_head_shift = nullptr;
+};
+
+// a fused ResNet bottleneck block (bottleneck_fused): the three convs it replaces stay alive as `parts` of the op
+// (they own the scale / shift arrays and the 3x3 fragments the fused kernel reads, and they are what runs when the
+// fusion is switched off at run time, conv variant bit 18)
+struct BlockOp {
+    int x_tensor = -1, out_tensor = -1, cin = 0, proj = 0, H = 0, W = 0;
+    uint16_t *d_w1 = nullptr, *d_w3 = nullptr;
+    float wmul[3] = {1.f, 1.f, 1.f};      // split mode: 2^-s of the three convs' weight pre-scales
+};
+
+struct Op {
+    OpType type;
+    std::string name;
+    double flops = 0, min_bytes = 0;
+    double issued_flops = 0;      // MFMA work the kernel really issues per patch (K padding, pre-summed taps, 3x in split mode)
+    ConvOp conv;
+    PoolOp pool;
+    HeadOp head;
+    TailOp tail;
+    BlockOp block;
+    std::vector<Op> parts;        // kBlock: the convs it fuses
+    double prof_ms = 0;
+    int64_t prof_launches = 0, prof_patches = 0;
+    int region_level = -1;        // >= 0: a decoder level of the owned-region chain (sbbseg_finalize: region_chain; region.h)
+    double exec_patches = 0;      // work executed since sbbseg_profile_reset, in whole-patch equivalents: a launch of n patches adds n, an
+                                  // owned-region launch n x (pixels walked / pixels of the whole grid)
+    double prof_exec_patches = 0; // the same, over the launches the profiling events timed (prof_ms)
+};
+
+struct PendingEvent { int op; hipEvent_t a, b; int patches; double exec; };
+
+// owned-region launches (region.h): tables of the chunk a lane is running
+struct RegionRun {
+    bool on = false;
+    int kind[kRegionMaxLevels] = {0};            // 0 = tile table, 1 = pixel map (what the level's kernel takes: dec_halo_* / tail vs conv_igemm_mfma)
+    int total[kRegionMaxLevels] = {0};           // entries (per class)
+    double frac[kRegionMaxLevels] = {0};         // pixels walked / pixels of the whole grid, over the chunk
+    uint32_t* tab[kRegionMaxLevels] = {nullptr};
+};
+
+}  // namespace sbbseg
+
+struct sbbseg_ctx {
+    int device = 0;
+    int precision = sbbseg::kBF16;
+    int elem = 2;                 // bytes per stored half-element (weights, one activation plane)
+    int planes = 1;               // 16-bit planes per activation element: 2 in the split mode (hi, lo), else 1
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+    // second lane: its own activation buffers and stream; a chunk of tiles is split over the two lanes so
+    // that one half's launch tails (few tiles left, most CUs idle) are filled by the other half's kernels
+    hipStream_t lane_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int lanes = 2, lane1_batch = 0;
+    int lane_prio = 0, prio_least = 0, prio_greatest = 0;      // priority class of lane_stream (never the own stream's class: see sbbseg_create)
+    int in_H = 0, in_W = 0, in_C = 0;
+    std::vector<sbbseg::Tensor> tensors;
+    std::vector<sbbseg::Op> ops;
+    int form_tensor[2] = {-1, -1};
+    int classes = 0, max_batch = 0;
+    bool finalized = false;
+    size_t device_bytes = 0;
+    // run-time buffers
+    float* d_lut = nullptr;
+    unsigned* d_hist = nullptr;   // [256] channel-0 histogram + [1] Otsu threshold (int) behind it
+    int* d_tile_xy = nullptr;          // [max_batch][2]
+    uint8_t* d_batch_labels = nullptr; // [max_batch][H][W] (predict / whole-image path)
+    float* d_probs = nullptr;          // [max_batch][H][W][classes], lazily allocated
+    float* d_xin = nullptr;            // predict(): staged float input, lazily allocated
+    float* d_ks_ws = nullptr; size_t ks_ws_cap = 0;      // split-K partial sums (whole-image branch)
+    bool ksplit = true, ksplit_now = false;              // SBBSEG_KSPLIT=0 switches it off; _now: inside the whole-image branch's run_plan
+    uint8_t* d_page = nullptr; size_t page_cap = 0;
+    uint8_t* d_page_labels = nullptr; size_t page_labels_cap = 0;
+    uint8_t* d_page_labels3 = nullptr; size_t page_labels3_cap = 0;   // 3-channel copy for label_channels == 3
+    int label_channels = 1;
+    uint8_t* d_tile_labels = nullptr; size_t tile_labels_cap = 0;
+    int *d_own_x = nullptr, *d_own_y = nullptr; size_t own_cap = 0;
+    int own_Hp = -1, own_Wp = -1, own_nyf = 0;
+    bool own_dedupe = false;          // the cached owner tables index the deduplicated grid (see fused_grid)
+    // Duplicate clamped tiles: when extent % mid lies in (0, tile - mid] the inward clamp (main.py:276-281) gives the LAST
+    // TWO tiles of an axis the same origin -- the reference runs the same forward twice and pastes the same labels twice.  The fused
+    // page paths skip the repeat (same label map, 1 / n of the forwards of that axis saved); the tile-indexed entry points
+    // (sbbseg_tile_grid, _segment_tile_range_dev, _stitch_dev: the multi-rank protocol) keep the reference's call list.
+    bool dedupe = true;               // sbbseg_set_dedupe / SBBSEG_DEDUPE=0
+    int64_t forwards = 0;             // patches run through the plan so far (sbbseg_debug_counter 1)
+    int *d_map = nullptr; size_t map_cap = 0;
+    int *d_wmap = nullptr; size_t wmap_cap = 0;      // gather tables of the whole-image branch, cached per geometry
+    int wmap_key[6] = {0, 0, 0, 0, 0, 0};            // {Hp, Wp, Hs, Ws, out_h, out_w} (0 = none)
+    int map_key[4] = {0, 0, 0, 0};     // {Hs, Ws, Hp, Wp} the nearest maps in d_map were built for (sbbseg_segment_crop_dev; 0 = none)
+    // stage glue scratch (morphology planes, union-find arrays, result words)
+    uint8_t *d_morph_a = nullptr, *d_morph_b = nullptr; size_t morph_a_cap = 0, morph_b_cap = 0;
+    // pipelined multi-page host path (sbbseg_segment_pages): copy streams, two slots of pinned staging + device buffers
+    hipStream_t copy_in = nullptr, copy_out = nullptr;
+    hipEvent_t pp_in[2] = {nullptr, nullptr}, pp_comp[2] = {nullptr, nullptr}, pp_out[2] = {nullptr, nullptr};
+    uint8_t *pp_h_in[2] = {nullptr, nullptr}, *pp_h_out[2] = {nullptr, nullptr}, *pp_d_in[2] = {nullptr, nullptr}, *pp_d_out[2] = {nullptr, nullptr},
+            *pp_d_out3[2] = {nullptr, nullptr};
+    size_t pp_in_cap = 0, pp_out_cap = 0, pp_out3_cap = 0;        // device buffers (bytes each)
+    size_t pp_hin_cap = 0, pp_hout_cap = 0;                       // pinned host staging (bytes each)
+    bool pp_ready = false;                                        // streams + events of the page pipeline exist
+    // RCCL communicator of the sharded path (sbbseg_comm_init; librccl is dlopen'ed on first use)
+    void* comm = nullptr;
+    int comm_rank = 0, comm_world = 1;
+    void* d_deskew = nullptr; size_t deskew_cap = 0;      // inverse maps | bicubic table | row counts of sbbseg_deskew_profiles
+    // sbbseg_run_page's resident buffers (owned by the handle passed as `border` / `layout` / `textline` respectively)
+    uint8_t *d_run_page = nullptr, *d_run_mask = nullptr, *d_run_a = nullptr, *d_run_b = nullptr;
+    size_t run_page_cap = 0, run_mask_cap = 0, run_a_cap = 0, run_b_cap = 0;
+    int *d_cc_parent = nullptr, *d_cc_count = nullptr; size_t cc_parent_cap = 0, cc_count_cap = 0;
+    bool force_host_contours = false;     // test hook (conv variant bit 21): always take the exact host ranking
+    int host_contour_calls = 0;           // how often the exact host ranking ran (sbbseg_debug_counter)
+    int* d_cc_list = nullptr;             // [6 + kCcMaxRivals]: launch_largest_contour's result record
+    int* d_cc_aux = nullptr; size_t cc_aux_cap = 0;      // five int planes: doubled cell area + bounding boxes per root (sbbseg_page_box_dev)
+    unsigned long long* d_cc_small = nullptr;      // [0] best key, [1..2] box (4 ints)
+    int* d_cc_bg = nullptr; size_t cc_bg_cap = 0;        // two int planes: labels of the complement, border flags (sbbseg_text_region_boxes_dev)
+    int* d_cc_roots = nullptr; size_t cc_roots_cap = 0;  // parentless roots, 6 ints each
+    void* d_rdk = nullptr; size_t rdk_cap = 0;           // sbbseg_region_deskew_profiles_dev: maps | table | geometry | crops | counts
+    void* d_pstat = nullptr; size_t pstat_cap = 0;       // sbbseg_profile_statistics_dev: weights | regions | spread | winner | state | workspace
+    long long line_launches = 0;                         // kernels queued by sbbseg_region_line_masks_dev (sbbseg_debug_counter 2)
+    void* d_lsplit = nullptr; size_t lsplit_cap = 0;     // sbbseg_line_split_dev: regions | info | lines | corners | rotated corners | workspace
+    void* d_line_w = nullptr; size_t line_w_cap = 0;     // ... its table of half Gaussian kernels: offsets | weights, uploaded when it differs from
+    std::vector<double> line_w_host;                     // ... this copy of the last one
+    int16_t* d_line_tab = nullptr;                       // sbbseg_region_line_masks_dev: the fixed-point bicubic table, built on first use
+    // profiling
+    bool profiling = false;
+    int conv_variant = 0;
+    bool ph8 = false;            // 8-phase schedule on the 256x256 tile (opt-in, conv variant bit 16)
+    int fg_min_ksteps = 9;             // convs with real taps take the fast gather from this many K-steps on (SBBSEG_FG_MIN)
+    int fg_pointwise_min_ksteps = 4;   // pointwise convs take the fast gather from this many K-steps on (SBBSEG_FG_POINTWISE_MIN)
+    bool ranged_walk = false;    // A/B: grouped launches walk XCD-contiguous tile ranges (conv variant bit 19)
+    bool block_pq = true;        // fused bottleneck blocks run the producer / consumer form (conv variant bit 20: the one-group form)
+    bool unfuse_blocks = false;  // A/B: run a fused bottleneck block as its three convs (conv variant bit 18)
+    bool unfuse_stem_pool = false;     // A/B: stem and max-pool as two launches (conv variant bit 22)
+    bool no_dec_halo = false;          // A/B: the 224 x 224 decoder conv on the generic kernel (conv variant bit 23)
+    bool no_expand_reduce = false;     // A/B: expand + next reduce 1x1 convs as two launches (conv variant bit 24)
+    bool no_c3er = false;              // A/B: the 3x3 conv of a stage-3 identity block as its own launch in front of expand_reduce (conv variant bit 25)
+    bool plain_gather = false;   // A/B: per-load address arithmetic instead of the fast gather (conv variant bit 17)
+    int contig_max_k = 0;        // short-K layers up to this K walk their tiles in per-block contiguous runs (tile map 2)
+    int fused_heads = 0;
+    int num_cus = 256;
+    std::vector<sbbseg::PendingEvent> pending;
+    std::vector<hipEvent_t> free_events;
+    // owned-region launches of the decoder (region.h; sbbseg_set_owned_regions): 0 = off, 1 = the fused page paths (default), 2 = the
+    // tile-range entry points of the multi-rank protocol too (their tile labels are then defined on the owned regions only)
+    int owned_mode = 1;
+    int region_levels = 0;                        // decoder levels of the chain found by sbbseg_finalize (0: the plan has none)
+    int region_op[sbbseg::kRegionMaxLevels] = {0};        // op index per level (level 0 = the tail)
+    uint32_t* d_rtab[2][sbbseg::kRegionMaxLevels] = {{nullptr}, {nullptr}};     // per lane and level: the chunk's table (allocated on first use)
+    size_t rtab_cap[2][sbbseg::kRegionMaxLevels] = {{0}, {0}};
+    sbbseg::RegionRun rr;                                 // the chunk run_plan is launching (set by tile_range_impl around run_plan)
+    double last_exec_frac = 1.0;                  // share of its output grid the op being launched walks (run_plan's accounting; launch_op resets
+                                                  // it to 1 when an A/B knob takes a level off its owned-region form)
+    std::vector<std::pair<void*, size_t>> user_bufs;      // sbbseg_device_alloc's buffers still alive (freed by sbbseg_destroy)
+};

@@ -57,6 +57,25 @@ def test_cpp_exception_becomes_status_not_abort(lib):
     assert lib.sbbseg_debug_inject_alloc_failure(0) == 0
 
 
+def test_alloc_failure_hook_reaches_the_glue_unit(lib):
+    """The library has ONE alloc-failure countdown: armed through the entry point in api.hip, it fires at an alloc_check() in
+    stage_glue.hip, disarms itself, and the next call gives the same table as before."""
+    before = _capi.region_line_table()
+    assert lib.sbbseg_debug_inject_alloc_failure(1) == 0
+    with pytest.raises(RuntimeError, match="out of host memory"):
+        _capi.region_line_table()
+    assert np.array_equal(_capi.region_line_table(), before)
+
+
+def test_error_message_crosses_units(lib):
+    """One thread-local message behind sbbseg_last_error(): a box check in stage_glue.hip (the size-only path: no handle) and
+    an argument check in api.hip both write it, one right after the other."""
+    with pytest.raises(RuntimeError, match="leaves the 8 x 8 plane"):
+        _capi.region_deskew_offsets([[0, 0, 9, 9]], 80, 8, 8)
+    with pytest.raises(RuntimeError, match="smaller than the model"):
+        _capi.tile_grid(300, 500, 448, 448)
+
+
 def test_nearest_map_rule(lib):
     """The library's INTER_NEAREST index rule (page rescale fused into the tile gather) against
     hand-computed cases (odd ratios, up and down) and against the oracle's restatement on the sizes the
@@ -104,7 +123,7 @@ def test_shipped_library_has_no_wrong_answer_probes(lib):
                  b"SBBSEG_BALANCED_GRID", b"SBBSEG_GRID_CUS", b"SBBSEG_TILE2D", b"SBBSEG_DEC_HALO", b"SBBSEG_EXPAND_REDUCE", b"SBBSEG_C3ER",
                  b"SBBSEG_STEM_POOL\0", b"SBBSEG_STEM_KERNEL", b"SBBSEG_DIRECT64_KERNEL"):
         assert name not in blob, name.decode()
-    for src in ("api.hip", "kernels.hip", "block_x3.hip", "expand_reduce_x3.hip"):
+    for src in ("api.hip", "stage_glue.hip", "kernels.hip", "block_x3.hip", "expand_reduce_x3.hip"):
         text = open(os.path.join(ROOT, "sbb_textline_detection_amd", "csrc", src)).read()
         # every use of the probe bits in device code goes through SBBSEG_PROBE(...) (constant false in the shipped build) ...
         for m in re.finditer(r"(variant_flags & (?:32|64)|p\.dbg & \d)", text):
