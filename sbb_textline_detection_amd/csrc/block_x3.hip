@@ -7,7 +7,7 @@
 //
 // Run as three launches in the split mode these layers move 4 bytes per element of the 256-channel tensor four times per
 // block (2.0 ms per 140 patches, 4.0-4.3 TB/s); fused, x is read once (+ the halo overlap, from L2) and y written once.
-// The 16-bit kernel (bottleneck_fused, kernels.hip) does not carry over: doubled operands do not fit its LDS / register
+// The 16-bit kernel (bottleneck_fused, bottleneck.hip) does not carry over: doubled operands do not fit its LDS / register
 // budget.  What changes here:
 //   * tile 4 x 16 output pixels (halo 6 x 18 = 108 pixels): inner x (the residual) is 64 VGPRs per lane
 //   * W1 and W3 (hi + lo: 64 KB each) fill the LDS; a (halo, 112 rows x 256 B) and b (64 rows x 256 B) SHARE one 28 KB region:
@@ -22,13 +22,9 @@
 //     the 16-lane groups of ds_read_b128 (two k-groups x eight consecutive rows -> the even and the odd slots)
 // One block of four waves per CU (up to 512 VGPRs per lane).  Wave w owns inner row w and border tile w (11 of the 44 border
 // pixels) in phases A and C, and the 16 output channels of MFMA row block w in phase B.
-#include "internal.h"
+#include "device_prims.h"
 
 namespace sbbseg {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 h8_t;
-typedef __attribute__((ext_vector_type(4))) float f4_t;
-template <int N> struct IC { static constexpr int value = N; };
 
 namespace {
 
@@ -38,21 +34,6 @@ constexpr int kW3Bytes = 2 * 16 * 2 * 1024;                     // [2 kk][16 mi]
 constexpr int kABBytes = 112 * 256;                             // a: 108 halo rows + 4 dump rows; b: rows 0..63
 constexpr int kCstBytes = (4 * 64 + 2 * 256) * 4;
 constexpr int kBlockX3LdsBytes = kW1Bytes + kW3Bytes + kABBytes + kCstBytes;      // 162 816 <= 163 840
-
-__device__ inline f4_t mma(h8_t a, h8_t b, f4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-// w * x with both operands split: small terms first
-__device__ inline f4_t mma3(h8_t wh, h8_t wl, h8_t xh, h8_t xl, f4_t c) { return mma(wh, xh, mma(wh, xl, mma(wl, xh, c))); }
-
-__device__ inline void split8(const float (&y)[8], h8_t& hi, h8_t& lo)
-{
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const float v = fminf(fmaxf(y[q], -65504.f), 65504.f);
-        const _Float16 h = (_Float16)v;
-        hi[q] = h;
-        lo[q] = (_Float16)(v - (float)h);
-    }
-}
 
 }  // namespace
 

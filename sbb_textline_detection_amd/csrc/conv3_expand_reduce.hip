@@ -23,88 +23,11 @@
 // tile and costs nothing measurable (the stores are acknowledged by then).  expand_reduce had the same tile top since round 4.  And the
 // wait is one statement, not an `if (first tile) ... else ...` pair: the `"+v"` ties of two asm statements in two branches make the
 // compiler copy the weight registers in front of one of them -- a copy of registers whose loads are still in flight.
-#include "internal.h"
+#include "device_prims.h"
 
 namespace sbbseg {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 h8_t;
-typedef __attribute__((ext_vector_type(4))) _Float16 h4_t;
-typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
-typedef __attribute__((ext_vector_type(4))) float f4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u4_t;
-typedef __attribute__((ext_vector_type(2))) unsigned u2_t;
-#define LDS_AS __attribute__((address_space(3)))
-
-template <int N> struct IC { static constexpr int value = N; };
-template <int B, int E, class F> __device__ __attribute__((always_inline)) inline void static_for(F&& f)
-{
-    if constexpr (B < E) {
-        f(IC<B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-
-__device__ inline f4_t mma(h8_t a, h8_t b, f4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-
-template <int N, class V> __device__ inline void split_n(const float (&y)[N], V& hi, V& lo)
-{
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        const float v = fminf(fmaxf(y[q], -65504.f), 65504.f);
-        const _Float16 h = (_Float16)v;
-        hi[q] = h;
-        lo[q] = (_Float16)(v - (float)h);
-    }
-}
-__device__ inline uint32_t pack_h2(float a, float b)
-{
-    a = fminf(fmaxf(a, -65504.f), 65504.f);
-    b = fminf(fmaxf(b, -65504.f), 65504.f);
-    h2_t v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __attribute__((always_inline)) inline void wload4(u4_t& a, u4_t& b, u4_t& c, u4_t& d, uint32_t voff, u4_t rsrc)
-{
-    asm volatile("buffer_load_dwordx4 %0, %4, %5, 0 offen\n\t"
-                 "buffer_load_dwordx4 %1, %4, %5, 0 offen offset:1024\n\t"
-                 "buffer_load_dwordx4 %2, %4, %5, 0 offen offset:2048\n\t"
-                 "buffer_load_dwordx4 %3, %4, %5, 0 offen offset:3072"
-                 : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d) : "v"(voff), "s"(rsrc) : "memory");
-}
-__device__ __attribute__((always_inline)) inline void wload2(u4_t& a, u4_t& b, uint32_t voff, u4_t rsrc)
-{
-    asm volatile("buffer_load_dwordx4 %0, %2, %3, 0 offen\n\t"
-                 "buffer_load_dwordx4 %1, %2, %3, 0 offen offset:1024"
-                 : "=&v"(a), "=&v"(b) : "v"(voff), "s"(rsrc) : "memory");
-}
-__device__ __attribute__((always_inline)) inline void xload2(u4_t& h, u4_t& l, uint32_t voff, u4_t rsrc)
-{
-    asm volatile("buffer_load_dwordx4 %0, %2, %3, 0 offen\n\t"
-                 "buffer_load_dwordx4 %1, %2, %3, 0 offen offset:64"
-                 : "=&v"(h), "=&v"(l) : "v"(voff), "s"(rsrc) : "memory");
-}
-template <int N> __device__ __attribute__((always_inline)) inline void wait4(u4_t& a, u4_t& b, u4_t& c, u4_t& d)
-{
-    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
-}
-__device__ __attribute__((always_inline)) inline void glds16_hidden(const void* gsrc, uint32_t lds_dst)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ inline u4_t make_rsrc(const void* base, uint32_t bytes)
-{
-    u4_t r;
-    const uint64_t b = (uint64_t)(uintptr_t)base;
-    r[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xffffu);
-    r[2] = __builtin_amdgcn_readfirstlane(bytes);
-    r[3] = 0x00020000u;
-    return r;
-}
 
 constexpr int kHaloPx = 100;                 // 10 x 10
 constexpr int kHaloInstr = 25;               // wave-instructions of 4 pixels x 256 B per piece

@@ -16,17 +16,11 @@
 //     granule G of a pixel at slot (G + (hx & ~1)) & 7 of its half: 16 distinct slots per group.  src0 rows are 256 B with the
 //     split kernel's rotation (G + 2 hx) & 15
 //   * every vector-memory operation of the loop is issued from inline asm and counted by hand, as in the split kernel
-#include "internal.h"
+#include "device_prims.h"
 
 namespace sbbseg {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 h8_t;
-typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
-typedef __attribute__((ext_vector_type(4))) float f4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u4_t;
-#define LDS_AS __attribute__((address_space(3)))
 
 constexpr int kS0Instr = 25, kSkInstr = 45;             // wave-instructions (1 KB) per halo: 100 pixels x 256 B; 10 pair rows x 18 x 256 B
 constexpr int kS0Bytes = kS0Instr * 1024;
@@ -36,45 +30,6 @@ constexpr int kSteps = 17;
 constexpr int kS0PerWave = 4, kSkPerWave = 6;           // DMA instructions per wave per tile (32 >= 25, 48 >= 45: the surplus repeats)
 constexpr int kDma = kS0PerWave + kSkPerWave;
 constexpr int kStores = 4;
-
-template <int N> struct IC { static constexpr int value = N; };
-template <int B, int E, class F> __device__ __attribute__((always_inline)) inline void static_for(F&& f)
-{
-    if constexpr (B < E) {
-        f(IC<B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-
-__device__ inline f4_t mma(h8_t a, h8_t b, f4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-
-// kernels.hip's pack_f16x2: saturate, round to nearest even
-__device__ inline uint32_t pack_h2(float a, float b)
-{
-    a = fminf(fmaxf(a, -65504.f), 65504.f);
-    b = fminf(fmaxf(b, -65504.f), 65504.f);
-    h2_t v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(uint32_t, v);
-}
-
-__device__ __attribute__((always_inline)) inline void wload4(u4_t& a, u4_t& b, u4_t& c, u4_t& d, uint32_t voff, u4_t rsrc)
-{
-    asm volatile("buffer_load_dwordx4 %0, %4, %5, 0 offen\n\t"
-                 "buffer_load_dwordx4 %1, %4, %5, 0 offen offset:1024\n\t"
-                 "buffer_load_dwordx4 %2, %4, %5, 0 offen offset:2048\n\t"
-                 "buffer_load_dwordx4 %3, %4, %5, 0 offen offset:3072"
-                 : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d) : "v"(voff), "s"(rsrc) : "memory");
-}
-template <int N> __device__ __attribute__((always_inline)) inline void wait_w(u4_t& a, u4_t& b, u4_t& c, u4_t& d)
-{
-    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
-}
-__device__ __attribute__((always_inline)) inline void glds16_hidden(const void* gsrc, uint32_t lds_dst)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 
 }  // namespace
 
@@ -263,10 +218,10 @@ __global__ __launch_bounds__(512, 2) void dec_halo_f16(const DecHaloParams p)
             // around the top of a tile the previous tile's 4 stores and the 10 DMA instructions (first tile: no stores yet).
             u4_t (&cw)[4] = w[s & 1];
             if constexpr (t == 0 || t == 1) {
-                if (s < kSteps && it == 0) wait_w<4 + kDma>(cw[0], cw[1], cw[2], cw[3]);
-                else wait_w<4 + kStores + kDma>(cw[0], cw[1], cw[2], cw[3]);
+                if (s < kSteps && it == 0) wait4<4 + kDma>(cw[0], cw[1], cw[2], cw[3]);
+                else wait4<4 + kStores + kDma>(cw[0], cw[1], cw[2], cw[3]);
             } else {
-                wait_w<4>(cw[0], cw[1], cw[2], cw[3]);
+                wait4<4>(cw[0], cw[1], cw[2], cw[3]);
             }
             const h8_t a[2][2] = {{__builtin_bit_cast(h8_t, cw[0]), __builtin_bit_cast(h8_t, cw[1])},
                                   {__builtin_bit_cast(h8_t, cw[2]), __builtin_bit_cast(h8_t, cw[3])}};

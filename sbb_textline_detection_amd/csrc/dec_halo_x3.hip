@@ -25,16 +25,11 @@
 //     wave, duplicates where 25 / 81 do not divide; the last tile re-issues its own halo), so the counts are constants
 //   * pixel rows are 256 B (16 granule slots); granule G of halo pixel (hy, hx) sits at slot (G + 2 hx) & 15 (src0) / (G + hx) & 15
 //     (skip, whose fragments take every second pixel): conflict-free for the 16-lane groups of ds_read_b128
-#include "internal.h"
+#include "device_prims.h"
 
 namespace sbbseg {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 h8_t;
-typedef __attribute__((ext_vector_type(4))) float f4_t;
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
 
 constexpr int kS0Px = 100, kSkPx = 324;                 // halo pixels: 10 x 10, 18 x 18
 constexpr int kS0Instr = 25, kSkInstr = 81;             // wave-instructions of 4 pixels x 256 B
@@ -42,54 +37,6 @@ constexpr int kS0Bytes = kS0Instr * 1024;               // one src0 piece (two c
 constexpr int kSkBytes = kSkInstr * 1024;
 constexpr int kDecHaloLdsBytes = 2 * kS0Bytes + kSkBytes;      // 134 144
 constexpr int kSteps = 34;                              // 4 groups x 4 taps of src0 + 2 groups x 9 taps of the skip
-
-template <int N> struct IC { static constexpr int value = N; };
-// f(IC<B>{}), f(IC<B + 1>{}), ... f(IC<E - 1>{}): the K-step index is a compile-time constant in every copy (register sets are
-// selected by t & 1; `#pragma unroll` left the 34-step loop rolled and the sets in scratch memory)
-template <int B, int E, class F> __device__ __attribute__((always_inline)) inline void static_for(F&& f)
-{
-    if constexpr (B < E) {
-        f(IC<B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-
-__device__ inline f4_t mma(h8_t a, h8_t b, f4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-
-__device__ inline void split8(const float (&y)[8], h8_t& hi, h8_t& lo)
-{
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const float v = fminf(fmaxf(y[q], -65504.f), 65504.f);
-        const _Float16 h = (_Float16)v;
-        hi[q] = h;
-        lo[q] = (_Float16)(v - (float)h);
-    }
-}
-
-typedef __attribute__((ext_vector_type(4))) unsigned u4_t;
-
-// four weight fragments (1 KB apart) of one K-step: 16 bytes per lane each, destination registers valid after wait_w
-__device__ __attribute__((always_inline)) inline void wload4(u4_t& a, u4_t& b, u4_t& c, u4_t& d, uint32_t voff, u4_t rsrc)
-{
-    asm volatile("buffer_load_dwordx4 %0, %4, %5, 0 offen\n\t"
-                 "buffer_load_dwordx4 %1, %4, %5, 0 offen offset:1024\n\t"
-                 "buffer_load_dwordx4 %2, %4, %5, 0 offen offset:2048\n\t"
-                 "buffer_load_dwordx4 %3, %4, %5, 0 offen offset:3072"
-                 : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d) : "v"(voff), "s"(rsrc) : "memory");
-}
-// all but the youngest N vector-memory operations of this wave have completed; ties the four registers to the wait
-template <int N> __device__ __attribute__((always_inline)) inline void wait_w(u4_t& a, u4_t& b, u4_t& c, u4_t& d)
-{
-    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
-}
-// one LDS-DMA wave-instruction hidden from the compiler: lane l's 16 bytes at gsrc(l) land at lds_dst + 16 l (M0 written in the statement that reads it)
-__device__ __attribute__((always_inline)) inline void glds16_hidden(const void* gsrc, uint32_t lds_dst)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 
 }  // namespace
 
@@ -284,12 +231,12 @@ __global__ __launch_bounds__(512, 2) void dec_halo_x3(const DecHaloParams p)
             // (First tile: the prologue's bursts were drained, nothing but the 4 loads of step t - 1 is younger.)
             u4_t (&cw)[4] = w[t & 1];
             if constexpr (t == 0 || t == 1) {
-                if (it == 0) wait_w<4>(cw[0], cw[1], cw[2], cw[3]);
-                else wait_w<4 + 11 + 8>(cw[0], cw[1], cw[2], cw[3]);
+                if (it == 0) wait4<4>(cw[0], cw[1], cw[2], cw[3]);
+                else wait4<4 + 11 + 8>(cw[0], cw[1], cw[2], cw[3]);
             } else if constexpr (t == 8 || t == 9 || t == 16 || t == 17) {
-                wait_w<4 + 4>(cw[0], cw[1], cw[2], cw[3]);
+                wait4<4 + 4>(cw[0], cw[1], cw[2], cw[3]);
             } else {
-                wait_w<4>(cw[0], cw[1], cw[2], cw[3]);
+                wait4<4>(cw[0], cw[1], cw[2], cw[3]);
             }
             const h8_t ch[2] = {__builtin_bit_cast(h8_t, cw[0]), __builtin_bit_cast(h8_t, cw[2])};
             const h8_t cl[2] = {__builtin_bit_cast(h8_t, cw[1]), __builtin_bit_cast(h8_t, cw[3])};

@@ -1,4 +1,4 @@
-// internal.h -- structures shared by the host plan (api.hip) and the gfx950 kernels (kernels.hip).
+// internal.h -- structures shared by the host plan (api.hip) and the gfx950 kernel units (kernels.hip and the other *.hip around it).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -114,7 +114,7 @@ struct ConvParams {
 
 // fused network tail: 3x3 conv over [nearest-x2-upsampled src0 (64 ch), image C8 (3 ch)] -> 32 ch
 // -> BN/ReLU -> 1x1 head -> softmax -> argmax, one launch, nothing but labels (and optional
-// probabilities) written.  See dec_tail_fused in kernels.hip.
+// probabilities) written.  See dec_tail_fused in dec_tail.hip.
 struct TailParams {
     const char* src0;         // buffer start (zero header), [n][PH][PW][64] 16-bit
     const char* img;          // buffer start (zero header), C8 form [n][2PH][2PW][8] (split mode: hi slots 4..6 repeat lo 0..2)
@@ -312,40 +312,52 @@ enum Precision { kBF16 = 0, kF32 = 1, kF16 = 2, kF16X3 = 3 };
 #endif
 inline bool is_split(int precision) { return precision == kF16X3; }
 
-// launchers implemented in kernels.hip ---------------------------------------------------------
+// launchers, by the unit that defines them ---------------------------------------------------
+// kernels.hip
 hipError_t launch_conv(const ConvParams& p, int precision, hipStream_t s);
 hipError_t launch_splitk_finish(const float* ws, int splits, long split_elems, long pixels, int cout, const float* scale, const float* shift,
                                 const void* residual, int relu, void* out, int precision, hipStream_t s);
+// dec_tail.hip, stem.hip, direct64.hip, bottleneck.hip
+hipError_t launch_tail(const TailParams& p, int precision, int num_cus, hipStream_t s);
+hipError_t launch_stem(const StemParams& p, int precision, int num_cus, hipStream_t s);
+hipError_t launch_direct64(const Direct64Params& p, int precision, int num_cus, hipStream_t s);
+constexpr int kTailKSteps = 6;      // 4 taps x 64 channels of src0 + 2 steps for the 9 image taps
+hipError_t launch_bottleneck(const BlockParams& p, int precision, int num_cus, hipStream_t s);
+// the split-mode and fused units
+hipError_t launch_dec_halo_x3(const DecHaloParams& p, int num_cus, hipStream_t s);     // split mode: dec4 with LDS-resident halos (dec_halo_x3.hip)
+hipError_t launch_dec_halo_f16(const DecHaloParams& p, int num_cus, hipStream_t s);    // ... plain fp16 mode (dec_halo_f16.hip)
+hipError_t launch_conv3_expand_reduce(const C3ERParams& p, int num_cus, hipStream_t s);   // 3x3 + expand + next reduce (conv3_expand_reduce.hip)
+hipError_t launch_expand_reduce_x3(const ExpRedParams& p, int num_cus, hipStream_t s);   // split mode: expand + next reduce 1x1 (expand_reduce_x3.hip)
+hipError_t launch_stem_pool_x3(const StemParams& p, int num_cus, hipStream_t s);      // split mode: stem + max-pool in one launch (stem_pool_x3.hip)
+hipError_t launch_block_x3(const BlockParams& p, int num_cus, hipStream_t s);      // split mode, identity blocks (block_x3.hip)
+// pixel_ops.hip
 hipError_t launch_maxpool(const void* src, void* dst, int n, int H, int W, int C, int k, int stride,
                           int Ho, int Wo, const float* pre_scale, const float* pre_shift, int pre_relu,
                           int precision, hipStream_t s);
 hipError_t launch_head(const HeadParams& p, int precision, hipStream_t s);
-hipError_t launch_tail(const TailParams& p, int precision, int num_cus, hipStream_t s);
-hipError_t launch_stem(const StemParams& p, int precision, int num_cus, hipStream_t s);
-hipError_t launch_dec_halo_x3(const DecHaloParams& p, int num_cus, hipStream_t s);     // split mode: dec4 with LDS-resident halos (dec_halo_x3.hip)
-hipError_t launch_dec_halo_f16(const DecHaloParams& p, int num_cus, hipStream_t s);
-hipError_t launch_conv3_expand_reduce(const C3ERParams& p, int num_cus, hipStream_t s);   // 3x3 + expand + next reduce (conv3_expand_reduce.hip)
-hipError_t launch_expand_reduce_x3(const ExpRedParams& p, int num_cus, hipStream_t s);   // split mode: expand + next reduce 1x1 (expand_reduce_x3.hip)    // ... plain fp16 mode (dec_halo_f16.hip)
-hipError_t launch_stem_pool_x3(const StemParams& p, int num_cus, hipStream_t s);      // split mode: stem + max-pool in one launch (stem_pool_x3.hip)
-hipError_t launch_direct64(const Direct64Params& p, int precision, int num_cus, hipStream_t s);
-constexpr int kTailKSteps = 6;      // 4 taps x 64 channels of src0 + 2 steps for the 9 image taps
 hipError_t launch_ingest_u8(const IngestParams& p, int precision, hipStream_t s);
-hipError_t launch_otsu(const uint8_t* page, int src_Wp, int Hp, int Wp, const int* map_y, const int* map_x,
-                       unsigned* hist, int* thr, int num_cus, hipStream_t s);
 hipError_t launch_ingest_f32(const float* x, int n, int H, int W, void* c8, void* pairs, int pad,
                              int pairs_w, int precision, hipStream_t s);
 hipError_t launch_stitch(const uint8_t* tile_labels, int H, int W, const int* own_x, const int* own_y,
                          int nyf, int Hp, int Wp, uint8_t* out, hipStream_t s);
 hipError_t launch_resize_labels(const uint8_t* labels, int H, int W, const int* map_y, const int* map_x,
                                 int out_h, int out_w, uint8_t* out, hipStream_t s);
+hipError_t launch_replicate3(const uint8_t* src, uint8_t* dst, size_t n, hipStream_t s);
+hipError_t launch_to_f32(const void* src, float* dst, size_t n, int precision, hipStream_t s);
+hipError_t launch_split_to_f32(const void* src, float* dst, size_t npix, int C, hipStream_t s);   // [pix][C hi][C lo] -> [pix][C]
+// page_glue.hip
+hipError_t launch_otsu(const uint8_t* page, int src_Wp, int Hp, int Wp, const int* map_y, const int* map_x,
+                       unsigned* hist, int* thr, int num_cus, hipStream_t s);
 // stage glue: iterated 5x5 erode / dilate as one separable clipped min / max filter; largest 8-connected component
 hipError_t launch_morph(const uint8_t* src, uint8_t* tmp, uint8_t* dst, int H, int W, int radius, int is_max, int binarize, hipStream_t s);
 constexpr int kCcMaxRivals = 250;    // rival roots sbbseg_page_box_dev gets back from the device (more: the host scans the label plane)
 hipError_t launch_largest_contour(const uint8_t* mask, int H, int W, int* parent, int* count, int* area2, int* bx0, int* by0, int* bx1,
                                   int* by1, unsigned long long* d_best, int* d_out, hipStream_t s);
-// the roots of the components without a parent (RETR_TREE), after launch_largest_contour on the same plane (kernels.hip)
+// the roots of the components without a parent (RETR_TREE), after launch_largest_contour on the same plane
 hipError_t launch_parentless_roots(const uint8_t* mask, uint8_t* inv, int H, int W, const int* parent, int* bg, int* touch, const int* area2,
                                    const int* bx0, const int* by0, const int* bx1, const int* by1, int* d_n, int* list, int cap, hipStream_t s);
+hipError_t launch_deskew_profiles(const uint8_t* mask, int H, int W, int S, int top, int left, const double* minv, const float* cubic,
+                                  int n_angles, int* counts, hipStream_t s);
 // batched per-region deskew profiles (region_deskew.hip): crop + erode every box of a label plane, then rotate-and-project all
 // (region, angle, row) of a sweep in one launch
 struct DeskewRegion {
@@ -441,13 +453,6 @@ struct LineSplitParams {
     int32_t* rot;             // [lines][4][2]
 };
 hipError_t launch_line_split(const LineSplitParams& p, bool any_long, hipStream_t s);      // 1 launch, 2 with a profile beyond kProfileLdsSamples
-hipError_t launch_replicate3(const uint8_t* src, uint8_t* dst, size_t n, hipStream_t s);
-hipError_t launch_to_f32(const void* src, float* dst, size_t n, int precision, hipStream_t s);
-hipError_t launch_deskew_profiles(const uint8_t* mask, int H, int W, int S, int top, int left, const double* minv, const float* cubic,
-                                  int n_angles, int* counts, hipStream_t s);
-hipError_t launch_bottleneck(const BlockParams& p, int precision, int num_cus, hipStream_t s);
-hipError_t launch_block_x3(const BlockParams& p, int num_cus, hipStream_t s);      // split mode, identity blocks (block_x3.hip)
-hipError_t launch_split_to_f32(const void* src, float* dst, size_t npix, int C, hipStream_t s);   // [pix][C hi][C lo] -> [pix][C]
 
 int conv_row_channel(int row, int cout);   // packed weight row -> output channel (16-bit modes)
 int conv_tile_bc(int cout);   // channel-tile width the bf16 conv kernel uses for `cout` (weights are padded to it)

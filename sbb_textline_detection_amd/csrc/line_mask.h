@@ -3,7 +3,7 @@
 // device code.  region_lines.hip runs these statements on the device, sbbseg_region_line_masks_host on the CPU.
 //
 // The rotation is cv2.warpAffine(INTER_CUBIC, BORDER_REPLICATE) of a uint8 image [EXT, unpinned: OpenCV 4.5.1 imgwarp.cpp restated]:
-//   * source coordinates in fixed point with 5 fractional bits, as the float path of the deskew sweep (kernels.hip) computes them;
+//   * source coordinates in fixed point with 5 fractional bits, as the float path of the deskew sweep (page_glue.hip) computes them;
 //   * the FIXED-POINT bicubic table (initInterTab2D): per (ay, ax) sixteen int16 i[r][c] = saturate_cast<short>(float(tab[ay][r] *
 //     tab[ax][c]) * 32768), rounded to nearest even; when they do not sum to 32768 the difference is taken from one entry of the 2 x 2
 //     block at rows / columns {2, 3}: the block is scanned row-major with both candidates starting at (2, 2), a strictly smaller entry

@@ -3,7 +3,7 @@
 //
 // Two small kernels build the eroded crops of every box, packed one after the other; one kernel then computes the row profile of
 // every (region, angle, destination row) of a sweep.  The arithmetic of a destination pixel is that of deskew_profile_kernel
-// (kernels.hip), statement for statement: fixed-point source coordinates, the float bicubic table, 16 taps added one by one in
+// (page_glue.hip), statement for statement: fixed-point source coordinates, the float bicubic table, 16 taps added one by one in
 // float64, no contraction, mask values as stored.  What differs is how the work is dealt out:
 //   * the grid is a work list of (region, angle, group of kRegionDeskewRows rows) built from prefix sums on the host -- a small
 //     region launches few blocks, not one 256-thread block per row;

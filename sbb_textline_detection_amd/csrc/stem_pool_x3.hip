@@ -17,14 +17,11 @@
 //     (hi + lo of the stored f1, one fma, ReLU): bit-identical to the two-launch form (tests/test_gpu_parity.py)
 //   * blocks b and b + 8 (same XCD under the round-robin dispatch) take the two channel halves of the same strip: the input halo
 //     is fetched into that XCD's L2 once
-#include "internal.h"
+#include "device_prims.h"
 
 namespace sbbseg {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 h8_t;
-typedef __attribute__((ext_vector_type(4))) float f4_t;
 
 constexpr int kSlots = 20;                          // granules per LDS halo row (x + g <= 15 + 3)
 constexpr int kHaloRows = 39;                       // 2 * 17 + 5: 16 output rows + the extra row below
@@ -39,19 +36,11 @@ constexpr int kWloBytes = 7 * 2 * 1024;              // the lo weight fragments 
 constexpr int kStemPoolLdsBytes = 2 * kPlaneBytes + kStageVBytes + kStageRBytes + kSaveBytes + kCstBytes + kWloBytes;      // 78 848: two blocks per CU
 constexpr int kStemPoolF16LdsBytes = kPlaneBytes + kStageVBytes + kStageRBytes + kSaveBytes + kCstBytes;                  // plain fp16 mode: one plane, no lo weights
 
-__device__ inline f4_t mma(h8_t a, h8_t b, f4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+// The halo goes to LDS with glds16_hidden (device_prims.h): behind the builtin LDS-DMA the epilogue's constant reads would drain the
+// queue, so the halo of the next tile could never be in flight during the epilogue.  The wait for these loads is the explicit vmcnt(0)
+// at the top of the tile loop.
 
-// One LDS-DMA wave-instruction (lane l's 16 bytes at gsrc(l) land at lds_dst + 16 l) hidden from the compiler: hipcc drains a
-// builtin LDS-DMA (s_waitcnt vmcnt(0)) in front of the next LDS access of the same basic-block chain, whatever it touches -- here
-// the epilogue's constant reads right behind the issue -- so the halo of the next tile could never be in flight during the epilogue.
-// The wait for these loads is the explicit vmcnt(0) at the top of the tile loop.  (M0 is written in the statement that reads it.)
-__device__ inline void glds16_hidden(const void* gsrc, uint32_t lds_dst)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
+// (not the shared split: this one clamps with v_med3_f32, the shared ones with a min / max pair)
 __device__ inline void split1(float v, _Float16& hi, _Float16& lo)
 {
     v = __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);      // = fminf(fmaxf(v, -65504), 65504) for every non-NaN v, one instruction

@@ -46,7 +46,7 @@ def scaled_size(h: int, w: int) -> Tuple[int, int]:
 def otsu_threshold_u8(ch: np.ndarray) -> int:
     """cv2.threshold(..., THRESH_BINARY + THRESH_OTSU) threshold value [EXT: OpenCV getThreshVal_Otsu_8u]:
     mean from the integer first moment times 1/N, probabilities h[i] * (1/N), strict `>` (first maximum).
-    Host mirror of the device kernel (csrc/kernels.hip otsu_threshold_kernel), for foreign model objects."""
+    Host mirror of the device kernel (csrc/page_glue.hip otsu_threshold_kernel), for foreign model objects."""
     h = np.bincount(np.ascontiguousarray(ch, np.uint8).reshape(-1), minlength=256)
     scale = 1.0 / float(h.sum())
     mu = 0.0

@@ -70,7 +70,7 @@ def _bf16(a32):
 
 
 def split_halves(v32):
-    """(hi, lo) fp16 halves of fp32 values, as fp32 arrays: hi = f16(v) saturating, lo = f16(v - hi) (kernels.hip split_f32)."""
+    """(hi, lo) fp16 halves of fp32 values, as fp32 arrays: hi = f16(v) saturating, lo = f16(v - hi) (device_prims.h split_f32)."""
     v32 = np.clip(np.asarray(v32, np.float32), -F16_MAX, F16_MAX)
     hi = v32.astype(np.float16).astype(np.float32)
     lo = (v32 - hi).astype(np.float16).astype(np.float32)

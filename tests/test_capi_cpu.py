@@ -123,8 +123,9 @@ def test_shipped_library_has_no_wrong_answer_probes(lib):
                  b"SBBSEG_BALANCED_GRID", b"SBBSEG_GRID_CUS", b"SBBSEG_TILE2D", b"SBBSEG_DEC_HALO", b"SBBSEG_EXPAND_REDUCE", b"SBBSEG_C3ER",
                  b"SBBSEG_STEM_POOL\0", b"SBBSEG_STEM_KERNEL", b"SBBSEG_DIRECT64_KERNEL"):
         assert name not in blob, name.decode()
-    for src in ("api.hip", "stage_glue.hip", "kernels.hip", "block_x3.hip", "expand_reduce_x3.hip"):
-        text = open(os.path.join(ROOT, "sbb_textline_detection_amd", "csrc", src)).read()
+    csrc = os.path.join(ROOT, "sbb_textline_detection_amd", "csrc")
+    for src in [s for s in _build.SOURCES if s.endswith(".hip")] + sorted(f for f in os.listdir(csrc) if f.endswith(".h")):
+        text = open(os.path.join(csrc, src)).read()
         # every use of the probe bits in device code goes through SBBSEG_PROBE(...) (constant false in the shipped build) ...
         for m in re.finditer(r"(variant_flags & (?:32|64)|p\.dbg & \d)", text):
             line = text[text.rfind("\n", 0, m.start()) + 1:text.find("\n", m.end())]

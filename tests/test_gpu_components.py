@@ -1,5 +1,5 @@
 """The device's connected-component labelling (-m gpu) against scipy on the adversarial planes of tests/cc_planes.py: the three product
-calls that rest on the lock-free union-find of csrc/kernels.hip -- sbbseg_page_box_dev, sbbseg_text_regions_present_dev and
+calls that rest on the lock-free union-find of csrc/page_glue.hip -- sbbseg_page_box_dev, sbbseg_text_regions_present_dev and
 sbbseg_text_region_boxes[_dev] -- must give what ``slopes_ref.oracle_boxes`` (scipy.ndimage.label, the 4-connected background, the
 oracle's contour area) and ``oracle.stage_glue.page_box`` give.  Every comparison is exact equality, box order included.
 tests/test_cc_planes_cpu.py shows that the planes hold the structures they are named after and that the library's host mirror agrees

@@ -1103,7 +1103,7 @@ def test_page_box_ranking_is_repeatable_on_equal_blobs(stitch_model):
     """Equal-area blobs: the LAST in raster order wins (oracle/stage_glue.largest_component_box: np.argmax over OpenCV's reversed
     contour list) -- every time.  Round 5 found the device ranking picking one of three equal blobs at random on a 4200 x 3000 mask:
     the flatten pass of the component labelling raced with other threads' path halving and left a few pixels pointing at a non-root
-    ancestor, so a blob's area came out short in some runs (kernels.hip cc_flatten_kernel).  Page-sized masks, many repeats; plus
+    ancestor, so a blob's area came out short in some runs (page_glue.hip cc_flatten_kernel).  Page-sized masks, many repeats; plus
     a mask whose largest blob beats the others by ONE cell, where a short count flips the ranking outright."""
     from oracle import stage_glue
     c = stitch_model.ctx

@@ -1,7 +1,7 @@
 // tail_probe.hip -- times launch_tail (split mode) on random data, standalone: hipcc --offload-arch=gfx950 -O3 -std=c++17
 //   -I sbb_textline_detection_amd/csrc tools/probes/tail_probe.hip -o tail_probe
 // usage: tail_probe [patches 140] [precision 3 = f16x3, 2 = f16] [probs 0|1].  Timing only (random operands): parity is what tests/ check.
-#include "kernels.hip"
+#include "dec_tail.hip"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,7 +17,7 @@ int main(int argc, char** argv)
     const size_t img_bytes = kZeroHeaderBytes + (size_t)n * 4 * PH * PW * 8 * 2 * planes;
     const size_t w_bytes = prec == kF16X3 ? (size_t)4 * 2 * kT3HalfSteps * 2 * 64 * 16 : (size_t)4 * kTailKSteps * 2 * 2 * 64 * 16;
     std::vector<uint16_t> h(1 << 20);
-    for (auto& v : h) v = f32_to_f16_rne((float)(rand() % 2001 - 1000) * 1e-3f);
+    for (auto& v : h) v = __builtin_bit_cast(uint16_t, (_Float16)((float)(rand() % 2001 - 1000) * 1e-3f));      // (|v| <= 1: nothing to saturate)
     char *src, *img, *w; float *cst; uint8_t* labels;
     CK(hipMalloc(&src, src_bytes)); CK(hipMalloc(&img, img_bytes)); CK(hipMalloc(&w, w_bytes)); CK(hipMalloc(&cst, 4096)); CK(hipMalloc(&labels, (size_t)n * 4 * PH * PW));
     for (size_t o = 0; o < src_bytes; o += h.size() * 2) CK(hipMemcpy(src + o, h.data(), std::min(h.size() * 2, src_bytes - o), hipMemcpyHostToDevice));
