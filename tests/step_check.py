@@ -320,9 +320,20 @@ def step_tensors(step):
     return [step.src], []
 
 
-def check_step(plan, step, vals, precision, probs=None):
+def _mask_of(mask, key, shape):
+    """bool array broadcastable to `shape` ([n, h, w, c]): the mask of output `key`, everything where there is none."""
+    if mask is None or key not in mask:
+        return np.ones((1,) * len(shape), bool)
+    m = np.asarray(mask[key], bool)
+    assert m.shape == tuple(shape[:3]), (key, m.shape, shape)
+    return m[..., None]
+
+
+def check_step(plan, step, vals, precision, probs=None, mask=None):
     """Compare what the device stored for `step` with its float64 reference.  `probs`: the device's softmax [n,H,W,classes], for a
-    step that carries the head.  Returns a report dict:
+    step that carries the head.  `mask`: dict keyed like the outputs ("out", "raw_out", "logits") of bool [n, out_h, out_w] on the
+    step's own output grid -- elements outside it count nowhere (an owned-region launch writes, and is owed, only a part of the grid);
+    an output without a key counts whole.  Returns a report dict:
       worst     largest |got - ref| / bound over all elements of all stored outputs (inf where the bound is 0 and the error is not)
       index     (output key, patch, y, x, channel) of that element, on the step's own output grid
       n_over    elements with |got - ref| > bound;  n_nan / n_inf  non-finite stored elements where the reference is finite
@@ -340,8 +351,10 @@ def check_step(plan, step, vals, precision, probs=None):
         r, b = ref[key], bound[key]
         g = np.asarray(g, np.float64)
         assert g.shape == r.shape, (step.name, key, g.shape, r.shape)
+        inside = _mask_of(mask, key, r.shape)
         ref_ok = np.isfinite(r) & np.isfinite(b)
-        rep["n_ref_bad"] += int((~ref_ok).sum())
+        rep["n_ref_bad"] += int((~ref_ok & inside).sum())
+        ref_ok &= inside
         rep["n_nan"] += int((np.isnan(g) & ref_ok).sum())
         rep["n_inf"] += int((np.isinf(g) & ref_ok).sum())
         ok = ref_ok & np.isfinite(g)
@@ -360,8 +373,10 @@ def check_step(plan, step, vals, precision, probs=None):
             rep["index"] = (key,) + tuple(int(i) for i in np.unravel_index(int(np.argmax(ratio)), ratio.shape))
     if "logits" in ref:
         lg, d = ref["logits"], bound["logits"]
+        inside = _mask_of(mask, "logits", lg.shape)[..., 0]
         fin = np.isfinite(lg).all(-1) & np.isfinite(d).all(-1)
-        rep["n_ref_bad"] += int((~fin).sum())
+        rep["n_ref_bad"] += int((~fin & inside).sum())
+        fin &= inside
         rep["ref_absmax"] = max(rep["ref_absmax"], float(np.abs(np.where(fin[..., None], lg, 0.0)).max()))
         if probs is not None:
             p = np.asarray(placed(probs, step) if step.kind == "conv" else probs, np.float64)

@@ -5,7 +5,10 @@ dec1 ... tail over that region (+ the halo the later levels read) only; everythi
 full launch, so the stitched label map must be the same byte for byte -- on every page size of the reference fixture, on the three
 model sizes of the fixture (448 x 448, the non-square 320 x 480 whose margin comes from the width, 224 x 224), in both 16-bit modes,
 under both lane settings, for pooled pages, and for the sharded tile ranges.  Activation buffers are filled with NaNs between the runs:
-a level that read something an owned-region launch below it did not write would show."""
+a level that read something an owned-region launch below it did not write shows HERE only if the NaN reaches a kept label -- a tap
+that feeds a finite but wrong halo value, or a table that covers more than it must, leaves the argmax of these random nets alone.
+This file compares label maps and nothing else; what every level writes (footprints, executed work, bit equality and a float64
+reference on the needed box) is held by tests/test_gpu_region_steps.py."""
 import json
 import os
 

@@ -332,3 +332,85 @@ def test_injected_defect_is_reported(defect, where, precision):
           f"{rep['n_over']} elements over; caught-by-new {sc.failed(rep)}; caught-by-old {old_caught} "
           f"(max|err| / max|ref| {rep['old_rel']:.3g} vs {TOL_LAYER_REL[precision]})")
     assert sc.failed(rep) and rep["n_over"] > 0, (DEFECTS[defect], step.name, rep)
+
+
+# ------------------------------------------------------------------------------------------------ mask
+def _masked_case(precision="f16"):
+    """A parity-split decoder conv of the clean run (class (py, px) reads rows y + py - 1, y + py of its source 0 for output row y);
+    mask = the upper left quarter of the step's own grid."""
+    model = "c2_64x96"
+    plan = _plan(model, precision)
+    clean_vals, _, _ = _clean_run(model, precision)
+    step = [s for s in plan.steps if s.kind == "conv" and s.out_stride == (2, 2) and s.out >= 0 and s.head is None][-1]      # the largest grid
+    assert step.out_h >= 8 and step.out_w >= 8 and step.srcs[0].shift == 0 and (step.srcs[0].kh, step.srcs[0].kw) == (2, 2)
+    vals = {k: v.copy() for k, v in clean_vals.items()}
+    mask = np.zeros((next(iter(vals.values())).shape[0], step.out_h, step.out_w), bool)
+    mask[:, :step.out_h // 2, :step.out_w // 2] = True
+    return plan, step, vals, mask
+
+
+def test_mask_none_is_the_unmasked_report():
+    plan, step, vals, mask = _masked_case()
+    a = sc.check_step(plan, step, vals, "f16")
+    b = sc.check_step(plan, step, vals, "f16", mask=None)
+    c = sc.check_step(plan, step, vals, "f16", mask={"out": np.ones_like(mask)})
+    assert a == b == c and not sc.failed(a)
+
+
+@pytest.mark.parametrize("precision", ["f16", "f16x3"])
+def test_mask_keeps_what_lies_outside_it_out_of_every_count(precision):
+    plan, step, vals, mask = _masked_case(precision)
+    g = step.srcs[0]
+    src = vals[g.tensor]
+    clean = sc.check_step(plan, step, vals, precision, mask={"out": mask})
+    assert not sc.failed(clean) and 0 < clean["n_elem"] == int(mask.sum()) * step.cout
+    # a NaN in the source that only output pixels OUTSIDE the mask read: the last row / column of the source
+    src[:, -1, -1, :] = np.nan
+    rep = sc.check_step(plan, step, vals, precision, mask={"out": mask})
+    assert not sc.failed(rep) and rep["n_ref_bad"] == 0 and rep["n_elem"] == clean["n_elem"], rep
+    assert rep["worst"] == clean["worst"] and rep["rms"] == clean["rms"] and rep["ref_absmax"] == clean["ref_absmax"]
+    assert sc.check_step(plan, step, vals, precision)["n_ref_bad"] > 0                   # unmasked, the same NaN is reported
+    # the same NaN where a masked-in pixel reads it
+    src[:, 1, 1, :] = np.nan
+    rep = sc.check_step(plan, step, vals, precision, mask={"out": mask})
+    assert sc.failed(rep) and rep["n_ref_bad"] > 0, rep
+
+
+def test_mask_reports_an_element_over_the_bound_inside_it_only():
+    plan, step, vals, mask = _masked_case()
+    out = sc.placed(vals[step.out], step)
+    out[0, step.out_h - 1, step.out_w - 1, 0] += 1.0                                     # outside the mask
+    rep = sc.check_step(plan, step, vals, "f16", mask={"out": mask})
+    assert not sc.failed(rep) and rep["n_over"] == 0, rep
+    out[0, 0, 0, 0] += 1.0                                                               # inside
+    rep = sc.check_step(plan, step, vals, "f16", mask={"out": mask})
+    assert sc.failed(rep) and rep["n_over"] == 1 and rep["index"] == ("out", 0, 0, 0, 0), rep
+
+
+def test_an_all_false_mask_proves_nothing_and_fails():
+    plan, step, vals, mask = _masked_case()
+    rep = sc.check_step(plan, step, vals, "f16", mask={"out": np.zeros_like(mask)})
+    assert rep["ref_absmax"] == 0 and rep["n_elem"] == 0 and sc.failed(rep), rep
+
+
+def test_mask_applies_to_the_logits_and_the_decided_labels():
+    precision = "f16"
+    plan = _plan("c2_64x96", precision)
+    clean_vals, probs, _ = _clean_run("c2_64x96", precision)
+    tail = plan.steps[-1]
+    assert tail.kind == "tail"
+    vals = {k: v.copy() for k, v in clean_vals.items()}
+    mask = np.zeros(probs.shape[:3], bool)
+    mask[:, :tail.out_h // 2] = True
+    whole = sc.check_step(plan, tail, vals, precision, probs=probs)
+    half = sc.check_step(plan, tail, vals, precision, probs=probs, mask={"logits": mask})
+    assert not sc.failed(half) and 0 < half["n_decided"] < whole["n_decided"] and half["p_err"] <= whole["p_err"]
+    vals[tail.src0][:, -1, :, :] = np.nan                                                # read by the last output rows only
+    rep = sc.check_step(plan, tail, vals, precision, probs=probs, mask={"logits": mask})
+    assert not sc.failed(rep) and rep["n_decided"] == half["n_decided"] and rep["p_err"] == half["p_err"], rep
+    assert sc.check_step(plan, tail, vals, precision, probs=probs)["n_ref_bad"] > 0
+    wrong = probs.copy()
+    wrong[0, 0, 0] = np.roll(wrong[0, 0, 0], 1)
+    wrong[0, -1, -1] = np.roll(wrong[0, -1, -1], 1)
+    rep = sc.check_step(plan, tail, vals, precision, probs=wrong, mask={"logits": mask})
+    assert rep["p_err"] > half["p_err"]
