@@ -1,4 +1,4 @@
-// ctx.h -- private, host only: what the translation units behind the C ABI (api.hip, stage_glue.hip) share -- the error and
+// ctx.h -- private, host only: what the translation units behind the C ABI (api.hip, plan_build.hip, stage_glue.hip) share -- the error and
 // exception plumbing, the allocation helpers, and the handle (struct sbbseg_ctx) with the plan structs it embeds.
 #pragma once
 
@@ -49,6 +49,8 @@ int upload(sbbseg_ctx* c, T** dptr, const T* host, size_t n)
     HIPCHK(hipMemcpy(*dptr, host, n * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
+template <typename T>
+int upload(sbbseg_ctx* c, T** dptr, const std::vector<T>& host) { return upload(c, dptr, host.data(), host.size()); }
 
 struct Tensor {
     int H = 0, W = 0, C = 0;
@@ -147,6 +149,8 @@ struct Op {
                                   // owned-region launch n x (pixels walked / pixels of the whole grid)
     double prof_exec_patches = 0; // the same, over the launches the profiling events timed (prof_ms)
 };
+
+constexpr int kMinLaneTiles = 8;      // a lane gets at least this many tiles, else the chunk runs whole on lane 0
 
 struct PendingEvent { int op; hipEvent_t a, b; int patches; double exec; };
 

@@ -1,7 +1,9 @@
-// internal.h -- structures shared by the host plan (api.hip) and the gfx950 kernel units (kernels.hip and the other *.hip around it).
+// internal.h -- structures shared by the host plan (api.hip, plan_build.hip, wpack.h) and the gfx950 kernel units (kernels.hip and the other *.hip around it).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "../../include/sbbseg.h"
 
 namespace sbbseg {
 
@@ -454,11 +456,33 @@ struct LineSplitParams {
 };
 hipError_t launch_line_split(const LineSplitParams& p, bool any_long, hipStream_t s);      // 1 launch, 2 with a profile beyond kProfileLdsSamples
 
-int conv_row_channel(int row, int cout);   // packed weight row -> output channel (16-bit modes)
-int conv_tile_bc(int cout);   // channel-tile width the bf16 conv kernel uses for `cout` (weights are padded to it)
+// channel-tile width the bf16 conv kernel uses for `cout` (weights are padded to it)
+inline int conv_tile_bc(int cout) { return cout >= 128 ? 128 : (cout > 32 ? 64 : 32); }
+// Channel stored in packed weight row `row` (16-bit modes).  Inside each wave tile of WCH channels
+// (64, or 32 when the channel tile is 32) MFMA row block mi, row rho is given channel
+// (mi>>1)*32 + (rho>>2)*8 + (mi&1)*4 + (rho&3): see the epilogue of conv_igemm_mfma.
+inline int conv_row_channel(int row, int cout)
+{
+    const int wch = conv_tile_bc(cout) == 32 ? 32 : 64;
+    const int base = (row / wch) * wch, t = row % wch;
+    const int mi = t >> 4, rho = t & 15;
+    return base + (mi >> 1) * 32 + (rho >> 2) * 8 + (mi & 1) * 4 + (rho & 3);
+}
 int set_error(const char* fmt, ...);   // fills sbbseg_last_error() (thread-local), returns 1
-uint16_t f32_to_bf16_rne(float f);
-uint16_t f32_to_f16_rne(float f);
+// host conversions f32 -> 16 bits, round to nearest even (device twins: device_prims.h)
+inline uint16_t f32_to_bf16_rne(float f)
+{
+    uint32_t u = __builtin_bit_cast(uint32_t, f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+inline uint16_t f32_to_f16_rne(float f)
+{
+    f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
+    _Float16 h = (_Float16)f;
+    return __builtin_bit_cast(uint16_t, h);
+}
 float bf16_to_f32(uint16_t h);
 
 }  // namespace sbbseg

@@ -12,7 +12,8 @@
 //   * MFMA "A" operand = weights, "B" = pixels, so a lane ends up with consecutive channels of one pixel: 16-byte NHWC
 //     epilogue stores; BN scale/shift, residual add and ReLU are applied in fp32 registers
 //   * X3 = the split-fp16 (label-exact) mode: hi + lo operands, three MFMAs per product.
-// Also here: conv_naive_f32 (the fp32 mode), splitk_finish, and the host conversions between f32 and the 16-bit formats.
+// Also here: conv_naive_f32 (the fp32 mode) and splitk_finish.  (The host conversions f32 -> 16 bits and the row order conv_row_channel
+// are inline in internal.h: the host-only packer wpack.h needs them without this unit.)
 // The other kernel families have a unit each: dec_tail.hip, stem.hip, direct64.hip, bottleneck.hip (direct kernels on LDS halo
 // tiles where an output tile has few channels), pixel_ops.hip (ingest, max-pool, head, stitch, resize) and page_glue.hip (Otsu,
 // morphology, components, deskew profiles); the primitives they share are in device_prims.h.
@@ -20,14 +21,7 @@
 
 namespace sbbseg {
 
-uint16_t f32_to_bf16_rne(float f) { return bf16_bits_rne(f); }
 float bf16_to_f32(uint16_t h) { uint32_t u = (uint32_t)h << 16; return __builtin_bit_cast(float, u); }
-uint16_t f32_to_f16_rne(float f)
-{
-    f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
-    _Float16 h = (_Float16)f;
-    return __builtin_bit_cast(uint16_t, h);
-}
 
 // split mode: add 8 consecutive channels of one stored pixel (hi halves at src, lo halves `plane` elements behind; cf. store_split8)
 __device__ inline void add_split8(const uint16_t* src, int plane, float (&y)[8])
@@ -1169,19 +1163,6 @@ __global__ __launch_bounds__(256) void conv_naive_f32(const ConvParams p)
             ((float*)p.out)[o + c] = y;
         }
     }
-}
-
-int conv_tile_bc(int cout) { return cout >= 128 ? 128 : (cout > 32 ? 64 : 32); }
-
-// Channel stored in packed weight row `row` (16-bit modes).  Inside each wave tile of WCH channels
-// (64, or 32 when the channel tile is 32) MFMA row block mi, row rho is given channel
-// (mi>>1)*32 + (rho>>2)*8 + (mi&1)*4 + (rho&3): see the epilogue of conv_igemm_mfma.
-int conv_row_channel(int row, int cout)
-{
-    const int wch = conv_tile_bc(cout) == 32 ? 32 : 64;
-    const int base = (row / wch) * wch, t = row % wch;
-    const int mi = t >> 4, rho = t & 15;
-    return base + (mi >> 1) * 32 + (rho >> 2) * 8 + (mi & 1) * 4 + (rho & 3);
 }
 
 // (magic, shift) with n / d == umulhi(n, magic) >> shift for every 0 <= n < 2^31; magic == 0: d is a power of two, n >> shift

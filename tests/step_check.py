@@ -7,7 +7,7 @@ evaluated in float64 with the weights quantised the way ``sbbseg_add_conv`` / ``
 element is held to the largest error correct device arithmetic can make on it.  The data model and the geometry are those of
 ``tests/plan_interp.py`` (``source_conv``), evaluated with ``torch.nn.functional.conv2d`` in float64.
 
-Weights (``quantise_weights``; csrc/api.hip wins over any prose):
+Weights (``quantise_weights``; csrc/wpack.h wins over any prose):
   * f32: unchanged.  f16 / bf16: one RNE rounding of the fp32 weight (``f32_to_f16_rne`` saturates at +-65504).
   * f16x3: one power of two ``pre`` per conv (``frexp``: the largest |w| of ALL the conv's sources lands in [256, 512)),
     ``hi = f16(w * pre)``, ``lo = f16(w * pre - hi)``; the kernels multiply with ``hi`` and ``lo`` and the epilogue multiplies
@@ -56,7 +56,7 @@ U_OUT = {"f16": 2.0 ** -11, "bf16": 2.0 ** -8, "f16x3": 2.0 ** -21, "f32": 2.0 *
 SUBNORMAL = {"f16": 2.0 ** -25, "bf16": 0.0, "f16x3": 2.0 ** -25, "f32": 0.0}
 F16_MAX = 65504.0
 SATURATING = ("f16", "f16x3")
-_PARITY_TAPS = {(0, 0): (0, 0), (0, 1): (1, 2), (1, 0): (0, 1), (1, 1): (2, 2)}      # [parity][t] -> first, last tap summed (api.hip `taps`)
+_PARITY_TAPS = {(0, 0): (0, 0), (0, 1): (1, 2), (1, 0): (0, 1), (1, 1): (2, 2)}      # [parity][t] -> first, last tap summed (wpack.h `taps`)
 
 
 # ------------------------------------------------------------------------------------------------ number formats
@@ -113,7 +113,7 @@ def split_weights(ws):
 def quantise_weights(precision, w):
     """Effective weights the device multiplies with, float64.  `w`: one fp32 array, or the list of arrays of ONE conv (they share
     the split mode's pre-scale).  Split mode: (hi + lo) / pre -- the epilogue's `scale / pre` is folded back in, so callers keep
-    the plan's own scale.  Differs from a per-array rule in exactly that: api.hip takes `wmax` over all sources of the conv."""
+    the plan's own scale.  Differs from a per-array rule in exactly that: plan_build.hip takes `wmax` over all sources of the conv."""
     single = isinstance(w, np.ndarray)
     ws = [w] if single else list(w)
     if precision == "f32":

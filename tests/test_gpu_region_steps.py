@@ -59,7 +59,7 @@ class Level:
 
 
 def find_chain(plan):
-    """The plan's side of find_region_chain (csrc/api.hip): the tail, then down through source 0 of the parity-split decoder convs."""
+    """The plan's side of find_region_chain (csrc/plan_build.hip): the tail, then down through source 0 of the parity-split decoder convs."""
     tail = plan.steps[-1]
     assert tail.kind == "tail"
     chain = [Level([tail], -1, tail.out_h, tail.out_w, 0)]

@@ -4,7 +4,7 @@
 "unfused": SBBSEG_FUSE_BLOCKS=0 and conv variant bits 22 | 23 | 24 | 25 -- every plan tensor reaches HBM, no step may be skipped.
 "default": what the product runs; a step is checked when all its sources and its outputs were written (activation buffers are
 filled with NaNs first).  The tensors that were not are exactly those a fused kernel keeps in LDS, re-derived here from the plan by
-the library's own fusion rules (csrc/api.hip fuse_bottlenecks / sbbseg_finalize) and tied to ``ctx.ops()`` by the block count.
+the library's own fusion rules (csrc/plan_build.hip fuse_bottlenecks / sbbseg_finalize) and tied to ``ctx.ops()`` by the block count.
 One table per configuration goes to results/step_check_<precision>_<H>x<W>_<plan>.md (the directory the GPU scripts of tools/ write
 their logs to, kept out of git; profiles/step_check.md keeps a copy)."""
 import os
