@@ -251,6 +251,28 @@ int sbbseg_segment_crop(sbbseg_ctx* c, const uint8_t* page_hwc, int Hs, int Ws, 
 int sbbseg_segment_crop_dev(sbbseg_ctx* c, const void* d_page_hwc, int Hs, int Ws, int Hp, int Wp, int cx, int cy, int cw, int ch,
                             int binarise, void* d_labels_hw, int* d_threshold);
 
+/* Many crops in one call: the tiles of differently sized pages and crops share launches.  A VIEW is what sbbseg_segment_crop_dev takes --
+ * the stored page [Hs][Ws][3], its size Hp x Wp after get_image_and_scales, the crop box on the upscaled page (the full page:
+ * {0, 0, Wp, Hp}), binarise, the label plane [ch][cw] to write and (optional, binarised views) a device int that receives the crop's Otsu
+ * threshold.  The result of view k equals sbbseg_segment_crop_dev on that view alone with the same handle settings, byte for byte.
+ * The tiles of all views form one list, view-major (within a view in the reference's call order, less the repeated clamped tile under
+ * sbbseg_set_dedupe), cut into chunks of <= max_batch tiles exactly as sbbseg_segment_pages_dev cuts its list; views are taken in groups
+ * of about eight chunks, which bounds the tile-label scratch whatever n_views is.  Per call ONE asynchronous upload carries the view
+ * table and the nearest maps of the rescaled views; per lane-chunk there is one ingest and one region-table launch however many views
+ * the chunk spans, per group one stitch launch (every pixel's owner tile in closed form); nothing in the call waits for the device unless a
+ * buffer has to grow.  A bad view (null pointer, box leaving the page, crop smaller than the model input) fails the call before anything is
+ * launched; sbbseg_last_error() names its index.
+ * sbbseg_segment_views: the same from and to host memory -- pages (views with equal d_page_hwc are uploaded once), label planes ([ch][cw],
+ * x3 with sbbseg_set_label_channels(3)) and thresholds[n_views] (0 for a view that is not binarised; may be NULL); d_threshold is ignored. */
+typedef struct sbbseg_view {
+    const void* d_page_hwc;
+    int Hs, Ws, Hp, Wp, cx, cy, cw, ch, binarise;
+    void* d_labels_hw;
+    int* d_threshold;
+} sbbseg_view;
+int sbbseg_segment_views_dev(sbbseg_ctx* c, int n_views, const sbbseg_view* views);
+int sbbseg_segment_views(sbbseg_ctx* c, int n_views, const sbbseg_view* views_host_pointers, int* thresholds);
+
 /* ---- seam 1, patches=False (main.py:368-380): nearest-resize page to the model size, one forward,
  * argmax, nearest-resize labels to out_h x out_w (cv2.INTER_NEAREST index rule). */
 int sbbseg_segment_whole(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, int Wp,
@@ -566,11 +588,14 @@ int sbbseg_debug_largest_contour_area2(const uint8_t* mask_hw, int H, int W, int
  * it: lo_hi[2 k], lo_hi[2 k + 1] for level k = 0 .. levels - 1, level_size[k] = rows of level k (level 0 = the network output) */
 int sbbseg_debug_owned_range(int extent, int tile, int margin, int n_tiles, int t, int* lo, int* hi);
 int sbbseg_debug_region_rows(int extent, int tile, int margin, int n_tiles, int t, int levels, const int32_t* level_size, int32_t* lo_hi);
+/* ... and the owner of every coordinate of such an axis as the stitch of sbbseg_segment_views_dev computes it (the same closed form, on
+ * the host): own[q] = (t << 16) | (q - origin(t)) for the last tile t in paste order that keeps q; own = [extent] */
+int sbbseg_debug_axis_owner(int extent, int tile, int margin, int n_tiles, int32_t* own);
 /* fill every activation buffer (both lanes) and the tile-label scratch with `byte_value` (tests: a launch that reads what an owned-region
  * launch did not write then shows; 0xFF = NaN in every 16-bit format) */
 int sbbseg_debug_poison_activations(sbbseg_ctx* c, int byte_value);
 /* counters: which 0 = how often sbbseg_page_box_dev had to fall back to the host ranking on this handle */
-int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value);      /* which: 0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by sbbseg_region_line_masks(_dev) */
+int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value);      /* which: 0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by sbbseg_region_line_masks(_dev), 3 = ingest + region-table + stitch kernels queued by sbbseg_segment_views_dev */
 /* Test hook for the no-abort guarantee: the nth_check-th next internal host-allocation checkpoint throws
  * std::bad_alloc, which every entry point turns into a non-zero status + sbbseg_last_error() instead of
  * terminating the process (main.py:2061-2157 relies on ordinary exceptions).  0 disarms.  Process-global. */

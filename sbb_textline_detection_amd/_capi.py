@@ -38,6 +38,7 @@ EXPORTS = [
     "sbbseg_profile_statistics_host", "sbbseg_profile_statistics_dev", "sbbseg_deskew_sweep_angles", "sbbseg_region_deskew_slopes_dev", "sbbseg_region_deskew_slopes",
     "sbbseg_region_line_masks_dev", "sbbseg_region_line_masks", "sbbseg_region_line_masks_host", "sbbseg_region_line_table",
     "sbbseg_line_split_host", "sbbseg_line_split_dev", "sbbseg_region_line_boxes_dev", "sbbseg_region_line_boxes",
+    "sbbseg_segment_views_dev", "sbbseg_segment_views", "sbbseg_debug_axis_owner",
 ]
 
 
@@ -51,6 +52,13 @@ class RunInfo(C.Structure):
     """sbbseg_run_info (include/sbbseg.h)"""
     _fields_ = [("box_xywh", C.c_int32 * 4), ("box_pixels", C.c_int64), ("otsu_threshold", C.c_int32), ("regions_ok", C.c_int32),
                 ("text_present", C.c_int32), ("textlines_ok", C.c_int32)]
+
+
+class View(C.Structure):
+    """sbbseg_view (include/sbbseg.h)"""
+    _fields_ = [("page", C.c_void_p), ("Hs", C.c_int32), ("Ws", C.c_int32), ("Hp", C.c_int32), ("Wp", C.c_int32), ("cx", C.c_int32),
+                ("cy", C.c_int32), ("cw", C.c_int32), ("ch", C.c_int32), ("binarise", C.c_int32), ("labels", C.c_void_p),
+                ("threshold", C.c_void_p)]
 
 
 class ConvDesc(C.Structure):
@@ -118,6 +126,9 @@ def load_library(path: Optional[str] = None):
         "sbbseg_allgather_labels_dev": [vp, vp, C.c_size_t, vp],
         "sbbseg_segment_crop": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, C.POINTER(C.c_int)],
         "sbbseg_segment_crop_dev": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],
+        "sbbseg_segment_views_dev": [vp, i32, C.POINTER(View)],
+        "sbbseg_segment_views": [vp, i32, C.POINTER(View), vp],
+        "sbbseg_debug_axis_owner": [i32, i32, i32, i32, vp],
         "sbbseg_otsu_dev": [vp, vp, i32, i32, vp],
         "sbbseg_segment_tile_range_bin_dev": [vp, vp, i32, i32, i32, i32, vp, vp],
         "sbbseg_segment_whole": [vp, vp, i32, i32, i32, i32, vp],
@@ -430,6 +441,47 @@ class Context:
         x, y, w, h = (int(v) for v in box)
         check(self.lib.sbbseg_segment_crop_dev(self.h, C.c_void_p(d_page), Hs, Ws, int(scaled_h), int(scaled_w), x, y, w, h,
                                                1 if binarise else 0, C.c_void_p(d_labels), C.c_void_p(d_threshold or None)), "sbbseg_segment_crop_dev")
+
+    def segment_views_dev(self, views):
+        """Many crops in one call, tiles pooled across them (sbbseg_segment_views_dev).  ``views``: a sequence of
+        (d_page, Hs, Ws, scaled_h, scaled_w, box, binarise, d_labels[, d_threshold]) -- the arguments of :meth:`segment_crop_dev`, per view."""
+        arr = (View * max(len(views), 1))()
+        for k, v in enumerate(views):
+            d_page, Hs, Ws, Hp, Wp, box, binarise, d_labels = v[:8]
+            x, y, w, h = (int(q) for q in box)
+            arr[k] = View(int(d_page) or None, int(Hs), int(Ws), int(Hp), int(Wp), x, y, w, h, 1 if binarise else 0, int(d_labels) or None,
+                          (int(v[8]) if len(v) > 8 else 0) or None)
+        check(self.lib.sbbseg_segment_views_dev(self.h, len(views), arr), "sbbseg_segment_views_dev")
+
+    def segment_views(self, views, channels: int = 1):
+        """The host form: ``views`` = a sequence of (page, scaled_h, scaled_w, box, binarise) as :meth:`segment_crop` takes them; views that
+        pass the same array object share one upload.  Returns [(labels [h][w] (x3), Otsu threshold or None), ...]."""
+        if channels not in (1, 3):
+            raise ValueError("channels must be 1 or 3")
+        check(self.lib.sbbseg_set_label_channels(self.h, channels), "sbbseg_set_label_channels")
+        arr = (View * max(len(views), 1))()
+        pages, outs = {}, []
+        for k, (page, Hp, Wp, box, binarise) in enumerate(views):
+            pg = pages.setdefault(id(page), np.ascontiguousarray(page, np.uint8))
+            if pg.ndim != 3 or pg.shape[2] != 3:
+                raise ValueError(f"view {k}: page must be uint8 [H,W,3], got {pg.shape}")
+            x, y, w, h = (int(q) for q in box)
+            if w < 1 or h < 1:
+                raise ValueError(f"view {k}: empty box {tuple(box)}")
+            outs.append(np.empty((h, w) if channels == 1 else (h, w, 3), np.uint8))
+            arr[k] = View(pg.ctypes.data, pg.shape[0], pg.shape[1], int(Hp), int(Wp), x, y, w, h, 1 if binarise else 0, outs[k].ctypes.data, None)
+        thr = np.zeros(max(len(views), 1), np.int32)
+        check(self.lib.sbbseg_segment_views(self.h, len(views), arr, _ptr(thr)), "sbbseg_segment_views")
+        return [(outs[k], int(thr[k]) if views[k][4] else None) for k in range(len(views))]
+
+    def views_launches(self) -> int:
+        """Ingest + region-table + stitch kernels :meth:`segment_views_dev` has queued on this handle so far (sbbseg_debug_counter 3)."""
+        return self.debug_counter(3)
+
+    def debug_counter(self, which: int) -> int:
+        v = C.c_int64(0)
+        check(self.lib.sbbseg_debug_counter(self.h, int(which), C.byref(v)), "sbbseg_debug_counter")
+        return int(v.value)
 
     # -- the sharded path's collective on RCCL, inside the library (no torch.distributed needed) ------------------
     def comm_init(self, rank: int, world: int, unique_id: bytes):
@@ -882,6 +934,14 @@ def region_rows(extent: int, tile: int, margin: int, n_tiles: int, t: int, level
     check(lib.sbbseg_debug_region_rows(int(extent), int(tile), int(margin), int(n_tiles), int(t), len(sizes), _ptr(sizes), _ptr(out)),
           "sbbseg_debug_region_rows")
     return out
+
+
+def host_axis_owner(extent: int, tile: int, margin: int, n_tiles: int) -> np.ndarray:
+    """int32 [extent]: (tile << 16) | offset inside it of the tile that owns each coordinate of an axis -- the closed form the stitch of
+    segment_views evaluates per pixel; no GPU."""
+    own = np.zeros(int(extent), np.int32)
+    check(load_library().sbbseg_debug_axis_owner(int(extent), int(tile), int(margin), int(n_tiles), _ptr(own)), "sbbseg_debug_axis_owner")
+    return own
 
 
 def host_largest_contour_area2(mask: np.ndarray) -> int:

@@ -410,6 +410,57 @@ struct LaneScope {
     }
 };
 
+// A pooled list of n_tiles tiles, cut into launches: run_chunk(lane, first, nb) queues tiles [first, first + nb) on lane `lane`.
+template <typename F>
+int run_chunked(sbbseg_ctx* c, int n_tiles, F&& run_chunk)
+{
+    // chunks of equal size (108 tiles at max_batch 70 -> 54 + 54, not 70 + 38): launches shrink evenly.
+    // (Profiling runs every launch alone on one lane: its chunks are capped at the size a LANE's launch has in normal operation -- half a
+    // chunk -- so that the per-op times describe the launches the product runs, partial last rounds of the persistent grids included.)
+    const int chunk_cap = (c->profiling && c->lanes == 2 && c->lane1_batch > 0 && c->max_batch >= 4 * kMinLaneTiles) ? (c->max_batch + 1) / 2 : c->max_batch;
+    const int n_chunks = (n_tiles + chunk_cap - 1) / chunk_cap;
+    const int chunk = n_chunks ? (n_tiles + n_chunks - 1) / n_chunks : 0;
+    bool forked = false;
+    for (int done = 0; done < n_tiles; done += chunk) {
+        const int nb = n_tiles - done < chunk ? n_tiles - done : chunk;
+        const bool two = c->lane1_batch > 0 && c->lanes == 2 && !c->profiling && nb >= 2 * kMinLaneTiles;
+        if (!two) {
+            if (forked) {                                       // (a one-lane chunk behind two-lane ones: lane 1 first)
+                HIPCHK(hipEventRecord(c->ev_join, c->lane_stream));
+                HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+                forked = false;
+            }
+            if (run_chunk(0, done, nb)) return 1;               // (not forked here: a fork in front was joined above)
+            continue;
+        }
+        const int na = (nb + 1) / 2, nb2 = nb - na;            // nb2 <= lane1_batch
+        // The lanes fork ONCE per tile range and join once behind its last chunk (round 5): a lane's halves of consecutive chunks follow each
+        // other on the lane's own stream and buffers, nothing of one lane depends on the other.  (Up to round 4 every chunk forked and joined:
+        // the lane that finished its half first waited for the other one -- 7-10 % of the timed region had ONE kernel in flight,
+        // profiles/r05_timeline_gaps.txt.)
+        if (!forked) {
+            HIPCHK(hipEventRecord(c->ev_fork, c->stream));     // page / threshold / earlier ranges are ordered before
+            HIPCHK(hipStreamWaitEvent(c->lane_stream, c->ev_fork, 0));
+            forked = true;
+        }
+        // (a failure from here on must still join the lanes: earlier chunks of this range are in flight on lane_stream, unordered against
+        //  whatever the caller does next on the handle's stream -- stitch, reuse of d_tile_labels, destroy)
+        auto join_on_error = [&]() -> int {
+            if (hipEventRecord(c->ev_join, c->lane_stream) != hipSuccess || hipStreamWaitEvent(c->stream, c->ev_join, 0) != hipSuccess)
+                (void)hipStreamSynchronize(c->lane_stream);
+            (void)hipGetLastError();
+            return 1;
+        };
+        if (run_chunk(0, done, na)) return join_on_error();
+        if (run_chunk(1, done + na, nb2)) return join_on_error();           // (starting lane 1 later -- after lane 0's op k -- measured 3-14 % slower)
+    }
+    if (forked) {
+        HIPCHK(hipEventRecord(c->ev_join, c->lane_stream));
+        HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    }
+    return 0;
+}
+
 // device label plane [pix] -> host buffer, as one plane or as the reference's three identical channels
 int labels_to_host(sbbseg_ctx* c, void* host, size_t pix)
 {
@@ -577,6 +628,8 @@ int sbbseg_destroy(sbbseg_ctx* c)
     (void)hipFree(c->d_lut); (void)hipFree(c->d_hist); (void)hipFree(c->d_tile_xy); (void)hipFree(c->d_batch_labels); (void)hipFree(c->d_probs); (void)hipFree(c->d_xin); (void)hipFree(c->d_ks_ws);
     (void)hipFree(c->d_page); (void)hipFree(c->d_page_labels); (void)hipFree(c->d_page_labels3); (void)hipFree(c->d_tile_labels);
     (void)hipFree(c->d_own_x); (void)hipFree(c->d_own_y); (void)hipFree(c->d_map); (void)hipFree(c->d_wmap);
+    (void)hipFree(c->d_views); (void)hipHostFree(c->h_views);
+    if (c->ev_views) (void)hipEventDestroy(c->ev_views);
     (void)hipFree(c->d_deskew);
     (void)hipFree(c->d_cc_bg); (void)hipFree(c->d_cc_roots); (void)hipFree(c->d_rdk); (void)hipFree(c->d_pstat); (void)hipFree(c->d_line_tab);
     (void)hipFree(c->d_lsplit); (void)hipFree(c->d_line_w);
@@ -894,6 +947,42 @@ static int fused_grid(const sbbseg_ctx* c, int Hp, int Wp, bool dedupe, int* nx,
     return 0;
 }
 
+// ---- what the pooled tile paths share (tile_range_impl: pages of one size; sbbseg_segment_views_dev: views of any size) ----
+// the plan's side of the owned-region geometry: levels, table kinds, output sizes (the page's side -- axes, grid -- is the caller's)
+static void region_plan_levels(const sbbseg_ctx* c, RegionGeom& rg)
+{
+    rg.n_levels = c->region_levels;
+    for (int L = 0; L < c->region_levels; ++L) {
+        const Op& lop = c->ops[c->region_op[L]];
+        if (L == 0) { rg.kind[L] = 0; rg.Rh[L] = c->in_H; rg.Rw[L] = c->in_W; rg.align_x[L] = 16; }
+        else {
+            const Tensor& to = c->tensors[lop.conv.d.out_tensor];
+            rg.kind[L] = runs_dec_halo(c, lop.conv) ? 0 : 1;
+            rg.Rh[L] = to.H; rg.Rw[L] = to.W; rg.align_x[L] = 2;
+        }
+    }
+}
+
+// level L's table of the chunk of nb patches lane `lane` is about to run: `total` entries as the host counted them -> c->rr; the lane's buffer
+// holds the largest table a full batch can need
+static int region_level_table(sbbseg_ctx* c, int lane, const RegionGeom& rg, int L, int nb, long total)
+{
+    const size_t batch_cap = (size_t)(lane == 0 ? c->max_batch : c->lane1_batch);
+    const size_t need = 4 * (rg.kind[L] ? 4 * batch_cap * (size_t)(rg.Rh[L] / 2) * (size_t)(rg.Rw[L] / 2)
+                                         : batch_cap * (size_t)(rg.Rh[L] / 16 + 1) * (size_t)(rg.Rw[L] / 16 + 1));
+    if (c->rtab_cap[lane][L] < need) {
+        HIPCHK(hipDeviceSynchronize());                  // (first use / a kind switched by an A/B knob: rare)
+        if (c->d_rtab[lane][L]) { HIPCHK(hipFree(c->d_rtab[lane][L])); c->device_bytes -= c->rtab_cap[lane][L]; c->d_rtab[lane][L] = nullptr; c->rtab_cap[lane][L] = 0; }
+        if (dmalloc(c, (void**)&c->d_rtab[lane][L], need)) return 1;
+        c->rtab_cap[lane][L] = need;
+    }
+    RegionRun& rr = c->rr;
+    rr.kind[L] = rg.kind[L]; rr.total[L] = (int)total; rr.tab[L] = c->d_rtab[lane][L];
+    rr.frac[L] = (double)total * (rg.kind[L] ? 4.0 : 256.0) / ((double)nb * rg.Rh[L] * rg.Rw[L]);
+    return 0;
+}
+struct RegionOff { sbbseg_ctx* c; ~RegionOff() { c->rr.on = false; } };
+
 // Tiles [first_tile, first_tile + n_tiles) of the tile list of `n_pages` equally sized pages (page-major: tile g = page g / tpp,
 // grid index g % tpp) -> d_tile_labels[g - first_tile].  Chunks of <= max_batch tiles may span pages: big launches fill the chip's
 // persistent grids better than one page's 70 tiles (profiles/r02_experiments.md).
@@ -925,46 +1014,26 @@ static int tile_range_impl(sbbseg_ctx* c, const void* const* d_pages, int n_page
     if (regions) {
         rg.ax = {Wp, c->in_W, margin, c->in_W - 2 * margin, nx};
         rg.ay = {Hp, c->in_H, margin, c->in_H - 2 * margin, ny};
-        rg.tpp = tpp; rg.ny = ny; rg.n_levels = c->region_levels;
-        for (int L = 0; L < c->region_levels; ++L) {
-            const Op& lop = c->ops[c->region_op[L]];
-            if (L == 0) { rg.kind[L] = 0; rg.Rh[L] = c->in_H; rg.Rw[L] = c->in_W; rg.align_x[L] = 16; }
-            else {
-                const Tensor& to = c->tensors[lop.conv.d.out_tensor];
-                rg.kind[L] = runs_dec_halo(c, lop.conv) ? 0 : 1;
-                rg.Rh[L] = to.H; rg.Rw[L] = to.W; rg.align_x[L] = 2;
-            }
-        }
+        rg.tpp = tpp; rg.ny = ny;
+        region_plan_levels(c, rg);
     }
     auto setup_regions = [&](int lane, int g_first, int nb) -> int {       // (inside the lane's scope: c->stream is the lane's stream)
         RegionBuildParams bp;
         memset(&bp, 0, sizeof(bp));
         bp.g = rg; bp.g0 = g_first; bp.nb = nb;
-        RegionRun& rr = c->rr;
-        const size_t batch_cap = (size_t)(lane == 0 ? c->max_batch : c->lane1_batch);
         for (int L = 0; L < rg.n_levels; ++L) {
             long total = 0;
             for (int q = 0; q < nb; ++q) {
                 const int local = (g_first + q) % tpp, i = local / ny, j = local - i * ny;
                 total += region_entries(rg, i, j, L);
             }
-            const size_t need = 4 * (rg.kind[L] ? 4 * batch_cap * (size_t)(rg.Rh[L] / 2) * (size_t)(rg.Rw[L] / 2)
-                                                 : batch_cap * (size_t)(rg.Rh[L] / 16 + 1) * (size_t)(rg.Rw[L] / 16 + 1));
-            if (c->rtab_cap[lane][L] < need) {
-                HIPCHK(hipDeviceSynchronize());                  // (first use / a kind switched by an A/B knob: rare)
-                if (c->d_rtab[lane][L]) { HIPCHK(hipFree(c->d_rtab[lane][L])); c->device_bytes -= c->rtab_cap[lane][L]; c->d_rtab[lane][L] = nullptr; c->rtab_cap[lane][L] = 0; }
-                if (dmalloc(c, (void**)&c->d_rtab[lane][L], need)) return 1;
-                c->rtab_cap[lane][L] = need;
-            }
+            if (region_level_table(c, lane, rg, L, nb, total)) return 1;
             bp.out[L] = c->d_rtab[lane][L]; bp.total[L] = (int)total;
-            rr.kind[L] = rg.kind[L]; rr.total[L] = (int)total; rr.tab[L] = c->d_rtab[lane][L];
-            rr.frac[L] = (double)total * (rg.kind[L] ? 4.0 : 256.0) / ((double)nb * rg.Rh[L] * rg.Rw[L]);
         }
         HIPCHK(launch_region_build(bp, c->stream));
-        rr.on = true;
+        c->rr.on = true;
         return 0;
     };
-    struct RegionOff { sbbseg_ctx* c; ~RegionOff() { c->rr.on = false; } };
     auto run_chunk = [&](int lane, int first, int nb) -> int {
         LaneScope scope(c, lane);
         RegionOff roff{c};
@@ -990,51 +1059,7 @@ static int tile_range_impl(sbbseg_ctx* c, const void* const* d_pages, int n_page
         }
         return run_plan(c, nb, (uint8_t*)d_tile_labels + first * per, nullptr);
     };
-    // chunks of equal size (108 tiles at max_batch 70 -> 54 + 54, not 70 + 38): launches shrink evenly.
-    // (Profiling runs every launch alone on one lane: its chunks are capped at the size a LANE's launch has in normal operation -- half a
-    // chunk -- so that the per-op times describe the launches the product runs, partial last rounds of the persistent grids included.)
-    const int chunk_cap = (c->profiling && c->lanes == 2 && c->lane1_batch > 0 && c->max_batch >= 4 * kMinLaneTiles) ? (c->max_batch + 1) / 2 : c->max_batch;
-    const int n_chunks = (n_tiles + chunk_cap - 1) / chunk_cap;
-    const int chunk = n_chunks ? (n_tiles + n_chunks - 1) / n_chunks : 0;
-    bool forked = false;
-    for (int done = 0; done < n_tiles; done += chunk) {
-        const int nb = n_tiles - done < chunk ? n_tiles - done : chunk;
-        const bool two = c->lane1_batch > 0 && c->lanes == 2 && !c->profiling && nb >= 2 * kMinLaneTiles;
-        if (!two) {
-            if (forked) {                                       // (a one-lane chunk behind two-lane ones: lane 1 first)
-                HIPCHK(hipEventRecord(c->ev_join, c->lane_stream));
-                HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-                forked = false;
-            }
-            if (run_chunk(0, done, nb)) return 1;               // (not forked here: a fork in front was joined above)
-            continue;
-        }
-        const int na = (nb + 1) / 2, nb2 = nb - na;            // nb2 <= lane1_batch
-        // The lanes fork ONCE per tile range and join once behind its last chunk (round 5): a lane's halves of consecutive chunks follow each
-        // other on the lane's own stream and buffers, nothing of one lane depends on the other.  (Up to round 4 every chunk forked and joined:
-        // the lane that finished its half first waited for the other one -- 7-10 % of the timed region had ONE kernel in flight,
-        // profiles/r05_timeline_gaps.txt.)
-        if (!forked) {
-            HIPCHK(hipEventRecord(c->ev_fork, c->stream));     // page / threshold / earlier ranges are ordered before
-            HIPCHK(hipStreamWaitEvent(c->lane_stream, c->ev_fork, 0));
-            forked = true;
-        }
-        // (a failure from here on must still join the lanes: earlier chunks of this range are in flight on lane_stream, unordered against
-        //  whatever the caller does next on the handle's stream -- stitch, reuse of d_tile_labels, destroy)
-        auto join_on_error = [&]() -> int {
-            if (hipEventRecord(c->ev_join, c->lane_stream) != hipSuccess || hipStreamWaitEvent(c->stream, c->ev_join, 0) != hipSuccess)
-                (void)hipStreamSynchronize(c->lane_stream);
-            (void)hipGetLastError();
-            return 1;
-        };
-        if (run_chunk(0, done, na)) return join_on_error();
-        if (run_chunk(1, done + na, nb2)) return join_on_error();           // (starting lane 1 later -- after lane 0's op k -- measured 3-14 % slower)
-    }
-    if (forked) {
-        HIPCHK(hipEventRecord(c->ev_join, c->lane_stream));
-        HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-    }
-    return 0;
+    return run_chunked(c, n_tiles, run_chunk);
 }
 
 int sbbseg_segment_tile_range_dev(sbbseg_ctx* c, const void* d_page_hwc, int Hp, int Wp, int first_tile, int n_tiles,
@@ -1396,6 +1421,216 @@ int sbbseg_segment_crop(sbbseg_ctx* c, const uint8_t* page_hwc, int Hs, int Ws, 
     if (binarise) HIPCHK(hipMemcpyAsync(&thr, (int*)(c->d_hist + 256), sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (threshold) *threshold = thr;
+    return 0;
+    API_END
+}
+
+// ---- many views in one call: tiles of differently sized pages and crops share launches (include/sbbseg.h) ----
+// Per call: the view table (region.h ViewRec), a fallback threshold int per view and the nearest maps of the rescaled views are laid out in
+// pinned staging and go up in one asynchronous copy; per group of views (about eight chunks of tiles, which bounds the tile-label scratch):
+// the pooled tile list through run_chunked -- one ingest and one region-table launch per lane-chunk -- and one stitch launch.
+int sbbseg_segment_views_dev(sbbseg_ctx* c, int n_views, const sbbseg_view* views)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    REQUIRE(n_views >= 1, "n_views %d < 1", n_views);
+    REQUIRE(views, "null view array");
+    alloc_check();
+    const int margin = margin_of(c->in_W);
+    const size_t per = (size_t)c->in_H * c->in_W;
+    struct Group { int v0, v1, tiles; unsigned blocks; };
+    struct MapAt { int src, dst, off; };
+    std::vector<ViewRec> recs(n_views);
+    std::vector<Group> groups;
+    std::vector<MapAt> map_at;
+    std::vector<int> maps, one;
+    auto map_offset = [&](int src, int dst) -> int {          // (the views of one document share their maps)
+        for (const MapAt& m : map_at)
+            if (m.src == src && m.dst == dst) return m.off;
+        nearest_map(src, dst, one);        // scaled row -> stored row   (main.py:214 -> 112-113)
+        map_at.push_back({src, dst, (int)maps.size()});
+        maps.insert(maps.end(), one.begin(), one.end());
+        return map_at.back().off;
+    };
+    const int group_cap = 8 * c->max_batch;
+    for (int k = 0; k < n_views; ++k) {
+        const sbbseg_view& v = views[k];
+        REQUIRE(v.d_page_hwc && v.d_labels_hw, "view %d: null page / label pointer", k);
+        REQUIRE(v.Hs > 0 && v.Ws > 0 && v.Hp > 0 && v.Wp > 0, "view %d: bad page size %dx%d (stored %dx%d)", k, v.Hp, v.Wp, v.Hs, v.Ws);
+        REQUIRE(v.cx >= 0 && v.cy >= 0 && v.cw > 0 && v.ch > 0 && (long)v.cx + v.cw <= v.Wp && (long)v.cy + v.ch <= v.Hp,
+                "view %d: crop box {%d,%d,%d,%d} leaves the %dx%d page", k, v.cx, v.cy, v.cw, v.ch, v.Hp, v.Wp);
+        REQUIRE(v.ch >= c->in_H && v.cw >= c->in_W, "view %d: cropped page %dx%d is smaller than the model input %dx%d (unsupported by the reference too, main.py:278-281)",
+                k, v.ch, v.cw, c->in_H, c->in_W);
+        ViewRec& r = recs[k];
+        memset(&r, 0, sizeof(r));
+        if (fused_grid(c, v.ch, v.cw, c->dedupe, &r.nx, &r.ny)) return 1;
+        r.page = (const uint8_t*)v.d_page_hwc; r.labels = (uint8_t*)v.d_labels_hw; r.src_Wp = v.Ws; r.cw = v.cw; r.ch = v.ch;
+        r.n_tiles = r.nx * r.ny;
+        REQUIRE(r.n_tiles < 1 << 30, "view %d: %d x %d tiles are too many", k, r.nx, r.ny);
+        r.mapped = v.Hs != v.Hp || v.Ws != v.Wp;
+        r.my = r.mapped ? map_offset(v.Hs, v.Hp) + v.cy : v.cy;
+        r.mx = r.mapped ? map_offset(v.Ws, v.Wp) + v.cx : v.cx;
+        if (groups.empty() || groups.back().tiles + r.n_tiles > group_cap) groups.push_back({k, k, 0, 0u});
+        Group& g = groups.back();
+        r.first = g.tiles; r.blk_first = g.blocks;
+        const size_t blocks = ((size_t)v.ch * v.cw + 255) / 256;
+        REQUIRE(g.blocks + blocks < (size_t)1 << 31, "view %d: the group's label planes are too large for one stitch launch", k);
+        g.v1 = k + 1; g.tiles += r.n_tiles; g.blocks += (unsigned)blocks;
+    }
+    size_t most = 0;
+    for (const Group& g : groups) most = most > (size_t)g.tiles ? most : (size_t)g.tiles;
+    // one buffer: [n_views] ViewRec | [n_views] int thresholds (views that bring no device int of their own) | maps
+    const size_t thr_at = sizeof(ViewRec) * (size_t)n_views, maps_at = thr_at + sizeof(int) * (size_t)n_views;
+    const size_t bytes = maps_at + sizeof(int) * maps.size();
+    if (c->views_copy_pending) {                               // (the previous call's upload still reads the staging)
+        HIPCHK(hipEventSynchronize(c->ev_views));
+        c->views_copy_pending = false;
+    }
+    if (!c->ev_views) HIPCHK(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
+    if (c->h_views_cap < bytes) {
+        c->h_views_cap = 0;
+        (void)hipHostFree(c->h_views); c->h_views = nullptr;
+        const size_t cap = bytes + bytes / 2;
+        HIPCHK(hipHostMalloc(&c->h_views, cap, hipHostMallocDefault));
+        c->h_views_cap = cap;
+    }
+    if (c->views_cap < bytes && ensure(c, &c->d_views, &c->views_cap, bytes + bytes / 2)) return 1;
+    if (ensure(c, (void**)&c->d_tile_labels, &c->tile_labels_cap, most * per)) return 1;
+    const ViewRec* d_recs = (const ViewRec*)c->d_views;
+    int* d_thr = (int*)((char*)c->d_views + thr_at);
+    const int* d_maps = (const int*)((char*)c->d_views + maps_at);
+    for (int k = 0; k < n_views; ++k) recs[k].thr = views[k].binarise ? (views[k].d_threshold ? views[k].d_threshold : d_thr + k) : nullptr;
+    memcpy(c->h_views, recs.data(), thr_at);
+    memset((char*)c->h_views + thr_at, 0, maps_at - thr_at);
+    if (!maps.empty()) memcpy((char*)c->h_views + maps_at, maps.data(), sizeof(int) * maps.size());
+    HIPCHK(hipMemcpyAsync(c->d_views, c->h_views, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->ev_views, c->stream));
+    c->views_copy_pending = true;
+    c->d_views_thr = d_thr;
+    for (int k = 0; k < n_views; ++k) {                        // otsu_copy over exactly the crop's pixels (channel 0), view by view
+        const ViewRec& r = recs[k];
+        if (!r.thr) continue;
+        const uint8_t* pg = r.mapped ? r.page : r.page + ((size_t)r.my * r.src_Wp + r.mx) * 3;
+        HIPCHK(launch_otsu(pg, r.src_Wp, r.ch, r.cw, r.mapped ? d_maps + r.my : nullptr, r.mapped ? d_maps + r.mx : nullptr, c->d_hist,
+                           (int*)r.thr, c->num_cus, c->stream));
+    }
+    const bool regions = c->owned_mode >= 1 && c->region_levels > 0 && c->max_batch <= kRegionMaxPatches;
+    RegionViewsBuildParams bp;
+    memset(&bp, 0, sizeof(bp));
+    if (regions) region_plan_levels(c, bp.g);
+    bp.tile_h = c->in_H; bp.tile_w = c->in_W; bp.margin = margin;
+    for (const Group& g : groups) {
+        const ViewRec* gv = recs.data() + g.v0;
+        const int nv = g.v1 - g.v0;
+        auto run_chunk = [&](int lane, int first, int nb) -> int {
+            LaneScope scope(c, lane);
+            RegionOff roff{c};
+            if (regions) {                                     // the chunk's tables, on the lane's stream in front of its forward
+                RegionViewsBuildParams lp = bp;
+                lp.views = d_recs + g.v0; lp.n_views = nv; lp.g0 = first; lp.nb = nb;
+                for (int L = 0; L < lp.g.n_levels; ++L) {
+                    long total = 0;
+                    for (int q = 0, w = view_find(nv, (unsigned)first, [&](int m) { return (unsigned)gv[m].first; }); q < nb; ++q) {
+                        while (first + q >= gv[w].first + gv[w].n_tiles) ++w;
+                        const int local = first + q - gv[w].first, i = local / gv[w].ny, j = local - i * gv[w].ny;
+                        total += region_entries(lp.g, view_axis_x(gv[w], c->in_W, margin), view_axis_y(gv[w], c->in_H, margin), i, j, L);
+                    }
+                    if (region_level_table(c, lane, lp.g, L, nb, total)) return 1;
+                    lp.out[L] = c->d_rtab[lane][L]; lp.total[L] = (int)total;
+                }
+                HIPCHK(launch_region_build_views(lp, c->stream));
+                c->views_launches += 1;
+                c->rr.on = true;
+            }
+            IngestParams fp;
+            if (fill_ingest(c, fp)) return 1;                  // (input-form pointers of this lane)
+            IngestViewsParams ip;
+            memset(&ip, 0, sizeof(ip));
+            ip.views = d_recs + g.v0; ip.maps = d_maps; ip.n_views = nv; ip.g0 = first; ip.n_tiles = nb;
+            ip.H = c->in_H; ip.W = c->in_W; ip.margin = margin; ip.lut = fp.lut; ip.c8 = fp.c8; ip.pairs = fp.pairs; ip.pad = fp.pad; ip.pairs_w = fp.pairs_w;
+            HIPCHK(launch_ingest_views(ip, c->precision, c->stream));
+            c->views_launches += 1;
+            return run_plan(c, nb, c->d_tile_labels + (size_t)first * per, nullptr);
+        };
+        if (run_chunked(c, g.tiles, run_chunk)) return 1;
+        HIPCHK(launch_stitch_views(c->d_tile_labels, c->in_H, c->in_W, margin, d_recs + g.v0, nv, g.blocks, c->stream));
+        c->views_launches += 1;
+    }
+    return 0;
+    API_END
+}
+
+int sbbseg_segment_views(sbbseg_ctx* c, int n_views, const sbbseg_view* views_host_pointers, int* thresholds)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    REQUIRE(n_views >= 1, "n_views %d < 1", n_views);
+    REQUIRE(views_host_pointers, "null view array");
+    alloc_check();
+    std::vector<sbbseg_view> dv(views_host_pointers, views_host_pointers + n_views);
+    std::vector<size_t> page_at(n_views), plane_at(n_views);
+    size_t page_bytes = 0, plane_bytes = 0, most_pix = 0;
+    for (int k = 0; k < n_views; ++k) {
+        const sbbseg_view& v = dv[k];
+        REQUIRE(v.d_page_hwc && v.d_labels_hw, "view %d: null page / label pointer", k);
+        REQUIRE(v.Hs > 0 && v.Ws > 0 && v.cw > 0 && v.ch > 0, "view %d: bad page or crop size", k);
+        int same = 0;
+        while (same < k && dv[same].d_page_hwc != v.d_page_hwc) ++same;
+        if (same < k) {
+            REQUIRE(dv[same].Hs == v.Hs && dv[same].Ws == v.Ws, "view %d: the page of view %d with another stored size", k, same);
+            page_at[k] = page_at[same];
+        } else {
+            page_at[k] = page_bytes;
+            page_bytes += ((size_t)v.Hs * v.Ws * 3 + 15) & ~(size_t)15;
+        }
+        const size_t pix = (size_t)v.ch * v.cw;
+        plane_at[k] = plane_bytes;
+        plane_bytes += (pix + 4 + 15) & ~(size_t)15;
+        most_pix = most_pix > pix ? most_pix : pix;
+    }
+    if (ensure(c, (void**)&c->d_page, &c->page_cap, page_bytes)) return 1;
+    if (ensure(c, (void**)&c->d_page_labels, &c->page_labels_cap, plane_bytes)) return 1;
+    if (c->label_channels == 3 && ensure(c, (void**)&c->d_page_labels3, &c->page_labels3_cap, (most_pix + 3) / 4 * 12)) return 1;
+    for (int k = 0; k < n_views; ++k) {
+        int same = 0;
+        while (dv[same].d_page_hwc != dv[k].d_page_hwc) ++same;
+        if (same == k)
+            HIPCHK(hipMemcpyAsync(c->d_page + page_at[k], views_host_pointers[k].d_page_hwc, (size_t)dv[k].Hs * dv[k].Ws * 3, hipMemcpyHostToDevice, c->stream));
+    }
+    for (int k = 0; k < n_views; ++k) {                        // (after the search above: it compares the caller's host pointers)
+        dv[k].d_page_hwc = c->d_page + page_at[k];
+        dv[k].d_labels_hw = c->d_page_labels + plane_at[k];
+        dv[k].d_threshold = nullptr;
+    }
+    if (sbbseg_segment_views_dev(c, n_views, dv.data())) {
+        (void)hipStreamSynchronize(c->stream);                 // (the uploads read the caller's pages)
+        return 1;
+    }
+    for (int k = 0; k < n_views; ++k) {
+        const size_t pix = (size_t)dv[k].ch * dv[k].cw;
+        const uint8_t* plane = c->d_page_labels + plane_at[k];
+        if (c->label_channels == 3) {
+            HIPCHK(launch_replicate3(plane, c->d_page_labels3, pix, c->stream));
+            HIPCHK(hipMemcpyAsync(views_host_pointers[k].d_labels_hw, c->d_page_labels3, pix * 3, hipMemcpyDeviceToHost, c->stream));
+        } else {
+            HIPCHK(hipMemcpyAsync(views_host_pointers[k].d_labels_hw, plane, pix, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    std::vector<int> thr(n_views, 0);
+    HIPCHK(hipMemcpyAsync(thr.data(), c->d_views_thr, sizeof(int) * (size_t)n_views, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (thresholds)
+        for (int k = 0; k < n_views; ++k) thresholds[k] = dv[k].binarise ? thr[k] : 0;
+    return 0;
+    API_END
+}
+
+int sbbseg_debug_axis_owner(int extent, int tile, int margin, int n_tiles, int32_t* own)
+{
+    API_BEGIN
+    REQUIRE(own && tile > 2 * margin && margin >= 0 && extent >= tile && n_tiles >= 1, "bad arguments");
+    const RegionAxis a = {extent, tile, margin, tile - 2 * margin, n_tiles};
+    for (int q = 0; q < extent; ++q) own[q] = region_owner(a, q);
     return 0;
     API_END
 }
@@ -1782,8 +2017,8 @@ int sbbseg_allgather_labels_dev(sbbseg_ctx* c, const void* d_send, size_t bytes_
 int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value)
 {
     API_BEGIN
-    REQUIRE(c && value && which >= 0 && which <= 2, "unknown counter %d (0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by the line-mask calls)", which);
-    *value = which == 0 ? (int64_t)c->host_contour_calls : which == 1 ? (int64_t)c->forwards : (int64_t)c->line_launches;
+    REQUIRE(c && value && which >= 0 && which <= 3, "unknown counter %d (0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by the line-mask calls, 3 = ingest / region-table / stitch kernels queued by sbbseg_segment_views_dev)", which);
+    *value = which == 0 ? (int64_t)c->host_contour_calls : which == 1 ? (int64_t)c->forwards : which == 2 ? (int64_t)c->line_launches : c->views_launches;
     return 0;
     API_END
 }

@@ -212,6 +212,13 @@ struct sbbseg_ctx {
     int *d_wmap = nullptr; size_t wmap_cap = 0;      // gather tables of the whole-image branch, cached per geometry
     int wmap_key[6] = {0, 0, 0, 0, 0, 0};            // {Hp, Wp, Hs, Ws, out_h, out_w} (0 = none)
     int map_key[4] = {0, 0, 0, 0};     // {Hs, Ws, Hp, Wp} the nearest maps in d_map were built for (sbbseg_segment_crop_dev; 0 = none)
+    // sbbseg_segment_views_dev: the call's view table | fallback threshold ints | nearest maps, staged in pinned memory and uploaded in one
+    // asynchronous copy; ev_views marks that copy done (the staging may then be rewritten by the next call)
+    void* d_views = nullptr; size_t views_cap = 0;
+    void* h_views = nullptr; size_t h_views_cap = 0;
+    hipEvent_t ev_views = nullptr; bool views_copy_pending = false;
+    int* d_views_thr = nullptr;       // the last call's threshold ints inside d_views, one per view (sbbseg_segment_views reads them back)
+    int64_t views_launches = 0;       // ingest + region-build + stitch kernels sbbseg_segment_views_dev has queued (sbbseg_debug_counter 3)
     // stage glue scratch (morphology planes, union-find arrays, result words)
     uint8_t *d_morph_a = nullptr, *d_morph_b = nullptr; size_t morph_a_cap = 0, morph_b_cap = 0;
     // pipelined multi-page host path (sbbseg_segment_pages): copy streams, two slots of pinned staging + device buffers

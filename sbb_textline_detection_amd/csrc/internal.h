@@ -342,6 +342,21 @@ hipError_t launch_ingest_f32(const float* x, int n, int H, int W, void* c8, void
                              int pairs_w, int precision, hipStream_t s);
 hipError_t launch_stitch(const uint8_t* tile_labels, int H, int W, const int* own_x, const int* own_y,
                          int nyf, int Hp, int Wp, uint8_t* out, hipStream_t s);
+// sbbseg_segment_views_dev: tiles [g0, g0 + n_tiles) of a group's pooled tile list (region.h ViewRec) -> both input forms, in one launch;
+// the group's label planes out of its tile labels, in one launch (every owner in closed form: region_owner)
+struct ViewRec;
+struct IngestViewsParams {
+    const ViewRec* views;     // the group's views
+    const int* maps;          // the call's nearest maps, concatenated
+    int n_views, g0, n_tiles;
+    int H, W, margin;         // model input size, int(0.1 * W)
+    const float* lut;
+    void* c8;
+    void* pairs;
+    int pad, pairs_w;
+};
+hipError_t launch_ingest_views(const IngestViewsParams& p, int precision, hipStream_t s);
+hipError_t launch_stitch_views(const uint8_t* tile_labels, int H, int W, int margin, const ViewRec* views, int n_views, unsigned n_blocks, hipStream_t s);
 hipError_t launch_resize_labels(const uint8_t* labels, int H, int W, const int* map_y, const int* map_x,
                                 int out_h, int out_w, uint8_t* out, hipStream_t s);
 hipError_t launch_replicate3(const uint8_t* src, uint8_t* dst, size_t n, hipStream_t s);

@@ -1,6 +1,7 @@
 // pixel_ops.hip -- the HBM-bound per-pixel kernels around the convs: ingest (u8 page / f32 batch -> both network-input forms), max-pool,
 // the 1x1 head, the page stitch, label resize, and the conversions of stored tensors back to f32 / three channels.
 #include "device_prims.h"
+#include "region.h"
 
 namespace sbbseg {
 
@@ -148,6 +149,60 @@ hipError_t launch_ingest_u8(const IngestParams& p, int precision, hipStream_t s)
     else if (precision == kF16X3) hipLaunchKernelGGL((ingest_u8_kernel<_Float16, true>), dim3(grid), dim3(256), 0, s, p);
     else if (precision == kF16) hipLaunchKernelGGL(ingest_u8_kernel<_Float16>, dim3(grid), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(ingest_u8_kernel<uint16_t>, dim3(grid), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// ingest of a chunk that pools tiles of several views (sbbseg_segment_views_dev): blockIdx.y = tile of the chunk, so the view
+// (binary search of the pooled tile index in the views' first tiles) and the tile origin are uniform over the block; the pixel then goes
+// through exactly what ingest_u8_kernel does in grid mode -- nearest maps, the LUT or the binarise rule, both input forms.
+// ------------------------------------------------------------------------------------------------
+template <typename E, bool SPLIT = false>
+__global__ __launch_bounds__(256) void ingest_views_kernel(const IngestViewsParams p)
+{
+    const int t = blockIdx.y;
+    const int rem = blockIdx.x * 256 + threadIdx.x;
+    if (rem >= p.H * p.W) return;
+    const unsigned gt = (unsigned)(p.g0 + t);
+    const ViewRec& v = p.views[view_find(p.n_views, gt, [&](int m) { return (unsigned)p.views[m].first; })];
+    const int local = (int)gt - v.first;
+    const int gi = local / v.ny, gj = local - gi * v.ny;
+    const int y = rem / p.W, x = rem - y * p.W;
+    const int vx = min(gi * (p.W - 2 * p.margin), v.cw - p.W) + x;
+    const int vy = min(gj * (p.H - 2 * p.margin), v.ch - p.H) + y;
+    const int sy = v.mapped ? p.maps[v.my + vy] : v.my + vy, sx = v.mapped ? p.maps[v.mx + vx] : v.mx + vx;
+    const uint8_t* px = v.page + ((size_t)sy * v.src_Wp + sx) * 3;
+    const long idx = (long)t * (p.H * p.W) + rem;
+    float f[3];
+    if (v.thr) f[0] = f[1] = f[2] = (int)px[0] > *v.thr ? 1.f : 0.f;      // (otsu_copy: channel 0 into all three, see ingest_u8_kernel)
+    else { f[0] = p.lut[px[0]]; f[1] = p.lut[px[1]]; f[2] = p.lut[px[2]]; }
+    if constexpr (SPLIT) {
+        write_split_input<E>(f, p.c8, p.pairs, idx, t, y, x, p.H, p.pad, p.pairs_w);
+        return;
+    }
+    const E v0 = to_elem<E>(f[0]), v1 = to_elem<E>(f[1]), v2 = to_elem<E>(f[2]), z = to_elem<E>(0.f);
+    Vec8<E> o;
+    o.v[0] = v0; o.v[1] = v1; o.v[2] = v2;
+#pragma unroll
+    for (int i = 3; i < 8; ++i) o.v[i] = z;
+    ((Vec8<E>*)p.c8)[idx] = o;
+    if (p.pairs) {
+        const int PH = p.H + 2 * p.pad;
+        const int xp = x + p.pad;
+        E* dst = (E*)p.pairs + (((size_t)t * PH + (y + p.pad)) * p.pairs_w + (xp >> 1)) * 8 + (xp & 1) * 4;
+        Vec4<E> q; q.v[0] = v0; q.v[1] = v1; q.v[2] = v2; q.v[3] = z;
+        *(Vec4<E>*)dst = q;
+    }
+}
+
+hipError_t launch_ingest_views(const IngestViewsParams& p, int precision, hipStream_t s)
+{
+    if (p.n_tiles <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((p.H * p.W + 255) / 256), (unsigned)p.n_tiles);
+    if (precision == kF32) hipLaunchKernelGGL(ingest_views_kernel<float>, grid, dim3(256), 0, s, p);
+    else if (precision == kF16X3) hipLaunchKernelGGL((ingest_views_kernel<_Float16, true>), grid, dim3(256), 0, s, p);
+    else if (precision == kF16) hipLaunchKernelGGL(ingest_views_kernel<_Float16>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(ingest_views_kernel<uint16_t>, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
@@ -377,6 +432,27 @@ hipError_t launch_stitch(const uint8_t* tile_labels, int H, int W, const int* ow
     const long total = (long)Hp * Wp;
     hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, tile_labels, H, W,
                        own_x, own_y, nyf, Hp, Wp, out);
+    return hipGetLastError();
+}
+
+// the stitch of a group of views in one launch: block b serves 256 pixels of the plane of the view whose block range holds b (every plane
+// starts a new block); the owner of a pixel is region_owner's closed form on the view's two axes -- the value stitch_kernel reads from
+// its uploaded tables
+__global__ __launch_bounds__(256) void stitch_views_kernel(const uint8_t* tile_labels, int H, int W, int margin, const ViewRec* views, int n_views)
+{
+    const ViewRec& v = views[view_find(n_views, blockIdx.x, [&](int m) { return views[m].blk_first; })];
+    const long idx = (long)(blockIdx.x - v.blk_first) * 256 + threadIdx.x;
+    if (idx >= (long)v.ch * v.cw) return;
+    const int y = (int)(idx / v.cw), x = (int)(idx - (long)y * v.cw);
+    const int ex = region_owner(view_axis_x(v, W, margin), x), ey = region_owner(view_axis_y(v, H, margin), y);
+    const int t = v.first + (ex >> 16) * v.ny + (ey >> 16);
+    v.labels[idx] = tile_labels[((size_t)t * H + (ey & 0xffff)) * W + (ex & 0xffff)];
+}
+
+hipError_t launch_stitch_views(const uint8_t* tile_labels, int H, int W, int margin, const ViewRec* views, int n_views, unsigned n_blocks, hipStream_t s)
+{
+    if (n_blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(stitch_views_kernel, dim3(n_blocks), dim3(256), 0, s, tile_labels, H, W, margin, views, n_views);
     return hipGetLastError();
 }
 

@@ -63,16 +63,32 @@ SBBSEG_HD inline void region_down(int& lo, int& hi, int R_below)
     if (hi > R_below) hi = R_below;
 }
 
-// rows [lo, hi) / columns of level `level` that patch (i, j) of the grid must produce (before the level's own rounding below)
-SBBSEG_HD inline void region_needed(const RegionGeom& g, int i, int j, int level, int& ylo, int& yhi, int& xlo, int& xhi)
+// The owner of coordinate q of an axis: the last tile in paste order whose kept range [origin + lo, origin + hi) (region_own before its
+// cut) contains q, as (tile << 16) | (q - origin) -- the value stitch_kernel's uploaded tables hold.  Tiles 0 .. n - 2 sit on unclamped
+// origins (a clamped tile n - 2 repeats tile n - 1's origin and is overwritten by it wherever they differ), so their kept ranges
+// [t * mid + margin, (t + 1) * mid + margin) tile the axis; the last tile takes everything from its own margin on.
+SBBSEG_HD inline int region_owner(const RegionAxis& a, int q)
 {
-    region_own(g.ay, j, ylo, yhi);
-    region_own(g.ax, i, xlo, xhi);
+    int t = a.n - 1;
+    if (a.n > 1 && q < region_origin(a, a.n - 1) + a.margin) t = q < a.margin ? 0 : (q - a.margin) / a.mid;
+    return (t << 16) | (q - region_origin(a, t));
+}
+
+// rows [lo, hi) / columns of level `level` that patch (i, j) of the grid ax x ay must produce (before the level's own rounding below)
+SBBSEG_HD inline void region_needed(const RegionGeom& g, const RegionAxis& ax, const RegionAxis& ay, int i, int j, int level, int& ylo, int& yhi,
+                                    int& xlo, int& xhi)
+{
+    region_own(ay, j, ylo, yhi);
+    region_own(ax, i, xlo, xhi);
     if (yhi <= ylo || xhi <= xlo) { ylo = yhi = xlo = xhi = 0; return; }
     for (int k = 1; k <= level; ++k) {
         region_down(ylo, yhi, g.Rh[k]);
         region_down(xlo, xhi, g.Rw[k]);
     }
+}
+SBBSEG_HD inline void region_needed(const RegionGeom& g, int i, int j, int level, int& ylo, int& yhi, int& xlo, int& xhi)
+{
+    region_needed(g, g.ax, g.ay, i, j, level, ylo, yhi, xlo, xhi);
 }
 
 // kind 1: the range grows to an even length, so that the two parities of an axis have the same number of class rows
@@ -91,16 +107,17 @@ SBBSEG_HD inline int region_tile_origin(int lo, int align, int k, int R)
 }
 
 // table entries of patch (i, j) at `level`: kind 0 = tiles, kind 1 = pixels PER CLASS
-SBBSEG_HD inline int region_entries(const RegionGeom& g, int i, int j, int level)
+SBBSEG_HD inline int region_entries(const RegionGeom& g, const RegionAxis& ax, const RegionAxis& ay, int i, int j, int level)
 {
     int ylo, yhi, xlo, xhi;
-    region_needed(g, i, j, level, ylo, yhi, xlo, xhi);
+    region_needed(g, ax, ay, i, j, level, ylo, yhi, xlo, xhi);
     if (yhi <= ylo) return 0;
     if (g.kind[level] == 0) return region_tiles16(ylo, yhi, 2) * region_tiles16(xlo, xhi, g.align_x[level]);
     region_even(ylo, yhi, g.Rh[level]);
     region_even(xlo, xhi, g.Rw[level]);
     return ((yhi - ylo) >> 1) * ((xhi - xlo) >> 1);
 }
+SBBSEG_HD inline int region_entries(const RegionGeom& g, int i, int j, int level) { return region_entries(g, g.ax, g.ay, i, j, level); }
 
 // table entry: patch (10 bits) | y (11 bits) | x (11 bits).  kind 0: tile origin / 2; kind 1: class-grid pixel
 SBBSEG_HD inline uint32_t region_code(int n, int y, int x) { return ((uint32_t)n << 22) | ((uint32_t)y << 11) | (uint32_t)x; }
@@ -117,5 +134,43 @@ struct RegionBuildParams {
     int total[kRegionMaxLevels];          // entries (per class) of the whole chunk, as the host counted them
 };
 hipError_t launch_region_build(const RegionBuildParams& p, hipStream_t s);
+
+// One view of sbbseg_segment_views_dev, as the device sees it: a crop cw x ch of a (virtually upscaled) stored page with its own tile grid.
+// The views of a GROUP pool their tiles into one list, view-major; within a view tile i * ny + j as everywhere (x outer, y inner).
+struct ViewRec {
+    const uint8_t* page;          // stored page [Hs][Ws][3]
+    uint8_t* labels;              // [ch][cw] out
+    const int* thr;               // binarised view: its Otsu threshold (device int); else null
+    int src_Wp;                   // Ws
+    int cw, ch;                   // the page the tile grid lives on
+    int nx, ny;                   // tiles per axis, after the dedupe rule
+    int first, n_tiles;           // first pooled tile of the view in its group; nx * ny
+    int mapped;                   // 1: crop row r reads stored row maps[my + r] (column alike); 0: stored row my + r (no rescale: my = cy, mx = cx)
+    int my, mx;
+    unsigned blk_first;           // stitch: first 256-pixel block of the view's plane among its group's (every plane starts a new block)
+};
+SBBSEG_HD inline RegionAxis view_axis_x(const ViewRec& v, int tile, int margin) { return {v.cw, tile, margin, tile - 2 * margin, v.nx}; }
+SBBSEG_HD inline RegionAxis view_axis_y(const ViewRec& v, int tile, int margin) { return {v.ch, tile, margin, tile - 2 * margin, v.ny}; }
+// index of the view that holds element `key` of a prefix taken from the views (first pooled tile, first stitch block): the last v with prefix(v) <= key
+template <typename F>
+SBBSEG_HD inline int view_find(int n_views, unsigned key, F prefix)
+{
+    int lo = 0, hi = n_views - 1;
+    while (lo < hi) {
+        const int m = (lo + hi + 1) >> 1;
+        if (prefix(m) <= key) lo = m; else hi = m - 1;
+    }
+    return lo;
+}
+
+// the tables of a chunk whose patches come from several views: patch p is pooled tile g0 + p of the group; g.ax / g.ay / g.tpp / g.ny are not read
+struct RegionViewsBuildParams {
+    RegionGeom g;
+    const ViewRec* views;
+    int n_views, g0, nb, tile_h, tile_w, margin;
+    uint32_t* out[kRegionMaxLevels];
+    int total[kRegionMaxLevels];
+};
+hipError_t launch_region_build_views(const RegionViewsBuildParams& p, hipStream_t s);
 
 }  // namespace sbbseg

@@ -124,6 +124,12 @@ class SegModel:
         """uint8 [Hp,Wp,3] -> uint8 [out_h,out_w] == do_prediction(False, ...)[:, :, 0]."""
         return self.ctx.segment_whole(page_u8, out_h, out_w, channels)
 
+    def segment_views(self, views, channels: int = 1):
+        """Many crops of differently sized pages in one call, their tiles pooled into shared launches: ``views`` = a sequence of
+        (stored page uint8 [Hs,Ws,3], scaled_h, scaled_w, (x, y, w, h), binarise) -> [(labels [h,w] (x3), Otsu threshold or None), ...],
+        each equal to ``ctx.segment_crop`` on that view alone."""
+        return self.ctx.segment_views(views, channels)
+
     @property
     def ctx(self) -> _capi.Context:
         if self._ctx is None or self._ctx.h is None:

@@ -589,3 +589,44 @@ class InferenceStages:
             except Exception:                                       # main.py:2152-2157: the outer bare except -> empty result
                 textlines = None
         return page_mask, regions, textlines, page_coord
+
+    def run_pages(self, images):
+        """``[self.run(img) for img in images]``, with the two patch stages pooled over the pages: the border model and the page box run
+        page by page as in run(); the layout model then takes ALL pages' crops in one ``segment_views`` call (their tiles share launches
+        although every crop has its own size), cleaning and the text-region gate run per page, and the textline model takes the crops of
+        the pages that passed the gate in one more call.  A page whose crop cannot hold one input of a model is kept out of that model's
+        call and gets what run() gives it (regions = None / textlines = None); extract_page's errors propagate.  Foreign model objects
+        take the loop."""
+        images = list(images)
+        opened = [start_new_session_and_model(d, **self.kw) for d in (self.model_page_dir, self.model_region_dir, self.model_textline_dir)]
+        try:
+            (_, _), (m_region, _), (m_text, _) = opened
+            if not all(isinstance(m, SegModel) for m, _ in opened):
+                return [self.run(img) for img in images]
+
+            def fits(model, box):
+                H, W = model.ctx.model_info()[:2]
+                return box[3] >= H and box[2] >= W
+
+            pages = []
+            for img in images:
+                self.get_image_and_scales(img)
+                page_mask, box, page_coord = self.page_box_only()      # outside any try, like main.py:2061
+                pages.append(dict(stored=self.image_stored, hw=(self.img_hight_int, self.img_width_int), mask=page_mask, box=box,
+                                  coord=page_coord, regions=None, textlines=None, has_text=False))
+            todo = [p for p in pages if fits(m_region, p["box"])]
+            if todo:
+                out = m_region.segment_views([(p["stored"], p["hw"][0], p["hw"][1], p["box"], True) for p in todo], channels=3)
+                for p, (lab, thr) in zip(todo, out):
+                    p["regions"] = self.clean_text_regions(lab)         # main.py:2074-2075
+                    p["has_text"] = self.text_regions_present(p["regions"])      # main.py:2083, 2096
+                    self.otsu_threshold = thr
+            todo = [p for p in pages if p["has_text"] and fits(m_text, p["box"])]
+            if todo:
+                out = m_text.segment_views([(p["stored"], p["hw"][0], p["hw"][1], p["box"], False) for p in todo])
+                for p, (lab, _) in zip(todo, out):
+                    p["textlines"] = lab
+            return [(p["mask"], p["regions"], p["textlines"], p["coord"]) for p in pages]
+        finally:
+            for _, session in opened:
+                session.close()
