@@ -594,6 +594,39 @@ int sbbseg_debug_axis_owner(int extent, int tile, int margin, int n_tiles, int32
 /* fill every activation buffer (both lanes) and the tile-label scratch with `byte_value` (tests: a launch that reads what an owned-region
  * launch did not write then shows; 0xFF = NaN in every 16-bit format) */
 int sbbseg_debug_poison_activations(sbbseg_ctx* c, int byte_value);
+/* What the LAST launch of plan op `op` used (tests: which kernel route a launch size takes; written by the host where the launch is sized,
+ * nothing is read from the device).  out[0 .. min(cap, SBBSEG_LAUNCH_INTS)) =
+ *   [0] kernel family, SBBSEG_LAUNCH_* below; NONE: the op has launched nothing (it is fused into another op's launch, or has not run)
+ *   [1] BP, [2] BC, [3] LDS stages: pixels x channels of a work item (tile), stages of the staging ring (1 where there is none)
+ *   [4] fast_gather (0 plain, 1 masked, 2 pointwise), [5] tile_map (0 .. 3), [6] cls_minor: the generic conv only
+ *   [7] 1 = an owned-region table was passed
+ *   [8] work items of the launch, [9] blocks launched
+ *   [10] generic conv with a residual: 1 = the residual is read in the epilogue, 0 = prefetched with the tile's last K-step
+ *   [11] 1 = persistent blocks (grid sized by the CU count, every block loops over work items), 0 = one block per slice of the output
+ *   [12] 1 = the launch adds a stored residual
+ * A fused bottleneck block that runs as its three convs (conv variant bit 18) reports the last of them. */
+#define SBBSEG_LAUNCH_INTS 13
+#define SBBSEG_LAUNCH_NONE 0
+#define SBBSEG_LAUNCH_CONV_IGEMM 1
+#define SBBSEG_LAUNCH_CONV_NAIVE_F32 2
+#define SBBSEG_LAUNCH_CONV_SPLITK 3
+#define SBBSEG_LAUNCH_STEM 4
+#define SBBSEG_LAUNCH_STEM_POOL 5
+#define SBBSEG_LAUNCH_DIRECT64 6
+#define SBBSEG_LAUNCH_BOTTLENECK 7
+#define SBBSEG_LAUNCH_BOTTLENECK_PQ 8
+#define SBBSEG_LAUNCH_BLOCK_X3 9
+#define SBBSEG_LAUNCH_EXPAND_REDUCE 10
+#define SBBSEG_LAUNCH_CONV3_EXPAND_REDUCE 11
+#define SBBSEG_LAUNCH_DEC_HALO 12
+#define SBBSEG_LAUNCH_TAIL 13
+#define SBBSEG_LAUNCH_MAXPOOL 14
+#define SBBSEG_LAUNCH_HEAD 15
+int sbbseg_debug_op_launch(sbbseg_ctx* c, int op, int32_t* out, int cap);
+/* Bytes of activation tensor `tensor_id` in which patch i differs from patch i - period, over period <= i < n and the whole patch stride as
+ * stored (every plane, padding included): *count = differing bytes, *first = offset of the first one from the start of patch `period`
+ * (-1: none).  One kernel on the handle's stream, waited for (tests: a batch of cyclically repeated patches must come out periodic). */
+int sbbseg_debug_tensor_period_mismatches(sbbseg_ctx* c, int tensor_id, int n, int period, int64_t* count, int64_t* first);
 /* counters: which 0 = how often sbbseg_page_box_dev had to fall back to the host ranking on this handle */
 int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value);      /* which: 0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by sbbseg_region_line_masks(_dev), 3 = ingest + region-table + stitch kernels queued by sbbseg_segment_views_dev */
 /* Test hook for the no-abort guarantee: the nth_check-th next internal host-allocation checkpoint throws

@@ -39,6 +39,7 @@ EXPORTS = [
     "sbbseg_region_line_masks_dev", "sbbseg_region_line_masks", "sbbseg_region_line_masks_host", "sbbseg_region_line_table",
     "sbbseg_line_split_host", "sbbseg_line_split_dev", "sbbseg_region_line_boxes_dev", "sbbseg_region_line_boxes",
     "sbbseg_segment_views_dev", "sbbseg_segment_views", "sbbseg_debug_axis_owner",
+    "sbbseg_debug_op_launch", "sbbseg_debug_tensor_period_mismatches",
 ]
 
 
@@ -169,6 +170,8 @@ def load_library(path: Optional[str] = None):
         "sbbseg_debug_owned_range": [i32, i32, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)],
         "sbbseg_debug_region_rows": [i32, i32, i32, i32, i32, i32, vp, vp],
         "sbbseg_debug_poison_activations": [vp, i32],
+        "sbbseg_debug_op_launch": [vp, i32, vp, i32],
+        "sbbseg_debug_tensor_period_mismatches": [vp, i32, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
         "sbbseg_text_region_boxes_dev": [vp, vp, i32, i32, i32, C.c_double, C.c_double, vp, i32, C.POINTER(C.c_int)],
         "sbbseg_text_region_boxes": [vp, vp, i32, i32, i32, C.c_double, C.c_double, vp, i32, C.POINTER(C.c_int)],
         "sbbseg_region_deskew_profiles_dev": [vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp],
@@ -208,6 +211,11 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+# sbbseg_debug_op_launch: SBBSEG_LAUNCH_* family numbers and the order of the record's ints (include/sbbseg.h)
+LAUNCH_FAMILIES = ("none", "conv_igemm", "conv_naive_f32", "conv_splitk", "stem", "stem_pool", "direct64", "bottleneck", "bottleneck_pq",
+                   "block_x3", "expand_reduce", "conv3_expand_reduce", "dec_halo", "tail", "maxpool", "head")
+LAUNCH_FIELDS = ("family", "BP", "BC", "stages", "fast_gather", "tile_map", "cls_minor", "table", "n_tiles", "grid", "res_epilogue",
+                 "persistent", "residual")
 LINE_SIGMA_MAX = 128                                             # largest sigma of the line splitter's device table (csrc/line_split.h)
 LINES_OK, LINES_NONE, LINES_SIGMA_TOO_LARGE = 0, 1, 2
 
@@ -372,6 +380,25 @@ class Context:
     def poison_activations(self, byte_value: int = 0xFF):
         """Test hook: fill every activation buffer and the tile-label scratch with a byte (0xFF = NaN in every 16-bit format)."""
         check(self.lib.sbbseg_debug_poison_activations(self.h, int(byte_value)), "sbbseg_debug_poison_activations")
+
+    def op_launch(self, op: int) -> dict:
+        """Test hook: what the last launch of plan op `op` used -- {field of LAUNCH_FIELDS: int}, "family" as its name of
+        LAUNCH_FAMILIES ("none": the op launched nothing, it is fused into another op's launch)."""
+        rec = np.zeros(len(LAUNCH_FIELDS), np.int32)
+        check(self.lib.sbbseg_debug_op_launch(self.h, int(op), _ptr(rec), rec.size), "sbbseg_debug_op_launch")
+        out = {k: int(v) for k, v in zip(LAUNCH_FIELDS, rec)}
+        out["family"] = LAUNCH_FAMILIES[out["family"]]
+        return out
+
+    def tensor_period_mismatches(self, plan_tensor: int, n: int, period: int):
+        """Test hook: (bytes in which stored patch i differs from patch i - period over period <= i < n, offset of the first one from
+        the start of patch `period` or -1), compared on the device over the whole patch stride."""
+        if not self.tensor_ids and getattr(self, "ids_provider", None) is not None:
+            self.ids_provider()
+        cnt, first = C.c_int64(0), C.c_int64(-1)
+        check(self.lib.sbbseg_debug_tensor_period_mismatches(self.h, self.tensor_ids[plan_tensor], int(n), int(period), C.byref(cnt), C.byref(first)),
+              "sbbseg_debug_tensor_period_mismatches")
+        return int(cnt.value), int(first.value)
 
     def forwards(self) -> int:
         """Patches run through the plan on this handle so far."""

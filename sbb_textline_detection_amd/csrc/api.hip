@@ -146,10 +146,12 @@ bool runs_dec_halo(const sbbseg_ctx* c, const ConvOp& co) { return co.d_halo_wfr
 // ---- forward pass over n patches whose input forms are already filled -------------------------
 int launch_op(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
 {
+        op.last = LaunchRec{};            // (sbbseg_debug_op_launch: an op that returns below without a launch reports family NONE)
         if (op.type == kBlock) {
             if (c->unfuse_blocks) {
                 for (auto& part : op.parts)
                     if (launch_op(c, part, n, d_labels, d_probs)) return 1;
+                op.last = op.parts.back().last;
                 return 0;
             }
             const BlockOp& bo = op.block;
@@ -164,8 +166,8 @@ int launch_op(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
 #ifdef SBBSEG_PROBES
             { static const int blk_dbg = getenv("SBBSEG_BLOCK_DBG") ? atoi(getenv("SBBSEG_BLOCK_DBG")) : 0; bp.dbg = blk_dbg; }
 #endif
-            if (c->precision == kF16X3) HIPCHK(launch_block_x3(bp, c->num_cus, c->stream));
-            else HIPCHK(launch_bottleneck(bp, c->precision, c->num_cus, c->stream));
+            if (c->precision == kF16X3) HIPCHK(launch_block_x3(bp, c->num_cus, c->stream, &op.last));
+            else HIPCHK(launch_bottleneck(bp, c->precision, c->num_cus, c->stream, &op.last));
         } else if (op.type == kConv) {
             const ConvOp& co = op.conv;
             if (co.fused_into_expand && !c->no_expand_reduce && !(c->conv_variant & 3)) return 0;      // written by the expand conv's launch (expand_reduce_x3)
@@ -254,16 +256,16 @@ int launch_op(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
                     sp.pool_out = c->tensors[po.dst].data(); sp.pool_scale = po.d_pre_scale; sp.pool_shift = po.d_pre_shift;
                     sp.pool_relu = po.pre_relu; sp.pool_Ho = po.Ho; sp.pool_Wo = po.Wo;
                     sp.x3 = c->precision == kF16X3;
-                    HIPCHK(launch_stem_pool_x3(sp, c->num_cus, c->stream));
+                    HIPCHK(launch_stem_pool_x3(sp, c->num_cus, c->stream, &op.last));
                 } else
-                    HIPCHK(launch_stem(sp, c->precision, c->num_cus, c->stream));
+                    HIPCHK(launch_stem(sp, c->precision, c->num_cus, c->stream, &op.last));
             } else if (co.d_d64_wfrag && !(c->conv_variant & 3)) {
                 const Tensor& st = c->tensors[co.d.src[0].tensor];
                 Direct64Params dp;
                 dp.src = st.buf; dp.n = n; dp.H = st.H; dp.W = st.W; dp.wfrag = co.d_d64_wfrag;
                 dp.scale = co.d_scale; dp.shift = co.d_shift; dp.relu = co.d.relu; dp.out = c->tensors[co.d.out_tensor].data();
                 dp.wmul = co.wmul_cls[0];
-                HIPCHK(launch_direct64(dp, c->precision, c->num_cus, c->stream));
+                HIPCHK(launch_direct64(dp, c->precision, c->num_cus, c->stream, &op.last));
             } else if (co.fused_reduce >= 0 && !c->no_expand_reduce && !(c->conv_variant & 3)) {
                 const ConvOp& ro = c->ops[co.fused_reduce].conv;
                 if (co.fused_conv3 >= 0 && !c->no_c3er) {
@@ -277,7 +279,7 @@ int launch_op(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
                     cp.s2 = k3.d_scale; cp.h2 = k3.d_shift; cp.s3 = co.d_scale; cp.h3 = co.d_shift; cp.s1 = ro.d_scale; cp.h1 = ro.d_shift;
                     cp.wmul2 = k3.wmul_cls[0]; cp.wmul3 = co.wmul_cls[0]; cp.wmul1 = ro.wmul_cls[0];
                     cp.k0 = co.d_c3_k0;
-                    HIPCHK(launch_conv3_expand_reduce(cp, c->num_cus, c->stream));
+                    HIPCHK(launch_conv3_expand_reduce(cp, c->num_cus, c->stream, &op.last));
                     return 0;
                 }
                 ExpRedParams ep;
@@ -291,7 +293,7 @@ int launch_op(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
 #ifdef SBBSEG_PROBES
                 { static const int er_dbg = getenv("SBBSEG_ER_DBG") ? atoi(getenv("SBBSEG_ER_DBG")) : 0; ep.dbg = er_dbg; }
 #endif
-                HIPCHK(launch_expand_reduce_x3(ep, c->num_cus, c->stream));
+                HIPCHK(launch_expand_reduce_x3(ep, c->num_cus, c->stream, &op.last));
             } else if (runs_dec_halo(c, co)) {
                 const Tensor& s0 = c->tensors[co.d.src[0].tensor];
                 DecHaloParams hp;
@@ -300,8 +302,8 @@ int launch_op(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
                 for (int q = 0; q < 4; ++q) hp.wmul[q] = co.wmul_cls[q];
                 hp.relu = co.d.relu; hp.out = c->tensors[co.d.out_tensor].data();
                 if (rlv >= 0) { hp.ttab = c->rr.tab[rlv]; hp.n_tab = c->rr.total[rlv]; }
-                if (c->precision == kF16X3) HIPCHK(launch_dec_halo_x3(hp, c->num_cus, c->stream));
-                else HIPCHK(launch_dec_halo_f16(hp, c->num_cus, c->stream));
+                if (c->precision == kF16X3) HIPCHK(launch_dec_halo_x3(hp, c->num_cus, c->stream, &op.last));
+                else HIPCHK(launch_dec_halo_f16(hp, c->num_cus, c->stream, &op.last));
             } else {
                 // One patch through a long-K conv = 2-32 tiles of 100-400 K-steps at ~1 us a step on as many CUs: the whole-image branch
                 // (extract_page's border model, 1 forward per page) splits the K range over the idle CUs -- up to 16 blocks per tile, each
@@ -319,11 +321,11 @@ int launch_op(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
                     const size_t split_elems = (size_t)n * p.TH * p.TW * p.cout;
                     if (ensure(c, (void**)&c->d_ks_ws, &c->ks_ws_cap, (split_elems << ks) * sizeof(float))) return 1;
                     p.ks_shift = ks; p.ks_ws = c->d_ks_ws; p.ks_split_elems = (long)split_elems; p.tile_map = 0; p.cls_minor = 0;
-                    HIPCHK(launch_conv(p, c->precision, c->stream));
+                    HIPCHK(launch_conv(p, c->precision, c->stream, &op.last));
                     HIPCHK(launch_splitk_finish(c->d_ks_ws, 1 << ks, (long)split_elems, (long)n * p.TH * p.TW, p.cout, p.scale, p.shift, p.residual,
                                                 p.relu, p.out, c->precision, c->stream));
                 } else {
-                    HIPCHK(launch_conv(p, c->precision, c->stream));
+                    HIPCHK(launch_conv(p, c->precision, c->stream, &op.last));
                 }
             }
         } else if (op.type == kPool) {
@@ -332,7 +334,7 @@ int launch_op(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
             if (po.fused_into_stem && !c->unfuse_stem_pool && !(c->conv_variant & 3)) return 0;
             const Tensor& s = c->tensors[po.src];
             HIPCHK(launch_maxpool(s.data(), c->tensors[po.dst].data(), n, s.H, s.W, s.C, po.k, po.stride, po.Ho, po.Wo,
-                                  po.d_pre_scale, po.d_pre_shift, po.pre_relu, c->precision, c->stream));
+                                  po.d_pre_scale, po.d_pre_shift, po.pre_relu, c->precision, c->stream, &op.last));
         } else if (op.type == kTail) {
             const TailOp& to = op.tail;
             const Tensor& s0 = c->tensors[to.src0];
@@ -345,7 +347,7 @@ int launch_op(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
                 if (c->rr.total[op.region_level] == 0) return 0;
                 tp.ttab = c->rr.tab[op.region_level]; tp.n_tab = c->rr.total[op.region_level];
             }
-            HIPCHK(launch_tail(tp, c->precision, c->num_cus, c->stream));
+            HIPCHK(launch_tail(tp, c->precision, c->num_cus, c->stream, &op.last));
         } else {
             const HeadOp& ho = op.head;
             const Tensor& s = c->tensors[ho.src];
@@ -353,7 +355,7 @@ int launch_op(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
             hp.src = s.data(); hp.cin = ho.cin; hp.classes = ho.classes; hp.M = n * s.H * s.W;
             hp.w = ho.d_w; hp.scale = ho.d_scale; hp.shift = ho.d_shift;
             hp.labels = d_labels; hp.probs = d_probs;
-            HIPCHK(launch_head(hp, c->precision, c->stream));
+            HIPCHK(launch_head(hp, c->precision, c->stream, &op.last));
         }
     return 0;
 }
@@ -1942,6 +1944,42 @@ int sbbseg_debug_read_tensor(sbbseg_ctx* c, int tensor_id, int n, float* out, si
     if (c->planes == 2 && t.is_input_form && t.form == SBBSEG_INPUT_C8)      // (see sbbseg_debug_ingest)
         for (size_t i = 0; i < cnt; i += 8)
             for (int ch = 3; ch < 8; ++ch) out[i + ch] = 0.f;
+    return 0;
+    API_END
+}
+
+int sbbseg_debug_op_launch(sbbseg_ctx* c, int op, int32_t* out, int cap)
+{
+    API_BEGIN
+    REQUIRE(c && out && cap >= 0 && op >= 0 && op < (int)c->ops.size(), "op index out of range");
+    const LaunchRec& r = c->ops[op].last;
+    const int rec[kLaunchRecInts] = {r.family, r.bp, r.bc, r.stages, r.fast_gather, r.tile_map, r.cls_minor, r.table, r.n_tiles, r.grid,
+                                     r.res_epilogue, r.persistent, r.residual};
+    static_assert(kLaunchRecInts == SBBSEG_LAUNCH_INTS, "sbbseg.h documents the record");
+    for (int i = 0; i < cap && i < kLaunchRecInts; ++i) out[i] = rec[i];
+    return 0;
+    API_END
+}
+
+int sbbseg_debug_tensor_period_mismatches(sbbseg_ctx* c, int tensor_id, int n, int period, int64_t* count, int64_t* first)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    REQUIRE(tensor_id >= 0 && tensor_id < (int)c->tensors.size() && count && first && period >= 1 && n >= period && n <= c->max_batch, "bad arguments");
+    const Tensor& t = c->tensors[tensor_id];
+    const size_t stride = t.elems_per_patch * (size_t)c->elem * c->planes;          // bytes of one stored patch
+    REQUIRE(stride % 16 == 0, "patch stride %zu is not a multiple of 16 bytes", stride);
+    unsigned long long h_res[2] = {0ull, ~0ull};
+    unsigned long long* d_res = nullptr;
+    HIPCHK(hipMalloc((void**)&d_res, sizeof(h_res)));
+    hipError_t e = hipMemcpyAsync(d_res, h_res, sizeof(h_res), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_period_mismatches(t.data(), stride * period, stride * (size_t)(n - period), d_res, c->num_cus, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_res, d_res, sizeof(h_res), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_res);
+    HIPCHK(e);
+    *count = (int64_t)h_res[0];
+    *first = h_res[0] ? (int64_t)h_res[1] : -1;
     return 0;
     API_END
 }

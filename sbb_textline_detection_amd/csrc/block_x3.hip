@@ -410,11 +410,12 @@ __global__ __launch_bounds__(256, 1) void block_x3(const BlockParams p)
     }
 }
 
-hipError_t launch_block_x3(const BlockParams& p, int num_cus, hipStream_t s)
+hipError_t launch_block_x3(const BlockParams& p, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     const int n_tiles = p.n * ((p.H + 3) / 4) * ((p.W + 15) / 16);
     int grid = n_tiles < num_cus ? n_tiles : num_cus;
     grid = (grid + 7) & ~7;                                     // the XCD-contiguous walk needs a multiple of 8 blocks
+    launch_rec(rec, SBBSEG_LAUNCH_BLOCK_X3, 4 * 16, 256, 1, n_tiles, grid, 1, 0, !p.proj);
     static bool attr_done[64] = {};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);

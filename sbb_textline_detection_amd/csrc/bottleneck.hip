@@ -550,11 +550,12 @@ __global__ __launch_bounds__(512, 1) void bottleneck_fused_pq(const BlockParams 
     }
 }
 
-hipError_t launch_bottleneck(const BlockParams& p, int precision, int num_cus, hipStream_t s)
+hipError_t launch_bottleneck(const BlockParams& p, int precision, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     const int n_tiles = p.n * ((p.H + 7) / 8) * ((p.W + 15) / 16);
     int grid = n_tiles < num_cus ? n_tiles : num_cus;
     grid = (grid + 7) & ~7;                                     // the XCD-contiguous walk needs a multiple of 8 blocks
+    launch_rec(rec, p.pq ? SBBSEG_LAUNCH_BOTTLENECK_PQ : SBBSEG_LAUNCH_BOTTLENECK, 8 * 16, 256, 1, n_tiles, grid, 1, 0, !p.proj);
     auto go = [&](auto kernel, int lds) -> hipError_t {
         static bool attr_done[4][64] = {};
         int dev = 0;

@@ -473,7 +473,7 @@ __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int C, bool X3> static hipError_t launch_one(const C3ERParams& p, int num_cus, hipStream_t s)
+template <int C, bool X3> static hipError_t launch_one(const C3ERParams& p, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     constexpr int EB = X3 ? 4 : 2;
     constexpr int lds = (C * EB / 256) * kPieceBytes + 64 * C * EB + 64 * 256 * EB + 12 * C * 4;
@@ -490,13 +490,14 @@ template <int C, bool X3> static hipError_t launch_one(const C3ERParams& p, int 
     const int n_tiles = p.n * (p.H / 8) * (p.W / 8);
     if (n_tiles <= 0) return hipSuccess;
     const int grid = ((n_tiles < num_cus ? n_tiles : num_cus) + 7) & ~7;
+    launch_rec(rec, SBBSEG_LAUNCH_CONV3_EXPAND_REDUCE, 8 * 8, 4 * C, 1, n_tiles, grid, 1, 0, 1);
     hipLaunchKernelGGL((conv3_expand_reduce<C, X3>), dim3(grid), dim3(512), lds, s, p);
     return hipGetLastError();
 }
 
-hipError_t launch_conv3_expand_reduce(const C3ERParams& p, int num_cus, hipStream_t s)
+hipError_t launch_conv3_expand_reduce(const C3ERParams& p, int num_cus, hipStream_t s, LaunchRec* rec)
 {
-    if (p.C == 128) return p.x3 ? launch_one<128, true>(p, num_cus, s) : launch_one<128, false>(p, num_cus, s);
+    if (p.C == 128) return p.x3 ? launch_one<128, true>(p, num_cus, s, rec) : launch_one<128, false>(p, num_cus, s, rec);
     return hipErrorInvalidValue;
 }
 

@@ -148,6 +148,7 @@ struct Op {
     double exec_patches = 0;      // work executed since sbbseg_profile_reset, in whole-patch equivalents: a launch of n patches adds n, an
                                   // owned-region launch n x (pixels walked / pixels of the whole grid)
     double prof_exec_patches = 0; // the same, over the launches the profiling events timed (prof_ms)
+    LaunchRec last;               // what the op's last launch used (sbbseg_debug_op_launch): written by launch_op and the launcher it calls
 };
 
 constexpr int kMinLaneTiles = 8;      // a lane gets at least this many tiles, else the chunk runs whole on lane 0

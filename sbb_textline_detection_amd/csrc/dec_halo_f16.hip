@@ -273,7 +273,7 @@ __global__ __launch_bounds__(512, 2) void dec_halo_f16(const DecHaloParams p)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-hipError_t launch_dec_halo_f16(const DecHaloParams& p, int num_cus, hipStream_t s)
+hipError_t launch_dec_halo_f16(const DecHaloParams& p, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     static bool attr_done[64] = {};
     int dev = 0;
@@ -287,6 +287,7 @@ hipError_t launch_dec_halo_f16(const DecHaloParams& p, int num_cus, hipStream_t 
     const int n_tiles = p.ttab ? p.n_tab : p.n * (p.PH / 8) * (p.PW / 8);
     if (n_tiles <= 0) return hipSuccess;
     const int grid = ((n_tiles < num_cus ? n_tiles : num_cus) + 7) & ~7;
+    launch_rec(rec, SBBSEG_LAUNCH_DEC_HALO, 16 * 16, 64, 1, n_tiles, grid, 1, p.ttab != nullptr);
     hipLaunchKernelGGL(dec_halo_f16, dim3(grid), dim3(512), kDecHaloF16LdsBytes, s, p);
     return hipGetLastError();
 }

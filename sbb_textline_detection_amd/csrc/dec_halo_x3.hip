@@ -297,7 +297,7 @@ __global__ __launch_bounds__(512, 2) void dec_halo_x3(const DecHaloParams p)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the surplus loads of the last tile land before the registers / LDS go away
 }
 
-hipError_t launch_dec_halo_x3(const DecHaloParams& p, int num_cus, hipStream_t s)
+hipError_t launch_dec_halo_x3(const DecHaloParams& p, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     static bool attr_done[64] = {};
     int dev = 0;
@@ -311,6 +311,7 @@ hipError_t launch_dec_halo_x3(const DecHaloParams& p, int num_cus, hipStream_t s
     const int n_tiles = p.ttab ? p.n_tab : p.n * (p.PH / 8) * (p.PW / 8);
     if (n_tiles <= 0) return hipSuccess;
     const int grid = ((n_tiles < num_cus ? n_tiles : num_cus) + 7) & ~7;
+    launch_rec(rec, SBBSEG_LAUNCH_DEC_HALO, 16 * 16, 64, 1, n_tiles, grid, 1, p.ttab != nullptr);
     hipLaunchKernelGGL(dec_halo_x3, dim3(grid), dim3(512), kDecHaloLdsBytes, s, p);
     return hipGetLastError();
 }

@@ -597,11 +597,12 @@ __global__ __launch_bounds__(512, 2) void dec_tail_fused_x3ps(const TailParams p
     if (mh == 1) store_labels(my_tiles - 1);
 }
 
-hipError_t launch_tail(const TailParams& p, int precision, int num_cus, hipStream_t s)
+hipError_t launch_tail(const TailParams& p, int precision, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     const int n_tiles = p.ttab ? p.n_tab : p.n * (p.PH / 8) * (p.PW / 8);
     if (n_tiles <= 0) return hipSuccess;
     const int grid = ((n_tiles < 2 * num_cus ? n_tiles : 2 * num_cus) + 7) & ~7;      // (the XCD-contiguous walk: a multiple of 8)
+    launch_rec(rec, SBBSEG_LAUNCH_TAIL, 16 * 16, 32, 1, n_tiles, grid, 1, p.ttab != nullptr);
     auto go = [&](auto kern) -> hipError_t {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kTailLdsBytes);
         if (e != hipSuccess) return e;
@@ -611,6 +612,7 @@ hipError_t launch_tail(const TailParams& p, int precision, int num_cus, hipStrea
     hipError_t e;
     if (precision == kF16X3) {
         const int grid3 = ((n_tiles < num_cus ? n_tiles : num_cus) + 7) & ~7;
+        if (rec) rec->grid = grid3;
         auto gops = [&](auto kern) -> hipError_t {
             hipError_t e8 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kT3PsLdsBytes);
             if (e8 != hipSuccess) return e8;

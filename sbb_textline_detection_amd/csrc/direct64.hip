@@ -287,10 +287,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_direct_x3(const Direct64Pa
     }
 }
 
-hipError_t launch_direct64(const Direct64Params& p, int precision, int num_cus, hipStream_t s)
+hipError_t launch_direct64(const Direct64Params& p, int precision, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     const int n_tiles = p.n * ((p.H + 7) / 8) * ((p.W + 15) / 16);
     const int grid = ((n_tiles < 2 * num_cus ? n_tiles : 2 * num_cus) + 7) & ~7;      // (XCD-contiguous walk: a multiple of 8)
+    launch_rec(rec, SBBSEG_LAUNCH_DIRECT64, 8 * 16, 64, 1, n_tiles, precision == kF16X3 ? ((n_tiles < num_cus ? n_tiles : num_cus) + 7) & ~7 : grid, 1);
     if (precision == kF16X3) {
         static bool attr_done[64] = {};
         int dev = 0;

@@ -346,7 +346,7 @@ __global__ __launch_bounds__(512, 2) void expand_reduce(const ExpRedParams p)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int C, bool X3> static hipError_t launch_one(const ExpRedParams& p, int num_cus, hipStream_t s)
+template <int C, bool X3> static hipError_t launch_one(const ExpRedParams& p, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     constexpr int EB = X3 ? 4 : 2;
     constexpr int lds = 64 * C * EB + 64 * 256 * EB + 10 * C * 4;
@@ -361,14 +361,15 @@ template <int C, bool X3> static hipError_t launch_one(const ExpRedParams& p, in
     }
     const int n_tiles = (p.M + 63) / 64;
     const int grid = n_tiles < num_cus ? n_tiles : num_cus;
+    launch_rec(rec, SBBSEG_LAUNCH_EXPAND_REDUCE, 64, 4 * C, 1, n_tiles, grid, 1, 0, 1);
     hipLaunchKernelGGL((expand_reduce<C, X3>), dim3(grid), dim3(512), lds, s, p);
     return hipGetLastError();
 }
 
-hipError_t launch_expand_reduce_x3(const ExpRedParams& p, int num_cus, hipStream_t s)
+hipError_t launch_expand_reduce_x3(const ExpRedParams& p, int num_cus, hipStream_t s, LaunchRec* rec)
 {
-    if (p.C == 128) return p.x3 ? launch_one<128, true>(p, num_cus, s) : launch_one<128, false>(p, num_cus, s);
-    if (p.C == 256) return p.x3 ? launch_one<256, true>(p, num_cus, s) : launch_one<256, false>(p, num_cus, s);
+    if (p.C == 128) return p.x3 ? launch_one<128, true>(p, num_cus, s, rec) : launch_one<128, false>(p, num_cus, s, rec);
+    if (p.C == 256) return p.x3 ? launch_one<256, true>(p, num_cus, s, rec) : launch_one<256, false>(p, num_cus, s, rec);
     return hipErrorInvalidValue;
 }
 

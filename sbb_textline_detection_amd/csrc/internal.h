@@ -314,29 +314,53 @@ enum Precision { kBF16 = 0, kF32 = 1, kF16 = 2, kF16X3 = 3 };
 #endif
 inline bool is_split(int precision) { return precision == kF16X3; }
 
+// What the last launch of a plan op used (sbbseg_debug_op_launch; the field order is the order of the ints it returns, the family numbers are
+// SBBSEG_LAUNCH_* of sbbseg.h).  Every launcher fills the record it is handed where it sizes its grid -- plain host stores into the Op, nothing
+// is read back from the device and nothing waits.  persistent = 1: the grid is sized by the CU count and a block loops over the work items
+// b, b + G, ... or over a run of them; 0: one block per fixed slice of the output, no loop to carry state through.
+struct LaunchRec {
+    int family = 0;
+    int bp = 0, bc = 0, stages = 0;       // conv_igemm_mfma: pixels x channels of the tile, LDS stages; the direct kernels: output pixels of a work item, channels, 1
+    int fast_gather = 0, tile_map = 0, cls_minor = 0;       // conv_igemm_mfma only (ConvParams)
+    int table = 0;                        // an owned-region table was passed (ConvParams::rmap, ttab)
+    int n_tiles = 0, grid = 0;            // work items of the launch, blocks launched
+    int res_epilogue = 0;                 // conv_igemm_mfma with a residual: 1 = read in the epilogue, 0 = prefetched with the last K-step (or no residual)
+    int persistent = 0;
+    int residual = 0;                     // the launch adds a stored residual
+};
+constexpr int kLaunchRecInts = 13;
+static_assert(sizeof(LaunchRec) == kLaunchRecInts * sizeof(int), "sbbseg_debug_op_launch copies the record as ints");
+inline void launch_rec(LaunchRec* r, int family, int bp, int bc, int stages, int n_tiles, int grid, int persistent, int table = 0, int residual = 0)
+{
+    if (!r) return;
+    *r = LaunchRec{};
+    r->family = family; r->bp = bp; r->bc = bc; r->stages = stages; r->n_tiles = n_tiles; r->grid = grid; r->persistent = persistent;
+    r->table = table; r->residual = residual;
+}
+
 // launchers, by the unit that defines them ---------------------------------------------------
 // kernels.hip
-hipError_t launch_conv(const ConvParams& p, int precision, hipStream_t s);
+hipError_t launch_conv(const ConvParams& p, int precision, hipStream_t s, LaunchRec* rec = nullptr);
 hipError_t launch_splitk_finish(const float* ws, int splits, long split_elems, long pixels, int cout, const float* scale, const float* shift,
                                 const void* residual, int relu, void* out, int precision, hipStream_t s);
 // dec_tail.hip, stem.hip, direct64.hip, bottleneck.hip
-hipError_t launch_tail(const TailParams& p, int precision, int num_cus, hipStream_t s);
-hipError_t launch_stem(const StemParams& p, int precision, int num_cus, hipStream_t s);
-hipError_t launch_direct64(const Direct64Params& p, int precision, int num_cus, hipStream_t s);
+hipError_t launch_tail(const TailParams& p, int precision, int num_cus, hipStream_t s, LaunchRec* rec = nullptr);
+hipError_t launch_stem(const StemParams& p, int precision, int num_cus, hipStream_t s, LaunchRec* rec = nullptr);
+hipError_t launch_direct64(const Direct64Params& p, int precision, int num_cus, hipStream_t s, LaunchRec* rec = nullptr);
 constexpr int kTailKSteps = 6;      // 4 taps x 64 channels of src0 + 2 steps for the 9 image taps
-hipError_t launch_bottleneck(const BlockParams& p, int precision, int num_cus, hipStream_t s);
+hipError_t launch_bottleneck(const BlockParams& p, int precision, int num_cus, hipStream_t s, LaunchRec* rec = nullptr);
 // the split-mode and fused units
-hipError_t launch_dec_halo_x3(const DecHaloParams& p, int num_cus, hipStream_t s);     // split mode: dec4 with LDS-resident halos (dec_halo_x3.hip)
-hipError_t launch_dec_halo_f16(const DecHaloParams& p, int num_cus, hipStream_t s);    // ... plain fp16 mode (dec_halo_f16.hip)
-hipError_t launch_conv3_expand_reduce(const C3ERParams& p, int num_cus, hipStream_t s);   // 3x3 + expand + next reduce (conv3_expand_reduce.hip)
-hipError_t launch_expand_reduce_x3(const ExpRedParams& p, int num_cus, hipStream_t s);   // split mode: expand + next reduce 1x1 (expand_reduce_x3.hip)
-hipError_t launch_stem_pool_x3(const StemParams& p, int num_cus, hipStream_t s);      // split mode: stem + max-pool in one launch (stem_pool_x3.hip)
-hipError_t launch_block_x3(const BlockParams& p, int num_cus, hipStream_t s);      // split mode, identity blocks (block_x3.hip)
+hipError_t launch_dec_halo_x3(const DecHaloParams& p, int num_cus, hipStream_t s, LaunchRec* rec = nullptr);     // split mode: dec4 with LDS-resident halos (dec_halo_x3.hip)
+hipError_t launch_dec_halo_f16(const DecHaloParams& p, int num_cus, hipStream_t s, LaunchRec* rec = nullptr);    // ... plain fp16 mode (dec_halo_f16.hip)
+hipError_t launch_conv3_expand_reduce(const C3ERParams& p, int num_cus, hipStream_t s, LaunchRec* rec = nullptr);   // 3x3 + expand + next reduce (conv3_expand_reduce.hip)
+hipError_t launch_expand_reduce_x3(const ExpRedParams& p, int num_cus, hipStream_t s, LaunchRec* rec = nullptr);   // split mode: expand + next reduce 1x1 (expand_reduce_x3.hip)
+hipError_t launch_stem_pool_x3(const StemParams& p, int num_cus, hipStream_t s, LaunchRec* rec = nullptr);      // split mode: stem + max-pool in one launch (stem_pool_x3.hip)
+hipError_t launch_block_x3(const BlockParams& p, int num_cus, hipStream_t s, LaunchRec* rec = nullptr);      // split mode, identity blocks (block_x3.hip)
 // pixel_ops.hip
 hipError_t launch_maxpool(const void* src, void* dst, int n, int H, int W, int C, int k, int stride,
                           int Ho, int Wo, const float* pre_scale, const float* pre_shift, int pre_relu,
-                          int precision, hipStream_t s);
-hipError_t launch_head(const HeadParams& p, int precision, hipStream_t s);
+                          int precision, hipStream_t s, LaunchRec* rec = nullptr);
+hipError_t launch_head(const HeadParams& p, int precision, hipStream_t s, LaunchRec* rec = nullptr);
 hipError_t launch_ingest_u8(const IngestParams& p, int precision, hipStream_t s);
 hipError_t launch_ingest_f32(const float* x, int n, int H, int W, void* c8, void* pairs, int pad,
                              int pairs_w, int precision, hipStream_t s);
@@ -361,6 +385,7 @@ hipError_t launch_resize_labels(const uint8_t* labels, int H, int W, const int* 
                                 int out_h, int out_w, uint8_t* out, hipStream_t s);
 hipError_t launch_replicate3(const uint8_t* src, uint8_t* dst, size_t n, hipStream_t s);
 hipError_t launch_to_f32(const void* src, float* dst, size_t n, int precision, hipStream_t s);
+hipError_t launch_period_mismatches(const void* data, size_t shift_bytes, size_t tail_bytes, unsigned long long* res, int num_cus, hipStream_t s);   // sbbseg_debug_tensor_period_mismatches
 hipError_t launch_split_to_f32(const void* src, float* dst, size_t npix, int C, hipStream_t s);   // [pix][C hi][C lo] -> [pix][C]
 // page_glue.hip
 hipError_t launch_otsu(const uint8_t* page, int src_Wp, int Hp, int Wp, const int* map_y, const int* map_x,

@@ -65,6 +65,9 @@ struct ConvTile {
     static constexpr int kStageBytes = (BP + kWRows) * kRowBytes;
     static constexpr int kLdsBytes = NS * kStageBytes;
     static constexpr int kBlocksPerCU = (kWaves == 4 && 3 * kLdsBytes <= 160 * 1024) ? 3 : (kWaves == 4 && 2 * kLdsBytes <= 160 * 1024) ? 2 : 1;
+    // the residual of the tile being finished is prefetched into registers with its last K-step (else the epilogue reads it): the tiles whose
+    // epilogue registers leave room -- in the split mode (two planes) the 128 x 128 tile only
+    static constexpr bool prefetches_residual(bool x3) { return (kMI / 2) * kNI <= 8 && (!x3 || (BP == 128 && BC == 128)); }
     static_assert(GS == 8 || GS == 4, "stage = whole or half K-step");
     static_assert(BP % (kRowsPerInstr * kWaves) == 0 && kWRows % (kRowsPerInstr * kWaves) == 0, "tile rows must split over the waves");
     static_assert(kMI % 2 == 0, "epilogue pairs MFMA row blocks");
@@ -444,7 +447,7 @@ void conv_igemm_mfma(const ConvParams p)
     // residual tile of the tile being finished: requested BEFORE its last K-step's MFMAs so the HBM
     // round trip hides under them
     // (big wave tiles cannot spare the registers; the split mode's hi + lo pairs fit beside the 128x128 tile's 187 registers only)
-    constexpr bool kPrefetchRes = (T::kMI / 2) * T::kNI <= 8 && (!X3 || (BP == 128 && BC == 128));
+    constexpr bool kPrefetchRes = T::prefetches_residual(X3);
     uint4 res[kPrefetchRes ? T::kMI / 2 : 1][kPrefetchRes ? T::kNI : 1];
     uint4 res_lo[kPrefetchRes && X3 ? T::kMI / 2 : 1][kPrefetchRes && X3 ? T::kNI : 1];      // split mode: the lo halves
     auto prefetch_residual = [&](int tile) __attribute__((always_inline)) {
@@ -1178,7 +1181,7 @@ static void make_fast_div(uint32_t d, uint32_t* magic, uint32_t* shift)
 }
 
 template <int BP, int BC, int WP, int WC, int NS, bool F16, int GS, bool PH8, bool X3, bool FG, bool KS = false>
-static hipError_t launch_conv_impl(const ConvParams& p, hipStream_t s)
+static hipError_t launch_conv_impl(const ConvParams& p, hipStream_t s, LaunchRec* rec)
 {
     using T = ConvTile<BP, BC, WP, WC, NS, GS>;
     static bool attr_done[64] = {};
@@ -1199,6 +1202,11 @@ static hipError_t launch_conv_impl(const ConvParams& p, hipStream_t s)
     const int resident = p.persist_blocks > 0 ? p.persist_blocks * T::kBlocksPerCU : n_tiles;
     int grid = n_tiles < resident ? n_tiles : resident;
     if (p.tile_map >= 1) grid = (grid + 7) & ~7;          // the XCD-grouped walk needs a multiple of 8 blocks
+    if (rec) {
+        launch_rec(rec, KS ? SBBSEG_LAUNCH_CONV_SPLITK : SBBSEG_LAUNCH_CONV_IGEMM, BP, BC, NS, n_tiles, grid, p.persist_blocks > 0, p.rmap != nullptr, p.residual != nullptr);
+        rec->fast_gather = FG ? p.fast_gather : 0; rec->tile_map = p.tile_map; rec->cls_minor = p.cls_minor;
+        rec->res_epilogue = p.residual && !KS && !T::prefetches_residual(X3);
+    }
     ConvParams q = p;
     make_fast_div((uint32_t)(p.Ho * p.Wo), &q.howo_magic, &q.howo_shift);
     make_fast_div((uint32_t)p.Wo, &q.wo_magic, &q.wo_shift);
@@ -1208,13 +1216,13 @@ static hipError_t launch_conv_impl(const ConvParams& p, hipStream_t s)
 }
 
 template <int BP, int BC, int WP, int WC, int NS, bool F16, int GS = 8, bool PH8 = false, bool X3 = false>
-static hipError_t launch_conv_t(const ConvParams& p, hipStream_t s)
+static hipError_t launch_conv_t(const ConvParams& p, hipStream_t s, LaunchRec* rec)
 {
     if constexpr (!PH8 && GS == 8 && NS == 2) {        // (the opt-in half-stage, 3-stage and 8-phase forms keep the plain gather)
-        if (p.fast_gather) return launch_conv_impl<BP, BC, WP, WC, NS, F16, GS, PH8, X3, true>(p, s);
+        if (p.fast_gather) return launch_conv_impl<BP, BC, WP, WC, NS, F16, GS, PH8, X3, true>(p, s, rec);
     }
     if (p.rmap) return hipErrorInvalidValue;           // an owned-region table needs the fast-gather form (launch_op checks before it sets one)
-    return launch_conv_impl<BP, BC, WP, WC, NS, F16, GS, PH8, X3, false>(p, s);
+    return launch_conv_impl<BP, BC, WP, WC, NS, F16, GS, PH8, X3, false>(p, s, rec);
 }
 
 // Tile choice.  Measured on MI355X (profiles/r01_conv_variants.md): with two 4-wave blocks per CU the
@@ -1230,7 +1238,7 @@ static bool ph8_ok(const ConvParams& p)
 }
 
 template <bool F16>
-static hipError_t launch_conv_16(const ConvParams& p, hipStream_t s)
+static hipError_t launch_conv_16(const ConvParams& p, hipStream_t s, LaunchRec* rec)
 {
     const int bc = conv_tile_bc(p.cout);
     const int variant = p.variant;
@@ -1239,25 +1247,25 @@ static hipError_t launch_conv_16(const ConvParams& p, hipStream_t s)
     (void)big_blocks;
     if (p.ks_shift > 0) {                                       // split-K (see launch_conv_x3)
         if (bc != 128 || !p.fast_gather || p.tile_map != 0 || p.cls_minor || (p.total_ksteps & ((1 << p.ks_shift) - 1))) return hipErrorInvalidValue;
-        return launch_conv_impl<128, 128, 2, 2, 2, F16, 8, false, false, true, true>(p, s);
+        return launch_conv_impl<128, 128, 2, 2, 2, F16, 8, false, false, true, true>(p, s, rec);
     }
     if (p.half_stages) {   // A/B: half-K-step stages, 4-deep ring (3 stages in flight across the barriers)
         const long t256 = (long)p.n_cls * ((p.M + 255) / 256) * (p.cout / 256);
-        if (bc == 128 && !p.residual && p.cout % 256 == 0 && p.Ktot >= 512 && t256 >= 200) return launch_conv_t<256, 256, 2, 4, 4, F16, 4>(p, s);
-        if (bc == 128) return launch_conv_t<128, 128, 2, 2, 4, F16, 4>(p, s);
-        if (bc == 64) return launch_conv_t<256, 64, 4, 1, 4, F16, 4>(p, s);
+        if (bc == 128 && !p.residual && p.cout % 256 == 0 && p.Ktot >= 512 && t256 >= 200) return launch_conv_t<256, 256, 2, 4, 4, F16, 4>(p, s, rec);
+        if (bc == 128) return launch_conv_t<128, 128, 2, 2, 4, F16, 4>(p, s, rec);
+        if (bc == 64) return launch_conv_t<256, 64, 4, 1, 4, F16, 4>(p, s, rec);
     }
     if (variant == 3) {   // force: 8 waves, wave tile 128 px x 64 ch (64x64 for cout 64), 2 LDS stages, 1 block per CU
-        if (bc == 128 && p.cout % 256 == 0) return ph8_ok(p) ? launch_conv_t<256, 256, 2, 4, 2, F16, 8, true>(p, s) : launch_conv_t<256, 256, 2, 4, 2, F16>(p, s);
-        if (bc == 128) return launch_conv_t<512, 128, 4, 2, 2, F16>(p, s);
-        if (bc == 64) return launch_conv_t<512, 64, 8, 1, 2, F16>(p, s);
+        if (bc == 128 && p.cout % 256 == 0) return ph8_ok(p) ? launch_conv_t<256, 256, 2, 4, 2, F16, 8, true>(p, s, rec) : launch_conv_t<256, 256, 2, 4, 2, F16>(p, s, rec);
+        if (bc == 128) return launch_conv_t<512, 128, 4, 2, 2, F16>(p, s, rec);
+        if (bc == 64) return launch_conv_t<512, 64, 8, 1, 2, F16>(p, s, rec);
     }
     {   // round 5 (plain modes; profiles/r05_experiments.md section 13): residual layers on the 256 x 256 tile from this K on (0 = never) --
         // the stage-4 / stage-5 expands the fused pair kernel does not take, -3..-4 % each (the K = 128 one of stage 3 loses 1.5 %: left out)
         static const int kres256 = getenv("SBBSEG_F16_RES256_MINK") ? atoi(getenv("SBBSEG_F16_RES256_MINK")) : 256;
         if (variant == 0 && bc == 128 && p.residual && kres256 > 0 && p.cout % 256 == 0 && p.Ktot >= kres256 &&
             (long)p.n_cls * ((p.M + 255) / 256) * (p.cout / 256) >= 200)
-            return launch_conv_t<256, 256, 2, 4, 2, F16>(p, s);
+            return launch_conv_t<256, 256, 2, 4, 2, F16>(p, s, rec);
     }
     // (384 since round 5: the stage-3 projection merge, K = 384 channels, on the 256 x 256 tile: 0.40 -> 0.31 ms per 160 patches in fp16)
     static const int k256_16 = getenv("SBBSEG_F16_T256_MINK") ? atoi(getenv("SBBSEG_F16_T256_MINK")) : 384;
@@ -1267,22 +1275,22 @@ static hipError_t launch_conv_16(const ConvParams& p, hipStream_t s)
         // give every CU a block; short-K / residual (HBM-bound) layers and small grids stay on 128x128
         const long t256 = (long)p.n_cls * ((p.M + 255) / 256) * (p.cout / 256);
         const long t512 = (long)p.n_cls * ((p.M + 511) / 512) * ((p.cout + 127) / 128);
-        if (p.cout % 256 == 0 && p.Ktot >= k256_16 && t256 >= 200) return ph8_ok(p) ? launch_conv_t<256, 256, 2, 4, 2, F16, 8, true>(p, s) : launch_conv_t<256, 256, 2, 4, 2, F16>(p, s);
-        if (p.Ktot >= 1024 && t512 >= 200) return launch_conv_t<512, 128, 4, 2, 2, F16>(p, s);
+        if (p.cout % 256 == 0 && p.Ktot >= k256_16 && t256 >= 200) return ph8_ok(p) ? launch_conv_t<256, 256, 2, 4, 2, F16, 8, true>(p, s, rec) : launch_conv_t<256, 256, 2, 4, 2, F16>(p, s, rec);
+        if (p.Ktot >= 1024 && t512 >= 200) return launch_conv_t<512, 128, 4, 2, 2, F16>(p, s, rec);
     }
-    if (bc == 128) return big ? launch_conv_t<256, 128, 4, 2, 3, F16>(p, s) : launch_conv_t<128, 128, 2, 2, 2, F16>(p, s);
-    if (bc == 64) return big ? launch_conv_t<256, 64, 8, 1, 3, F16>(p, s) : launch_conv_t<256, 64, 4, 1, 2, F16>(p, s);
-    return big ? launch_conv_t<256, 32, 8, 1, 3, F16>(p, s) : launch_conv_t<256, 32, 4, 1, 2, F16>(p, s);
+    if (bc == 128) return big ? launch_conv_t<256, 128, 4, 2, 3, F16>(p, s, rec) : launch_conv_t<128, 128, 2, 2, 2, F16>(p, s, rec);
+    if (bc == 64) return big ? launch_conv_t<256, 64, 8, 1, 3, F16>(p, s, rec) : launch_conv_t<256, 64, 4, 1, 2, F16>(p, s, rec);
+    return big ? launch_conv_t<256, 32, 8, 1, 3, F16>(p, s, rec) : launch_conv_t<256, 32, 4, 1, 2, F16>(p, s, rec);
 }
 
 // split mode: the 4-wave tiles at 2 blocks per CU (3 MFMAs per product for the same LDS bytes: the matrix pipe, not the
 // staging path, is what fills first here)
-static hipError_t launch_conv_x3(const ConvParams& p, hipStream_t s)
+static hipError_t launch_conv_x3(const ConvParams& p, hipStream_t s, LaunchRec* rec)
 {
     const int bc = conv_tile_bc(p.cout);
     if (p.ks_shift > 0) {                                       // split-K (the caller has checked: 128-channel tiles, fast gather, whole K ranges)
         if (bc != 128 || !p.fast_gather || p.tile_map != 0 || p.cls_minor || (p.total_ksteps & ((1 << p.ks_shift) - 1))) return hipErrorInvalidValue;
-        return launch_conv_impl<128, 128, 2, 2, 2, true, 8, false, true, true, true>(p, s);
+        return launch_conv_impl<128, 128, 2, 2, 2, true, 8, false, true, true, true>(p, s, rec);
     }
     // Residual layers (the expand convs that `expand_reduce` does not take: the last block of stages 3 / 4, stage 5) on the 256 x 256 tile when
     // the launch still gives every CU a block: the pixel operand is re-read by half as many channel tiles; the residual is then read in the
@@ -1291,7 +1299,7 @@ static hipError_t launch_conv_x3(const ConvParams& p, hipStream_t s)
     static const int kres256 = getenv("SBBSEG_X3_RES256_MINK") ? atoi(getenv("SBBSEG_X3_RES256_MINK")) : 256;
     if (p.variant == 0 && bc == 128 && p.residual && kres256 > 0 && p.cout % 256 == 0 && p.Ktot >= kres256 &&
         (long)p.n_cls * ((p.M + 255) / 256) * (p.cout / 256) >= 200)
-        return launch_conv_t<256, 256, 2, 4, 2, true, 8, false, true>(p, s);
+        return launch_conv_t<256, 256, 2, 4, 2, true, 8, false, true>(p, s, rec);
     if (p.variant == 0 && bc == 128 && !p.residual) {          // the long-K decoder launches: same 8-wave tiles as the plain modes
         const long t256 = (long)p.n_cls * ((p.M + 255) / 256) * (p.cout / 256);
         const long t512 = (long)p.n_cls * ((p.M + 511) / 512) * ((p.cout + 127) / 128);
@@ -1299,15 +1307,15 @@ static hipError_t launch_conv_x3(const ConvParams& p, hipStream_t s)
         // (768 since round 5: the projection-shortcut merge at the head of stage 3 -- 128 + 256 -> 512 channels at 56 x 56, K = 384 channels -- takes
         //  the 256 x 256 tile too: 0.79 -> 0.68 ms per 160 patches; nothing else has a K between 768 and 1024)
         static const int k256 = getenv("SBBSEG_X3_T256_MINK") ? atoi(getenv("SBBSEG_X3_T256_MINK")) : 768;
-        if (p.cout % 256 == 0 && p.Ktot >= k256 && t256 >= 200) return launch_conv_t<256, 256, 2, 4, 2, true, 8, false, true>(p, s);
-        if (p.Ktot >= k512 && t512 >= 200) return launch_conv_t<512, 128, 4, 2, 2, true, 8, false, true>(p, s);
+        if (p.cout % 256 == 0 && p.Ktot >= k256 && t256 >= 200) return launch_conv_t<256, 256, 2, 4, 2, true, 8, false, true>(p, s, rec);
+        if (p.Ktot >= k512 && t512 >= 200) return launch_conv_t<512, 128, 4, 2, 2, true, 8, false, true>(p, s, rec);
     }
     // (launches of less than one round of tiles -- one patch, the border model's whole-image forward -- cost the latency of their K-steps'
     // loads, ~1.4 us a step; 3- and 4-stage rings of the 128 x 128 tile were probed there and LOST, 3.57 vs 2.67 ms per one-patch forward:
     // the deeper rings run the plain gather, whose address arithmetic outweighs the extra loads in flight; profiles/r04_experiments.md section 12)
-    if (bc == 128) return launch_conv_t<128, 128, 2, 2, 2, true, 8, false, true>(p, s);
-    if (bc == 64) return launch_conv_t<256, 64, 4, 1, 2, true, 8, false, true>(p, s);
-    return launch_conv_t<256, 32, 4, 1, 2, true, 8, false, true>(p, s);
+    if (bc == 128) return launch_conv_t<128, 128, 2, 2, 2, true, 8, false, true>(p, s, rec);
+    if (bc == 64) return launch_conv_t<256, 64, 4, 1, 2, true, 8, false, true>(p, s, rec);
+    return launch_conv_t<256, 32, 4, 1, 2, true, 8, false, true>(p, s, rec);
 }
 
 // Second half of a split-K launch: partial sums of the 2^ks_shift splits added in split order, then the conv's epilogue -- scale / shift,
@@ -1375,18 +1383,19 @@ hipError_t launch_splitk_finish(const float* ws, int splits, long split_elems, l
     return hipGetLastError();
 }
 
-hipError_t launch_conv(const ConvParams& p0, int precision, hipStream_t s)
+hipError_t launch_conv(const ConvParams& p0, int precision, hipStream_t s, LaunchRec* rec)
 {
-    if (precision == kF16X3) return launch_conv_x3(p0, s);
+    if (precision == kF16X3) return launch_conv_x3(p0, s, rec);
     static const bool split_issue = !(getenv("SBBSEG_SPLIT_ISSUE") && getenv("SBBSEG_SPLIT_ISSUE")[0] == '0');      // A/B (plain 16-bit modes)
     ConvParams p = p0;
     if (!split_issue) p.variant_flags |= 8;
     if (precision == kF32) {
         const long total = (long)p.M * (p.cout / 4);
+        launch_rec(rec, SBBSEG_LAUNCH_CONV_NAIVE_F32, 256, 4, 1, (int)((total + 255) / 256), (int)((total + 255) / 256), 0, 0, p.residual != nullptr);
         hipLaunchKernelGGL(conv_naive_f32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
         return hipGetLastError();
     }
-    return precision == kF16 ? launch_conv_16<true>(p, s) : launch_conv_16<false>(p, s);
+    return precision == kF16 ? launch_conv_16<true>(p, s, rec) : launch_conv_16<false>(p, s, rec);
 }
 
 }  // namespace sbbseg

@@ -333,10 +333,11 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const E* src, E* dst, int 
 
 hipError_t launch_maxpool(const void* src, void* dst, int n, int H, int W, int C, int k, int stride,
                           int Ho, int Wo, const float* pre_scale, const float* pre_shift, int pre_relu,
-                          int precision, hipStream_t s)
+                          int precision, hipStream_t s, LaunchRec* rec)
 {
     const long total = (long)n * Ho * ((Wo + 3) / 4) * (C / 8);
     const unsigned grid = (unsigned)((total + 255) / 256);
+    launch_rec(rec, SBBSEG_LAUNCH_MAXPOOL, 256 * 4, 8, 1, (int)grid, (int)grid, 0);
     if (precision == kF32)
         hipLaunchKernelGGL(maxpool_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)src, (float*)dst, n, H, W, C, k, stride, Ho, Wo, pre_scale, pre_shift, pre_relu);
     else if (precision == kF16X3)
@@ -401,9 +402,10 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadParams p)
     p.labels[m] = (uint8_t)best;
 }
 
-hipError_t launch_head(const HeadParams& p, int precision, hipStream_t s)
+hipError_t launch_head(const HeadParams& p, int precision, hipStream_t s, LaunchRec* rec)
 {
     const unsigned grid = (unsigned)((p.M + 255) / 256);
+    launch_rec(rec, SBBSEG_LAUNCH_HEAD, 256, p.classes, 1, (int)grid, (int)grid, 0);
     if (precision == kF32) hipLaunchKernelGGL(head_kernel<float>, dim3(grid), dim3(256), 0, s, p);
     else if (precision == kF16X3) hipLaunchKernelGGL((head_kernel<_Float16, true>), dim3(grid), dim3(256), 0, s, p);
     else if (precision == kF16) hipLaunchKernelGGL(head_kernel<_Float16>, dim3(grid), dim3(256), 0, s, p);
@@ -516,6 +518,53 @@ hipError_t launch_replicate3(const uint8_t* src, uint8_t* dst, size_t n, hipStre
 {
     const size_t n4 = (n + 3) / 4;                   // buffers are padded to a multiple of 4 labels by the caller
     hipLaunchKernelGGL(replicate3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, src, dst, n4);
+    return hipGetLastError();
+}
+
+// sbbseg_debug_tensor_period_mismatches: 16-byte word i of the tail [shift_words, shift_words + n_words) of a buffer against word i - shift_words
+// (patch q against patch q - period: shift = period patches).  res[0] += differing bytes, res[1] = min(first differing byte offset into the tail);
+// a grid-stride loop, a block reduction in LDS, then one atomic pair per block that found something.
+__global__ __launch_bounds__(256) void period_mismatch_kernel(const uint4* __restrict__ base, size_t shift_words, size_t n_words,
+                                                               unsigned long long* __restrict__ res)
+{
+    __shared__ unsigned long long s_cnt[256], s_first[256];
+    unsigned long long cnt = 0, first = ~0ull;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (size_t)gridDim.x * 256) {
+        const uint4 a = base[i], b = base[i + shift_words];
+        const uint32_t d[4] = {a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w};
+        if ((d[0] | d[1] | d[2] | d[3]) == 0) continue;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if ((d[w] >> (8 * k)) & 255u) {
+                    ++cnt;
+                    const unsigned long long off = (unsigned long long)i * 16 + w * 4 + k;
+                    if (off < first) first = off;
+                }
+    }
+    s_cnt[threadIdx.x] = cnt; s_first[threadIdx.x] = first;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+            s_cnt[threadIdx.x] += s_cnt[threadIdx.x + h];
+            if (s_first[threadIdx.x + h] < s_first[threadIdx.x]) s_first[threadIdx.x] = s_first[threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && s_cnt[0]) {
+        atomicAdd(&res[0], s_cnt[0]);
+        atomicMin(&res[1], s_first[0]);
+    }
+}
+
+hipError_t launch_period_mismatches(const void* data, size_t shift_bytes, size_t tail_bytes, unsigned long long* res, int num_cus, hipStream_t s)
+{
+    if ((shift_bytes | tail_bytes | (size_t)(uintptr_t)data) & 15) return hipErrorInvalidValue;
+    const size_t n_words = tail_bytes / 16;
+    if (n_words == 0) return hipSuccess;
+    const size_t want = (n_words + 255) / 256, cap = (size_t)(num_cus > 0 ? num_cus : 256) * 8;
+    hipLaunchKernelGGL(period_mismatch_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, s, (const uint4*)data, shift_bytes / 16, n_words, res);
     return hipGetLastError();
 }
 

@@ -252,10 +252,11 @@ __global__ __launch_bounds__(256, 1) void stem_conv_pairs_x3(const StemParams p)
     }
 }
 
-hipError_t launch_stem(const StemParams& p, int precision, int num_cus, hipStream_t s)
+hipError_t launch_stem(const StemParams& p, int precision, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     const int n_tiles = p.n * (p.Ho / 16) * (p.Wo / 16);
     const int grid = n_tiles < 2 * num_cus ? n_tiles : 2 * num_cus;
+    launch_rec(rec, SBBSEG_LAUNCH_STEM, 16 * 16, 64, 1, n_tiles, precision == kF16X3 ? (n_tiles < num_cus ? n_tiles : num_cus) : grid, 1);
     if (precision == kF16X3) {
         hipLaunchKernelGGL(stem_conv_pairs_x3, dim3(n_tiles < num_cus ? n_tiles : num_cus), dim3(256), kStemX3LdsBytes, s, p);
         return hipGetLastError();

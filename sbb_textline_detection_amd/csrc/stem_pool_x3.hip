@@ -348,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool(const StemParams p)
     }
 }
 
-hipError_t launch_stem_pool_x3(const StemParams& p, int num_cus, hipStream_t s)
+hipError_t launch_stem_pool_x3(const StemParams& p, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     static bool attr_done[64] = {};
     int dev = 0;
@@ -366,6 +366,7 @@ hipError_t launch_stem_pool_x3(const StemParams& p, int num_cus, hipStream_t s)
     int groups = (n_strips + 7) / 8;
     const int max_groups = (2 * num_cus) / 16 > 0 ? (2 * num_cus) / 16 : 1;
     if (groups > max_groups) groups = max_groups;
+    launch_rec(rec, SBBSEG_LAUNCH_STEM_POOL, 16 * 16, 32, 1, 2 * n_strips, groups * 16, 1);      // work item = a strip of 16 x 16 tiles x a channel half
     if (p.x3) hipLaunchKernelGGL(stem_pool<true>, dim3(groups * 16), dim3(256), kStemPoolLdsBytes, s, p);
     else hipLaunchKernelGGL(stem_pool<false>, dim3(groups * 16), dim3(256), kStemPoolF16LdsBytes, s, p);
     return hipGetLastError();

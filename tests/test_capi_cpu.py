@@ -76,6 +76,19 @@ def test_error_message_crosses_units(lib):
         _capi.tile_grid(300, 500, 448, 448)
 
 
+def test_launch_record_names_follow_the_header(lib):
+    """sbbseg_debug_op_launch returns plain ints: the binding's family names and field order are the header's SBBSEG_LAUNCH_* numbers and
+    SBBSEG_LAUNCH_INTS; a bad handle is a status, not a crash."""
+    hdr = open(os.path.join(ROOT, "include", "sbbseg.h")).read()
+    defs = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define SBBSEG_LAUNCH_([A-Z0-9_]+) (\d+)", hdr)}
+    assert defs.pop("INTS") == len(_capi.LAUNCH_FIELDS)
+    assert sorted(defs.values()) == list(range(len(_capi.LAUNCH_FAMILIES)))
+    assert [name.lower() for name, _ in sorted(defs.items(), key=lambda kv: kv[1])] == list(_capi.LAUNCH_FAMILIES)
+    rec = np.zeros(len(_capi.LAUNCH_FIELDS), np.int32)
+    assert lib.sbbseg_debug_op_launch(None, 0, rec.ctypes.data, rec.size) != 0
+    assert b"out of range" in lib.sbbseg_last_error()
+
+
 def test_nearest_map_rule(lib):
     """The library's INTER_NEAREST index rule (page rescale fused into the tile gather) against
     hand-computed cases (odd ratios, up and down) and against the oracle's restatement on the sizes the

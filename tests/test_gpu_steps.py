@@ -77,6 +77,37 @@ def _kernel_name(step, ops):
     return names.pop() if len(names) == 1 else "-"
 
 
+def check_steps(plan, vals, precision, probs, unwritten, ops, tag):
+    """Every step of `plan` whose sources and outputs were all written, against its float64 reference on `vals` (tests/step_check.py).
+    Returns (rows [(step name, kernel name, report)], skipped step names, failures, max |p - p_ref64|, wrong labels, decided pixels)."""
+    rows, skipped, bad = [], [], []
+    p_err = label_bad = decided = 0
+    for s in plan.steps:
+        src, dst = sc.step_tensors(s)
+        if unwritten & set(src + dst):
+            skipped.append(s.name)
+            continue
+        rep = sc.check_step(plan, s, vals, precision, probs=probs)
+        print(f"[step {tag}] {s.name}: K {rep['K']} worst err/bound {rep['worst']:.4f} at {rep['index']} rms {rep['rms']:.4f} "
+              f"over {rep['n_over']} nan {rep['n_nan']} inf {rep['n_inf']} refbad {rep['n_ref_bad']} |ref|max {rep['ref_absmax']:.4g}"
+              + (f" p_err {rep['p_err']:.3e} label_bad {rep['label_bad']} / {rep['n_decided']} decided" if rep["p_err"] is not None else ""))
+        rows.append((s.name, _kernel_name(s, ops), rep))
+        if rep["p_err"] is not None:
+            p_err, label_bad, decided = max(p_err, rep["p_err"]), label_bad + rep["label_bad"], decided + rep["n_decided"]
+        if sc.failed(rep):
+            bad.append((s.name, {k: rep[k] for k in ("worst", "index", "n_over", "n_nan", "n_inf", "n_ref_bad", "label_bad", "ref_absmax")}))
+    return rows, skipped, bad, p_err, label_bad, decided
+
+
+def write_table(f, title, rows, skipped, p_err, label_bad, decided):
+    f.write(f"### {title}\n\n")
+    f.write(f"worst err / bound {max(r['worst'] for _, _, r in rows):.4f}; head: max |p - p_ref64| {p_err:.3e}, "
+            f"{label_bad} wrong labels among {decided} decided pixels; skipped steps: {', '.join(skipped) or 'none'}\n\n")
+    f.write("| step | kernel | K | worst err / bound | at (output, patch, y, x, channel) | rms err / bound |\n|---|---|---|---|---|---|\n")
+    for name, kern, r in rows:
+        f.write(f"| {name} | {kern} | {r['K']} | {r['worst']:.4f} | {r['index']} | {r['rms']:.4f} |\n")
+
+
 @pytest.mark.parametrize("precision,h,w,classes,n,mode", CONFIGS, ids=[f"{c[0]}-{c[1]}x{c[2]}-{c[5]}" for c in CONFIGS])
 def test_every_step_matches_its_float64_reference(precision, h, w, classes, n, mode, monkeypatch):
     if mode == "unfused":
@@ -100,31 +131,11 @@ def test_every_step_matches_its_float64_reference(precision, h, w, classes, n, m
     expect = expected_unwritten(plan, precision, ops) if mode == "default" else set()
     names = lambda ids: sorted(plan.tensors[t].name for t in ids)
     assert unwritten == expect, (names(unwritten), names(expect))
-    rows, skipped, bad = [], [], []
-    p_err = label_bad = decided = 0
-    for s in plan.steps:
-        src, dst = sc.step_tensors(s)
-        if unwritten & set(src + dst):
-            skipped.append(s.name)
-            continue
-        rep = sc.check_step(plan, s, vals, precision, probs=probs)
-        print(f"[step {precision} {h}x{w} {mode}] {s.name}: K {rep['K']} worst err/bound {rep['worst']:.4f} at {rep['index']} rms {rep['rms']:.4f} "
-              f"over {rep['n_over']} nan {rep['n_nan']} inf {rep['n_inf']} refbad {rep['n_ref_bad']} |ref|max {rep['ref_absmax']:.4g}"
-              + (f" p_err {rep['p_err']:.3e} label_bad {rep['label_bad']} / {rep['n_decided']} decided" if rep["p_err"] is not None else ""))
-        rows.append((s.name, _kernel_name(s, ops), rep))
-        if rep["p_err"] is not None:
-            p_err, label_bad, decided = max(p_err, rep["p_err"]), label_bad + rep["label_bad"], decided + rep["n_decided"]
-        if sc.failed(rep):
-            bad.append((s.name, {k: rep[k] for k in ("worst", "index", "n_over", "n_nan", "n_inf", "n_ref_bad", "label_bad", "ref_absmax")}))
+    rows, skipped, bad, p_err, label_bad, decided = check_steps(plan, vals, precision, probs, unwritten, ops, f"{precision} {h}x{w} {mode}")
     want_skipped = [s.name for s in plan.steps if expect & set(sum(sc.step_tensors(s), []))]
     os.makedirs(OUT_DIR, exist_ok=True)
     with open(os.path.join(OUT_DIR, f"step_check_{precision}_{h}x{w}_{mode}.md"), "w") as f:
-        f.write(f"### {precision} {h} x {w}, {classes} classes, n = {n}, {mode} plan\n\n")
-        f.write(f"worst err / bound {max(r['worst'] for _, _, r in rows):.4f}; head: max |p - p_ref64| {p_err:.3e}, "
-                f"{label_bad} wrong labels among {decided} decided pixels; skipped steps: {', '.join(skipped) or 'none'}\n\n")
-        f.write("| step | kernel | K | worst err / bound | at (output, patch, y, x, channel) | rms err / bound |\n|---|---|---|---|---|---|\n")
-        for name, kern, r in rows:
-            f.write(f"| {name} | {kern} | {r['K']} | {r['worst']:.4f} | {r['index']} | {r['rms']:.4f} |\n")
+        write_table(f, f"{precision} {h} x {w}, {classes} classes, n = {n}, {mode} plan", rows, skipped, p_err, label_bad, decided)
     assert skipped == want_skipped, (skipped, want_skipped)
     assert mode == "default" or not skipped
     assert not bad, bad
