@@ -591,8 +591,9 @@ int sbbseg_debug_region_rows(int extent, int tile, int margin, int n_tiles, int 
 /* ... and the owner of every coordinate of such an axis as the stitch of sbbseg_segment_views_dev computes it (the same closed form, on
  * the host): own[q] = (t << 16) | (q - origin(t)) for the last tile t in paste order that keeps q; own = [extent] */
 int sbbseg_debug_axis_owner(int extent, int tile, int margin, int n_tiles, int32_t* own);
-/* fill every activation buffer (both lanes) and the tile-label scratch with `byte_value` (tests: a launch that reads what an owned-region
- * launch did not write then shows; 0xFF = NaN in every 16-bit format) */
+/* fill every activation buffer (both lanes), the tile-label scratch and -- once the whole-image branch has allocated it -- the split-K
+ * workspace of fp32 partial sums with `byte_value` (tests: a launch that reads what an owned-region launch did not write, or a split whose
+ * partial sums were never written, then shows; 0xFF = NaN in every 16-bit format and in fp32) */
 int sbbseg_debug_poison_activations(sbbseg_ctx* c, int byte_value);
 /* What the LAST launch of plan op `op` used (tests: which kernel route a launch size takes; written by the host where the launch is sized,
  * nothing is read from the device).  out[0 .. min(cap, SBBSEG_LAUNCH_INTS)) =

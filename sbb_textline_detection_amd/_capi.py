@@ -378,7 +378,8 @@ class Context:
         return int(mode.value), int(levels.value)
 
     def poison_activations(self, byte_value: int = 0xFF):
-        """Test hook: fill every activation buffer and the tile-label scratch with a byte (0xFF = NaN in every 16-bit format)."""
+        """Test hook: fill every activation buffer, the tile-label scratch and the split-K workspace of the whole-image branch (where
+        one has been allocated) with a byte (0xFF = NaN in every 16-bit format and in fp32)."""
         check(self.lib.sbbseg_debug_poison_activations(self.h, int(byte_value)), "sbbseg_debug_poison_activations")
 
     def op_launch(self, op: int) -> dict:

@@ -774,6 +774,8 @@ int sbbseg_debug_poison_activations(sbbseg_ctx* c, int byte_value)
         }
     }
     if (c->d_tile_labels) HIPCHK(hipMemset(c->d_tile_labels, byte_value & 255, c->tile_labels_cap));
+    // the split-K partial sums too: a split that a later pass does not write must not find the last pass's (equal) value there
+    if (c->d_ks_ws) HIPCHK(hipMemset(c->d_ks_ws, byte_value & 255, c->ks_ws_cap));
     HIPCHK(hipDeviceSynchronize());
     return 0;
     API_END

@@ -23,6 +23,11 @@ on absolute values; K = sum over sources of kh * kw * channels, the number of pr
     whether the MFMA accumulator rounds to nearest or truncates.  The products themselves are exact in fp32 (11 x 11 or 8 x 8 bit
     significands); in the f32 mode every product is fused into its addition (``fmaf``).  n_add = K, and 3 K in the split mode,
     which issues hi*hi, hi*lo and lo*hi as three MFMAs per product.  Zero padding of K adds exact zeros.
+    Split-K launch (the whole-image branch: ``conv_igemm_mfma<..KS>`` + ``splitk_finish``), ``extra_adds = splits - 1``: each of the
+    `splits` blocks of a tile accumulates its own contiguous K-range in fp32 as above -- together the same K (3 K) roundings, every
+    partial sum still bounded by S -- and stores it multiplied by the power-of-two ``wmul_cls`` (exact).  The finish adds the `splits`
+    planes in split order starting from 0.f: the first addition to zero is exact, the other splits - 1 each round a partial sum
+    bounded by S once more.  So n_add = K (3 K) + splits - 1; the epilogue behind it is the unsplit one.  No other term.
   * split mode only, ``2^-21 * S``: the dropped lo * lo products.  |lo| <= 2^-11 |hi| on both sides gives 2^-22 S; the stored
     operands ARE hi + lo (activations as read back, weights as quantised here), so no representation residue is left on top, and
     the term is kept at the 2^-21 S the format is held to elsewhere (a factor of two above what is derived, not below).
@@ -221,14 +226,14 @@ def _head(hd, z, e):
     return _add(lg, err, np.asarray(hd.shift, np.float64))
 
 
-def _conv_outputs(s, vals, precision, weff):
+def _conv_outputs(s, vals, precision, weff, extra_adds=0):
     split = precision == "f16x3"
     y = S = 0.0
     for g, w in zip(s.srcs, weff):
         a = source_input(vals, g)
         y = y + source_conv64(a, w, g, s.out_h, s.out_w)
         S = S + source_conv64(np.abs(a), np.abs(w), g, s.out_h, s.out_w)
-    n_add = step_K(s) * (3 if split else 1)
+    n_add = step_K(s) * (3 if split else 1) + extra_adds
     acc = n_add * 2.0 ** -23 * S + (2.0 ** -21 * S if split else 0.0)
     ref, bound = {}, {}
     if s.raw_out >= 0:
@@ -253,11 +258,13 @@ def _maxpool64(x, k, stride):
     return F.max_pool2d(t, k, stride).permute(0, 2, 3, 1).numpy()
 
 
-def step_reference(plan, step, vals, precision):
+def step_reference(plan, step, vals, precision, extra_adds=0):
     """(ref, bound): dicts of float64 arrays keyed by the outputs the step has -- "out", "raw_out" (on the step's own output grid,
-    see `placed`) and "logits" ([n, out_h, out_w, classes] of a head, fused or not)."""
+    see `placed`) and "logits" ([n, out_h, out_w, classes] of a head, fused or not).  `extra_adds`: further fp32 additions of partial
+    sums on top of the K (3 K) of the contraction -- ``splits - 1`` for a conv launched split-K (module docstring); convs only."""
+    assert extra_adds == 0 or step.kind == "conv", (step.name, step.kind, extra_adds)
     if step.kind == "conv":
-        return _conv_outputs(step, vals, precision, quantise_weights(precision, [g.w for g in step.srcs]))
+        return _conv_outputs(step, vals, precision, quantise_weights(precision, [g.w for g in step.srcs]), extra_adds)
     if step.kind == "tail":
         classes = tail_class_steps(step)
         flat = quantise_weights(precision, [c.srcs[0].w for c in classes] + [classes[0].srcs[1].w])      # one pre-scale for all
@@ -329,11 +336,11 @@ def _mask_of(mask, key, shape):
     return m[..., None]
 
 
-def check_step(plan, step, vals, precision, probs=None, mask=None):
+def check_step(plan, step, vals, precision, probs=None, mask=None, extra_adds=0):
     """Compare what the device stored for `step` with its float64 reference.  `probs`: the device's softmax [n,H,W,classes], for a
     step that carries the head.  `mask`: dict keyed like the outputs ("out", "raw_out", "logits") of bool [n, out_h, out_w] on the
     step's own output grid -- elements outside it count nowhere (an owned-region launch writes, and is owed, only a part of the grid);
-    an output without a key counts whole.  Returns a report dict:
+    an output without a key counts whole.  `extra_adds`: see step_reference (``splits - 1`` of a split-K launch).  Returns a report dict:
       worst     largest |got - ref| / bound over all elements of all stored outputs (inf where the bound is 0 and the error is not)
       index     (output key, patch, y, x, channel) of that element, on the step's own output grid
       n_over    elements with |got - ref| > bound;  n_nan / n_inf  non-finite stored elements where the reference is finite
@@ -342,7 +349,7 @@ def check_step(plan, step, vals, precision, probs=None, mask=None):
       abs_err, old_rel   max |err| and max |err| / max |ref| (the range-relative criterion of the per-layer tests)
       label_bad labels (argmax of probs) that differ from the float64 argmax where the top-2 logit margin exceeds 2 d; n_decided
       p_err     max |probs - softmax64(ref logits)|"""
-    ref, bound = step_reference(plan, step, vals, precision)
+    ref, bound = step_reference(plan, step, vals, precision, extra_adds)
     got = step_got(plan, step, vals)
     rep = dict(name=step.name, kind=step.kind, K=step_K(step), worst=0.0, index=None, n_over=0, n_nan=0, n_inf=0, n_ref_bad=0,
                rms=0.0, ref_absmax=0.0, abs_err=0.0, old_rel=0.0, label_bad=0, n_decided=0, p_err=None, n_elem=0)

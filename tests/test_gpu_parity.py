@@ -1583,6 +1583,8 @@ def test_whole_image_branch_split_k_matches_oracle_and_the_unsplit_launches(prec
     got = split.segment_whole(page, 448, 448)
     again = split.segment_whole(page, 448, 448)
     assert split.ctx.forwards() - f0 == 2
+    splitk_ops = lambda m: [o["name"] for o in m.ctx.ops() if m.ctx.op_launch(o["index"])["family"] == "conv_splitk"]
+    assert splitk_ops(split), "no op of the whole-image launch took the split-K route"
     assert np.array_equal(got, again)
     # split mode: the label-exact margin rule; plain fp16: labels may differ where the oracle's margin is inside twice the mode's softmax tolerance
     lim = EXACT_MARGIN if precision == "f16x3" else 2 * TOL_SOFTMAX["f16"]
@@ -1592,6 +1594,7 @@ def test_whole_image_branch_split_k_matches_oracle_and_the_unsplit_launches(prec
     plain = SegModel(cfg, w, device=0, max_batch=2, precision=precision)
     plain.ctx.set_ksplit(False)
     base = plain.segment_whole(page, 448, 448)
+    assert not splitk_ops(plain), splitk_ops(plain)
     differ = got != base
     assert differ.mean() < (1e-4 if precision == "f16x3" else 2e-3) and not (differ & (margin > lim)).any()
     assert np.array_equal(p_split, plain.predict(x))           # seam 2 is batch-size independent: never split

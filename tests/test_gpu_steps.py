@@ -6,7 +6,13 @@
 filled with NaNs first).  The tensors that were not are exactly those a fused kernel keeps in LDS, re-derived here from the plan by
 the library's own fusion rules (csrc/plan_build.hip fuse_bottlenecks / sbbseg_finalize) and tied to ``ctx.ops()`` by the block count.
 One table per configuration goes to results/step_check_<precision>_<H>x<W>_<plan>.md (the directory the GPU scripts of tools/ write
-their logs to, kept out of git; profiles/step_check.md keeps a copy)."""
+their logs to, kept out of git; profiles/step_check.md keeps a copy).
+
+The plans above are all the synthetic ResNet-50-U-Net.  test_every_step_of_the_small_plans_... runs the three small nets of
+tests/small_plans.py the same way (default plan, n = 3, all four precisions): a 7 x 4 stem tap at stride (2, 1) on 8 channels, 8- to
+32-channel convs (K padded inside one K-step), a stride-2 1 x 1 projection, second sources at offset (1, 1), stride-2 3 x 3 convs without
+top / left padding, Conv2DTranspose classes of 1 x 1 to 2 x 2 taps placed at stride (2, 2), a 3-class head in a conv's epilogue.  Their
+tables go to results/step_check_<precision>_<name>.md with the launch records."""
 import os
 
 import numpy as np
@@ -16,6 +22,7 @@ pytestmark = pytest.mark.gpu
 
 import step_check as sc  # noqa: E402
 from gpu_common import TOL_STEP_HEAD_PROB, make_model, patches_from_page  # noqa: E402
+from small_plans import SMALL_PLANS, assert_odd_geometries, small_net  # noqa: E402
 
 UNFUSED_BITS = (1 << 22) | (1 << 23) | (1 << 24) | (1 << 25)
 OUT_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "results")
@@ -77,9 +84,9 @@ def _kernel_name(step, ops):
     return names.pop() if len(names) == 1 else "-"
 
 
-def check_steps(plan, vals, precision, probs, unwritten, ops, tag):
+def check_steps(plan, vals, precision, probs, unwritten, ops, tag, extra_adds=None):
     """Every step of `plan` whose sources and outputs were all written, against its float64 reference on `vals` (tests/step_check.py).
-    Returns (rows [(step name, kernel name, report)], skipped step names, failures, max |p - p_ref64|, wrong labels, decided pixels)."""
+    `extra_adds`: {step name: splits - 1} of the steps a split-K launch ran (tests/test_gpu_steps_whole.py).  Returns (rows [(step name, kernel name, report)], skipped step names, failures, max |p - p_ref64|, wrong labels, decided pixels)."""
     rows, skipped, bad = [], [], []
     p_err = label_bad = decided = 0
     for s in plan.steps:
@@ -87,7 +94,7 @@ def check_steps(plan, vals, precision, probs, unwritten, ops, tag):
         if unwritten & set(src + dst):
             skipped.append(s.name)
             continue
-        rep = sc.check_step(plan, s, vals, precision, probs=probs)
+        rep = sc.check_step(plan, s, vals, precision, probs=probs, extra_adds=(extra_adds or {}).get(s.name, 0))
         print(f"[step {tag}] {s.name}: K {rep['K']} worst err/bound {rep['worst']:.4f} at {rep['index']} rms {rep['rms']:.4f} "
               f"over {rep['n_over']} nan {rep['n_nan']} inf {rep['n_inf']} refbad {rep['n_ref_bad']} |ref|max {rep['ref_absmax']:.4g}"
               + (f" p_err {rep['p_err']:.3e} label_bad {rep['label_bad']} / {rep['n_decided']} decided" if rep["p_err"] is not None else ""))
@@ -99,13 +106,17 @@ def check_steps(plan, vals, precision, probs, unwritten, ops, tag):
     return rows, skipped, bad, p_err, label_bad, decided
 
 
-def write_table(f, title, rows, skipped, p_err, label_bad, decided):
+def write_table(f, title, rows, skipped, p_err, label_bad, decided, splits=None):
+    """p_err None: the pass stored no probabilities (labels only).  `splits`: {step name: splits of its split-K launch} -> a column."""
     f.write(f"### {title}\n\n")
-    f.write(f"worst err / bound {max(r['worst'] for _, _, r in rows):.4f}; head: max |p - p_ref64| {p_err:.3e}, "
+    head = f"max |p - p_ref64| {p_err:.3e}" if p_err is not None else "no probabilities stored, no p_err (the returned labels as one-hot planes)"
+    f.write(f"worst err / bound {max(r['worst'] for _, _, r in rows):.4f}; head: {head}, "
             f"{label_bad} wrong labels among {decided} decided pixels; skipped steps: {', '.join(skipped) or 'none'}\n\n")
-    f.write("| step | kernel | K | worst err / bound | at (output, patch, y, x, channel) | rms err / bound |\n|---|---|---|---|---|---|\n")
+    more = ("| splits (bound: + splits - 1 additions) ", "|---") if splits is not None else ("", "")
+    f.write(f"| step | kernel | K {more[0]}| worst err / bound | at (output, patch, y, x, channel) | rms err / bound |\n|---|---|---{more[1]}|---|---|---|\n")
     for name, kern, r in rows:
-        f.write(f"| {name} | {kern} | {r['K']} | {r['worst']:.4f} | {r['index']} | {r['rms']:.4f} |\n")
+        col = f"| {splits.get(name, '-')} " if splits is not None else ""
+        f.write(f"| {name} | {kern} | {r['K']} {col}| {r['worst']:.4f} | {r['index']} | {r['rms']:.4f} |\n")
 
 
 @pytest.mark.parametrize("precision,h,w,classes,n,mode", CONFIGS, ids=[f"{c[0]}-{c[1]}x{c[2]}-{c[5]}" for c in CONFIGS])
@@ -141,3 +152,42 @@ def test_every_step_matches_its_float64_reference(precision, h, w, classes, n, m
     assert not bad, bad
     assert decided > 0 and label_bad == 0
     assert p_err < TOL_STEP_HEAD_PROB[precision], p_err
+
+
+@pytest.mark.parametrize("precision", ["f16", "f16x3", "bf16", "f32"])
+@pytest.mark.parametrize("name", SMALL_PLANS)
+def test_every_step_of_the_small_plans_matches_its_float64_reference(name, precision):
+    """The non-ResNet plans, step by step, with the assertions of the test above.  They fuse nothing: every plan tensor must be written and
+    no step skipped.  Gather (from the launch records, asserted below): at these channel counts no conv of keras23 takes the fast gather in
+    any mode, and the Conv2DTranspose nets take it only for the two 32- / 64-channel 3 x 3 convs of the split mode; every other conv -- the
+    7 x 4 stem tap, the stride-2 convs without padding, every parity class -- runs conv_igemm_mfma's plain gather (conv_naive_f32 in the
+    f32 mode), which no ResNet plan exercises on such geometries."""
+    from sbb_textline_detection_amd.model import SegModel
+    from test_gpu_steps_at_scale import launch_records, write_routes
+    cfg, wts, x = small_net(name)
+    n = x.shape[0]
+    model = SegModel(cfg, wts, device=0, max_batch=n, precision=precision)
+    try:
+        ctx, plan = model.ctx, model.plan
+        ops = ctx.ops()
+        ctx.poison_activations(0xFF)
+        probs = model.predict(x)
+        recs = launch_records(ctx, ops)
+        vals = {tid: ctx.debug_read_tensor(tid, n, (t.H, t.W, t.C)) for tid, t in enumerate(plan.tensors) if t.kind != "unused"}
+    finally:
+        model.release()
+    assert_odd_geometries(name, plan, precision)
+    unwritten = {tid for tid, a in vals.items() if np.isnan(a).all()}
+    assert not unwritten, sorted(plan.tensors[t].name for t in unwritten)
+    rows, skipped, bad, p_err, label_bad, decided = check_steps(plan, vals, precision, probs, unwritten, ops, f"{precision} {name}")
+    os.makedirs(OUT_DIR, exist_ok=True)
+    with open(os.path.join(OUT_DIR, f"step_check_{precision}_{name}.md"), "w") as f:
+        write_table(f, f"{precision} {name} ({plan.in_h} x {plan.in_w}, {plan.classes} classes), n = {n}, default plan", rows, skipped, p_err, label_bad, decided)
+        write_routes(f, n, recs)
+    assert not skipped, skipped
+    assert not bad, bad
+    assert decided > 0 and label_bad == 0
+    assert p_err < TOL_STEP_HEAD_PROB[precision], p_err
+    convs = [r for r in recs if r["family"] in ("conv_igemm", "conv_naive_f32")]
+    assert convs and len(convs) == sum(1 for r in recs if r["name"].startswith("conv")), [(r["name"], r["family"]) for r in recs]
+    assert any(r["fast_gather"] == 0 for r in convs), [(r["name"], r["fast_gather"]) for r in convs]

@@ -86,13 +86,16 @@ def assert_periodic(ctx, plan, n, k, probs, written):
 
 def write_routes(f, n, recs):
     f.write(f"\nlaunch records at n = {n} (route = family, BP x BC, LDS stages, fast gather, tile map, class-minor, residual in the epilogue)\n\n")
-    f.write("| op | family | BP x BC | stages | fast gather | tile map | class-minor | residual (epilogue) | n_tiles / grid |\n|---|---|---|---|---|---|---|---|---|\n")
+    ks = any("splits" in r for r in recs)                     # (tests/test_gpu_steps_whole.py adds the split count of a conv_splitk launch)
+    f.write("| op | family | BP x BC | stages | fast gather | tile map | class-minor | residual (epilogue) | n_tiles / grid |" + (" splits |" if ks else "")
+            + "\n|---|---|---|---|---|---|---|---|---|" + ("---|" if ks else "") + "\n")
     for r in recs:
         if r["family"] == "none":
-            f.write(f"| {r['name']} | none (in another op's launch) | | | | | | | |\n")
+            f.write(f"| {r['name']} | none (in another op's launch) | | | | | | | |" + (" |" if ks else "") + "\n")
         else:
             f.write(f"| {r['name']} | {r['family']} | {r['BP']} x {r['BC']} | {r['stages']} | {r['fast_gather']} | {r['tile_map']} | {r['cls_minor']} | "
-                    f"{r['residual']} ({r['res_epilogue']}) | {r['n_tiles']} / {r['grid']} = {r['n_tiles'] / r['grid']:.2f} |\n")
+                    f"{r['residual']} ({r['res_epilogue']}) | {r['n_tiles']} / {r['grid']} = {r['n_tiles'] / r['grid']:.2f} |"
+                    + (f" {r.get('splits', '-')} |" if ks else "") + "\n")
 
 
 def big_launch(model, plan, n, k, h, w, variant=0, reference=True):

@@ -2,9 +2,14 @@
 
 A numpy stand-in for the device runs small plans step by step: operands quantised as the host code quantises them, products
 accumulated in FLOAT32 in K-chunks of 16 or 32 walked in a shuffled (seeded) order, epilogue in float32, outputs rounded to the
-storage format.  (1) Correct arithmetic stays inside the derived bound in all four precisions; (2) each of ten one-line kernel
+storage format.  (1) Correct arithmetic stays inside the derived bound in all four precisions; (2) each of thirteen one-line kernel
 defects, injected into the stand-in, puts the step it was injected into over the bound in f16 and f16x3 -- and the range-relative
-criterion of the per-layer tests (``TOL_LAYER_REL``) is evaluated on the same tensor to show what it lets through."""
+criterion of the per-layer tests (``TOL_LAYER_REL``) is evaluated on the same tensor to show what it lets through.
+
+Split-K (the whole-image branch's one-patch launches, csrc/api.hip launch_op): ``StandIn.conv(splits=...)`` deals the K-chunks to
+`splits` contiguous ranges, sums each in fp32 on its own and adds the partial sums in split order; the bound gets
+``extra_adds = splits - 1`` (tests/step_check.py).  Defects 11 to 13 are defects of that route.  The three small non-ResNet plans of
+tests/small_plans.py run clean through the same stand-in."""
 import copy
 import functools
 import zlib
@@ -14,6 +19,7 @@ import pytest
 
 import step_check as sc
 from plan_interp import make_input_forms
+from small_plans import SMALL_PLANS, assert_odd_geometries, small_net, small_plan
 from sbb_textline_detection_amd.keras_graph import parse_model_config
 from sbb_textline_detection_amd.planner import build_plan
 from sbb_textline_detection_amd.synthetic import synthetic_page
@@ -24,7 +30,11 @@ PRECISIONS = ["f16", "f16x3", "bf16", "f32"]
 # (classes, H, W, planner switches beyond what SegModel derives from the precision).  The second net keeps the decoder convs
 # whole (SBBSEG_PARITY_SPLIT=0: two-source 3x3 convs over an upsampled source, `shift`) and the head in a conv's epilogue.
 MODELS = {"c2_64x96": (2, 64, 96, {}), "c4_64x64": (4, 64, 64, dict(parity_split=False, fuse_tail=False))}
-PIXEL_TILE = 64          # the stand-in's pixel tile (defect 8)
+PIXEL_TILE = 64          # the stand-in's pixel tile (defects 8 and 11)
+SPLIT_PRECISIONS = ["f16", "f16x3", "bf16"]                                  # (launch_op splits nothing in the f32 mode)
+# splits of the launch a split-K defect is injected into: one plane of sixteen missing / one residual too many is the smallest error the
+# defect can make; as on the device a split holds at least 4 K-steps of 32 (no plane of the stand-in is empty), and there are at least 2
+DEFECT_SPLITS = {11: 16, 12: 2, 13: 2}
 
 
 @functools.lru_cache(maxsize=None)
@@ -67,24 +77,39 @@ class StandIn:
     def __init__(self, precision, seed=0):
         self.precision, self.seed = precision, seed
 
-    def _accumulate(self, A, W, rng, drop=None):
-        """float32 sum over K in shuffled chunks; A, W lists of operand planes multiplied pairwise (split: hi*hi, hi*lo, lo*hi)."""
+    def _accumulate(self, A, W, rng, drop=None, splits=1, skip_tail=None):
+        """float32 sum over K in shuffled chunks; A, W lists of operand planes multiplied pairwise (split: hi*hi, hi*lo, lo*hi).
+        splits > 1 (split-K): the chunks are dealt to `splits` contiguous ranges, each summed in fp32 on its own (shuffled inside the
+        range); the partial sums are multiplied by the class multiplier -- 1 here, `pre` is folded into `scale` -- and added in split
+        order starting from zero.  skip_tail = (split, first row): defect 11."""
         K = A[0].shape[1]
         size = 16 if rng.randint(2) else 32
         chunks = [(k, min(k + size, K)) for k in range(0, K, size)]
-        acc = np.zeros((A[0].shape[0], W[0].shape[1]), np.float32)
-        for i in rng.permutation(len(chunks)):
-            k0, k1 = chunks[i]
-            for a, w in zip(A, W):
-                wc = w[k0:k1]
-                if drop is not None and i == len(chunks) - 1:
-                    wc = wc.copy()
-                    wc[:, drop] = 0                                      # defect 10: the last K-chunk dropped for one channel
-                acc += a[:, k0:k1] @ wc
-        return acc
+        shape = (A[0].shape[0], W[0].shape[1])
+        parts = []
+        for ids in np.array_split(np.arange(len(chunks)), splits):
+            acc = np.zeros(shape, np.float32)
+            for i in (ids[rng.permutation(len(ids))] if len(ids) else ids):
+                k0, k1 = chunks[i]
+                for a, w in zip(A, W):
+                    wc = w[k0:k1]
+                    if drop is not None and i == len(chunks) - 1:
+                        wc = wc.copy()
+                        wc[:, drop] = 0                                  # defect 10: the last K-chunk dropped for one channel
+                    acc += a[:, k0:k1] @ wc
+            parts.append(acc)
+        if splits == 1:
+            return parts[0]
+        total = np.zeros(shape, np.float32)
+        for q, part in enumerate(parts):
+            part = part * np.float32(1)
+            if skip_tail is not None and q == skip_tail[0]:
+                part[skip_tail[1]:] = 0                                  # defect 11: this split's plane not added for the ragged last pixel tile
+            total += part
+        return total
 
-    def conv(self, s, vals, ws, defect=None):
-        """-> dict of fp32 outputs on the step's grid: "out", "raw_out", "probs"."""
+    def conv(self, s, vals, ws, defect=None, splits=1):
+        """-> dict of fp32 outputs on the step's grid: "out", "raw_out", "probs".  splits > 1: the step as a split-K launch."""
         prec = self.precision
         rng = np.random.RandomState(self.seed + (zlib.crc32(s.name.encode()) & 0xFFFF))
         n = vals[s.srcs[0].tensor].shape[0]
@@ -116,7 +141,10 @@ class StandIn:
             Ap = [Ah, Ah, A - Ah]
         else:
             Ap = [A]
-        acc = self._accumulate(Ap, Wp, rng, drop=5 if defect == 10 else None)
+        tail = ((splits - 1) // 2, (A.shape[0] // PIXEL_TILE) * PIXEL_TILE) if defect == 11 else None     # a middle split (the first of two)
+        acc = self._accumulate(Ap, Wp, rng, drop=5 if defect == 10 else None, splits=splits, skip_tail=tail)
+        if defect == 13:
+            acc = acc * np.float32(2)                                    # this parity class's partial sums miss their class multiplier
         f32 = lambda v: np.asarray(v, np.float32)
         scale, shift = f32(s.scale) / np.float32(pre), f32(s.shift).copy()
         if defect == 5:
@@ -132,6 +160,9 @@ class StandIn:
             z = acc * scale + shift
             if res is not None:
                 z = z + res
+                if defect == 12:
+                    for _ in range(splits - 1):
+                        z = z + res                                      # residual added once per split instead of once
         if s.relu:
             keep = z[:, 1].copy()
             z = np.maximum(z, 0)
@@ -166,8 +197,9 @@ class StandIn:
             o[:, -1] = win(s.k - 1)[:, -1]                               # 2 x 2 window instead of 3 x 3 on the last row
         return sc.round_storage(self.precision, o) if s.pre_scale is not None else o
 
-    def run_step(self, plan, s, vals, probs, defect=None):
-        """Run one step on the stored inputs in `vals`; writes its outputs into `vals` / `probs` (fp32 images of the stored values)."""
+    def run_step(self, plan, s, vals, probs, defect=None, splits=1):
+        """Run one step on the stored inputs in `vals`; writes its outputs into `vals` / `probs` (fp32 images of the stored values).
+        splits > 1: a conv step runs as a split-K launch."""
         n = next(iter(vals.values())).shape[0]
 
         def tensor(tid):
@@ -176,7 +208,7 @@ class StandIn:
                 vals[tid] = np.zeros((n, t.H, t.W, t.C), np.float32)
             return vals[tid]
         if s.kind == "conv":
-            o = self.conv(s, vals, [g.w for g in s.srcs], defect)
+            o = self.conv(s, vals, [g.w for g in s.srcs], defect, splits)
             if s.out >= 0:
                 sc.placed(tensor(s.out), s)[...] = o["out"]
             if s.raw_out >= 0:
@@ -232,6 +264,13 @@ def _clean_run(model, precision):
     return vals, probs, reports
 
 
+def _splittable(s):
+    """The steps launch_op's split-K rule can take at one patch: the 128-channel tile (cout >= 128), a stored 16-bit output and nothing
+    else in the epilogue, a single class on the whole grid or one of the four parity classes of a decoder conv."""
+    return (s.kind == "conv" and s.out >= 0 and s.raw_out < 0 and s.head is None and s.cout >= 128 and s.cout % 8 == 0
+            and ((s.out_stride, s.out_off) == ((1, 1), (0, 0)) or s.out_stride == (2, 2)))
+
+
 def _step_kind(plan, s):
     if s.kind != "conv":
         return s.kind
@@ -276,6 +315,73 @@ def test_correct_arithmetic_stays_inside_the_bound(model, precision):
     assert plan.steps[1].kind == "maxpool" and plan.steps[1].pre_scale is not None
 
 
+@pytest.mark.parametrize("splits", [2, 16])
+@pytest.mark.parametrize("precision", SPLIT_PRECISIONS)
+@pytest.mark.parametrize("model", list(MODELS))
+def test_correct_split_k_arithmetic_stays_inside_the_bound(model, precision, splits):
+    """Every step the device's rule would split, re-run on the clean run's stored inputs as a split-K launch of `splits` partial sums,
+    against the bound with extra_adds = splits - 1."""
+    plan = _plan(model, precision)
+    clean_vals, clean_probs, _ = _clean_run(model, precision)
+    cand = [s for s in plan.steps if _splittable(s)]
+    assert any(s.out_stride == (1, 1) and s.residual >= 0 for s in cand) and any(s.out_stride == (1, 1) and s.residual < 0 for s in cand)
+    if model == "c2_64x96":
+        assert sum(1 for s in cand if s.out_stride == (2, 2)) >= 4               # the four classes of a decoder conv
+    worst = 0.0
+    for s in cand:
+        vals = {k: v.copy() for k, v in clean_vals.items()}
+        StandIn(precision, seed=11).run_step(plan, s, vals, clean_probs.copy(), splits=splits)
+        rep = sc.check_step(plan, s, vals, precision, extra_adds=splits - 1)
+        worst = max(worst, rep["worst"])
+        assert not sc.failed(rep), (s.name, rep)
+    print(f"\n[stand-in {model} {precision} splits {splits}] {len(cand)} steps, worst err / bound {worst:.3f}")
+
+
+def test_no_extra_additions_is_the_report_of_the_unsplit_step():
+    """extra_adds = 0 changes nothing, and a positive count changes the bound only: by extra_adds * 2^-23 * S in front of the epilogue."""
+    for precision in ("f16", "f16x3"):
+        plan = _plan("c2_64x96", precision)
+        vals, probs, reports = _clean_run("c2_64x96", precision)
+        for s, r in zip(plan.steps, reports):
+            assert sc.check_step(plan, s, vals, precision, probs=probs, extra_adds=0) == r, s.name
+        s = max((q for q in plan.steps if _splittable(q)), key=sc.step_K)
+        ref0, b0 = sc.step_reference(plan, s, vals, precision)
+        ref1, b1 = sc.step_reference(plan, s, vals, precision, extra_adds=15)
+        assert np.array_equal(ref0["out"], ref1["out"]) and (b1["out"] >= b0["out"]).all() and (b1["out"] > b0["out"]).any()
+        n_add = sc.step_K(s) * (3 if precision == "f16x3" else 1)
+        # the accumulation term is linear in n_add and everything behind it is monotone: the bound grows by at most the term's own ratio
+        assert (b1["out"] <= b0["out"] * (n_add + 15) / n_add * (1 + 1e-12)).all()
+        with pytest.raises(AssertionError):
+            sc.step_reference(plan, plan.steps[1], vals, precision, extra_adds=1)          # (a max-pool has no partial sums)
+
+
+# ------------------------------------------------------------------------------------------------ the small non-ResNet plans
+@functools.lru_cache(maxsize=None)
+def _small_clean_run(name, precision):
+    plan, x = small_plan(name, precision), small_net(name)[2]
+    dev = StandIn(precision, seed=11)
+    vals, probs = _fresh(plan, precision, x)
+    for s in plan.steps:
+        dev.run_step(plan, s, vals, probs)
+    return plan, [sc.check_step(plan, s, vals, precision, probs=probs) for s in plan.steps]
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("name", SMALL_PLANS)
+def test_correct_arithmetic_stays_inside_the_bound_on_the_small_plans(name, precision):
+    """keras23 (3 patches of 32 x 48) and the two Conv2DTranspose U-Nets (3 patches of 64 x 96), weights and inputs of their end-to-end
+    GPU tests: the checker and the stand-in handle geometries no ResNet plan has, so a failure of test_gpu_steps.py on them is the device's."""
+    plan, reports = _small_clean_run(name, precision)
+    assert_odd_geometries(name, plan, precision)
+    for s, r in zip(plan.steps, reports):
+        assert not sc.failed(r), (s.name, r)
+    heads = [r for r in reports if r["p_err"] is not None]
+    decided, total = sum(r["n_decided"] for r in heads), 3 * plan.in_h * plan.in_w
+    print(f"\n[stand-in {name} {precision}] worst err / bound {max(r['worst'] for r in reports):.3f}, decided {decided} of {total}, "
+          f"wrong labels {sum(r['label_bad'] for r in heads)}")
+    assert heads and decided > 0.9 * total and all(r["label_bad"] == 0 for r in heads)
+
+
 # ------------------------------------------------------------------------------------------------ defects
 DEFECTS = {
     1: "one spatial tap skipped for the last output column only",
@@ -288,6 +394,9 @@ DEFECTS = {
     8: "output channels 16..31 of a ragged last tile written from the tile before",
     9: "max-pool window 2 x 2 instead of 3 x 3 on the last row",
     10: "the last K-chunk dropped for one output channel",
+    11: "split-K: one split's plane of partial sums not added for the ragged last pixel tile",
+    12: "split-K: the residual added once per split instead of once",
+    13: "split-K: one parity class's partial sums miss their class multiplier (accumulator x 2)",
 }
 
 
@@ -299,6 +408,8 @@ def _applies(plan, s, defect, n):
         return False
     g = s.srcs[0]
     M = n * s.out_h * s.out_w
+    if defect >= 11:                                                     # defects of the split-K route: a step the device's rule would split
+        return _splittable(s) and {11: M % PIXEL_TILE != 0 and M > PIXEL_TILE, 12: s.residual >= 0, 13: s.out_stride == (2, 2)}[defect]
     return {1: g.kh * g.kw > 1, 2: g.kh * g.kw > 1, 3: s.residual >= 0, 4: s.relu, 5: True,
             6: any(q.pad_left + q.off_x > 0 for q in s.srcs), 7: sc.step_K(s) >= 16,
             8: s.cout >= 32 and M % PIXEL_TILE != 0 and M > PIXEL_TILE, 10: True}[defect]
@@ -325,8 +436,9 @@ def test_injected_defect_is_reported(defect, where, precision):
     cand = [s for s in plan.steps if _applies(plan, s, defect, n)]
     step = cand[0] if where == "first" else max(cand, key=sc.step_K)
     vals = {k: v.copy() for k, v in clean_vals.items()}
-    StandIn(precision, seed=11).run_step(plan, step, vals, clean_probs.copy(), defect=defect)
-    rep = sc.check_step(plan, step, vals, precision)
+    splits = max(2, min(DEFECT_SPLITS[defect], sc.step_K(step) // 128)) if defect in DEFECT_SPLITS else 1
+    StandIn(precision, seed=11).run_step(plan, step, vals, clean_probs.copy(), defect=defect, splits=splits)
+    rep = sc.check_step(plan, step, vals, precision, extra_adds=splits - 1)
     old_caught = not rep["old_rel"] < TOL_LAYER_REL[precision]
     print(f"\n[defect {defect:2d} {where} {precision}] {DEFECTS[defect]} -> step {step.name} (K {rep['K']}): worst err / bound {rep['worst']:.3g} at {rep['index']}, "
           f"{rep['n_over']} elements over; caught-by-new {sc.failed(rep)}; caught-by-old {old_caught} "
