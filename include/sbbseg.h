@@ -283,6 +283,25 @@ int sbbseg_segment_whole(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, int Wp,
 int sbbseg_segment_whole_scaled(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, int Wp, int Hs, int Ws,
                                 int out_h, int out_w, uint8_t* labels_out);
 
+/* The same branch for MANY pages in shared launches: one patch per view, the list cut into chunks of <= max_batch patches exactly as
+ * sbbseg_segment_pages_dev cuts its tile list (9 views at max_batch 4: 3 + 3 + 3), the chunks one after the other on the handle's stream.
+ * View k's plane equals sbbseg_segment_whole_scaled on that page alone on the same handle with split-K off, byte for byte: the network
+ * kernels give a patch the same bits whatever else is in the batch.  SPLIT-K RULE: n_views == 1 takes exactly the one-page route, split-K
+ * included when the handle has it on (sbbseg_set_ksplit); n_views >= 2 never splits, not even in a chunk that ends up holding one page.
+ * Per call ONE asynchronous upload carries the view table and all nearest maps (the composed model row -> page row -> stored row maps and
+ * the output row -> model row maps, shared between views of equal geometry); per chunk there is one ingest launch and one label-resize
+ * launch however many views the chunk holds; nothing in the call waits for the device unless a buffer has to grow.  The label planes may
+ * start at any address and have any width.  A bad view (null pointer, non-positive size) fails the call before anything is launched;
+ * sbbseg_last_error() names its index. */
+typedef struct sbbseg_whole_view {
+    const void* d_page_hwc;        /* stored page, uint8 [stored_h][stored_w][3], device */
+    int stored_h, stored_w;        /* its size */
+    int page_h, page_w;            /* size after get_image_and_scales (== stored: no rescale) */
+    int out_h, out_w;              /* size of the label plane (main.py:378) */
+    void* d_labels_out;            /* uint8 [out_h][out_w], device */
+} sbbseg_whole_view;
+int sbbseg_segment_whole_views_dev(sbbseg_ctx* c, int n_views, const sbbseg_whole_view* views);
+
 /* ---- stage glue either side of the models, on u8 label planes [H][W]:
  * cv2.erode / cv2.dilate with a ksize x ksize kernel of ones (the reference's self.kernel is 5x5, main.py:57), `iterations` times,
  * OpenCV's default border (outside pixels never win): text_regions erode x 3 / dilate x 4 (main.py:2074-2075), border mask
@@ -315,6 +334,13 @@ int sbbseg_extract_page_box(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, int 
  * result). */
 int sbbseg_extract_page_box_dev(sbbseg_ctx* c, const void* d_page_hwc, int Hp, int Wp, int Hs, int Ws, void* d_mask_out,
                                 int32_t* box_xywh, int64_t* pixels);
+
+/* extract_page's model + glue for MANY pages: sbbseg_segment_whole_views_dev on all of them (the border forwards at batch width; the
+ * split-K rule above applies), then sbbseg_page_box_dev plane by plane -- the component labelling itself is not batched.  Every view's
+ * out_h x out_w must equal its page_h x page_w; d_labels_out may be NULL, that page's mask then lives in library scratch.  boxes_xywh
+ * [n_pages][4] and pixels [n_pages] (may be NULL) are host arrays; an empty mask gives {0,0,0,0} / 0 for that page and is not an error
+ * here.  Per page the results equal sbbseg_extract_page_box_dev with split-K off.  Synchronises the handle's stream. */
+int sbbseg_extract_page_boxes_dev(sbbseg_ctx* c, int n_pages, const sbbseg_whole_view* views, int32_t* boxes_xywh, int64_t* pixels);
 
 /* get_text_region_contours_and_boxes' existence test (main.py:456-480), the `if len(contours) > 0` that decides whether run() calls
  * the textline model at all (main.py:2083-2096): pixels == label -> 255, cv2.morphologyEx MORPH_OPEN then MORPH_CLOSE with the 5x5
@@ -369,6 +395,29 @@ typedef struct sbbseg_run_info {
 } sbbseg_run_info;
 int sbbseg_run_page(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline, const uint8_t* page_hwc, int Hp, int Wp, int Hs, int Ws,
                     int channels, uint8_t* page_mask_out, uint8_t* regions_out, uint8_t* textlines_out, sbbseg_run_info* info);
+
+/* The same for MANY pages in one resident, pooled call (the reference walks a directory one run() at a time, ocrd_cli.py:51 ->
+ * main.py:2056).  All stored pages are uploaded once into buffers of the border handle; sbbseg_extract_page_boxes_dev runs for all of
+ * them; the layout model takes the crops of all pages that have a box and can hold one model input in ONE sbbseg_segment_views_dev call
+ * (binarised); erode x 3 / dilate x 4 and the text-region gate run per page on the device; the textline model takes the crops of the pages
+ * that passed the gate and fit in one more sbbseg_segment_views_dev call; then the results come back.  Per page the fields are those of
+ * sbbseg_run_page (Hp x Wp = the stored size, Hs x Ws = the upscaled size; outputs sized for the worst case, page_mask_out may be NULL).
+ * A page whose crop cannot hold a model input is kept out of that model's call by a geometry test and gets regions_ok = 0 /
+ * textlines_ok = 0 exactly as sbbseg_run_page gives it; an empty border mask sets that page's status to 1 and leaves its other outputs
+ * untouched, the call still returns 0; a device or allocation error fails the whole call.  With sbbseg_set_ksplit off on the border handle
+ * every output byte, info field and status of page k equals one sbbseg_run_page call for that page on the same handles; with split-K on
+ * (the default) only the border mask may differ, at near-ties of the split and unsplit forwards (n_pages >= 2 never splits).
+ * DEVICE MEMORY, all of it held at once (the caller chooses n_pages), growing only when a call needs more than the last:
+ *   border handle:  sum over pages of (3 x Hp x Wp + Hs x Ws) bytes  -- the stored pages and one mask plane per page
+ *   layout handle:  2 x sum over pages with a box of (w x h) bytes    -- two crop planes per page (raw / textline map, cleaned layout map)
+ * each plane rounded up to 16 bytes, beside what the per-page calls use (the component labelling works on one plane at a time). */
+typedef struct sbbseg_run_page_io {
+    const uint8_t* page_hwc; int Hp, Wp, Hs, Ws;          /* as sbbseg_run_page */
+    uint8_t *page_mask_out, *regions_out, *textlines_out; /* as sbbseg_run_page, worst-case sized; mask may be NULL */
+    sbbseg_run_info info;
+    int32_t status;   /* 0 ok; 1 = extract_page failed for THIS page (empty border mask, main.py:399-401): its other outputs are untouched */
+} sbbseg_run_page_io;
+int sbbseg_run_pages(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline, int n_pages, sbbseg_run_page_io* pages, int channels);
 
 /* ---- stage glue: the rotate-and-project of the deskew search (return_deskew_slope, main.py:1601-1718; per text region,
  * 80 angles in [-25, 25] and 30 more in [-90, -50] -- the reference spreads the regions over cpu_count() processes,
@@ -629,7 +678,7 @@ int sbbseg_debug_op_launch(sbbseg_ctx* c, int op, int32_t* out, int cap);
  * (-1: none).  One kernel on the handle's stream, waited for (tests: a batch of cyclically repeated patches must come out periodic). */
 int sbbseg_debug_tensor_period_mismatches(sbbseg_ctx* c, int tensor_id, int n, int period, int64_t* count, int64_t* first);
 /* counters: which 0 = how often sbbseg_page_box_dev had to fall back to the host ranking on this handle */
-int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value);      /* which: 0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by sbbseg_region_line_masks(_dev), 3 = ingest + region-table + stitch kernels queued by sbbseg_segment_views_dev */
+int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value);      /* which: 0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by sbbseg_region_line_masks(_dev), 3 = ingest + region-table + stitch kernels queued by sbbseg_segment_views_dev, 4 = ingest + label-resize kernels queued by the whole-views calls (sbbseg_segment_whole_views_dev, sbbseg_extract_page_boxes_dev, sbbseg_run_pages: 2 per chunk) */
 /* Test hook for the no-abort guarantee: the nth_check-th next internal host-allocation checkpoint throws
  * std::bad_alloc, which every entry point turns into a non-zero status + sbbseg_last_error() instead of
  * terminating the process (main.py:2061-2157 relies on ordinary exceptions).  0 disarms.  Process-global. */

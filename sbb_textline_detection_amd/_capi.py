@@ -40,6 +40,7 @@ EXPORTS = [
     "sbbseg_line_split_host", "sbbseg_line_split_dev", "sbbseg_region_line_boxes_dev", "sbbseg_region_line_boxes",
     "sbbseg_segment_views_dev", "sbbseg_segment_views", "sbbseg_debug_axis_owner",
     "sbbseg_debug_op_launch", "sbbseg_debug_tensor_period_mismatches",
+    "sbbseg_segment_whole_views_dev", "sbbseg_extract_page_boxes_dev", "sbbseg_run_pages",
 ]
 
 
@@ -60,6 +61,19 @@ class View(C.Structure):
     _fields_ = [("page", C.c_void_p), ("Hs", C.c_int32), ("Ws", C.c_int32), ("Hp", C.c_int32), ("Wp", C.c_int32), ("cx", C.c_int32),
                 ("cy", C.c_int32), ("cw", C.c_int32), ("ch", C.c_int32), ("binarise", C.c_int32), ("labels", C.c_void_p),
                 ("threshold", C.c_void_p)]
+
+
+class WholeView(C.Structure):
+    """sbbseg_whole_view (include/sbbseg.h)"""
+    _fields_ = [("page", C.c_void_p), ("stored_h", C.c_int32), ("stored_w", C.c_int32), ("page_h", C.c_int32), ("page_w", C.c_int32),
+                ("out_h", C.c_int32), ("out_w", C.c_int32), ("labels", C.c_void_p)]
+
+
+class RunPageIO(C.Structure):
+    """sbbseg_run_page_io (include/sbbseg.h)"""
+    _fields_ = [("page", C.c_void_p), ("Hp", C.c_int32), ("Wp", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32),
+                ("page_mask_out", C.c_void_p), ("regions_out", C.c_void_p), ("textlines_out", C.c_void_p), ("info", RunInfo),
+                ("status", C.c_int32)]
 
 
 class ConvDesc(C.Structure):
@@ -130,6 +144,9 @@ def load_library(path: Optional[str] = None):
         "sbbseg_segment_views_dev": [vp, i32, C.POINTER(View)],
         "sbbseg_segment_views": [vp, i32, C.POINTER(View), vp],
         "sbbseg_debug_axis_owner": [i32, i32, i32, i32, vp],
+        "sbbseg_segment_whole_views_dev": [vp, i32, C.POINTER(WholeView)],
+        "sbbseg_extract_page_boxes_dev": [vp, i32, C.POINTER(WholeView), vp, vp],
+        "sbbseg_run_pages": [vp, vp, vp, i32, C.POINTER(RunPageIO), i32],
         "sbbseg_otsu_dev": [vp, vp, i32, i32, vp],
         "sbbseg_segment_tile_range_bin_dev": [vp, vp, i32, i32, i32, i32, vp, vp],
         "sbbseg_segment_whole": [vp, vp, i32, i32, i32, i32, vp],
@@ -552,6 +569,33 @@ class Context:
                                                    _ptr(out)), "sbbseg_segment_whole_scaled")
         return out
 
+    @staticmethod
+    def _whole_views(views):
+        arr = (WholeView * max(len(views), 1))()
+        for k, (d_page, stored_h, stored_w, page_h, page_w, out_h, out_w, d_labels) in enumerate(views):
+            arr[k] = WholeView(int(d_page) or None, int(stored_h), int(stored_w), int(page_h), int(page_w), int(out_h), int(out_w), int(d_labels) or None)
+        return arr
+
+    def segment_whole_views_dev(self, views):
+        """The whole-image branch for many pages in shared launches (sbbseg_segment_whole_views_dev).  ``views``: a sequence of
+        (d_page, stored_h, stored_w, page_h, page_w, out_h, out_w, d_labels) -- device pointers, the stored page's size, its size after
+        get_image_and_scales, and the size of the label plane to write."""
+        check(self.lib.sbbseg_segment_whole_views_dev(self.h, len(views), self._whole_views(views)), "sbbseg_segment_whole_views_dev")
+
+    def extract_page_boxes_dev(self, views):
+        """Border model + page box for many pages (sbbseg_extract_page_boxes_dev).  ``views`` as :meth:`segment_whole_views_dev` takes
+        them, out size == page size, d_labels = 0: the mask stays in library scratch.  Returns [((x, y, w, h), pixels), ...]; an empty
+        mask gives ((0, 0, 0, 0), 0)."""
+        n = len(views)
+        boxes = np.zeros((max(n, 1), 4), np.int32)
+        px = np.zeros(max(n, 1), np.int64)
+        check(self.lib.sbbseg_extract_page_boxes_dev(self.h, n, self._whole_views(views), _ptr(boxes), _ptr(px)), "sbbseg_extract_page_boxes_dev")
+        return [(tuple(int(v) for v in boxes[k]), int(px[k])) for k in range(n)]
+
+    def whole_launches(self) -> int:
+        """Ingest + label-resize kernels the whole-views calls have queued on this handle so far (sbbseg_debug_counter 4)."""
+        return self.debug_counter(4)
+
     def segment_page_dev(self, d_page: int, Hp: int, Wp: int, d_labels: int):
         check(self.lib.sbbseg_segment_page_dev(self.h, C.c_void_p(d_page), Hp, Wp, C.c_void_p(d_labels)), "sbbseg_segment_page_dev")
 
@@ -944,6 +988,42 @@ def run_page(border: "Context", layout: "Context", textline: "Context", page: np
     r = regions[:h * w * channels].reshape((h, w, 3) if channels == 3 else (h, w)).copy() if info.regions_ok else None
     t = lines[:h * w].reshape(h, w).copy() if info.textlines_ok else None
     return mask, r, t, info
+
+
+def run_pages(border: "Context", layout: "Context", textline: "Context", pages, channels: int = 3, want_mask: bool = True):
+    """:func:`run_page` for many pages in one resident, pooled library call (``sbbseg_run_pages``).  ``pages``: a sequence of
+    (stored page uint8 [H, W, 3], scaled_h, scaled_w).  Returns one (page mask or None, regions or None, textlines or None, RunInfo,
+    status) per page; status 1 = the border model found no page there (what makes :func:`run_page` raise): its arrays are None."""
+    if channels not in (1, 3):
+        raise ValueError("channels must be 1 or 3")
+    n = len(pages)
+    io = (RunPageIO * max(n, 1))()
+    keep = []
+    for k, (page, scaled_h, scaled_w) in enumerate(pages):
+        page = np.ascontiguousarray(page, np.uint8)
+        if page.ndim != 3 or page.shape[2] != 3:
+            raise ValueError(f"page {k}: must be uint8 [H,W,3], got {page.shape}")
+        scaled_h, scaled_w = int(scaled_h), int(scaled_w)
+        pix = scaled_h * scaled_w
+        mask = np.empty((scaled_h, scaled_w, 3) if channels == 3 else (scaled_h, scaled_w), np.uint8) if want_mask else None
+        regions = np.empty(pix * channels, np.uint8)
+        lines = np.empty(pix, np.uint8)
+        keep.append((page, mask, regions, lines))
+        io[k].page, io[k].Hp, io[k].Wp, io[k].Hs, io[k].Ws = page.ctypes.data, page.shape[0], page.shape[1], scaled_h, scaled_w
+        io[k].page_mask_out = mask.ctypes.data if want_mask else None
+        io[k].regions_out, io[k].textlines_out = regions.ctypes.data, lines.ctypes.data
+    check(border.lib.sbbseg_run_pages(border.h, layout.h, textline.h, n, io, channels), "sbbseg_run_pages")
+    out = []
+    for k, (_, mask, regions, lines) in enumerate(keep):
+        info = RunInfo.from_buffer_copy(io[k].info)
+        if io[k].status != 0:
+            out.append((None, None, None, info, int(io[k].status)))
+            continue
+        w, h = int(info.box_xywh[2]), int(info.box_xywh[3])
+        r = regions[:h * w * channels].reshape((h, w, 3) if channels == 3 else (h, w)).copy() if info.regions_ok else None
+        t = lines[:h * w].reshape(h, w).copy() if info.textlines_ok else None
+        out.append((mask, r, t, info, 0))
+    return out
 
 
 def owned_range(extent: int, tile: int, margin: int, n_tiles: int, t: int):

@@ -23,6 +23,7 @@ using namespace sbbseg;
 namespace sbbseg {
 
 thread_local std::string g_err;
+thread_local int g_err_kind = kErrOther;
 int g_alloc_fail_countdown = 0;
 
 int set_error(const char* fmt, ...)
@@ -33,6 +34,7 @@ int set_error(const char* fmt, ...)
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
     g_err = buf;
+    g_err_kind = kErrOther;
     return 1;
 }
 
@@ -882,7 +884,7 @@ int sbbseg_tile_grid(int Hp, int Wp, int H, int W, int32_t* tile_xy, int capacit
     std::vector<int> ox, oy;
     const int margin = margin_of(W);
     const int nx = axis_tiles(Wp, W, margin, ox), ny = axis_tiles(Hp, H, margin, oy);
-    REQUIRE(nx > 0 && ny > 0, "page %dx%d is smaller than the model input %dx%d (unsupported by the reference too, main.py:278-281)", Hp, Wp, H, W);
+    REQUIRE_GEOMETRY(nx > 0 && ny > 0, "page %dx%d is smaller than the model input %dx%d (unsupported by the reference too, main.py:278-281)", Hp, Wp, H, W);
     if (nxf) *nxf = nx;
     if (nyf) *nyf = ny;
     if (tile_xy) {
@@ -1082,7 +1084,7 @@ static int prepare_owner(sbbseg_ctx* c, int Hp, int Wp, bool dedupe)
     std::vector<int> ox, oy, own_x, own_y;
     const int margin = margin_of(c->in_W);
     int nx = axis_tiles(Wp, c->in_W, margin, ox), ny = axis_tiles(Hp, c->in_H, margin, oy);
-    REQUIRE(nx > 0 && ny > 0, "page %dx%d is smaller than the model input", Hp, Wp);
+    REQUIRE_GEOMETRY(nx > 0 && ny > 0, "page %dx%d is smaller than the model input", Hp, Wp);
     if (dedupe) {                              // (fused_grid: the repeated last tile of an axis is not computed)
         if (nx >= 2 && ox[nx - 1] == ox[nx - 2]) ox.resize(--nx);
         if (ny >= 2 && oy[ny - 1] == oy[ny - 2]) oy.resize(--ny);
@@ -1174,7 +1176,7 @@ int sbbseg_segment_pages(sbbseg_ctx* c, int n_pages, const uint8_t* const* pages
     if (check_ready(c)) return 1;
     REQUIRE(n_pages >= 1 && pages_hwc && labels_hw, "bad arguments");
     for (int k = 0; k < n_pages; ++k) REQUIRE(pages_hwc[k] && labels_hw[k], "null page / label pointer (page %d)", k);
-    REQUIRE(Hp >= c->in_H && Wp >= c->in_W, "page %dx%d is smaller than the model input %dx%d (unsupported by the reference too, main.py:278-281)", Hp, Wp, c->in_H, c->in_W);
+    REQUIRE_GEOMETRY(Hp >= c->in_H && Wp >= c->in_W, "page %dx%d is smaller than the model input %dx%d (unsupported by the reference too, main.py:278-281)", Hp, Wp, c->in_H, c->in_W);
     int nx = 0, ny = 0;
     if (fused_grid(c, Hp, Wp, c->dedupe, &nx, &ny)) return 1;
     const size_t pix = (size_t)Hp * Wp, in_b = pix * 3, ch = c->label_channels == 3 ? 3 : 1, out_b = pix * ch;
@@ -1267,7 +1269,7 @@ int sbbseg_segment_page(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, int Wp, 
     API_BEGIN
     if (check_ready(c)) return 1;
     REQUIRE(page_hwc && labels_hw, "bad arguments");
-    REQUIRE(Hp >= c->in_H && Wp >= c->in_W, "page %dx%d is smaller than the model input %dx%d (unsupported by the reference too, main.py:278-281)", Hp, Wp, c->in_H, c->in_W);
+    REQUIRE_GEOMETRY(Hp >= c->in_H && Wp >= c->in_W, "page %dx%d is smaller than the model input %dx%d (unsupported by the reference too, main.py:278-281)", Hp, Wp, c->in_H, c->in_W);
     const size_t pix = (size_t)Hp * Wp;
     if (ensure(c, (void**)&c->d_page, &c->page_cap, pix * 3)) return 1;
     if (ensure(c, (void**)&c->d_page_labels, &c->page_labels_cap, pix + 4)) return 1;
@@ -1284,7 +1286,7 @@ int sbbseg_segment_page_scaled(sbbseg_ctx* c, const uint8_t* page_hwc, int Hs, i
     API_BEGIN
     if (check_ready(c)) return 1;
     REQUIRE(page_hwc && labels_hw && Hs > 0 && Ws > 0, "bad arguments");
-    REQUIRE(Hp >= c->in_H && Wp >= c->in_W, "scaled page %dx%d is smaller than the model input %dx%d", Hp, Wp, c->in_H, c->in_W);
+    REQUIRE_GEOMETRY(Hp >= c->in_H && Wp >= c->in_W, "scaled page %dx%d is smaller than the model input %dx%d", Hp, Wp, c->in_H, c->in_W);
     const size_t spix = (size_t)Hs * Ws, pix = (size_t)Hp * Wp;
     if (ensure(c, (void**)&c->d_page, &c->page_cap, spix * 3)) return 1;
     if (ensure(c, (void**)&c->d_page_labels, &c->page_labels_cap, pix + 4)) return 1;
@@ -1336,7 +1338,7 @@ int sbbseg_segment_page_otsu(sbbseg_ctx* c, const uint8_t* page_hwc, int Hs, int
     API_BEGIN
     if (check_ready(c)) return 1;
     REQUIRE(page_hwc && labels_hw && Hs > 0 && Ws > 0, "bad arguments");
-    REQUIRE(Hp >= c->in_H && Wp >= c->in_W, "page %dx%d is smaller than the model input %dx%d", Hp, Wp, c->in_H, c->in_W);
+    REQUIRE_GEOMETRY(Hp >= c->in_H && Wp >= c->in_W, "page %dx%d is smaller than the model input %dx%d", Hp, Wp, c->in_H, c->in_W);
     const size_t spix = (size_t)Hs * Ws, pix = (size_t)Hp * Wp;
     const bool scaled = Hs != Hp || Ws != Wp;
     if (ensure(c, (void**)&c->d_page, &c->page_cap, spix * 3)) return 1;
@@ -1382,7 +1384,7 @@ int sbbseg_segment_crop_dev(sbbseg_ctx* c, const void* d_page_hwc, int Hs, int W
     if (check_ready(c)) return 1;
     REQUIRE(d_page_hwc && d_labels_hw && Hs > 0 && Ws > 0 && Hp > 0 && Wp > 0, "bad arguments");
     REQUIRE(cx >= 0 && cy >= 0 && cw > 0 && ch > 0 && cx + cw <= Wp && cy + ch <= Hp, "crop box {%d,%d,%d,%d} leaves the %dx%d page", cx, cy, cw, ch, Hp, Wp);
-    REQUIRE(ch >= c->in_H && cw >= c->in_W, "cropped page %dx%d is smaller than the model input %dx%d (unsupported by the reference too, main.py:278-281)",
+    REQUIRE_GEOMETRY(ch >= c->in_H && cw >= c->in_W, "cropped page %dx%d is smaller than the model input %dx%d (unsupported by the reference too, main.py:278-281)",
             ch, cw, c->in_H, c->in_W);
     if (c->map_key[0] != Hs || c->map_key[1] != Ws || c->map_key[2] != Hp || c->map_key[3] != Wp || !c->d_map) {
         std::vector<int> my, mx;
@@ -1429,6 +1431,26 @@ int sbbseg_segment_crop(sbbseg_ctx* c, const uint8_t* page_hwc, int Hs, int Ws, 
     API_END
 }
 
+// The per-call tables of the many-view entry points (sbbseg_segment_views_dev, sbbseg_segment_whole_views_dev): c->h_views (pinned) and
+// c->d_views hold at least `bytes`, and the staging may be rewritten (the previous call's upload has read it).
+static int views_staging(sbbseg_ctx* c, size_t bytes)
+{
+    if (c->views_copy_pending) {                               // (the previous call's upload still reads the staging)
+        HIPCHK(hipEventSynchronize(c->ev_views));
+        c->views_copy_pending = false;
+    }
+    if (!c->ev_views) HIPCHK(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
+    if (c->h_views_cap < bytes) {
+        c->h_views_cap = 0;
+        (void)hipHostFree(c->h_views); c->h_views = nullptr;
+        const size_t cap = bytes + bytes / 2;
+        HIPCHK(hipHostMalloc(&c->h_views, cap, hipHostMallocDefault));
+        c->h_views_cap = cap;
+    }
+    if (c->views_cap < bytes && ensure(c, &c->d_views, &c->views_cap, bytes + bytes / 2)) return 1;
+    return 0;
+}
+
 // ---- many views in one call: tiles of differently sized pages and crops share launches (include/sbbseg.h) ----
 // Per call: the view table (region.h ViewRec), a fallback threshold int per view and the nearest maps of the rescaled views are laid out in
 // pinned staging and go up in one asynchronous copy; per group of views (about eight chunks of tiles, which bounds the tile-label scratch):
@@ -1463,7 +1485,7 @@ int sbbseg_segment_views_dev(sbbseg_ctx* c, int n_views, const sbbseg_view* view
         REQUIRE(v.Hs > 0 && v.Ws > 0 && v.Hp > 0 && v.Wp > 0, "view %d: bad page size %dx%d (stored %dx%d)", k, v.Hp, v.Wp, v.Hs, v.Ws);
         REQUIRE(v.cx >= 0 && v.cy >= 0 && v.cw > 0 && v.ch > 0 && (long)v.cx + v.cw <= v.Wp && (long)v.cy + v.ch <= v.Hp,
                 "view %d: crop box {%d,%d,%d,%d} leaves the %dx%d page", k, v.cx, v.cy, v.cw, v.ch, v.Hp, v.Wp);
-        REQUIRE(v.ch >= c->in_H && v.cw >= c->in_W, "view %d: cropped page %dx%d is smaller than the model input %dx%d (unsupported by the reference too, main.py:278-281)",
+        REQUIRE_GEOMETRY(v.ch >= c->in_H && v.cw >= c->in_W, "view %d: cropped page %dx%d is smaller than the model input %dx%d (unsupported by the reference too, main.py:278-281)",
                 k, v.ch, v.cw, c->in_H, c->in_W);
         ViewRec& r = recs[k];
         memset(&r, 0, sizeof(r));
@@ -1486,19 +1508,7 @@ int sbbseg_segment_views_dev(sbbseg_ctx* c, int n_views, const sbbseg_view* view
     // one buffer: [n_views] ViewRec | [n_views] int thresholds (views that bring no device int of their own) | maps
     const size_t thr_at = sizeof(ViewRec) * (size_t)n_views, maps_at = thr_at + sizeof(int) * (size_t)n_views;
     const size_t bytes = maps_at + sizeof(int) * maps.size();
-    if (c->views_copy_pending) {                               // (the previous call's upload still reads the staging)
-        HIPCHK(hipEventSynchronize(c->ev_views));
-        c->views_copy_pending = false;
-    }
-    if (!c->ev_views) HIPCHK(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
-    if (c->h_views_cap < bytes) {
-        c->h_views_cap = 0;
-        (void)hipHostFree(c->h_views); c->h_views = nullptr;
-        const size_t cap = bytes + bytes / 2;
-        HIPCHK(hipHostMalloc(&c->h_views, cap, hipHostMallocDefault));
-        c->h_views_cap = cap;
-    }
-    if (c->views_cap < bytes && ensure(c, &c->d_views, &c->views_cap, bytes + bytes / 2)) return 1;
+    if (views_staging(c, bytes)) return 1;
     if (ensure(c, (void**)&c->d_tile_labels, &c->tile_labels_cap, most * per)) return 1;
     const ViewRec* d_recs = (const ViewRec*)c->d_views;
     int* d_thr = (int*)((char*)c->d_views + thr_at);
@@ -1647,13 +1657,14 @@ int sbbseg_segment_whole(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, int Wp,
 }
 
 // do_prediction(patches=False) on the page as upscaled to Hs x Ws: the page comes from host memory (page_hwc) or is already on the
-// device (d_page_in); the label plane lands in c->d_page_labels and, if labels_out is given, in host memory too.
+// device (d_page_in); the label plane lands in c->d_page_labels and, if labels_out is given, in host memory too -- or, with d_dst, in that
+// device buffer alone (labels_out is then NULL).
 static int whole_scaled_impl(sbbseg_ctx* c, const uint8_t* page_hwc, const void* d_page_in, int Hp, int Wp, int Hs, int Ws, int out_h, int out_w,
-                             uint8_t* labels_out)
+                             uint8_t* labels_out, void* d_dst = nullptr)
 {
     const size_t pix = (size_t)Hp * Wp, opix = (size_t)out_h * out_w;
     if (!d_page_in && ensure(c, (void**)&c->d_page, &c->page_cap, pix * 3)) return 1;
-    if (ensure(c, (void**)&c->d_page_labels, &c->page_labels_cap, opix + 4)) return 1;
+    if (!d_dst && ensure(c, (void**)&c->d_page_labels, &c->page_labels_cap, opix + 4)) return 1;
     const size_t need = sizeof(int) * (size_t)(c->in_H + c->in_W + out_h + out_w);
     const bool cached = c->d_wmap && c->wmap_cap >= need && c->wmap_key[0] == Hp && c->wmap_key[1] == Wp && c->wmap_key[2] == Hs &&
                         c->wmap_key[3] == Ws && c->wmap_key[4] == out_h && c->wmap_key[5] == out_w;
@@ -1695,7 +1706,7 @@ static int whole_scaled_impl(sbbseg_ctx* c, const uint8_t* page_hwc, const void*
         } scope(c);
         if (run_plan(c, 1, c->d_batch_labels, nullptr)) return 1;
     }
-    HIPCHK(launch_resize_labels(c->d_batch_labels, c->in_H, c->in_W, d_oy, d_ox, out_h, out_w, c->d_page_labels, c->stream));
+    HIPCHK(launch_resize_labels(c->d_batch_labels, c->in_H, c->in_W, d_oy, d_ox, out_h, out_w, d_dst ? (uint8_t*)d_dst : c->d_page_labels, c->stream));
     if (labels_out) {
         if (labels_to_host(c, labels_out, opix)) return 1;
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -1710,6 +1721,103 @@ int sbbseg_segment_whole_scaled(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, 
     if (check_ready(c)) return 1;
     REQUIRE(page_hwc && labels_out && Hp > 0 && Wp > 0 && Hs > 0 && Ws > 0 && out_h > 0 && out_w > 0, "bad arguments");
     return whole_scaled_impl(c, page_hwc, nullptr, Hp, Wp, Hs, Ws, out_h, out_w, labels_out);
+    API_END
+}
+
+// ---- the whole-image branch for many pages in shared launches (include/sbbseg.h): one patch per view, chunks of <= max_batch patches one
+// after the other on the handle's stream.  Per call the view table (internal.h WholeViewRec) and every view's four nearest maps -- the
+// composed model -> page -> stored maps and the output -> model maps of whole_scaled_impl, shared between views of equal geometry -- go up
+// in one asynchronous copy; per chunk one ingest and one label-resize launch.  n_views == 1 is whole_scaled_impl itself (split-K as the
+// handle has it); from two views on nothing splits: ksplit_now is only ever set inside whole_scaled_impl.
+static int check_whole_views(int n_views, const sbbseg_whole_view* views, bool planes_required)
+{
+    REQUIRE(n_views >= 1, "n_views %d < 1", n_views);
+    REQUIRE(views, "null view array");
+    for (int k = 0; k < n_views; ++k) {
+        const sbbseg_whole_view& v = views[k];
+        REQUIRE(v.d_page_hwc && (v.d_labels_out || !planes_required), "view %d: null page / label pointer", k);
+        REQUIRE(v.stored_h > 0 && v.stored_w > 0 && v.page_h > 0 && v.page_w > 0 && v.out_h > 0 && v.out_w > 0,
+                "view %d: bad size (stored %dx%d, page %dx%d, labels %dx%d)", k, v.stored_h, v.stored_w, v.page_h, v.page_w, v.out_h, v.out_w);
+    }
+    return 0;
+}
+
+static int whole_views_impl(sbbseg_ctx* c, int n_views, const sbbseg_whole_view* views)
+{
+    if (check_whole_views(n_views, views, true)) return 1;
+    if (n_views == 1) {
+        const sbbseg_whole_view& v = views[0];
+        if (whole_scaled_impl(c, nullptr, v.d_page_hwc, v.stored_h, v.stored_w, v.page_h, v.page_w, v.out_h, v.out_w, nullptr, v.d_labels_out)) return 1;
+        c->whole_launches += 2;
+        return 0;
+    }
+    alloc_check();
+    // chunks of equal size, as run_chunked cuts a tile list (9 views at max_batch 4: 3 + 3 + 3)
+    const int n_chunks = (n_views + c->max_batch - 1) / c->max_batch, chunk = (n_views + n_chunks - 1) / n_chunks;
+    struct MapAt { int a, b, m, off; };
+    std::vector<MapAt> map_at;
+    std::vector<int> maps, one, two;
+    auto map_offset = [&](int stored, int page, int model) -> int {       // model index -> stored index; page = 0: destination index -> model index
+        for (const MapAt& m : map_at)
+            if (m.a == stored && m.b == page && m.m == model) return m.off;
+        if (page == 0) nearest_map(model, stored, one);                   // (a = the destination length here: main.py:378)
+        else {
+            nearest_map(page, model, one);                                // model row -> row of the page do_prediction was handed (main.py:371)
+            if (page != stored) {                                         // ... itself the nearest-upscaled stored image (main.py:214): compose
+                nearest_map(stored, page, two);
+                for (auto& q : one) q = two[q];
+            }
+        }
+        map_at.push_back({stored, page, model, (int)maps.size()});
+        maps.insert(maps.end(), one.begin(), one.end());
+        return map_at.back().off;
+    };
+    std::vector<WholeViewRec> recs(n_views);
+    std::vector<unsigned> chunk_blocks(n_chunks, 0u);
+    for (int k = 0; k < n_views; ++k) {
+        const sbbseg_whole_view& v = views[k];
+        WholeViewRec& r = recs[k];
+        memset(&r, 0, sizeof(r));
+        r.page = (const uint8_t*)v.d_page_hwc; r.out = (uint8_t*)v.d_labels_out; r.stored_w = v.stored_w; r.out_h = v.out_h; r.out_w = v.out_w;
+        r.my = map_offset(v.stored_h, v.page_h, c->in_H); r.mx = map_offset(v.stored_w, v.page_w, c->in_W);
+        r.oy = map_offset(v.out_h, 0, c->in_H); r.ox = map_offset(v.out_w, 0, c->in_W);
+        r.lead = (unsigned)((uintptr_t)v.d_labels_out & 15);
+        unsigned& blocks = chunk_blocks[k / chunk];
+        r.blk_first = blocks;
+        const size_t nb = ((size_t)r.lead + (size_t)v.out_h * v.out_w + kResizeViewsBlockBytes - 1) / kResizeViewsBlockBytes;
+        REQUIRE(blocks + nb < (size_t)1 << 31, "view %d: the chunk's label planes are too large for one resize launch", k);
+        blocks += (unsigned)nb;
+    }
+    const size_t maps_at = sizeof(WholeViewRec) * (size_t)n_views, bytes = maps_at + sizeof(int) * maps.size();
+    if (views_staging(c, bytes)) return 1;
+    memcpy(c->h_views, recs.data(), maps_at);
+    memcpy((char*)c->h_views + maps_at, maps.data(), sizeof(int) * maps.size());
+    HIPCHK(hipMemcpyAsync(c->d_views, c->h_views, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->ev_views, c->stream));
+    c->views_copy_pending = true;
+    const WholeViewRec* d_recs = (const WholeViewRec*)c->d_views;
+    const int* d_maps = (const int*)((char*)c->d_views + maps_at);
+    for (int q = 0, first = 0; first < n_views; ++q, first += chunk) {
+        const int nb = n_views - first < chunk ? n_views - first : chunk;
+        IngestParams fp;
+        if (fill_ingest(c, fp)) return 1;
+        IngestWholeViewsParams ip;
+        memset(&ip, 0, sizeof(ip));
+        ip.views = d_recs + first; ip.maps = d_maps; ip.n_views = nb; ip.H = c->in_H; ip.W = c->in_W;
+        ip.lut = fp.lut; ip.c8 = fp.c8; ip.pairs = fp.pairs; ip.pad = fp.pad; ip.pairs_w = fp.pairs_w;
+        HIPCHK(launch_ingest_whole_views(ip, c->precision, c->stream));
+        if (run_plan(c, nb, c->d_batch_labels, nullptr)) return 1;              // (ksplit_now is false: no launch splits, whatever nb is)
+        HIPCHK(launch_resize_labels_views(c->d_batch_labels, c->in_H, c->in_W, d_recs + first, d_maps, nb, chunk_blocks[q], c->stream));
+        c->whole_launches += 2;
+    }
+    return 0;
+}
+
+int sbbseg_segment_whole_views_dev(sbbseg_ctx* c, int n_views, const sbbseg_whole_view* views)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    return whole_views_impl(c, n_views, views);
     API_END
 }
 
@@ -1820,6 +1928,38 @@ int sbbseg_extract_page_box_dev(sbbseg_ctx* c, const void* d_page_hwc, int Hp, i
     API_END
 }
 
+// extract_page's model + glue for many pages: the border forwards at batch width (whole_views_impl), then the box search plane by plane.
+int sbbseg_extract_page_boxes_dev(sbbseg_ctx* c, int n_pages, const sbbseg_whole_view* views, int32_t* boxes_xywh, int64_t* pixels)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    REQUIRE(boxes_xywh, "bad arguments");
+    if (check_whole_views(n_pages, views, false)) return 1;
+    alloc_check();
+    std::vector<sbbseg_whole_view> v(views, views + n_pages);
+    std::vector<size_t> at(n_pages, 0);
+    size_t scratch = 0;
+    for (int k = 0; k < n_pages; ++k) {
+        REQUIRE(v[k].out_h == v[k].page_h && v[k].out_w == v[k].page_w, "view %d: the mask %dx%d must have the page's size %dx%d", k, v[k].out_h, v[k].out_w,
+                v[k].page_h, v[k].page_w);
+        REQUIRE((size_t)v[k].page_h * v[k].page_w < ((size_t)1 << 31), "view %d: mask too large for 32-bit pixel indices", k);
+        if (v[k].d_labels_out) continue;
+        at[k] = scratch;
+        scratch += ((size_t)v[k].page_h * v[k].page_w + 15) & ~(size_t)15;
+    }
+    if (scratch && ensure(c, (void**)&c->d_page_labels, &c->page_labels_cap, scratch + 16)) return 1;      // (the masks nobody asked for)
+    for (int k = 0; k < n_pages; ++k)
+        if (!v[k].d_labels_out) v[k].d_labels_out = c->d_page_labels + at[k];
+    if (whole_views_impl(c, n_pages, v.data())) return 1;
+    for (int k = 0; k < n_pages; ++k) {                        // main.py:394-404 per plane; an empty mask: {0, 0, 0, 0} / 0
+        int64_t px = 0;
+        if (sbbseg_page_box_dev(c, v[k].d_labels_out, v[k].page_h, v[k].page_w, boxes_xywh + 4 * k, &px)) return 1;
+        if (pixels) pixels[k] = px;
+    }
+    return 0;
+    API_END
+}
+
 // ---- the model-running part of run() (main.py:2056-2107) in ONE call: the stored page is uploaded once and stays in device memory for
 // all three stages, the border mask and the region map never leave the device between their model and their glue.
 //   extract_page (main.py:2061, 384-437)            border model on the page as upscaled to Hs x Ws, dilate x 6, largest contour, box;
@@ -1853,11 +1993,12 @@ int sbbseg_run_page(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline
     // "no lines"; a device or allocation error fails the call with its message in sbbseg_last_error(): a fault must not look like an empty page.
     auto stage_failed = [&](sbbseg_ctx* h) -> bool {          // true: a geometry failure (swallowed, as the reference swallows it)
         const std::string msg = g_err;
+        const int kind = g_err_kind;
         (void)hipStreamSynchronize(h->stream);
         if (h->lane_stream) (void)hipStreamSynchronize(h->lane_stream);
         (void)hipGetLastError();
-        g_err = msg;
-        return msg.find("smaller than the model input") != std::string::npos;
+        g_err = msg; g_err_kind = kind;
+        return kind == kErrGeometry;
     };
     // layout stage + its post-processing: the reference's bare try / except (main.py:2069-2091)
     int present = 0;
@@ -1886,6 +2027,109 @@ int sbbseg_run_page(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline
             ok = true;
         } while (0);
         if (!ok && !stage_failed(textline)) return 1;
+    }
+    return 0;
+    API_END
+}
+
+// ---- sbbseg_run_page for many pages: the stored pages go up once, the border forwards run at batch width, the layout and textline models
+// take all pages' crops in one sbbseg_segment_views_dev call each; masks, region maps and textline maps stay on the device between their
+// model and their glue.  What run() swallows for a page -- a crop that cannot hold a model input -- is decided by geometry before the
+// pooled call; any failure of a library call is a device or allocation error and fails the whole call.
+int sbbseg_run_pages(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline, int n_pages, sbbseg_run_page_io* pages, int channels)
+{
+    API_BEGIN
+    if (check_ready(border) || check_ready(layout) || check_ready(textline)) return 1;
+    REQUIRE(n_pages >= 1 && pages && (channels == 1 || channels == 3), "bad arguments");
+    REQUIRE(border->device == layout->device && border->device == textline->device, "the three handles must live on one device");
+    alloc_check();
+    std::vector<size_t> page_at(n_pages), mask_at(n_pages), crop_at(n_pages, 0);
+    size_t page_bytes = 0, mask_bytes = 0, crop_bytes = 0;
+    for (int k = 0; k < n_pages; ++k) {
+        sbbseg_run_page_io& pg = pages[k];
+        REQUIRE(pg.page_hwc && pg.regions_out && pg.textlines_out && pg.Hp > 0 && pg.Wp > 0 && pg.Hs > 0 && pg.Ws > 0, "page %d: bad arguments", k);
+        memset(&pg.info, 0, sizeof(pg.info));
+        pg.status = 0;
+        page_at[k] = page_bytes; page_bytes += ((size_t)pg.Hp * pg.Wp * 3 + 15) & ~(size_t)15;
+        mask_at[k] = mask_bytes; mask_bytes += ((size_t)pg.Hs * pg.Ws + 15) & ~(size_t)15;
+    }
+    if (ensure(border, (void**)&border->d_run_page, &border->run_page_cap, page_bytes)) return 1;
+    if (ensure(border, (void**)&border->d_run_mask, &border->run_mask_cap, mask_bytes)) return 1;
+    // A failed step: wait for whatever is queued (uploads read the caller's pages, kernels read buffers the next call may reallocate)
+    auto failed = [&](sbbseg_ctx* h) -> int {
+        const std::string msg = g_err;
+        const int kind = g_err_kind;
+        (void)hipStreamSynchronize(h->stream);
+        if (h->lane_stream) (void)hipStreamSynchronize(h->lane_stream);
+        (void)hipGetLastError();
+        g_err = msg; g_err_kind = kind;
+        return 1;
+    };
+    std::vector<sbbseg_whole_view> wv(n_pages);
+    std::vector<int32_t> boxes(4 * (size_t)n_pages);
+    std::vector<int64_t> px(n_pages);
+    for (int k = 0; k < n_pages; ++k) {
+        const sbbseg_run_page_io& pg = pages[k];
+        if (hipMemcpyAsync(border->d_run_page + page_at[k], pg.page_hwc, (size_t)pg.Hp * pg.Wp * 3, hipMemcpyHostToDevice, border->stream) != hipSuccess) {
+            set_error("upload of page %d failed", k);
+            return failed(border);
+        }
+        wv[k] = {border->d_run_page + page_at[k], pg.Hp, pg.Wp, pg.Hs, pg.Ws, pg.Hs, pg.Ws, border->d_run_mask + mask_at[k]};
+    }
+    if (sbbseg_extract_page_boxes_dev(border, n_pages, wv.data(), boxes.data(), px.data())) return failed(border);
+    HIPCHK(hipStreamSynchronize(border->stream));              // the hand-over: the other two handles read the pages from here on
+    for (int k = 0; k < n_pages; ++k) {
+        sbbseg_run_page_io& pg = pages[k];
+        memcpy(pg.info.box_xywh, &boxes[4 * (size_t)k], sizeof(pg.info.box_xywh));
+        pg.info.box_pixels = px[k];
+        if (px[k] <= 0) { pg.status = 1; continue; }            // main.py:399-401 raises for this page: nothing else of it is written
+        if (pg.page_mask_out && sbbseg_download_labels(border, pg.page_mask_out, border->d_run_mask + mask_at[k], (size_t)pg.Hs * pg.Ws, channels)) return failed(border);
+        crop_at[k] = crop_bytes;
+        crop_bytes += ((size_t)pg.info.box_xywh[2] * pg.info.box_xywh[3] + 4 + 15) & ~(size_t)15;
+    }
+    auto fits = [](const sbbseg_ctx* h, const sbbseg_run_page_io& pg) { return pg.info.box_xywh[3] >= h->in_H && pg.info.box_xywh[2] >= h->in_W; };
+    auto crop_view = [&](const sbbseg_run_page_io& pg, int k, int binarise) -> sbbseg_view {
+        const int32_t* b = pg.info.box_xywh;
+        return {border->d_run_page + page_at[k], pg.Hp, pg.Wp, pg.Hs, pg.Ws, b[0], b[1], b[2], b[3], binarise, layout->d_run_a + crop_at[k], nullptr};
+    };
+    // layout stage (main.py:2069-2091): every page that has a box and whose crop holds one input of the layout model
+    std::vector<int> todo;
+    std::vector<sbbseg_view> lv;
+    for (int k = 0; k < n_pages; ++k)
+        if (pages[k].status == 0 && fits(layout, pages[k])) todo.push_back(k);
+    if (todo.empty()) return 0;
+    if (ensure(layout, (void**)&layout->d_run_a, &layout->run_a_cap, crop_bytes) || ensure(layout, (void**)&layout->d_run_b, &layout->run_b_cap, crop_bytes)) return 1;
+    for (int k : todo) lv.push_back(crop_view(pages[k], k, 1));
+    if (sbbseg_segment_views_dev(layout, (int)lv.size(), lv.data())) return failed(layout);
+    std::vector<int> thr(lv.size(), 0);
+    if (sbbseg_download(layout, thr.data(), layout->d_views_thr, sizeof(int) * lv.size())) return failed(layout);
+    for (size_t q = 0; q < todo.size(); ++q) {
+        const int k = todo[q];
+        sbbseg_run_page_io& pg = pages[k];
+        const int w = pg.info.box_xywh[2], h = pg.info.box_xywh[3];
+        uint8_t* raw = layout->d_run_a + crop_at[k];
+        uint8_t* clean = layout->d_run_b + crop_at[k];
+        int present = 0;
+        if (sbbseg_morph_dev(layout, raw, h, w, SBBSEG_MORPH_ERODE, 5, 3, clean) ||                                         // main.py:2074
+            sbbseg_morph_dev(layout, clean, h, w, SBBSEG_MORPH_DILATE, 5, 4, clean) ||                                      // main.py:2075
+            sbbseg_text_regions_present_dev(layout, clean, h, w, 1, 0.00001, &present) ||                                   // main.py:2083, 2096
+            sbbseg_download_labels(layout, pg.regions_out, clean, (size_t)w * h, channels)) return failed(layout);
+        pg.info.otsu_threshold = thr[q];
+        pg.info.regions_ok = 1;
+        pg.info.text_present = present;
+    }
+    // textline stage (main.py:2096-2107), on the pages the gate let through.  Its planes take the place of the raw layout maps: every
+    // download above has waited for the layout handle's stream, nothing reads them any more.
+    todo.clear(); lv.clear();
+    for (int k = 0; k < n_pages; ++k)
+        if (pages[k].info.text_present && fits(textline, pages[k])) todo.push_back(k);
+    if (todo.empty()) return 0;
+    for (int k : todo) lv.push_back(crop_view(pages[k], k, 0));
+    if (sbbseg_segment_views_dev(textline, (int)lv.size(), lv.data())) return failed(textline);
+    for (int k : todo) {
+        sbbseg_run_page_io& pg = pages[k];
+        if (sbbseg_download_labels(textline, pg.textlines_out, layout->d_run_a + crop_at[k], (size_t)pg.info.box_xywh[2] * pg.info.box_xywh[3], 1)) return failed(textline);
+        pg.info.textlines_ok = 1;
     }
     return 0;
     API_END
@@ -2057,8 +2301,8 @@ int sbbseg_allgather_labels_dev(sbbseg_ctx* c, const void* d_send, size_t bytes_
 int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value)
 {
     API_BEGIN
-    REQUIRE(c && value && which >= 0 && which <= 3, "unknown counter %d (0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by the line-mask calls, 3 = ingest / region-table / stitch kernels queued by sbbseg_segment_views_dev)", which);
-    *value = which == 0 ? (int64_t)c->host_contour_calls : which == 1 ? (int64_t)c->forwards : which == 2 ? (int64_t)c->line_launches : c->views_launches;
+    REQUIRE(c && value && which >= 0 && which <= 4, "unknown counter %d (0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by the line-mask calls, 3 = ingest / region-table / stitch kernels queued by sbbseg_segment_views_dev, 4 = ingest / label-resize kernels queued by the whole-views calls)", which);
+    *value = which == 0 ? (int64_t)c->host_contour_calls : which == 1 ? (int64_t)c->forwards : which == 2 ? (int64_t)c->line_launches : which == 3 ? c->views_launches : c->whole_launches;
     return 0;
     API_END
 }

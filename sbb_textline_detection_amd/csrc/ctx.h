@@ -20,6 +20,9 @@
     } while (0)
 
 #define REQUIRE(cond, ...) do { if (!(cond)) return sbbseg::set_error(__VA_ARGS__); } while (0)
+// ... for the one failure the reference's run() swallows: a page or crop that cannot hold one model input (main.py:278-285 under the bare
+// try / except of 2069-2091 and 2152-2157).  Callers that mirror run() branch on g_err_kind, not on the message's wording.
+#define REQUIRE_GEOMETRY(cond, ...) do { if (!(cond)) { sbbseg::set_error(__VA_ARGS__); sbbseg::g_err_kind = sbbseg::kErrGeometry; return 1; } } while (0)
 
 // Every extern "C" body runs inside API_BEGIN / API_END: a C++ exception (std::bad_alloc from a std::vector, ...)
 // becomes a non-zero status + sbbseg_last_error() instead of terminating the caller's process -- the reference's
@@ -35,6 +38,8 @@ namespace sbbseg {
 
 // Defined once in the library (api.hip): sbbseg_last_error() and sbbseg_debug_inject_alloc_failure() serve every unit.
 extern thread_local std::string g_err;          // written by set_error() (internal.h)
+enum ErrKind { kErrOther = 0, kErrGeometry = 1 };
+extern thread_local int g_err_kind;             // kind of the error in g_err: set_error() says kErrOther, REQUIRE_GEOMETRY kErrGeometry
 extern int g_alloc_fail_countdown;              // test hook (sbbseg_debug_inject_alloc_failure): the n-th next alloc_check() throws std::bad_alloc
 inline void alloc_check() { if (g_alloc_fail_countdown > 0 && --g_alloc_fail_countdown == 0) throw std::bad_alloc(); }
 
@@ -220,6 +225,7 @@ struct sbbseg_ctx {
     hipEvent_t ev_views = nullptr; bool views_copy_pending = false;
     int* d_views_thr = nullptr;       // the last call's threshold ints inside d_views, one per view (sbbseg_segment_views reads them back)
     int64_t views_launches = 0;       // ingest + region-build + stitch kernels sbbseg_segment_views_dev has queued (sbbseg_debug_counter 3)
+    int64_t whole_launches = 0;       // ingest + label-resize kernels the whole-views calls have queued (sbbseg_debug_counter 4)
     // stage glue scratch (morphology planes, union-find arrays, result words)
     uint8_t *d_morph_a = nullptr, *d_morph_b = nullptr; size_t morph_a_cap = 0, morph_b_cap = 0;
     // pipelined multi-page host path (sbbseg_segment_pages): copy streams, two slots of pinned staging + device buffers
@@ -234,7 +240,8 @@ struct sbbseg_ctx {
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;
     void* d_deskew = nullptr; size_t deskew_cap = 0;      // inverse maps | bicubic table | row counts of sbbseg_deskew_profiles
-    // sbbseg_run_page's resident buffers (owned by the handle passed as `border` / `layout` / `textline` respectively)
+    // sbbseg_run_page's / sbbseg_run_pages' resident buffers (owned by the handle passed as `border` / `layout` / `textline` respectively;
+    // sbbseg_run_pages: all pages' planes one after the other, and the textline planes in the layout handle's d_run_a)
     uint8_t *d_run_page = nullptr, *d_run_mask = nullptr, *d_run_a = nullptr, *d_run_b = nullptr;
     size_t run_page_cap = 0, run_mask_cap = 0, run_a_cap = 0, run_b_cap = 0;
     int *d_cc_parent = nullptr, *d_cc_count = nullptr; size_t cc_parent_cap = 0, cc_count_cap = 0;

@@ -383,6 +383,32 @@ hipError_t launch_ingest_views(const IngestViewsParams& p, int precision, hipStr
 hipError_t launch_stitch_views(const uint8_t* tile_labels, int H, int W, int margin, const ViewRec* views, int n_views, unsigned n_blocks, hipStream_t s);
 hipError_t launch_resize_labels(const uint8_t* labels, int H, int W, const int* map_y, const int* map_x,
                                 int out_h, int out_w, uint8_t* out, hipStream_t s);
+// sbbseg_segment_whole_views_dev: one patch per view (the whole-image branch, main.py:368-380).  Patch p of a chunk is view v0 + p of the
+// call's table; its pixel (y, x) reads stored pixel (maps[my + y], maps[mx + x]) (the composed model -> page -> stored nearest maps) and
+// pixel (y, x) of its label plane reads label (maps[oy + y], maps[ox + x]) of the patch's H x W label map.
+struct WholeViewRec {
+    const uint8_t* page;      // stored page [stored_h][stored_w][3]
+    uint8_t* out;             // label plane [out_h][out_w], any alignment
+    int stored_w;
+    int my, mx, oy, ox;       // offsets of the view's four maps in the call's map array
+    int out_h, out_w;
+    unsigned lead;            // out & 15: bytes between the 16-byte line the plane starts in and the plane
+    unsigned blk_first;       // label resize: first block of the view among its chunk's (prefix sum of ceil((lead + out_h * out_w) / 4096))
+};
+struct IngestWholeViewsParams {
+    const WholeViewRec* views;    // the chunk's views
+    const int* maps;
+    int n_views;                  // = patches of the launch
+    int H, W;
+    const float* lut;
+    void* c8;
+    void* pairs;
+    int pad, pairs_w;
+};
+hipError_t launch_ingest_whole_views(const IngestWholeViewsParams& p, int precision, hipStream_t s);
+constexpr int kResizeViewsBlockBytes = 256 * 16;      // plane bytes a block of resize_labels_views_kernel covers: 16 per lane
+hipError_t launch_resize_labels_views(const uint8_t* labels, int H, int W, const WholeViewRec* views, const int* maps, int n_views, unsigned n_blocks,
+                                      hipStream_t s);
 hipError_t launch_replicate3(const uint8_t* src, uint8_t* dst, size_t n, hipStream_t s);
 hipError_t launch_to_f32(const void* src, float* dst, size_t n, int precision, hipStream_t s);
 hipError_t launch_period_mismatches(const void* data, size_t shift_bytes, size_t tail_bytes, unsigned long long* res, int num_cus, hipStream_t s);   // sbbseg_debug_tensor_period_mismatches

@@ -206,6 +206,53 @@ hipError_t launch_ingest_views(const IngestViewsParams& p, int precision, hipStr
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// ingest of a chunk of the whole-image branch for many pages (sbbseg_segment_whole_views_dev): blockIdx.y = patch of the chunk = one view,
+// so the view's record is uniform over the block (the compiler fetches it through the scalar cache); the pixel goes through the view's two
+// composed nearest maps (model row -> page row -> stored row), then through what ingest_u8_kernel does in whole mode -- the LUT, both forms.
+// ------------------------------------------------------------------------------------------------
+template <typename E, bool SPLIT = false>
+__global__ __launch_bounds__(256) void ingest_whole_views_kernel(const IngestWholeViewsParams p)
+{
+    const int t = blockIdx.y;
+    const int rem = blockIdx.x * 256 + threadIdx.x;
+    if (rem >= p.H * p.W) return;
+    const WholeViewRec& v = p.views[t];
+    const int y = rem / p.W, x = rem - y * p.W;
+    const int sy = p.maps[v.my + y], sx = p.maps[v.mx + x];
+    const uint8_t* px = v.page + ((size_t)sy * v.stored_w + sx) * 3;
+    const long idx = (long)t * (p.H * p.W) + rem;
+    const float f[3] = {p.lut[px[0]], p.lut[px[1]], p.lut[px[2]]};
+    if constexpr (SPLIT) {
+        write_split_input<E>(f, p.c8, p.pairs, idx, t, y, x, p.H, p.pad, p.pairs_w);
+        return;
+    }
+    const E v0 = to_elem<E>(f[0]), v1 = to_elem<E>(f[1]), v2 = to_elem<E>(f[2]), z = to_elem<E>(0.f);
+    Vec8<E> o;
+    o.v[0] = v0; o.v[1] = v1; o.v[2] = v2;
+#pragma unroll
+    for (int i = 3; i < 8; ++i) o.v[i] = z;
+    ((Vec8<E>*)p.c8)[idx] = o;
+    if (p.pairs) {
+        const int PH = p.H + 2 * p.pad;
+        const int xp = x + p.pad;
+        E* dst = (E*)p.pairs + (((size_t)t * PH + (y + p.pad)) * p.pairs_w + (xp >> 1)) * 8 + (xp & 1) * 4;
+        Vec4<E> q; q.v[0] = v0; q.v[1] = v1; q.v[2] = v2; q.v[3] = z;
+        *(Vec4<E>*)dst = q;
+    }
+}
+
+hipError_t launch_ingest_whole_views(const IngestWholeViewsParams& p, int precision, hipStream_t s)
+{
+    if (p.n_views <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((p.H * p.W + 255) / 256), (unsigned)p.n_views);
+    if (precision == kF32) hipLaunchKernelGGL(ingest_whole_views_kernel<float>, grid, dim3(256), 0, s, p);
+    else if (precision == kF16X3) hipLaunchKernelGGL((ingest_whole_views_kernel<_Float16, true>), grid, dim3(256), 0, s, p);
+    else if (precision == kF16) hipLaunchKernelGGL(ingest_whole_views_kernel<_Float16>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(ingest_whole_views_kernel<uint16_t>, grid, dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 hipError_t launch_ingest_f32(const float* x, int n, int H, int W, void* c8, void* pairs, int pad,
                              int pairs_w, int precision, hipStream_t s)
 {
@@ -473,6 +520,55 @@ hipError_t launch_resize_labels(const uint8_t* labels, int H, int W, const int* 
     const long total = (long)out_h * out_w;
     hipLaunchKernelGGL(resize_labels_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, labels, H, W,
                        map_y, map_x, out_h, out_w, out);
+    return hipGetLastError();
+}
+
+// The label resize of a chunk of views in one launch: patch p's 1 x H x W label map -> view p's out_h x out_w plane (main.py:378, the index
+// rule of resize_labels_kernel).  A plane is walked as the run of bytes it is, in the 16-byte lines of its address: a lane owns one line
+// and stores it as one 16-byte word -- a border mask is 12.6 MB per page, a byte store per lane issues sixteen times the stores -- except
+// the line the plane starts in and the one it ends in, which belong to it only in part and are stored byte by byte (planes start anywhere,
+// rows have any width: a line may hold the end of one row and the start of the next).  Block b serves lines of the view whose block range
+// holds b (prefix sums, every plane starts a new block); the view's record depends on blockIdx only and comes through the scalar cache.
+__global__ __launch_bounds__(256) void resize_labels_views_kernel(const uint8_t* labels, int H, int W, const WholeViewRec* views, const int* maps,
+                                                                  int n_views)
+{
+    const int p = view_find(n_views, blockIdx.x, [&](int m) { return views[m].blk_first; });
+    const WholeViewRec& v = views[p];
+    const long total = (long)v.out_h * v.out_w;
+    const long first = ((long)(blockIdx.x - v.blk_first) * 256 + threadIdx.x) * 16 - (long)v.lead;      // plane byte of the line's byte 0
+    if (first >= total) return;
+    const uint8_t* src = labels + (size_t)p * H * W;
+    const int* map_y = maps + v.oy;
+    const int* map_x = maps + v.ox;
+    const long i0 = first < 0 ? 0 : first;
+    int y = (int)(i0 / v.out_w), x = (int)(i0 - (long)y * v.out_w);
+    const uint8_t* row = src + (size_t)map_y[y] * W;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const long i = first + k;
+        if (i >= 0 && i < total) {
+            w[k >> 2] |= (uint32_t)row[map_x[x]] << (8 * (k & 3));
+            if (++x == v.out_w) {
+                x = 0; ++y;
+                if (i + 1 < total) row = src + (size_t)map_y[y] * W;
+            }
+        }
+    }
+    if (first >= 0 && first + 16 <= total) {
+        *(uint4*)(v.out + first) = make_uint4(w[0], w[1], w[2], w[3]);      // (out - lead is a multiple of 16, and so is first + lead)
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (first + k >= 0 && first + k < total) v.out[first + k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+    }
+}
+
+hipError_t launch_resize_labels_views(const uint8_t* labels, int H, int W, const WholeViewRec* views, const int* maps, int n_views, unsigned n_blocks,
+                                      hipStream_t s)
+{
+    if (n_blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(resize_labels_views_kernel, dim3(n_blocks), dim3(256), 0, s, labels, H, W, views, maps, n_views);
     return hipGetLastError();
 }
 

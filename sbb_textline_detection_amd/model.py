@@ -130,6 +130,33 @@ class SegModel:
         each equal to ``ctx.segment_crop`` on that view alone."""
         return self.ctx.segment_views(views, channels)
 
+    def segment_whole_views(self, pages):
+        """The whole-image branch (``do_prediction(patches=False)``) for many pages in shared launches: ``pages`` = a sequence of
+        (stored page uint8 [H,W,3], page_h, page_w, out_h, out_w) -- the page's size after get_image_and_scales and the size of the label
+        plane -> [labels uint8 [out_h,out_w], ...], each equal to ``ctx.segment_whole_scaled`` on that page alone with split-K off."""
+        ctx = self.ctx
+        items, at, total = [], [], 0
+        for k, (page, page_h, page_w, out_h, out_w) in enumerate(pages):
+            pg = np.ascontiguousarray(page, np.uint8)
+            if pg.ndim != 3 or pg.shape[2] != 3:
+                raise ValueError(f"page {k}: must be uint8 [H,W,3], got {pg.shape}")
+            if min(int(page_h), int(page_w), int(out_h), int(out_w)) < 1:
+                raise ValueError(f"page {k}: sizes must be positive")
+            items.append((pg, int(page_h), int(page_w), int(out_h), int(out_w)))
+            at.append((total, total + (pg.nbytes + 15) // 16 * 16))
+            total = at[-1][1] + (int(out_h) * int(out_w) + 15) // 16 * 16
+        if not items:
+            return []
+        d_buf = ctx.device_alloc(total)
+        try:
+            for (pg, *_), (a, _) in zip(items, at):
+                ctx.upload(d_buf + a, pg)
+            ctx.segment_whole_views_dev([(d_buf + a, pg.shape[0], pg.shape[1], ph, pw, oh, ow, d_buf + b)
+                                         for (pg, ph, pw, oh, ow), (a, b) in zip(items, at)])
+            return [ctx.download(d_buf + b, (oh, ow)) for (_, _, _, oh, ow), (_, b) in zip(items, at)]
+        finally:
+            ctx.device_free(d_buf)
+
     @property
     def ctx(self) -> _capi.Context:
         if self._ctx is None or self._ctx.h is None:

@@ -590,19 +590,35 @@ class InferenceStages:
                 textlines = None
         return page_mask, regions, textlines, page_coord
 
-    def run_pages(self, images):
+    def run_pages(self, images, resident: bool = False):
         """``[self.run(img) for img in images]``, with the two patch stages pooled over the pages: the border model and the page box run
         page by page as in run(); the layout model then takes ALL pages' crops in one ``segment_views`` call (their tiles share launches
         although every crop has its own size), cleaning and the text-region gate run per page, and the textline model takes the crops of
         the pages that passed the gate in one more call.  A page whose crop cannot hold one input of a model is kept out of that model's
         call and gets what run() gives it (regions = None / textlines = None); extract_page's errors propagate.  Foreign model objects
-        take the loop."""
+        take the loop.
+        ``resident=True`` (opt-in): ONE library call, ``sbbseg_run_pages`` -- every stored page is uploaded once and stays on the device for
+        all three stages, the border forwards run at batch width (never split-K: the masks equal run()'s with split-K off on the border
+        handle), the region maps stay on the device between the layout model, the cleaning and the gate.  Same tuples; raises what run()
+        raises for the first page without a page box."""
         images = list(images)
         opened = [start_new_session_and_model(d, **self.kw) for d in (self.model_page_dir, self.model_region_dir, self.model_textline_dir)]
         try:
             (_, _), (m_region, _), (m_text, _) = opened
             if not all(isinstance(m, SegModel) for m, _ in opened):
                 return [self.run(img) for img in images]
+            if resident:
+                from . import _capi
+                stored = [np.ascontiguousarray(img, np.uint8) for img in images]
+                out = _capi.run_pages(opened[0][0].ctx, m_region.ctx, m_text.ctx,
+                                      [(img,) + scaled_size(*img.shape[:2]) for img in stored], channels=3) if stored else []
+                results = []
+                for mask, regions, textlines, info, status in out:
+                    if status != 0:
+                        raise ValueError("attempt to get argmax of an empty sequence")          # what main.py:401 raises
+                    x, y, w, h = (int(v) for v in info.box_xywh)
+                    results.append((mask, regions, textlines, [y, y + h, x, x + w]))
+                return results
 
             def fits(model, box):
                 H, W = model.ctx.model_info()[:2]
