@@ -1,5 +1,6 @@
-// ctx.h -- private, host only: what the translation units behind the C ABI (api.hip, plan_build.hip, stage_glue.hip) share -- the error and
-// exception plumbing, the allocation helpers, and the handle (struct sbbseg_ctx) with the plan structs it embeds.
+// ctx.h -- private, host only: what the translation units behind the C ABI (api.hip, forward.hip, pages.hip, whole.hip, comm.hip -- these five
+// through exec.h -- plan_build.hip, stage_glue.hip) share: the error and exception plumbing, the allocation helpers, and the handle
+// (struct sbbseg_ctx) with the plan structs it embeds.
 #pragma once
 
 #include <new>

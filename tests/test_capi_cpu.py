@@ -69,7 +69,7 @@ def test_alloc_failure_hook_reaches_the_glue_unit(lib):
 
 def test_error_message_crosses_units(lib):
     """One thread-local message behind sbbseg_last_error(): a box check in stage_glue.hip (the size-only path: no handle) and
-    an argument check in api.hip both write it, one right after the other."""
+    an argument check in pages.hip both write it, one right after the other."""
     with pytest.raises(RuntimeError, match="leaves the 8 x 8 plane"):
         _capi.region_deskew_offsets([[0, 0, 9, 9]], 80, 8, 8)
     with pytest.raises(RuntimeError, match="smaller than the model"):

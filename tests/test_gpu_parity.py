@@ -961,6 +961,35 @@ def test_scaled_page_equals_oracle_resize(stitch_model):
         assert a.shape == (hs, ws) and np.array_equal(a, b), (h, w, hs, ws)
 
 
+def test_scaled_otsu_and_crop_calls_share_one_map_cache(stitch_model):
+    """segment_page_scaled, segment_page_otsu and segment_crop keep their nearest maps in one buffer of the handle, cached by geometry.
+    Interleaved on one handle, at geometries whose maps differ but fit the buffer the call before left behind (4 tiles each), every call must
+    equal segment_page / segment_page_otsu of the page resized by the ORACLE's nearest rule and cropped on the host; a repeated geometry
+    (served from the cache) must repeat its result byte for byte."""
+    from oracle import stage_glue
+    m = stitch_model
+    rng = np.random.RandomState(11)
+    A = rng.randint(0, 256, (520, 480, 3)).astype(np.uint8)
+    B = rng.randint(0, 256, (505, 470, 3)).astype(np.uint8)
+    up = lambda page, h, w: np.ascontiguousarray(tiling.resize_nearest(page, h, w))
+    crop = lambda page, box: np.ascontiguousarray(page[box[1]:box[1] + box[3], box[0]:box[0] + box[2]])
+    box2, box5 = (30, 20, 500, 470), (60, 40, 500, 470)
+    crops = [crop(up(B, 650, 600), box2), crop(up(B, 650, 600), box5)]
+    want1 = m.segment_page(up(A, 620, 560))
+    want2, want5 = (m.segment_page(stage_glue.otsu_copy(cr).astype(np.uint8)) for cr in crops)
+    want3, thr3 = m.ctx.segment_page_otsu(up(A, 600, 500))
+    got1 = m.ctx.segment_page_scaled(A, 620, 560)
+    got2, thr2 = m.ctx.segment_crop(B, 650, 600, box2, binarise=True)
+    got3, got_thr3 = m.ctx.segment_page_otsu(A, 600, 500)
+    got4 = m.ctx.segment_page_scaled(A, 620, 560)
+    got5, thr5 = m.ctx.segment_crop(B, 650, 600, box5, binarise=True)
+    assert got1.shape == (620, 560) and np.array_equal(got1, want1)
+    assert got2.shape == (470, 500) and np.array_equal(got2, want2) and thr2 == stage_glue.otsu_threshold(crops[0][:, :, 0])
+    assert got3.shape == (600, 500) and np.array_equal(got3, want3) and got_thr3 == thr3 == stage_glue.otsu_threshold(up(A, 600, 500)[:, :, 0])
+    assert got4.tobytes() == got1.tobytes()
+    assert got5.shape == (470, 500) and np.array_equal(got5, want5) and thr5 == stage_glue.otsu_threshold(crops[1][:, :, 0])
+
+
 def test_whole_image_branch_fused_equals_reference_structure(stitch_model):
     """patches=False (main.py:368-380): the fused device path (resize gather -> forward -> argmax -> resize back) must equal,
     bit for bit, the oracle's restatement of the branch -- itself pinned to the imported reference by the whole_cases

@@ -1,7 +1,7 @@
 """-m gpu: the per-step float64 check of tests/test_gpu_steps.py on the whole-image launch (``sbbseg_segment_whole*``, the border model
 of ``run_page``), the only caller of the split-K route.
 
-With one patch, ``launch_op`` (csrc/api.hip, the last ``else`` of the conv branch) sends every long-K generic conv of the 128-channel tile
+With one patch, ``launch_op`` (csrc/forward.hip, the last ``else`` of the conv branch) sends every long-K generic conv of the 128-channel tile
 through ``conv_igemm_mfma<..KS>`` -- 2^ks blocks per tile, each writing its K-range's fp32 partial sums x ``wmul_cls`` to a workspace -- and
 ``splitk_finish<MODE>``, which adds the planes in split order and runs its own copy of the epilogue.  Recipe of one configuration (one lane,
 max_batch 2): a page whose sides are no multiples of the model's, so that the whole-image gather of ``ingest_u8_kernel`` really resamples;

@@ -6,7 +6,7 @@ storage format.  (1) Correct arithmetic stays inside the derived bound in all fo
 defects, injected into the stand-in, puts the step it was injected into over the bound in f16 and f16x3 -- and the range-relative
 criterion of the per-layer tests (``TOL_LAYER_REL``) is evaluated on the same tensor to show what it lets through.
 
-Split-K (the whole-image branch's one-patch launches, csrc/api.hip launch_op): ``StandIn.conv(splits=...)`` deals the K-chunks to
+Split-K (the whole-image branch's one-patch launches, csrc/forward.hip launch_op): ``StandIn.conv(splits=...)`` deals the K-chunks to
 `splits` contiguous ranges, sums each in fp32 on its own and adds the partial sums in split order; the bound gets
 ``extra_adds = splits - 1`` (tests/step_check.py).  Defects 11 to 13 are defects of that route.  The three small non-ResNet plans of
 tests/small_plans.py run clean through the same stand-in."""
