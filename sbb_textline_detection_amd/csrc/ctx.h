@@ -1,5 +1,5 @@
 // ctx.h -- private, host only: what the translation units behind the C ABI (api.hip, forward.hip, pages.hip, whole.hip, comm.hip -- these five
-// through exec.h -- plan_build.hip, stage_glue.hip) share: the error and exception plumbing, the allocation helpers, and the handle
+// through exec.h, forward.hip and pages.hip through route.h too -- plan_build.hip, stage_glue.hip) share: the error and exception plumbing, the allocation helpers, and the handle
 // (struct sbbseg_ctx) with the plan structs it embeds.
 #pragma once
 
@@ -96,12 +96,11 @@ struct ConvOp {
     int fused_reduce = -1;                // split mode: index of the NEXT block's first 1x1 conv, computed by this (expand) conv's launch too
                                           // (expand_reduce_x3.hip; sbbseg_finalize), or -1
     uint16_t *d_er_w3 = nullptr, *d_er_w1 = nullptr;      //   ... the two convs' packed rows as MFMA A fragments
-    bool fused_into_expand = false;       // split mode: this op's output is written by the launch of the op before it; it launches nothing
     int fused_conv3 = -1;                 // on an expand conv with fused_reduce: index of the block's 3x3 conv, which the same launch computes too
                                           // (conv3_expand_reduce.hip; sbbseg_finalize), or -1
     uint16_t* d_c3_w2 = nullptr;          //   ... the 3x3 conv's packed rows as MFMA A fragments, and its K-steps (taps / channel groups) in order
     int* d_c3_k0 = nullptr;
-    bool fused_into_c3 = false;           // the 3x3 conv of such a block: its output tensor lives in LDS only, the op launches nothing
+                                          // (that conv's output tensor then lives in LDS only)
     std::vector<float> h_w[2];            // host copy of a small 1x1 conv's weights ([cin][cout] per source): bottleneck fusion
                                           // (sbbseg_finalize) repacks them as MFMA A fragments
     bool fg_ok = true;                    // every K-step (of every class) regular: the fast gather of conv_igemm_mfma applies
@@ -114,7 +113,6 @@ struct ConvOp {
 
 struct PoolOp {
     int src, dst, k, stride, Ho, Wo; float *d_pre_scale = nullptr, *d_pre_shift = nullptr; int pre_relu = 0;
-    bool fused_into_stem = false;         // split mode: the stem op before it writes this pool's output too (stem_pool_x3); the op then launches nothing
 };
 
 struct HeadOp {
@@ -150,6 +148,9 @@ struct Op {
     std::vector<Op> parts;        // kBlock: the convs it fuses
     double prof_ms = 0;
     int64_t prof_launches = 0, prof_patches = 0;
+    int absorbed_by = -1;         // >= 0: index of the op whose launch can write this op's output too -- the stem of a max-pool (fused_pool), the
+                                  // expand conv of a reduce conv (fused_reduce) or of a 3x3 conv (fused_conv3); sbbseg_finalize.  The op launches
+                                  // nothing when that op takes the fused route (route.h)
     int region_level = -1;        // >= 0: a decoder level of the owned-region chain (sbbseg_finalize: region_chain; region.h)
     double exec_patches = 0;      // work executed since sbbseg_profile_reset, in whole-patch equivalents: a launch of n patches adds n, an
                                   // owned-region launch n x (pixels walked / pixels of the whole grid)

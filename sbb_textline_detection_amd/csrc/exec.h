@@ -7,7 +7,6 @@
 namespace sbbseg {
 
 // forward.hip
-bool runs_dec_halo(const sbbseg_ctx* c, const ConvOp& co);                           // the conv takes the LDS-resident-halo kernel
 int run_plan(sbbseg_ctx* c, int n, uint8_t* d_labels, float* d_probs);                // the plan over n patches whose input forms are filled
 int fill_ingest(sbbseg_ctx* c, IngestParams& ip);                                     // the input-form pointers of the lane in use
 int resolve_pending(sbbseg_ctx* c);                                                   // profiling events still in flight -> the ops' totals

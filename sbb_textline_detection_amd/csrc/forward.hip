@@ -1,9 +1,11 @@
-// forward.hip -- the forward pass over n patches whose input forms are filled: every plan op's launch (launch_op), the plan loop with its
-// per-op accounting and profiling events (run_plan), and the profiling entry points that read them.
+// forward.hip -- the forward pass over n patches whose input forms are filled: every plan op's launch (launch_op: a dispatch on route.h's
+// route_of to one function per kernel family), the plan loop with its per-op accounting and profiling events (run_plan), and the profiling
+// entry points that read them.
 #include <stdlib.h>
 #include <string.h>
 
 #include "exec.h"
+#include "route.h"
 
 using namespace sbbseg;
 
@@ -21,217 +23,274 @@ int get_event(sbbseg_ctx* c, hipEvent_t* e)
 }
 
 // ---- forward pass over n patches whose input forms are already filled -------------------------
+// One function per kernel family (route.h): each fills its family's parameter struct and launches it.
+
+int launch_block(sbbseg_ctx* c, Op& op, int n)
+{
+    const BlockOp& bo = op.block;
+    BlockParams bp;
+    bp.x = c->tensors[bo.x_tensor].buf; bp.n = n; bp.H = bo.H; bp.W = bo.W; bp.proj = bo.proj; bp.pq = c->block_pq ? 1 : 0;
+    bp.w1 = bo.d_w1; bp.w2 = op.parts[1].conv.d_d64_wfrag; bp.w3 = bo.d_w3;
+    bp.s1 = op.parts[0].conv.d_scale; bp.b1 = op.parts[0].conv.d_shift;
+    bp.s2 = op.parts[1].conv.d_scale; bp.b2 = op.parts[1].conv.d_shift;
+    bp.s3 = op.parts[2].conv.d_scale; bp.b3 = op.parts[2].conv.d_shift;
+    bp.out = c->tensors[bo.out_tensor].data();
+    bp.wmul1 = bo.wmul[0]; bp.wmul2 = bo.wmul[1]; bp.wmul3 = bo.wmul[2];
+#ifdef SBBSEG_PROBES
+    { static const int blk_dbg = getenv("SBBSEG_BLOCK_DBG") ? atoi(getenv("SBBSEG_BLOCK_DBG")) : 0; bp.dbg = blk_dbg; }
+#endif
+    if (c->precision == kF16X3) HIPCHK(launch_block_x3(bp, c->num_cus, c->stream, &op.last));
+    else HIPCHK(launch_bottleneck(bp, c->precision, c->num_cus, c->stream, &op.last));
+    return 0;
+}
+
+// the stem alone, or (with_pool) the stem and the max-pool behind it in one launch
+int launch_stem_route(sbbseg_ctx* c, Op& op, int n, bool with_pool)
+{
+    const ConvOp& co = op.conv;
+    const Tensor& st = c->tensors[co.d.src[0].tensor];
+    StemParams sp;
+    sp.pairs = st.buf; sp.PHt = st.H; sp.PWt = st.W; sp.n = n; sp.Ho = co.Ho; sp.Wo = co.Wo;
+    sp.wfrag = co.d_stem_wfrag; sp.scale = co.d_scale; sp.shift = co.d_shift; sp.relu = co.d.relu; sp.wmul = co.wmul_cls[0];
+    sp.out = c->tensors[co.d.out_tensor].data();
+    if (!with_pool) {
+        HIPCHK(launch_stem(sp, c->precision, c->num_cus, c->stream, &op.last));
+        return 0;
+    }
+    const PoolOp& po = c->ops[co.fused_pool].pool;
+    sp.pool_out = c->tensors[po.dst].data(); sp.pool_scale = po.d_pre_scale; sp.pool_shift = po.d_pre_shift;
+    sp.pool_relu = po.pre_relu; sp.pool_Ho = po.Ho; sp.pool_Wo = po.Wo;
+    sp.x3 = c->precision == kF16X3;
+    HIPCHK(launch_stem_pool_x3(sp, c->num_cus, c->stream, &op.last));
+    return 0;
+}
+
+int launch_direct64_route(sbbseg_ctx* c, Op& op, int n)
+{
+    const ConvOp& co = op.conv;
+    const Tensor& st = c->tensors[co.d.src[0].tensor];
+    Direct64Params dp;
+    dp.src = st.buf; dp.n = n; dp.H = st.H; dp.W = st.W; dp.wfrag = co.d_d64_wfrag;
+    dp.scale = co.d_scale; dp.shift = co.d_shift; dp.relu = co.d.relu; dp.out = c->tensors[co.d.out_tensor].data();
+    dp.wmul = co.wmul_cls[0];
+    HIPCHK(launch_direct64(dp, c->precision, c->num_cus, c->stream, &op.last));
+    return 0;
+}
+
+// the expand conv's launch computes the block's 3x3 conv in front of it and the next block's reduce conv behind it too
+int launch_c3er(sbbseg_ctx* c, Op& op, int n)
+{
+    const ConvOp& co = op.conv;
+    const ConvOp& ro = c->ops[co.fused_reduce].conv;
+    const ConvOp& k3 = c->ops[co.fused_conv3].conv;
+    const Tensor& ta = c->tensors[k3.d.src[0].tensor];
+    C3ERParams cp;
+    cp.a = ta.buf; cp.x = c->tensors[co.d.residual_tensor].buf;
+    cp.y = c->tensors[co.d.out_tensor].buf; cp.a2 = c->tensors[ro.d.out_tensor].buf;
+    cp.n = n; cp.H = ta.H; cp.W = ta.W; cp.C = co.d.src[0].channels; cp.x3 = c->precision == kF16X3;
+    cp.w2frag = co.d_c3_w2; cp.w3frag = co.d_er_w3; cp.w1frag = co.d_er_w1;
+    cp.s2 = k3.d_scale; cp.h2 = k3.d_shift; cp.s3 = co.d_scale; cp.h3 = co.d_shift; cp.s1 = ro.d_scale; cp.h1 = ro.d_shift;
+    cp.wmul2 = k3.wmul_cls[0]; cp.wmul3 = co.wmul_cls[0]; cp.wmul1 = ro.wmul_cls[0];
+    cp.k0 = co.d_c3_k0;
+    HIPCHK(launch_conv3_expand_reduce(cp, c->num_cus, c->stream, &op.last));
+    return 0;
+}
+
+// the expand conv's launch writes the next block's reduce conv too
+int launch_expand_reduce(sbbseg_ctx* c, Op& op, int n)
+{
+    const ConvOp& co = op.conv;
+    const ConvOp& ro = c->ops[co.fused_reduce].conv;
+    ExpRedParams ep;
+    ep.b = c->tensors[co.d.src[0].tensor].buf; ep.x = c->tensors[co.d.residual_tensor].buf;
+    ep.y = c->tensors[co.d.out_tensor].buf; ep.a2 = c->tensors[ro.d.out_tensor].buf;
+    ep.M = n * co.Ho * co.Wo; ep.C = co.d.src[0].channels; ep.x3 = c->precision == kF16X3;
+    ep.w3frag = co.d_er_w3; ep.w1frag = co.d_er_w1;
+    ep.s3 = co.d_scale; ep.h3 = co.d_shift; ep.s1 = ro.d_scale; ep.h1 = ro.d_shift;
+    ep.wmul3 = co.wmul_cls[0]; ep.wmul1 = ro.wmul_cls[0];
+    ep.dbg = 0;
+#ifdef SBBSEG_PROBES
+    { static const int er_dbg = getenv("SBBSEG_ER_DBG") ? atoi(getenv("SBBSEG_ER_DBG")) : 0; ep.dbg = er_dbg; }
+#endif
+    HIPCHK(launch_expand_reduce_x3(ep, c->num_cus, c->stream, &op.last));
+    return 0;
+}
+
+int launch_dec_halo(sbbseg_ctx* c, Op& op, int n)
+{
+    const ConvOp& co = op.conv;
+    const Tensor& s0 = c->tensors[co.d.src[0].tensor];
+    DecHaloParams hp;
+    hp.src0 = s0.buf; hp.skip = c->tensors[co.d.src[1].tensor].buf; hp.PH = s0.H; hp.PW = s0.W; hp.n = n;
+    hp.wfrag = co.d_halo_wfrag; hp.taps = co.d_halo_taps; hp.scale = co.d_scale; hp.shift = co.d_shift;
+    for (int q = 0; q < 4; ++q) hp.wmul[q] = co.wmul_cls[q];
+    hp.relu = co.d.relu; hp.out = c->tensors[co.d.out_tensor].data();
+    // owned-region launch (region.h): the chunk's tile table -- region_plan_levels asked route_of too, so the level's table is of that kind
+    if (c->rr.on && op.region_level >= 0) { hp.ttab = c->rr.tab[op.region_level]; hp.n_tab = c->rr.total[op.region_level]; }
+    if (c->precision == kF16X3) HIPCHK(launch_dec_halo_x3(hp, c->num_cus, c->stream, &op.last));
+    else HIPCHK(launch_dec_halo_f16(hp, c->num_cus, c->stream, &op.last));
+    return 0;
+}
+
+// conv_igemm_mfma.  What depends on the call and not on the plan is decided here: the tile walk, whether an owned-region level gets its
+// pixel map, split-K.
+int launch_generic_conv(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
+{
+    const ConvOp& co = op.conv;
+    ConvParams p;
+    memset(&p, 0, sizeof(p));
+    p.n_src = co.d.n_src;
+    // (short-K layers keep the plain gather: the per-tile mask set-up costs them 1-10 %; from ~9 K-steps on the fast
+    // gather wins 2-10 %, profiles/r02_experiments.md)
+    bool fg = co.d_fgstep_cls[0] && !c->plain_gather;
+    for (int s = 0; s < co.d.n_src; ++s) {
+        const Tensor& t = c->tensors[co.d.src[s].tensor];
+        SrcDesc& sd = p.src[s];
+        sd.base = t.buf;
+        sd.PH = t.H; sd.PW = t.W;
+        sd.pix_bytes = t.C * c->elem * c->planes;
+        sd.lo_off = c->planes == 2 ? split_group(t.C) * c->elem : 64;       // split mode: hi -> lo inside a channel group
+        sd.shift = co.d.src[s].up_shift;
+        sd.lim_y = t.H << sd.shift; sd.lim_x = t.W << sd.shift;
+        sd.ksteps = co.ksteps[s];
+        sd.sy_shift = co.d.src[s].stride_y == 2; sd.sx_shift = co.d.src[s].stride_x == 2;
+        const size_t bytes = kZeroHeaderBytes + t.elems_per_patch * (size_t)n * c->elem * c->planes;
+        sd.bytes = (uint32_t)bytes;
+        // fast gather: bit 31 of a lane offset marks an out-of-bounds tap, so every real offset must stay below 2^31
+        sd.tap_lo_y = co.tap_lo[s][0]; sd.tap_lo_x = co.tap_lo[s][1];
+        if (bytes + (size_t)kFgBiasPixels(t.W) * sd.pix_bytes >= ((size_t)1 << 31)) fg = false;
+    }
+    p.fast_gather = fg ? (co.fg_pointwise ? 2 : 1) : 0;
+    p.ktab = co.d_ktab; p.kstep = co.d_kstep; p.half_stages = (c->conv_variant & 16) ? 1 : 0;
+    p.variant = c->conv_variant & 3; p.persist_blocks = (c->conv_variant & 4) ? 0 : c->num_cus;
+    p.M = n * co.Ho * co.Wo;
+    p.variant_flags = ((c->conv_variant & 64) ? 1 : 0) | ((c->conv_variant & 128) ? 2 : 0) | (c->ph8 ? 4 : 0);
+#ifdef SBBSEG_PROBES
+    { static const int probe_local = getenv("SBBSEG_CONV_PROBE_LOCAL") ? atoi(getenv("SBBSEG_CONV_PROBE_LOCAL")) : 0; if (probe_local) p.variant_flags |= 32; }
+    { static const int probe_whot = getenv("SBBSEG_CONV_PROBE_WHOT") ? atoi(getenv("SBBSEG_CONV_PROBE_WHOT")) : 0; if (probe_whot) p.variant_flags |= 64; }
+#endif
+    // XCD-grouped walk for single-class layers: measured neutral-to-slower (it removes the n_ct-fold
+    // re-fetch of the pixel operand, but those layers are not bound by fetch bytes) -> opt-in, bit 5
+    // (split mode: on by default -- twice the pixel bytes; +0.7 % page throughput in two runs, profiles/r03_experiments.md)
+    // (SBBSEG_PSHARE_MAX_MB: weight-matrix size up to which the pixel-sharing walk is taken; round 6 experiment -- the K >= 768 merge / reduce
+    //  convs of stages 4 / 5 and dec0 re-fetch their pixel operand once per channel tile under map 0: PMC FETCH = n_ct x the input)
+    static const size_t pshare_max = (size_t)(getenv("SBBSEG_PSHARE_MAX_MB") ? atoi(getenv("SBBSEG_PSHARE_MAX_MB")) : 2) << 20;
+    p.tile_map = (((c->conv_variant & 32) || c->precision == kF16X3) && !(c->conv_variant & 8) && (c->conv_variant & 4) == 0 && co.d.cout > conv_tile_bc(co.d.cout) && p.M >= 256 * 128 &&
+                  (size_t)co.cout_pad * co.Ktot * c->elem <= pshare_max) ? 1 : 0;
+    if (p.tile_map == 1 && co.n_cls == 1 && co.Ktot <= c->contig_max_k) p.tile_map = 2;
+    p.w = co.d_w; p.Ktot = co.Ktot; p.total_ksteps = co.total_ksteps;
+    p.Ho = co.Ho; p.Wo = co.Wo;
+    p.TH = co.TH; p.TW = co.TW; p.osy = co.d.out_stride_y; p.osx = co.d.out_stride_x;
+    p.ooy = co.d.out_off_y; p.oox = co.d.out_off_x;
+    p.n_cls = co.n_cls;
+    p.cls_minor = 0;
+    if (co.n_cls > 1 && (co.n_cls & (co.n_cls - 1)) == 0 && !(c->conv_variant & 8) && !(c->conv_variant & 4) &&
+        (size_t)co.cout_pad * co.Ktot * c->elem <= ((size_t)16 << 20)) {     // (dec1/dec2 too: fetch -30 / -53 %, time unchanged)
+        p.cls_minor = 1;      // small weights: let the classes share their source pixels in one L2
+        p.tile_map = c->ranged_walk ? 3 : 1;
+    }
+    for (int q = 0; q < 4; ++q) {
+        p.w_cls[q] = co.d_w_cls[q]; p.kstep_cls[q] = co.d_kstep_cls[q]; p.ktab_cls[q] = co.d_ktab_cls[q]; p.fgstep_cls[q] = co.d_fgstep_cls[q];
+        p.ooy_cls[q] = co.ooy_cls[q]; p.oox_cls[q] = co.oox_cls[q]; p.wmul_cls[q] = co.wmul_cls[q];
+    }
+    p.head_classes = co.d.head_classes; p.head_w = co.d_head_w; p.head_scale = co.d_head_scale;
+    p.head_shift = co.d_head_shift; p.labels = d_labels; p.probs = d_probs;
+    p.cout = co.d.cout; p.scale = co.d_scale; p.shift = co.d_shift;
+    p.out = co.d.out_tensor >= 0 ? c->tensors[co.d.out_tensor].data() : nullptr;
+    p.residual = co.d.residual_tensor >= 0 ? c->tensors[co.d.residual_tensor].data() : nullptr;
+    p.raw_out = co.d.raw_out_tensor >= 0 ? c->tensors[co.d.raw_out_tensor].data() : nullptr;
+    p.raw_scale = co.d_rscale; p.raw_shift = co.d_rshift; p.relu = co.d.relu;
+    // owned-region launch of a decoder level (region.h): the chunk's table replaces the walk over the whole output grid
+    const int rlv = c->rr.on ? op.region_level : -1;
+    if (rlv >= 0 && c->rr.kind[rlv] == 1) {
+        // the pixel table is read by the fast-gather form of conv_igemm_mfma, 2-stage whole-K-step tiles only (what every decoder conv
+        // runs by default); under an A/B knob that takes the level elsewhere it is launched whole -- a superset, same results
+        if (p.fast_gather && !p.half_stages && p.variant != 2 && !(p.variant_flags & 4)) { p.rmap = c->rr.tab[rlv]; p.M = c->rr.total[rlv]; }
+        else c->last_exec_frac = 1.0;
+    }
+    // One patch through a long-K conv = 2-32 tiles of 100-400 K-steps at ~1 us a step on as many CUs: the whole-image branch
+    // (extract_page's border model, 1 forward per page) splits the K range over the idle CUs -- up to 16 blocks per tile, each
+    // at least 4 K-steps, fp32 partial sums added in split order by splitk_finish.  Only there: a split launch differs from
+    // the unsplit one in the last bits, and seam 2 / the patch paths promise batch-size-independent results.
+    int ks = 0;
+    if (c->ksplit_now && n == 1 && c->precision != kF32 && p.fast_gather && conv_tile_bc(p.cout) == 128 && !p.raw_out && !p.head_classes &&
+        p.out && p.cout % 8 == 0 &&
+        ((p.n_cls == 1 && p.osy == 1 && p.osx == 1 && p.ooy == 0 && p.oox == 0 && p.TH == p.Ho && p.TW == p.Wo) ||
+         (p.n_cls == 4 && p.osy == 2 && p.osx == 2 && p.TH == 2 * p.Ho && p.TW == 2 * p.Wo))) {
+        const long tiles = (long)p.n_cls * ((p.M + 127) / 128) * ((p.cout + 127) / 128);
+        while (ks < 4 && (tiles << (ks + 1)) <= 512 && p.total_ksteps % (2 << ks) == 0 && (p.total_ksteps >> (ks + 1)) >= 4) ++ks;
+    }
+    if (ks > 0) {
+        const size_t split_elems = (size_t)n * p.TH * p.TW * p.cout;
+        if (ensure(c, (void**)&c->d_ks_ws, &c->ks_ws_cap, (split_elems << ks) * sizeof(float))) return 1;
+        p.ks_shift = ks; p.ks_ws = c->d_ks_ws; p.ks_split_elems = (long)split_elems; p.tile_map = 0; p.cls_minor = 0;
+        HIPCHK(launch_conv(p, c->precision, c->stream, &op.last));
+        HIPCHK(launch_splitk_finish(c->d_ks_ws, 1 << ks, (long)split_elems, (long)n * p.TH * p.TW, p.cout, p.scale, p.shift, p.residual,
+                                    p.relu, p.out, c->precision, c->stream));
+    } else {
+        HIPCHK(launch_conv(p, c->precision, c->stream, &op.last));
+    }
+    return 0;
+}
+
+int launch_pool(sbbseg_ctx* c, Op& op, int n)
+{
+    const PoolOp& po = op.pool;
+    const Tensor& s = c->tensors[po.src];
+    HIPCHK(launch_maxpool(s.data(), c->tensors[po.dst].data(), n, s.H, s.W, s.C, po.k, po.stride, po.Ho, po.Wo,
+                          po.d_pre_scale, po.d_pre_shift, po.pre_relu, c->precision, c->stream, &op.last));
+    return 0;
+}
+
+int launch_tail_route(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
+{
+    const TailOp& to = op.tail;
+    const Tensor& s0 = c->tensors[to.src0];
+    TailParams tp;
+    tp.src0 = s0.buf; tp.img = c->tensors[to.img].buf; tp.PH = s0.H; tp.PW = s0.W; tp.n = n;
+    tp.wfrag = to.d_wfrag; tp.scale = to.d_scale; tp.shift = to.d_shift; tp.classes = to.classes;
+    tp.head_w = to.d_head_w; tp.head_scale = to.d_head_scale; tp.head_shift = to.d_head_shift;
+    tp.labels = d_labels; tp.probs = d_probs;
+    if (c->rr.on && op.region_level >= 0) { tp.ttab = c->rr.tab[op.region_level]; tp.n_tab = c->rr.total[op.region_level]; }
+    HIPCHK(launch_tail(tp, c->precision, c->num_cus, c->stream, &op.last));
+    return 0;
+}
+
+int launch_head_route(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
+{
+    const HeadOp& ho = op.head;
+    const Tensor& s = c->tensors[ho.src];
+    HeadParams hp;
+    hp.src = s.data(); hp.cin = ho.cin; hp.classes = ho.classes; hp.M = n * s.H * s.W;
+    hp.w = ho.d_w; hp.scale = ho.d_scale; hp.shift = ho.d_shift;
+    hp.labels = d_labels; hp.probs = d_probs;
+    HIPCHK(launch_head(hp, c->precision, c->stream, &op.last));
+    return 0;
+}
+
 int launch_op(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
 {
     op.last = LaunchRec{};            // (sbbseg_debug_op_launch: an op that returns below without a launch reports family NONE)
-    if (op.type == kBlock) {
-        if (c->unfuse_blocks) {
-            for (auto& part : op.parts)
-                if (launch_op(c, part, n, d_labels, d_probs)) return 1;
-            op.last = op.parts.back().last;
-            return 0;
-        }
-        const BlockOp& bo = op.block;
-        BlockParams bp;
-        bp.x = c->tensors[bo.x_tensor].buf; bp.n = n; bp.H = bo.H; bp.W = bo.W; bp.proj = bo.proj; bp.pq = c->block_pq ? 1 : 0;
-        bp.w1 = bo.d_w1; bp.w2 = op.parts[1].conv.d_d64_wfrag; bp.w3 = bo.d_w3;
-        bp.s1 = op.parts[0].conv.d_scale; bp.b1 = op.parts[0].conv.d_shift;
-        bp.s2 = op.parts[1].conv.d_scale; bp.b2 = op.parts[1].conv.d_shift;
-        bp.s3 = op.parts[2].conv.d_scale; bp.b3 = op.parts[2].conv.d_shift;
-        bp.out = c->tensors[bo.out_tensor].data();
-        bp.wmul1 = bo.wmul[0]; bp.wmul2 = bo.wmul[1]; bp.wmul3 = bo.wmul[2];
-#ifdef SBBSEG_PROBES
-        { static const int blk_dbg = getenv("SBBSEG_BLOCK_DBG") ? atoi(getenv("SBBSEG_BLOCK_DBG")) : 0; bp.dbg = blk_dbg; }
-#endif
-        if (c->precision == kF16X3) HIPCHK(launch_block_x3(bp, c->num_cus, c->stream, &op.last));
-        else HIPCHK(launch_bottleneck(bp, c->precision, c->num_cus, c->stream, &op.last));
-    } else if (op.type == kConv) {
-        const ConvOp& co = op.conv;
-        if (co.fused_into_expand && !c->no_expand_reduce && !(c->conv_variant & 3)) return 0;      // written by the expand conv's launch (expand_reduce_x3)
-        if (co.fused_into_c3 && !c->no_c3er && !c->no_expand_reduce && !(c->conv_variant & 3)) return 0;     // computed by the expand conv's launch (conv3_expand_reduce)
-        ConvParams p;
-        memset(&p, 0, sizeof(p));
-        p.n_src = co.d.n_src;
-        // (short-K layers keep the plain gather: the per-tile mask set-up costs them 1-10 %; from ~9 K-steps on the fast
-        // gather wins 2-10 %, profiles/r02_experiments.md)
-        bool fg = co.d_fgstep_cls[0] && !c->plain_gather;
-        for (int s = 0; s < co.d.n_src; ++s) {
-            const Tensor& t = c->tensors[co.d.src[s].tensor];
-            SrcDesc& sd = p.src[s];
-            sd.base = t.buf;
-            sd.PH = t.H; sd.PW = t.W;
-            sd.pix_bytes = t.C * c->elem * c->planes;
-            sd.lo_off = c->planes == 2 ? split_group(t.C) * c->elem : 64;       // split mode: hi -> lo inside a channel group
-            sd.shift = co.d.src[s].up_shift;
-            sd.lim_y = t.H << sd.shift; sd.lim_x = t.W << sd.shift;
-            sd.ksteps = co.ksteps[s];
-            sd.sy_shift = co.d.src[s].stride_y == 2; sd.sx_shift = co.d.src[s].stride_x == 2;
-            const size_t bytes = kZeroHeaderBytes + t.elems_per_patch * (size_t)n * c->elem * c->planes;
-            sd.bytes = (uint32_t)bytes;
-            // fast gather: bit 31 of a lane offset marks an out-of-bounds tap, so every real offset must stay below 2^31
-            sd.tap_lo_y = co.tap_lo[s][0]; sd.tap_lo_x = co.tap_lo[s][1];
-            if (bytes + (size_t)kFgBiasPixels(t.W) * sd.pix_bytes >= ((size_t)1 << 31)) fg = false;
-        }
-        p.fast_gather = fg ? (co.fg_pointwise ? 2 : 1) : 0;
-        p.ktab = co.d_ktab; p.kstep = co.d_kstep; p.half_stages = (c->conv_variant & 16) ? 1 : 0;
-        p.variant = c->conv_variant & 3; p.persist_blocks = (c->conv_variant & 4) ? 0 : c->num_cus;
-        p.M = n * co.Ho * co.Wo;
-        p.variant_flags = ((c->conv_variant & 64) ? 1 : 0) | ((c->conv_variant & 128) ? 2 : 0) | (c->ph8 ? 4 : 0);
-#ifdef SBBSEG_PROBES
-        { static const int probe_local = getenv("SBBSEG_CONV_PROBE_LOCAL") ? atoi(getenv("SBBSEG_CONV_PROBE_LOCAL")) : 0; if (probe_local) p.variant_flags |= 32; }
-        { static const int probe_whot = getenv("SBBSEG_CONV_PROBE_WHOT") ? atoi(getenv("SBBSEG_CONV_PROBE_WHOT")) : 0; if (probe_whot) p.variant_flags |= 64; }
-#endif
-        // XCD-grouped walk for single-class layers: measured neutral-to-slower (it removes the n_ct-fold
-        // re-fetch of the pixel operand, but those layers are not bound by fetch bytes) -> opt-in, bit 5
-        // (split mode: on by default -- twice the pixel bytes; +0.7 % page throughput in two runs, profiles/r03_experiments.md)
-        // (SBBSEG_PSHARE_MAX_MB: weight-matrix size up to which the pixel-sharing walk is taken; round 6 experiment -- the K >= 768 merge / reduce
-        //  convs of stages 4 / 5 and dec0 re-fetch their pixel operand once per channel tile under map 0: PMC FETCH = n_ct x the input)
-        static const size_t pshare_max = (size_t)(getenv("SBBSEG_PSHARE_MAX_MB") ? atoi(getenv("SBBSEG_PSHARE_MAX_MB")) : 2) << 20;
-        p.tile_map = (((c->conv_variant & 32) || c->precision == kF16X3) && !(c->conv_variant & 8) && (c->conv_variant & 4) == 0 && co.d.cout > conv_tile_bc(co.d.cout) && p.M >= 256 * 128 &&
-                      (size_t)co.cout_pad * co.Ktot * c->elem <= pshare_max) ? 1 : 0;
-        if (p.tile_map == 1 && co.n_cls == 1 && co.Ktot <= c->contig_max_k) p.tile_map = 2;
-        p.w = co.d_w; p.Ktot = co.Ktot; p.total_ksteps = co.total_ksteps;
-        p.Ho = co.Ho; p.Wo = co.Wo; p.M = n * co.Ho * co.Wo;
-        p.TH = co.TH; p.TW = co.TW; p.osy = co.d.out_stride_y; p.osx = co.d.out_stride_x;
-        p.ooy = co.d.out_off_y; p.oox = co.d.out_off_x;
-        p.n_cls = co.n_cls;
-        p.cls_minor = 0;
-        if (co.n_cls > 1 && (co.n_cls & (co.n_cls - 1)) == 0 && !(c->conv_variant & 8) && !(c->conv_variant & 4) &&
-            (size_t)co.cout_pad * co.Ktot * c->elem <= ((size_t)16 << 20)) {     // (dec1/dec2 too: fetch -30 / -53 %, time unchanged)
-            p.cls_minor = 1;      // small weights: let the classes share their source pixels in one L2
-            p.tile_map = c->ranged_walk ? 3 : 1;
-        }
-        for (int q = 0; q < 4; ++q) {
-            p.w_cls[q] = co.d_w_cls[q]; p.kstep_cls[q] = co.d_kstep_cls[q]; p.ktab_cls[q] = co.d_ktab_cls[q]; p.fgstep_cls[q] = co.d_fgstep_cls[q];
-            p.ooy_cls[q] = co.ooy_cls[q]; p.oox_cls[q] = co.oox_cls[q]; p.wmul_cls[q] = co.wmul_cls[q];
-        }
-        p.head_classes = co.d.head_classes; p.head_w = co.d_head_w; p.head_scale = co.d_head_scale;
-        p.head_shift = co.d_head_shift; p.labels = d_labels; p.probs = d_probs;
-        p.cout = co.d.cout; p.scale = co.d_scale; p.shift = co.d_shift;
-        p.out = co.d.out_tensor >= 0 ? c->tensors[co.d.out_tensor].data() : nullptr;
-        p.residual = co.d.residual_tensor >= 0 ? c->tensors[co.d.residual_tensor].data() : nullptr;
-        p.raw_out = co.d.raw_out_tensor >= 0 ? c->tensors[co.d.raw_out_tensor].data() : nullptr;
-        p.raw_scale = co.d_rscale; p.raw_shift = co.d_rshift; p.relu = co.d.relu;
-        // owned-region launch of a decoder level (region.h): the chunk's table replaces the walk over the whole output grid
-        const int rlv = c->rr.on ? op.region_level : -1;
-        if (rlv >= 0 && c->rr.total[rlv] == 0) return 0;                         // (no patch of the chunk keeps anything)
-        if (rlv >= 0 && c->rr.kind[rlv] == 1) {
-            // the pixel table is read by the fast-gather form of conv_igemm_mfma, 2-stage whole-K-step tiles only (what every decoder conv
-            // runs by default); under an A/B knob that takes the level elsewhere it is launched whole -- a superset, same results
-            if (p.fast_gather && !p.half_stages && p.variant != 2 && !(p.variant_flags & 4)) { p.rmap = c->rr.tab[rlv]; p.M = c->rr.total[rlv]; }
-            else c->last_exec_frac = 1.0;
-        }
-        if (co.d_stem_wfrag && !(c->conv_variant & 3)) {
-            const Tensor& st = c->tensors[co.d.src[0].tensor];
-            StemParams sp;
-            sp.pairs = st.buf; sp.PHt = st.H; sp.PWt = st.W; sp.n = n; sp.Ho = co.Ho; sp.Wo = co.Wo;
-            sp.wfrag = co.d_stem_wfrag; sp.scale = co.d_scale; sp.shift = co.d_shift; sp.relu = co.d.relu; sp.wmul = co.wmul_cls[0];
-            sp.out = c->tensors[co.d.out_tensor].data();
-            if (co.fused_pool >= 0 && !c->unfuse_stem_pool) {
-                const PoolOp& po = c->ops[co.fused_pool].pool;
-                sp.pool_out = c->tensors[po.dst].data(); sp.pool_scale = po.d_pre_scale; sp.pool_shift = po.d_pre_shift;
-                sp.pool_relu = po.pre_relu; sp.pool_Ho = po.Ho; sp.pool_Wo = po.Wo;
-                sp.x3 = c->precision == kF16X3;
-                HIPCHK(launch_stem_pool_x3(sp, c->num_cus, c->stream, &op.last));
-            } else
-                HIPCHK(launch_stem(sp, c->precision, c->num_cus, c->stream, &op.last));
-        } else if (co.d_d64_wfrag && !(c->conv_variant & 3)) {
-            const Tensor& st = c->tensors[co.d.src[0].tensor];
-            Direct64Params dp;
-            dp.src = st.buf; dp.n = n; dp.H = st.H; dp.W = st.W; dp.wfrag = co.d_d64_wfrag;
-            dp.scale = co.d_scale; dp.shift = co.d_shift; dp.relu = co.d.relu; dp.out = c->tensors[co.d.out_tensor].data();
-            dp.wmul = co.wmul_cls[0];
-            HIPCHK(launch_direct64(dp, c->precision, c->num_cus, c->stream, &op.last));
-        } else if (co.fused_reduce >= 0 && !c->no_expand_reduce && !(c->conv_variant & 3)) {
-            const ConvOp& ro = c->ops[co.fused_reduce].conv;
-            if (co.fused_conv3 >= 0 && !c->no_c3er) {
-                const ConvOp& k3 = c->ops[co.fused_conv3].conv;
-                const Tensor& ta = c->tensors[k3.d.src[0].tensor];
-                C3ERParams cp;
-                cp.a = ta.buf; cp.x = c->tensors[co.d.residual_tensor].buf;
-                cp.y = c->tensors[co.d.out_tensor].buf; cp.a2 = c->tensors[ro.d.out_tensor].buf;
-                cp.n = n; cp.H = ta.H; cp.W = ta.W; cp.C = co.d.src[0].channels; cp.x3 = c->precision == kF16X3;
-                cp.w2frag = co.d_c3_w2; cp.w3frag = co.d_er_w3; cp.w1frag = co.d_er_w1;
-                cp.s2 = k3.d_scale; cp.h2 = k3.d_shift; cp.s3 = co.d_scale; cp.h3 = co.d_shift; cp.s1 = ro.d_scale; cp.h1 = ro.d_shift;
-                cp.wmul2 = k3.wmul_cls[0]; cp.wmul3 = co.wmul_cls[0]; cp.wmul1 = ro.wmul_cls[0];
-                cp.k0 = co.d_c3_k0;
-                HIPCHK(launch_conv3_expand_reduce(cp, c->num_cus, c->stream, &op.last));
-                return 0;
-            }
-            ExpRedParams ep;
-            ep.b = c->tensors[co.d.src[0].tensor].buf; ep.x = c->tensors[co.d.residual_tensor].buf;
-            ep.y = c->tensors[co.d.out_tensor].buf; ep.a2 = c->tensors[ro.d.out_tensor].buf;
-            ep.M = n * co.Ho * co.Wo; ep.C = co.d.src[0].channels; ep.x3 = c->precision == kF16X3;
-            ep.w3frag = co.d_er_w3; ep.w1frag = co.d_er_w1;
-            ep.s3 = co.d_scale; ep.h3 = co.d_shift; ep.s1 = ro.d_scale; ep.h1 = ro.d_shift;
-            ep.wmul3 = co.wmul_cls[0]; ep.wmul1 = ro.wmul_cls[0];
-            ep.dbg = 0;
-#ifdef SBBSEG_PROBES
-            { static const int er_dbg = getenv("SBBSEG_ER_DBG") ? atoi(getenv("SBBSEG_ER_DBG")) : 0; ep.dbg = er_dbg; }
-#endif
-            HIPCHK(launch_expand_reduce_x3(ep, c->num_cus, c->stream, &op.last));
-        } else if (runs_dec_halo(c, co)) {
-            const Tensor& s0 = c->tensors[co.d.src[0].tensor];
-            DecHaloParams hp;
-            hp.src0 = s0.buf; hp.skip = c->tensors[co.d.src[1].tensor].buf; hp.PH = s0.H; hp.PW = s0.W; hp.n = n;
-            hp.wfrag = co.d_halo_wfrag; hp.taps = co.d_halo_taps; hp.scale = co.d_scale; hp.shift = co.d_shift;
-            for (int q = 0; q < 4; ++q) hp.wmul[q] = co.wmul_cls[q];
-            hp.relu = co.d.relu; hp.out = c->tensors[co.d.out_tensor].data();
-            if (rlv >= 0) { hp.ttab = c->rr.tab[rlv]; hp.n_tab = c->rr.total[rlv]; }
-            if (c->precision == kF16X3) HIPCHK(launch_dec_halo_x3(hp, c->num_cus, c->stream, &op.last));
-            else HIPCHK(launch_dec_halo_f16(hp, c->num_cus, c->stream, &op.last));
-        } else {
-            // One patch through a long-K conv = 2-32 tiles of 100-400 K-steps at ~1 us a step on as many CUs: the whole-image branch
-            // (extract_page's border model, 1 forward per page) splits the K range over the idle CUs -- up to 16 blocks per tile, each
-            // at least 4 K-steps, fp32 partial sums added in split order by splitk_finish.  Only there: a split launch differs from
-            // the unsplit one in the last bits, and seam 2 / the patch paths promise batch-size-independent results.
-            int ks = 0;
-            if (c->ksplit_now && n == 1 && c->precision != kF32 && p.fast_gather && conv_tile_bc(p.cout) == 128 && !p.raw_out && !p.head_classes &&
-                p.out && p.cout % 8 == 0 &&
-                ((p.n_cls == 1 && p.osy == 1 && p.osx == 1 && p.ooy == 0 && p.oox == 0 && p.TH == p.Ho && p.TW == p.Wo) ||
-                 (p.n_cls == 4 && p.osy == 2 && p.osx == 2 && p.TH == 2 * p.Ho && p.TW == 2 * p.Wo))) {
-                const long tiles = (long)p.n_cls * ((p.M + 127) / 128) * ((p.cout + 127) / 128);
-                while (ks < 4 && (tiles << (ks + 1)) <= 512 && p.total_ksteps % (2 << ks) == 0 && (p.total_ksteps >> (ks + 1)) >= 4) ++ks;
-            }
-            if (ks > 0) {
-                const size_t split_elems = (size_t)n * p.TH * p.TW * p.cout;
-                if (ensure(c, (void**)&c->d_ks_ws, &c->ks_ws_cap, (split_elems << ks) * sizeof(float))) return 1;
-                p.ks_shift = ks; p.ks_ws = c->d_ks_ws; p.ks_split_elems = (long)split_elems; p.tile_map = 0; p.cls_minor = 0;
-                HIPCHK(launch_conv(p, c->precision, c->stream, &op.last));
-                HIPCHK(launch_splitk_finish(c->d_ks_ws, 1 << ks, (long)split_elems, (long)n * p.TH * p.TW, p.cout, p.scale, p.shift, p.residual,
-                                            p.relu, p.out, c->precision, c->stream));
-            } else {
-                HIPCHK(launch_conv(p, c->precision, c->stream, &op.last));
-            }
-        }
-    } else if (op.type == kPool) {
-        const PoolOp& po = op.pool;
-        // written by the stem's launch (stem_pool_x3) -- under exactly the condition that sends the stem there (launch_op, kConv)
-        if (po.fused_into_stem && !c->unfuse_stem_pool && !(c->conv_variant & 3)) return 0;
-        const Tensor& s = c->tensors[po.src];
-        HIPCHK(launch_maxpool(s.data(), c->tensors[po.dst].data(), n, s.H, s.W, s.C, po.k, po.stride, po.Ho, po.Wo,
-                              po.d_pre_scale, po.d_pre_shift, po.pre_relu, c->precision, c->stream, &op.last));
-    } else if (op.type == kTail) {
-        const TailOp& to = op.tail;
-        const Tensor& s0 = c->tensors[to.src0];
-        TailParams tp;
-        tp.src0 = s0.buf; tp.img = c->tensors[to.img].buf; tp.PH = s0.H; tp.PW = s0.W; tp.n = n;
-        tp.wfrag = to.d_wfrag; tp.scale = to.d_scale; tp.shift = to.d_shift; tp.classes = to.classes;
-        tp.head_w = to.d_head_w; tp.head_scale = to.d_head_scale; tp.head_shift = to.d_head_shift;
-        tp.labels = d_labels; tp.probs = d_probs;
-        if (c->rr.on && op.region_level >= 0) {
-            if (c->rr.total[op.region_level] == 0) return 0;
-            tp.ttab = c->rr.tab[op.region_level]; tp.n_tab = c->rr.total[op.region_level];
-        }
-        HIPCHK(launch_tail(tp, c->precision, c->num_cus, c->stream, &op.last));
-    } else {
-        const HeadOp& ho = op.head;
-        const Tensor& s = c->tensors[ho.src];
-        HeadParams hp;
-        hp.src = s.data(); hp.cin = ho.cin; hp.classes = ho.classes; hp.M = n * s.H * s.W;
-        hp.w = ho.d_w; hp.scale = ho.d_scale; hp.shift = ho.d_shift;
-        hp.labels = d_labels; hp.probs = d_probs;
-        HIPCHK(launch_head(hp, c->precision, c->stream, &op.last));
+    // an owned-region level (a decoder conv or the tail) none of whose pixels any patch of the chunk keeps
+    if (c->rr.on && op.region_level >= 0 && c->rr.total[op.region_level] == 0) return 0;
+    switch (route_of(c, op)) {
+    case kRouteNone: return 0;        // written by its absorber's launch
+    case kRouteBlockFused: return launch_block(c, op, n);
+    case kRouteBlockParts:
+        for (auto& part : op.parts)
+            if (launch_op(c, part, n, d_labels, d_probs)) return 1;
+        op.last = op.parts.back().last;
+        return 0;
+    case kRouteStem: return launch_stem_route(c, op, n, false);
+    case kRouteStemPool: return launch_stem_route(c, op, n, true);
+    case kRouteDirect64: return launch_direct64_route(c, op, n);
+    case kRouteC3ER: return launch_c3er(c, op, n);
+    case kRouteExpandReduce: return launch_expand_reduce(c, op, n);
+    case kRouteDecHalo: return launch_dec_halo(c, op, n);
+    case kRouteConv: return launch_generic_conv(c, op, n, d_labels, d_probs);
+    case kRoutePool: return launch_pool(c, op, n);
+    case kRouteTail: return launch_tail_route(c, op, n, d_labels, d_probs);
+    case kRouteHead: return launch_head_route(c, op, n, d_labels, d_probs);
     }
     return 0;
 }
@@ -258,10 +317,6 @@ int resolve_pending(sbbseg_ctx* c)
     c->pending.clear();
     return 0;
 }
-
-// the 224 x 224 decoder conv takes the LDS-resident-halo kernel (dec_halo_x3 / dec_halo_f16) -- also decides which table an
-// owned-region chunk builds for that level (tile origins vs class-grid pixels)
-bool runs_dec_halo(const sbbseg_ctx* c, const ConvOp& co) { return co.d_halo_wfrag && !c->no_dec_halo && !(c->conv_variant & 3); }
 
 int run_plan(sbbseg_ctx* c, int n, uint8_t* d_labels, float* d_probs)
 {

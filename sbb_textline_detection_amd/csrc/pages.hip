@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "exec.h"
+#include "route.h"
 
 using namespace sbbseg;
 
@@ -193,7 +194,7 @@ static void region_plan_levels(const sbbseg_ctx* c, RegionGeom& rg)
         if (L == 0) { rg.kind[L] = 0; rg.Rh[L] = c->in_H; rg.Rw[L] = c->in_W; rg.align_x[L] = 16; }
         else {
             const Tensor& to = c->tensors[lop.conv.d.out_tensor];
-            rg.kind[L] = runs_dec_halo(c, lop.conv) ? 0 : 1;
+            rg.kind[L] = route_of(c, lop) == kRouteDecHalo ? 0 : 1;        // tile origins for dec_halo_*, class-grid pixels for conv_igemm_mfma
             rg.Rh[L] = to.H; rg.Rw[L] = to.W; rg.align_x[L] = 2;
         }
     }

@@ -661,7 +661,7 @@ static int fuse_expand_reduce(sbbseg_ctx* c)
         ConvOp& r = c->ops[i + 1].conv;
         const int C = e.d.src[0].channels;
         if ((C != 128 && C != 256) || !pointwise(e, C, 4 * C) || !pointwise(r, 4 * C, C)) continue;
-        if (e.d.residual_tensor < 0 || r.d.residual_tensor >= 0 || r.d.src[0].tensor != e.d.out_tensor || e.fused_into_expand) continue;
+        if (e.d.residual_tensor < 0 || r.d.residual_tensor >= 0 || r.d.src[0].tensor != e.d.out_tensor || c->ops[i].absorbed_by >= 0) continue;
         const Tensor &tx = c->tensors[e.d.residual_tensor], &ty = c->tensors[e.d.out_tensor], &ta = c->tensors[r.d.out_tensor];
         if (tx.C != 4 * C || tx.H != ty.H || tx.W != ty.W || ty.C != 4 * C || ty.H != e.d.out_h || ty.W != e.d.out_w || ta.C != C ||
             ta.H != ty.H || ta.W != ty.W || tx.is_input_form)
@@ -677,7 +677,7 @@ static int fuse_expand_reduce(sbbseg_ctx* c)
         matrix_frags(f1, m1.data(), r.Ktot, 0, C / 16, 4 * C / kch);
         if (upload(c, &e.d_er_w3, f3) || upload(c, &e.d_er_w1, f1)) return 1;
         e.fused_reduce = (int)(i + 1);
-        r.fused_into_expand = true;
+        c->ops[i + 1].absorbed_by = (int)i;
     }
     return 0;
 }
@@ -703,7 +703,7 @@ static int fuse_conv3_expand_reduce(sbbseg_ctx* c)
             d.src[0].stride_y != 1 || d.src[0].stride_x != 1 || d.src[0].pad_top != 1 || d.src[0].pad_left != 1 || d.src[0].up_shift || d.src[0].off_y ||
             d.src[0].off_x || !d.relu || d.residual_tensor >= 0 || d.raw_out_tensor >= 0 || d.head_classes > 0 || d.out_tensor != e.d.src[0].tensor ||
             d.out_stride_y != 1 || d.out_stride_x != 1 || d.out_off_y || d.out_off_x || k3.d_stem_wfrag || k3.d_d64_wfrag || k3.d_halo_wfrag ||
-            k3.fused_into_expand || k3.fused_reduce >= 0 || k3.total_ksteps != ks0 || k3.Ktot != ks0 * 64 || k3.cout_pad < C ||
+            c->ops[i - 1].absorbed_by >= 0 || k3.fused_reduce >= 0 || k3.total_ksteps != ks0 || k3.Ktot != ks0 * 64 || k3.cout_pad < C ||
             (int)k3.h_ksteps_cls[0].size() != ks0 || readers(c, d.out_tensor) != 1)
             continue;
         const Tensor &ta = c->tensors[d.src[0].tensor], &tb = c->tensors[d.out_tensor];
@@ -723,7 +723,7 @@ static int fuse_conv3_expand_reduce(sbbseg_ctx* c)
         matrix_frags(f2, m2.data(), k3.Ktot, 0, C / 16, ks0);
         if (upload(c, &e.d_c3_w2, f2) || upload(c, &e.d_c3_k0, k0)) return 1;
         e.fused_conv3 = (int)(i - 1);
-        k3.fused_into_c3 = true;
+        c->ops[i - 1].absorbed_by = (int)i;
     }
     return 0;
 }
@@ -746,7 +746,7 @@ static void fuse_stem_pool(sbbseg_ctx* c)
             po.Ho != f1.H / 2 - 1 || po.Wo != f1.W / 2 - 1)
             continue;
         a.conv.fused_pool = (int)(i + 1);
-        b.pool.fused_into_stem = true;
+        b.absorbed_by = (int)i;
     }
 }
 
@@ -783,8 +783,8 @@ int sbbseg_finalize(sbbseg_ctx* c, int max_batch)
     // a 3x3 conv that conv3_expand_reduce computes never writes its output tensor: give the buffers a defined content (zeros) -- the debug
     // read-back of a plan tensor and the tests that compare whole plans then see the same bytes in every run
     for (const Op& op : c->ops)
-        if (op.type == kConv && op.conv.fused_into_c3 && op.conv.d.out_tensor >= 0) {
-            Tensor& t = c->tensors[op.conv.d.out_tensor];
+        if (op.type == kConv && op.conv.fused_conv3 >= 0) {
+            Tensor& t = c->tensors[c->ops[op.conv.fused_conv3].conv.d.out_tensor];        // (= the expand conv's source: fuse_conv3_expand_reduce)
             for (int lane = 0; lane < 2; ++lane)
                 if (t.lane_buf[lane])
                     HIPCHK(hipMemset(t.lane_buf[lane], 0, kZeroHeaderBytes + t.elems_per_patch * (size_t)(lane == 0 ? max_batch : c->lane1_batch) * c->elem * c->planes));
