@@ -22,7 +22,7 @@
 //     the 16-lane groups of ds_read_b128 (two k-groups x eight consecutive rows -> the even and the odd slots)
 // One block of four waves per CU (up to 512 VGPRs per lane).  Wave w owns inner row w and border tile w (11 of the 44 border
 // pixels) in phases A and C, and the 16 output channels of MFMA row block w in phase B.
-#include "device_prims.h"
+#include "tile_walk.h"
 
 namespace sbbseg {
 
@@ -63,13 +63,11 @@ __global__ __launch_bounds__(256, 1) void block_x3(const BlockParams p)
     const int tiles_x = (p.W + 15) / 16, tiles_y = (p.H + 3) / 4;
     const int tiles_per_patch = tiles_x * tiles_y;
     const int n_tiles = p.n * tiles_per_patch;
-    // XCD-contiguous walk: XCD x = block % 8 owns tiles [x * per_xcd, (x + 1) * per_xcd) -- vertical halo neighbours share an L2
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, GX = gridDim.x >> 3;
-    const int per_xcd = (n_tiles + 7) >> 3;
-    const int xcd_lo = xcd * per_xcd, xcd_hi = min(n_tiles, xcd_lo + per_xcd);
-    const int my_tiles = xcd_lo + slot < xcd_hi ? (xcd_hi - xcd_lo - slot + GX - 1) / GX : 0;
+    // XCD-contiguous walk (tile_walk.h): XCD x = block % 8 owns a contiguous eighth of the tiles -- vertical halo neighbours share an L2
+    const XcdWalk walk = xcd_walk(n_tiles, blockIdx, gridDim);
+    const int my_tiles = walk.my_tiles;
     if (my_tiles <= 0) return;
-    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return xcd_lo + slot + it * GX; };
+    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return walk.tile_at(it); };
 
     // ---- one-time: weights and constants to LDS, this wave's 3x3 fragments to registers
     if constexpr (!PROJ)
@@ -413,22 +411,13 @@ __global__ __launch_bounds__(256, 1) void block_x3(const BlockParams p)
 hipError_t launch_block_x3(const BlockParams& p, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     const int n_tiles = p.n * ((p.H + 3) / 4) * ((p.W + 15) / 16);
-    int grid = n_tiles < num_cus ? n_tiles : num_cus;
-    grid = (grid + 7) & ~7;                                     // the XCD-contiguous walk needs a multiple of 8 blocks
+    const int grid = xcd_grid(n_tiles, num_cus);
     launch_rec(rec, SBBSEG_LAUNCH_BLOCK_X3, 4 * 16, 256, 1, n_tiles, grid, 1, 0, !p.proj);
-    static bool attr_done[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static bool attr_done[3][64] = {};                         // one per kernel
+    hipError_t e = dynamic_lds_once((const void*)block_x3<true, false>, kBlockX3LdsBytes, attr_done[0]);
+    if (e == hipSuccess) e = dynamic_lds_once((const void*)block_x3<false, false>, kBlockX3LdsBytes, attr_done[1]);
+    if (e == hipSuccess) e = dynamic_lds_once((const void*)block_x3<true, true>, kBlockX3LdsBytes, attr_done[2]);
     if (e != hipSuccess) return e;
-    if (!attr_done[dev & 63]) {
-        e = hipFuncSetAttribute((const void*)block_x3<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kBlockX3LdsBytes);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)block_x3<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kBlockX3LdsBytes);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)block_x3<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kBlockX3LdsBytes);
-        if (e != hipSuccess) return e;
-        attr_done[dev & 63] = true;
-    }
     if (p.proj) hipLaunchKernelGGL((block_x3<true, true>), dim3(grid), dim3(256), kBlockX3LdsBytes, s, p);
     // identity blocks: the full next-tile buffer is the default since round 4 (its inner x is requested a whole tile ahead; with the
     // constants of phase C single-buffered it fits 256 + 248 registers without scratch: 1.23 -> 1.18 ms per 140 patches); conv variant

@@ -1,6 +1,6 @@
 // bottleneck.hip -- a whole stage-2 ResNet bottleneck block per launch in the 16-bit modes: bottleneck_fused and its two-group form
 // bottleneck_fused_pq.  (The split mode's block is block_x3.hip.)
-#include "device_prims.h"
+#include "tile_walk.h"
 
 namespace sbbseg {
 
@@ -54,11 +54,9 @@ __global__ __launch_bounds__(256, 1) void bottleneck_fused(const BlockParams p)
     const int tiles_x = (p.W + 15) / 16, tiles_y = (p.H + 7) / 8;
     const int tiles_per_patch = tiles_x * tiles_y;
     const int n_tiles = p.n * tiles_per_patch;
-    // XCD-contiguous walk: XCD x = block % 8 owns tiles [x * per_xcd, (x + 1) * per_xcd)
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, GX = gridDim.x >> 3;
-    const int per_xcd = (n_tiles + 7) >> 3;
-    const int xcd_lo = xcd * per_xcd, xcd_hi = min(n_tiles, xcd_lo + per_xcd);
-    const int my_tiles = xcd_lo + slot < xcd_hi ? (xcd_hi - xcd_lo - slot + GX - 1) / GX : 0;
+    // XCD-contiguous walk (tile_walk.h): XCD x = block % 8 owns a contiguous eighth of the tiles
+    const XcdWalk walk = xcd_walk(n_tiles, blockIdx, gridDim);
+    const int my_tiles = walk.my_tiles;
     if (my_tiles <= 0) return;
 
     // ---- one-time: weights and constants to LDS, this wave's 3x3 fragments to registers
@@ -114,7 +112,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_fused(const BlockParams p)
             for (int kk = 0; kk < KA; ++kk) dst[j][kk] = *(const bf16x8_t*)(p.x + off[j] + kk * 64);
     };
 
-    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return xcd_lo + slot + it * GX; };
+    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return walk.tile_at(it); };
     locate(tile_at(0), inimg, xoff);
     fetch(xoff, xcur);
     __syncthreads();                                            // weights / constants visible
@@ -308,12 +306,10 @@ __global__ __launch_bounds__(512, 1) void bottleneck_fused_pq(const BlockParams 
     const int tiles_x = (p.W + 15) / 16, tiles_y = (p.H + 7) / 8;
     const int tiles_per_patch = tiles_x * tiles_y;
     const int n_tiles = p.n * tiles_per_patch;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, GX = gridDim.x >> 3;
-    const int per_xcd = (n_tiles + 7) >> 3;
-    const int xcd_lo = xcd * per_xcd, xcd_hi = min(n_tiles, xcd_lo + per_xcd);
-    const int my_tiles = xcd_lo + slot < xcd_hi ? (xcd_hi - xcd_lo - slot + GX - 1) / GX : 0;
+    const XcdWalk walk = xcd_walk(n_tiles, blockIdx, gridDim);
+    const int my_tiles = walk.my_tiles;
     if (my_tiles <= 0) return;
-    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return xcd_lo + slot + it * GX; };
+    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return walk.tile_at(it); };
 
     for (int i = tid; i < KA * 4 * 64; i += 512) ((uint4*)lds_w1)[i] = ((const uint4*)p.w1)[i];
     for (int i = tid; i < KC * 16 * 64; i += 512) ((uint4*)lds_w3)[i] = ((const uint4*)p.w3)[i];
@@ -553,35 +549,22 @@ __global__ __launch_bounds__(512, 1) void bottleneck_fused_pq(const BlockParams 
 hipError_t launch_bottleneck(const BlockParams& p, int precision, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     const int n_tiles = p.n * ((p.H + 7) / 8) * ((p.W + 15) / 16);
-    int grid = n_tiles < num_cus ? n_tiles : num_cus;
-    grid = (grid + 7) & ~7;                                     // the XCD-contiguous walk needs a multiple of 8 blocks
+    const int grid = xcd_grid(n_tiles, num_cus);
     launch_rec(rec, p.pq ? SBBSEG_LAUNCH_BOTTLENECK_PQ : SBBSEG_LAUNCH_BOTTLENECK, 8 * 16, 256, 1, n_tiles, grid, 1, 0, !p.proj);
     auto go = [&](auto kernel, int lds) -> hipError_t {
         static bool attr_done[4][64] = {};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
         const int slot = (precision == kF16 ? 0 : 1) + (p.proj ? 2 : 0);
-        if (!attr_done[slot][dev & 63]) {
-            e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return e;
-            attr_done[slot][dev & 63] = true;
-        }
+        const hipError_t e = dynamic_lds_once((const void*)kernel, lds, attr_done[slot]);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, s, p);
         return hipGetLastError();
     };
     if (p.pq) {
         auto go8 = [&](auto kernel, int lds) -> hipError_t {
             static bool attr_done8[4][64] = {};
-            int dev = 0;
-            hipError_t e = hipGetDevice(&dev);
-            if (e != hipSuccess) return e;
             const int slot = (precision == kF16 ? 0 : 1) + (p.proj ? 2 : 0);
-            if (!attr_done8[slot][dev & 63]) {
-                e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                if (e != hipSuccess) return e;
-                attr_done8[slot][dev & 63] = true;
-            }
+            const hipError_t e = dynamic_lds_once((const void*)kernel, lds, attr_done8[slot]);
+            if (e != hipSuccess) return e;
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, s, p);
             return hipGetLastError();
         };

@@ -7,10 +7,11 @@
 //
 // As two launches (conv_igemm_mfma for the 3x3, expand_reduce for the pair) b makes a round trip through HBM, the 3x3 is MFMA-bound
 // with the memory system idle and the pair is HBM-bound with the matrix pipe 25 % busy.  Here a block of eight waves owns an 8 x 8
-// pixel tile: the 10 x 10 halo of `a` is copied to LDS (LDS-DMA, in pieces of 256 bytes per pixel, rotated as in dec_halo_*), GEMM 0
+// pixel tile: the 10 x 10 halo of `a` is copied to LDS (LDS-DMA, in pieces of 256 bytes per pixel, rotated as in dec_halo_*: tile_walk.h), GEMM 0
 // contracts it tap by tap into b, which goes from the epilogue registers straight into the LDS image expand_reduce's GEMM 1 reads; the
 // halo of the NEXT tile is fetched while GEMM 1 / GEMM 2 of this one run, and the x / y streams of the pair run under GEMM 0 of the next.
-// From GEMM 1 on this IS expand_reduce (same K-steps, same order, same MFMA triple, same epilogue arithmetic), and GEMM 0 walks the
+// From GEMM 1 on this IS expand_reduce (same K-steps, same order, same MFMA triple, same epilogue arithmetic: the same functions, pair_steps.h,
+// with this kernel's pixel-block offsets), and GEMM 0 walks the
 // K-steps of the conv it replaces in that conv's order (taken from its K-step records) with its epilogue arithmetic: b, y and a' are
 // bit-identical to the three launches (tests/test_gpu_parity.py).  b itself is never written to HBM.
 // Every vector-memory operation of the loop is issued from inline asm and waited for by a hand-counted vmcnt (see dec_halo_x3.hip).
@@ -23,15 +24,14 @@
 // tile and costs nothing measurable (the stores are acknowledged by then).  expand_reduce had the same tile top since round 4.  And the
 // wait is one statement, not an `if (first tile) ... else ...` pair: the `"+v"` ties of two asm statements in two branches make the
 // compiler copy the weight registers in front of one of them -- a copy of registers whose loads are still in flight.
-#include "device_prims.h"
+#include "pair_steps.h"
+#include "tile_walk.h"
 
 namespace sbbseg {
 
 namespace {
 
-constexpr int kHaloPx = 100;                 // 10 x 10
-constexpr int kHaloInstr = 25;               // wave-instructions of 4 pixels x 256 B per piece
-constexpr int kPieceBytes = kHaloInstr * 1024;
+constexpr int kPieceBytes = kHalo10Bytes;    // one 256-byte piece of every pixel of the 10 x 10 halo (tile_walk.h)
 
 }  // namespace
 
@@ -42,23 +42,15 @@ template <int C, bool X3>
 __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p)
 {
     static_assert(C == 128, "stage 3 only (LDS: the split mode's halo + b + y chunk fill it at C = 128)");
-    constexpr int EB = X3 ? 4 : 2;                              // stored bytes per channel
-    constexpr int KCH = X3 ? 32 : 64;                           // channels per K-step
-    constexpr int KS0 = 9 * C / KCH;                            // K-steps of GEMM 0
-    constexpr int KS1 = C / KCH;                                // K-steps of GEMM 1
-    constexpr int G2S = 256 / KCH;                              // K-steps of GEMM 2 per chunk
-    constexpr int NCH = C / 64;                                 // 256-channel chunks of y
-    constexpr int MI2 = C / 128;                                // row blocks of b / a' per wave
-    constexpr int LG2 = 2 * MI2;                                // weight loads per K-step of GEMM 0 / GEMM 2
-    constexpr int PB = C * EB, PY = 4 * C * EB, PA = C * EB;    // bytes per stored pixel: a / b, y / x, a'
+    using S = PairShape<C, X3>;                                 // the pair's shape (pair_steps.h), under the names the schedule below uses
+    constexpr int EB = S::EB, KS1 = S::KS1, G2S = S::G2S, NCH = S::NCH, MI2 = S::MI2, LG2 = S::LG2, PB = S::PB, PY = S::PY, PA = S::PA, YROW = S::YROW;
+    constexpr int SLB = S::SLB, SLY = S::SLY, kEpi1 = S::kEpi1;
+    constexpr int KS0 = 9 * C / S::KCH;                         // K-steps of GEMM 0 (LG2 weight loads each, as GEMM 2)
     constexpr int NP = PB / 256;                                // 256-byte pieces of a halo pixel
-    constexpr int YROW = 256 * EB;
-    constexpr int SLB = PB / 16, SLY = YROW / 16;
     constexpr int kHaloBytes = NP * kPieceBytes, kBBytes = 64 * PB, kYBytes = 64 * YROW;
     constexpr int PER = KS1 + G2S;                              // K-steps of one chunk
     constexpr int STEPS = KS0 + NCH * PER;                      // K-steps per tile, all three GEMMs (even)
-    constexpr int kEpi1 = X3 ? 16 : 8, kEpi2 = X3 ? 8 : 4;      // vector-memory operations of the epilogues: y stores + x loads; a' stores
-    constexpr int kDma = 4 * NP;                                // halo DMA instructions per wave and tile
+    constexpr int kDma = kHalo10PerWave * NP;                   // halo DMA instructions per wave and tile
     static_assert(STEPS % 2 == 0 && KS0 % 2 == 0, "the weight ring alternates two register sets");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const lds_a = smem;                                   // NP pieces of [100 px][256 B]
@@ -74,13 +66,9 @@ __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p
     const int tiles_x = p.W >> 3, tiles_y = p.H >> 3;
     const int tpp = tiles_x * tiles_y;
     const int n_tiles = p.n * tpp;
-    // XCD-contiguous walk: neighbouring tiles share halo lines in one L2
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, GX = gridDim.x >> 3;
-    const int per_xcd = (n_tiles + 7) >> 3;
-    const int xcd_lo = xcd * per_xcd, xcd_hi = min(n_tiles, xcd_lo + per_xcd);
-    const int my_tiles = xcd_lo + slot < xcd_hi ? (xcd_hi - xcd_lo - slot + GX - 1) / GX : 0;
+    const XcdWalk walk = xcd_walk(n_tiles, blockIdx, gridDim);      // (neighbouring tiles share halo lines in one L2)
+    const int my_tiles = walk.my_tiles;
     if (my_tiles <= 0) return;
-    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return xcd_lo + slot + (it < my_tiles ? it : my_tiles - 1) * GX; };
     // tile -> patch, first pixel row / column
     auto tile_coords = [&](int tile, int& n, int& y0, int& x0) __attribute__((always_inline)) {
         n = tile / tpp;
@@ -96,25 +84,19 @@ __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p
         cst[10 * C + i] = p.s2[i] * p.wmul2; cst[11 * C + i] = p.h2[i];
     }
 
-    // ---- halo DMA: instruction k of a piece fills halo pixels 4 k .. 4 k + 3 (256 B each); lane l writes slot l & 15 of pixel 4 k + (l >> 4),
-    // i.e. fetches granule (slot - 2 hx) & 15 of the piece.  Wave w issues k = w, w + 8, w + 16, w + 24 (past 24: k - 25 again, same bytes to
-    // the same place): every wave issues 4 loads per piece
-    int halo_e[4];                                              // hy | hx << 8 | source granule << 16 | instruction << 24
+    // ---- halo DMA (tile_walk.h: halo10_*): NP pieces, kHalo10PerWave loads per wave each
+    int halo_e[kHalo10PerWave];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        int k = wave + 8 * m;
-        k = k < kHaloInstr ? k : k - kHaloInstr;
-        const int hp = 4 * k + (lane >> 4);
-        const int hy = hp / 10, hx = hp - hy * 10;
-        halo_e[m] = hy | (hx << 8) | ((((lane & 15) - 2 * hx) & 15) << 16) | (k << 24);
-    }
+    for (int m = 0; m < kHalo10PerWave; ++m) halo_e[m] = halo10_desc(wave, lane, m);
     auto issue_halo = [&](int tile) __attribute__((always_inline)) {
         int n, y0, x0;
         tile_coords(tile, n, y0, x0);
+        // (halo10_issue's loop, written out: through the shared function one addition of the prologue's burst comes out with its operands
+        //  swapped -- profiles/kernel_share.md)
 #pragma unroll
         for (int pc = 0; pc < NP; ++pc)
 #pragma unroll
-            for (int m = 0; m < 4; ++m) {
+            for (int m = 0; m < kHalo10PerWave; ++m) {
                 const int e = halo_e[m];
                 const int Y = y0 - 1 + (e & 255), X = x0 - 1 + ((e >> 8) & 255);
                 const bool ok = (unsigned)Y < (unsigned)p.H && (unsigned)X < (unsigned)p.W;
@@ -161,27 +143,16 @@ __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p
             else wload2(d[0], d[1], wlane + (uint32_t)(u * 8 * 2048), w2rsrc);
             return;
         }
-        const int v = u - KS0, j = v / PER, r = v % PER;
-        if (r < KS1) wload4(d[0], d[1], d[2], d[3], wlane + (uint32_t)((j * KS1 + r) * 8 * 4096), w3rsrc);
-        else if constexpr (MI2 == 2) wload4(d[0], d[1], d[2], d[3], wlane + (uint32_t)((j * G2S + r - KS1) * 8 * 4096), w1rsrc);
-        else wload2(d[0], d[1], wlane + (uint32_t)((j * G2S + r - KS1) * 8 * 2048), w1rsrc);
+        const int v = u - KS0;
+        pair_issue_w<S>(v / PER, v % PER, d, wlane, 1u, w3rsrc, w1rsrc);
     };
-    auto issue_x = [&](uint32_t pix0, int j) __attribute__((always_inline)) {             // 8 loads (plain mode: 4)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            const uint32_t off = xlane + pix0 * (uint32_t)PY + (uint32_t)ni * ni_y + (uint32_t)(j * YROW);
-            if constexpr (X3) xload2(xh[ni], xl[ni], off, xrsrc);
-            else asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=&v"(xh[ni]) : "v"(off), "s"(xrsrc) : "memory");
-        }
+    auto issue_x = [&](uint32_t pix0, int j) __attribute__((always_inline)) {             // kEpi1 / 2 loads
+        pair_issue_x<X3>(xh, xl, xrsrc, [&](int ni) __attribute__((always_inline)) -> uint32_t {
+            return xlane + pix0 * (uint32_t)PY + (uint32_t)ni * ni_y + (uint32_t)(j * YROW);
+        });
     };
     auto load_frags = [&](const char* base, int row_bytes, int slots, int k, h8_t (&dh)[4], h8_t (&dl)[4]) __attribute__((always_inline)) {
-        const int sh = (rot + 8 * k) & (slots - 1), sl = (rot + 8 * k + 4) & (slots - 1);
-        const char* a = base + frv * row_bytes;
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            dh[ni] = *(const h8_t*)(a + ni * 16 * row_bytes + (sh << 4));
-            dl[ni] = *(const h8_t*)(a + ni * 16 * row_bytes + (sl << 4));
-        }
+        pair_load_frags(base, row_bytes, slots, k, rot, frv, dh, dl);
     };
     // GEMM 0, K-step t: tap (dy, dx) of channel group cg: piece cg >> 1, granules 8 (cg & 1) + fg (first fragment) and + 4 (second) of halo pixel
     // (2 ni + i0 + dy + 1, j0 + dx + 1); slot = (granule + 2 hx) & 15
@@ -200,9 +171,9 @@ __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p
 
     // ---- prologue: the first tile's halo and its first chunk of x
     int cn, cy0, cx0;
-    tile_coords(tile_at(0), cn, cy0, cx0);
+    tile_coords(walk.tile_at_clamped(0), cn, cy0, cx0);
     uint32_t pix0 = (uint32_t)((cn * p.H + cy0) * p.W + cx0);
-    issue_halo(tile_at(0));
+    issue_halo(walk.tile_at_clamped(0));
     issue_x(pix0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
@@ -216,7 +187,7 @@ __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p
 
     for (int it = 0; it < my_tiles; ++it) {
         int nn, ny0, nx0;
-        tile_coords(tile_at(it + 1), nn, ny0, nx0);
+        tile_coords(walk.tile_at_clamped(it + 1), nn, ny0, nx0);
         const uint32_t pix_next = (uint32_t)((nn * p.H + ny0) * p.W + nx0);
         asm volatile("" : "+v"(rot), "+v"(xlane), "+v"(alane), "+v"(wlane), "+v"(frv), "+v"(fgv), "+v"(a0), "+v"(r0));
 #pragma unroll
@@ -270,51 +241,13 @@ __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p
             if constexpr (g1) {
                 const h8_t ah[2] = {__builtin_bit_cast(h8_t, cw[0]), __builtin_bit_cast(h8_t, cw[2])};       // (plain mode: k-half 0)
                 const h8_t al[2] = {__builtin_bit_cast(h8_t, cw[1]), __builtin_bit_cast(h8_t, cw[3])};       // (             k-half 1)
-                if constexpr (X3) {
-#pragma unroll
-                    for (int m = 0; m < 2; ++m)
-#pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) acc1[m][ni] = mma(al[m], ph[ni], acc1[m][ni]);
-#pragma unroll
-                    for (int m = 0; m < 2; ++m)
-#pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) acc1[m][ni] = mma(ah[m], pl[ni], acc1[m][ni]);
-                }
-#pragma unroll
-                for (int m = 0; m < 2; ++m)
-#pragma unroll
-                    for (int ni = 0; ni < 4; ++ni) acc1[m][ni] = mma(ah[m], ph[ni], acc1[m][ni]);
-                if constexpr (!X3) {
-#pragma unroll
-                    for (int m = 0; m < 2; ++m)
-#pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) acc1[m][ni] = mma(al[m], pl[ni], acc1[m][ni]);
-                }
+                mma_step<X3, 2>(acc1, ah, al, ph, pl);
             } else {
                 // GEMM 0 and GEMM 2: C / 8 output channels x 64 pixels per wave
                 h8_t ah[MI2], al[MI2];
 #pragma unroll
                 for (int m = 0; m < MI2; ++m) { ah[m] = __builtin_bit_cast(h8_t, cw[2 * m]); al[m] = __builtin_bit_cast(h8_t, cw[2 * m + 1]); }
-                if constexpr (X3) {
-#pragma unroll
-                    for (int m = 0; m < MI2; ++m)
-#pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) acc2[m][ni] = mma(al[m], ph[ni], acc2[m][ni]);
-#pragma unroll
-                    for (int m = 0; m < MI2; ++m)
-#pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) acc2[m][ni] = mma(ah[m], pl[ni], acc2[m][ni]);
-                }
-#pragma unroll
-                for (int m = 0; m < MI2; ++m)
-#pragma unroll
-                    for (int ni = 0; ni < 4; ++ni) acc2[m][ni] = mma(ah[m], ph[ni], acc2[m][ni]);
-                if constexpr (!X3) {
-#pragma unroll
-                    for (int m = 0; m < MI2; ++m)
-#pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) acc2[m][ni] = mma(al[m], pl[ni], acc2[m][ni]);
-                }
+                mma_step<X3, MI2>(acc2, ah, al, ph, pl);
             }
             // this set's weights are spent: step u + 2 (of the next tile behind the last two; always issued: the counts stay constant)
             issue_w((u + 2) % STEPS, cw);
@@ -323,7 +256,7 @@ __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p
             if constexpr (g0 && k == KS0 - 1) {
                 // ---- epilogue 0: b = ReLU(s2 * acc + h2) -> the LDS image GEMM 1 reads (granule G of pixel p at slot (G + 2 (p & 15)) mod SLB).
                 // No vector-memory operation here: the hand-counted queue is untouched
-                const int c0 = MI2 == 2 ? wave * 32 + fgv * 8 : (wave >> 1) * 32 + fgv * 8 + (wave & 1) * 4;
+                const int c0 = MI2 == 2 ? wave * 32 + fgv * 8 : (wave >> 1) * 32 + fgv * 8 + (wave & 1) * 4;      // (= pair_c0)
                 float sc[4 * MI2], sh[4 * MI2];
                 *(float4*)&sc[0] = *(const float4*)(cst + 10 * C + c0);
                 *(float4*)&sh[0] = *(const float4*)(cst + 11 * C + c0);
@@ -343,25 +276,12 @@ __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p
                     }
                     char* row = lds_b + (ni * 16 + frv) * PB;
                     const int s_hi = ((boff >> 4) + 2 * frv) & (SLB - 1), s_lo = (((boff + 64) >> 4) + 2 * frv) & (SLB - 1);
-                    if constexpr (X3 && MI2 == 2) {
-                        h8_t vh, vl;
-                        split_n<8>(y, vh, vl);
-                        *(h8_t*)(row + (s_hi << 4)) = vh;
-                        *(h8_t*)(row + (s_lo << 4)) = vl;
-                    } else if constexpr (X3) {
-                        h4_t vh, vl;
-                        split_n<4>(y, vh, vl);
-                        *(h4_t*)(row + (s_hi << 4) + (boff & 8)) = vh;
-                        *(h4_t*)(row + (s_lo << 4) + (boff & 8)) = vl;
-                    } else if constexpr (MI2 == 2) {
-                        u4_t vv;
-                        vv[0] = pack_h2(y[0], y[1]); vv[1] = pack_h2(y[2], y[3]); vv[2] = pack_h2(y[4 % (4 * MI2)], y[5 % (4 * MI2)]); vv[3] = pack_h2(y[6 % (4 * MI2)], y[7 % (4 * MI2)]);
-                        *(u4_t*)(row + (s_hi << 4)) = vv;
-                    } else {
-                        u2_t vv;
-                        vv[0] = pack_h2(y[0], y[1]); vv[1] = pack_h2(y[2], y[3]);
-                        *(u2_t*)(row + (s_hi << 4) + (boff & 8)) = vv;
-                    }
+                    // (epilogue 2's packing; to LDS where that stores.  MI2 == 1: 8 bytes, the half of the granule boff points into)
+                    using V = typename PairPack<X3, MI2>::V;
+                    V vh, vl;
+                    PairPack<X3, MI2>::pack(y, vh, vl);
+                    *(V*)(row + (s_hi << 4) + (MI2 == 2 ? 0 : boff & 8)) = vh;
+                    if constexpr (X3) *(V*)(row + (s_lo << 4) + (MI2 == 2 ? 0 : boff & 8)) = vl;
                 }
 #pragma unroll
                 for (int m = 0; m < MI2; ++m)
@@ -370,50 +290,19 @@ __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();                   // b is complete; every wave has taken its last fragment from the halo
                 asm volatile("" ::: "memory");
-                issue_halo(tile_at(it + 1));                    // the next tile's halo lands under GEMM 1 / GEMM 2 (kDma loads per wave)
+                issue_halo(walk.tile_at_clamped(it + 1));                    // the next tile's halo lands under GEMM 1 / GEMM 2 (kDma loads per wave)
             }
             if constexpr (g1 && k == KS1 - 1) {
                 // ---- epilogue 1 (expand_reduce's): y = ReLU(s3 * acc + h3 + x) -> hi | lo: to HBM and into the LDS image of the chunk
-                if constexpr (X3)
-                    asm volatile("s_waitcnt vmcnt(%8)" : "+v"(xh[0]), "+v"(xh[1]), "+v"(xh[2]), "+v"(xh[3]), "+v"(xl[0]), "+v"(xl[1]), "+v"(xl[2]), "+v"(xl[3])
-                                 : "n"(2 * LG2) : "memory");
-                else
-                    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(xh[0]), "+v"(xh[1]), "+v"(xh[2]), "+v"(xh[3]) : "n"(2 * LG2) : "memory");
+                pair_wait_x<X3, 2 * LG2>(xh, xl);
                 const int c0 = j * 256 + wave * 32 + fgv * 8;
-                float sc[8], sh[8];
+                float sc[8], sh[8];                             // (loaded here, where `cst` is a constant address: profiles/kernel_share.md)
                 *(float4*)&sc[0] = *(const float4*)(cst + c0); *(float4*)&sc[4] = *(const float4*)(cst + c0 + 4);
                 *(float4*)&sh[0] = *(const float4*)(cst + 4 * C + c0); *(float4*)&sh[4] = *(const float4*)(cst + 4 * C + c0 + 4);
-                const int s_hi = (wave * (X3 ? 8 : 4) + rot) & (SLY - 1), s_lo = (wave * 8 + 4 + rot) & (SLY - 1);
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) {
-                    float y[8];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        y[q] = __builtin_fmaf(acc1[0][ni][q], sc[q], sh[q]);
-                        y[4 + q] = __builtin_fmaf(acc1[1][ni][q], sc[4 + q], sh[4 + q]);
-                    }
-                    const uint32_t off = xlane + pix0 * (uint32_t)PY + (uint32_t)ni * ni_y + (uint32_t)(j * YROW);
-                    char* row = lds_y + (ni * 16 + frv) * YROW;
-                    if constexpr (X3) {
-                        const h8_t rh = __builtin_bit_cast(h8_t, xh[ni]), rl = __builtin_bit_cast(h8_t, xl[ni]);
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) y[q] = fmaxf(__fadd_rn(y[q], __fadd_rn((float)rh[q], (float)rl[q])), 0.f);
-                        h8_t vh, vl;
-                        split_n<8>(y, vh, vl);
-                        asm volatile("buffer_store_dwordx4 %1, %0, %3, 0 offen\n\tbuffer_store_dwordx4 %2, %0, %3, 0 offen offset:64\n\ts_nop 1"
-                                     :: "v"(off), "v"(vh), "v"(vl), "s"(yrsrc) : "memory");
-                        *(h8_t*)(row + (s_hi << 4)) = vh;
-                        *(h8_t*)(row + (s_lo << 4)) = vl;
-                    } else {
-                        const h8_t rr = __builtin_bit_cast(h8_t, xh[ni]);
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) y[q] = fmaxf(__fadd_rn(y[q], (float)rr[q]), 0.f);
-                        u4_t vv;
-                        vv[0] = pack_h2(y[0], y[1]); vv[1] = pack_h2(y[2], y[3]); vv[2] = pack_h2(y[4], y[5]); vv[3] = pack_h2(y[6], y[7]);
-                        asm volatile("buffer_store_dwordx4 %1, %0, %2, 0 offen\n\ts_nop 1" :: "v"(off), "v"(vv), "s"(yrsrc) : "memory");
-                        *(u4_t*)(row + (s_hi << 4)) = vv;
-                    }
-                }
+                pair_epilogue1<S, X3>(
+                    acc1, xh, xl, sc, sh, wave, rot, yrsrc,
+                    [&](int ni) __attribute__((always_inline)) -> uint32_t { return xlane + pix0 * (uint32_t)PY + (uint32_t)ni * ni_y + (uint32_t)(j * YROW); },
+                    [&](int ni) __attribute__((always_inline)) -> char* { return lds_y + (ni * 16 + frv) * YROW; });
                 // the residual of the chunk after this one (the next tile's first behind the last)
                 if constexpr (j + 1 < NCH) issue_x(pix0, j + 1);
                 else issue_x(pix_next, 0);
@@ -430,16 +319,10 @@ __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p
 
         // ---- epilogue 2: a' = ReLU(s1 * acc + h1) -> hi | lo.  EXACTLY kEpi2 stores per wave.
         {
-            const int c0 = MI2 == 2 ? wave * 32 + fgv * 8 : (wave >> 1) * 32 + fgv * 8 + (wave & 1) * 4;
             float sc[4 * MI2], sh[4 * MI2];
-            *(float4*)&sc[0] = *(const float4*)(cst + 8 * C + c0);
-            *(float4*)&sh[0] = *(const float4*)(cst + 9 * C + c0);
-            if constexpr (MI2 == 2) {
-                *(float4*)&sc[4] = *(const float4*)(cst + 8 * C + c0 + 4);
-                *(float4*)&sh[4] = *(const float4*)(cst + 9 * C + c0 + 4);
-            }
+            pair_bn_consts<MI2>(cst + 8 * C, cst + 9 * C, pair_c0<MI2>(wave, fgv), sc, sh);
 #pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
+            for (int ni = 0; ni < S::kNI; ++ni) {
                 const uint32_t off = alane + pix0 * (uint32_t)PA + (uint32_t)ni * ni_a;
                 float y[4 * MI2];
 #pragma unroll
@@ -447,25 +330,7 @@ __global__ __launch_bounds__(512, 2) void conv3_expand_reduce(const C3ERParams p
                     y[q] = fmaxf(__builtin_fmaf(acc2[0][ni][q], sc[q], sh[q]), 0.f);
                     if constexpr (MI2 == 2) y[4 + q] = fmaxf(__builtin_fmaf(acc2[MI2 - 1][ni][q], sc[4 * (MI2 - 1) + q], sh[4 * (MI2 - 1) + q]), 0.f);
                 }
-                if constexpr (X3 && MI2 == 2) {
-                    h8_t vh, vl;
-                    split_n<8>(y, vh, vl);
-                    asm volatile("buffer_store_dwordx4 %1, %0, %3, 0 offen\n\tbuffer_store_dwordx4 %2, %0, %3, 0 offen offset:64\n\ts_nop 1"
-                                 :: "v"(off), "v"(vh), "v"(vl), "s"(arsrc) : "memory");
-                } else if constexpr (X3) {
-                    h4_t vh, vl;
-                    split_n<4>(y, vh, vl);
-                    asm volatile("buffer_store_dwordx2 %1, %0, %3, 0 offen\n\tbuffer_store_dwordx2 %2, %0, %3, 0 offen offset:64\n\ts_nop 1"
-                                 :: "v"(off), "v"(vh), "v"(vl), "s"(arsrc) : "memory");
-                } else if constexpr (MI2 == 2) {
-                    u4_t vv;
-                    vv[0] = pack_h2(y[0], y[1]); vv[1] = pack_h2(y[2], y[3]); vv[2] = pack_h2(y[4 % (4 * MI2)], y[5 % (4 * MI2)]); vv[3] = pack_h2(y[6 % (4 * MI2)], y[7 % (4 * MI2)]);
-                    asm volatile("buffer_store_dwordx4 %1, %0, %2, 0 offen\n\ts_nop 1" :: "v"(off), "v"(vv), "s"(arsrc) : "memory");
-                } else {
-                    u2_t vv;
-                    vv[0] = pack_h2(y[0], y[1]); vv[1] = pack_h2(y[2], y[3]);
-                    asm volatile("buffer_store_dwordx2 %1, %0, %2, 0 offen\n\ts_nop 1" :: "v"(off), "v"(vv), "s"(arsrc) : "memory");
-                }
+                pair_pack_store<X3, MI2>(y, off, arsrc);
             }
         }
         pix0 = pix_next;
@@ -479,17 +344,11 @@ template <int C, bool X3> static hipError_t launch_one(const C3ERParams& p, int 
     constexpr int lds = (C * EB / 256) * kPieceBytes + 64 * C * EB + 64 * 256 * EB + 12 * C * 4;
     static_assert(lds <= 160 * 1024, "conv3_expand_reduce: LDS");
     static bool attr_done[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = dynamic_lds_once((const void*)conv3_expand_reduce<C, X3>, lds, attr_done);
     if (e != hipSuccess) return e;
-    if (!attr_done[dev & 63]) {
-        e = hipFuncSetAttribute((const void*)conv3_expand_reduce<C, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_done[dev & 63] = true;
-    }
     const int n_tiles = p.n * (p.H / 8) * (p.W / 8);
     if (n_tiles <= 0) return hipSuccess;
-    const int grid = ((n_tiles < num_cus ? n_tiles : num_cus) + 7) & ~7;
+    const int grid = xcd_grid(n_tiles, num_cus);
     launch_rec(rec, SBBSEG_LAUNCH_CONV3_EXPAND_REDUCE, 8 * 8, 4 * C, 1, n_tiles, grid, 1, 0, 1);
     hipLaunchKernelGGL((conv3_expand_reduce<C, X3>), dim3(grid), dim3(512), lds, s, p);
     return hipGetLastError();

@@ -16,18 +16,18 @@
 //     granule G of a pixel at slot (G + (hx & ~1)) & 7 of its half: 16 distinct slots per group.  src0 rows are 256 B with the
 //     split kernel's rotation (G + 2 hx) & 15
 //   * every vector-memory operation of the loop is issued from inline asm and counted by hand, as in the split kernel
-#include "device_prims.h"
+#include "tile_walk.h"
 
 namespace sbbseg {
 
 namespace {
 
-constexpr int kS0Instr = 25, kSkInstr = 45;             // wave-instructions (1 KB) per halo: 100 pixels x 256 B; 10 pair rows x 18 x 256 B
-constexpr int kS0Bytes = kS0Instr * 1024;
+constexpr int kSkInstr = 45;                            // wave-instructions (1 KB) of the skip halo: 10 pair rows x 18 x 256 B (src0: tile_walk.h, 100 pixels x 256 B)
+constexpr int kS0Bytes = kHalo10Bytes;
 constexpr int kSkBytes = kSkInstr * 1024;
 constexpr int kDecHaloF16LdsBytes = 2 * kS0Bytes + 2 * kSkBytes;      // 143 360
 constexpr int kSteps = 17;
-constexpr int kS0PerWave = 4, kSkPerWave = 6;           // DMA instructions per wave per tile (32 >= 25, 48 >= 45: the surplus repeats)
+constexpr int kS0PerWave = kHalo10PerWave, kSkPerWave = 6;     // DMA instructions per wave per tile (32 >= 25, 48 >= 45: the surplus repeats)
 constexpr int kDma = kS0PerWave + kSkPerWave;
 constexpr int kStores = 4;
 
@@ -48,28 +48,20 @@ __global__ __launch_bounds__(512, 2) void dec_halo_f16(const DecHaloParams p)
     const int H = 2 * p.PH, W = 2 * p.PW;
     const int tiles_x = W / 16, tiles_y = H / 16;
     const int tiles_per_patch = tiles_x * tiles_y;
-    // owned-region launch (DecHaloParams::ttab, region.h): the tiles are the table's entries, see dec_halo_x3
+    // owned-region launch (DecHaloParams::ttab, region.h): the tiles are the table's entries, see tile_walk.h (dec_tile_coords)
     const int n_tiles = p.ttab ? p.n_tab : p.n * tiles_per_patch;
     const __attribute__((address_space(4))) uint32_t* ttab = (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)p.ttab;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, GX = gridDim.x >> 3;
-    const int per_xcd = (n_tiles + 7) >> 3;
-    const int xcd_lo = xcd * per_xcd, xcd_hi = min(n_tiles, xcd_lo + per_xcd);
-    const int my_tiles = xcd_lo + slot < xcd_hi ? (xcd_hi - xcd_lo - slot + GX - 1) / GX : 0;
+    const XcdWalk walk = xcd_walk(n_tiles, blockIdx, gridDim);
+    const int my_tiles = walk.my_tiles;
     if (my_tiles <= 0) return;
-    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return xcd_lo + slot + (it < my_tiles ? it : my_tiles - 1) * GX; };
+    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return walk.tile_at_clamped(it); };
 
-    // ---- halo DMA.  src0 instruction k: halo pixels 4 k .. 4 k + 3, lane l -> slot l & 15 of pixel 4 k + (l >> 4).  skip instruction k:
+    // ---- halo DMA.  src0: the 10 x 10 halo of tile_walk.h (halo10_*).  skip instruction k:
     // pair rows 4 k .. 4 k + 3 (row r = pair * 18 + hx), lane l -> half (l >> 3) & 1, slot l & 7 of row 4 k + (l >> 4); pair P holds halo
     // rows hy = 4 (P >> 1) + (P & 1) [half 0] and hy + 2 [half 1]
     int s0_e[kS0PerWave], sk_e[kSkPerWave];                    // hy | hx << 8 | source granule << 16 | instruction << 24
 #pragma unroll
-    for (int m = 0; m < kS0PerWave; ++m) {
-        int k = wave + 8 * m;
-        k = k < kS0Instr ? k : k - kS0Instr;
-        const int hp = 4 * k + (lane >> 4);
-        const int hy = hp / 10, hx = hp - hy * 10;
-        s0_e[m] = hy | (hx << 8) | ((((lane & 15) - 2 * hx) & 15) << 16) | (k << 24);
-    }
+    for (int m = 0; m < kS0PerWave; ++m) s0_e[m] = halo10_desc(wave, lane, m);
 #pragma unroll
     for (int m = 0; m < kSkPerWave; ++m) {
         int k = wave + 8 * m;
@@ -80,29 +72,12 @@ __global__ __launch_bounds__(512, 2) void dec_halo_f16(const DecHaloParams p)
         sk_e[m] = hy | (hx << 8) | ((((lane & 7) - (hx & ~1)) & 7) << 16) | (k << 24);
     }
     auto tile_coords = [&](int tile, int& n, int& y0, int& x0) __attribute__((always_inline)) {      // patch, origin of the 16 x 16 outputs
-        if (ttab) {
-            const uint32_t code = ttab[tile];
-            n = (int)(code >> 22); y0 = (int)((code >> 11) & 2047u) * 2; x0 = (int)(code & 2047u) * 2;
-        } else {
-            n = tile / tiles_per_patch;
-            const int rem = tile - n * tiles_per_patch;
-            const int ty = rem / tiles_x;
-            y0 = ty * 16;
-            x0 = (rem - ty * tiles_x) * 16;
-        }
+        dec_tile_coords(ttab, tile, tiles_per_patch, tiles_x, n, y0, x0);
     };
     auto issue_halos = [&](int tile, int buf) __attribute__((always_inline)) {            // kDma loads per wave
         int n, y0, x0;
         tile_coords(tile, n, y0, x0);
-#pragma unroll
-        for (int m = 0; m < kS0PerWave; ++m) {
-            const int e = s0_e[m];
-            const int Y = (y0 >> 1) - 1 + (e & 255), X = (x0 >> 1) - 1 + ((e >> 8) & 255);
-            const bool ok = (unsigned)Y < (unsigned)p.PH && (unsigned)X < (unsigned)p.PW;
-            const uint32_t off = ok ? (uint32_t)((n * p.PH + Y) * p.PW + X) * 256u + (uint32_t)(((e >> 16) & 15) * 16 + kZeroHeaderBytes) : 0u;
-            const uint32_t dst = lds0 + (uint32_t)(buf * kS0Bytes) + (uint32_t)__builtin_amdgcn_readfirstlane(e >> 24) * 1024u;
-            glds16_hidden(p.src0 + off, dst);
-        }
+        halo10_issue(s0_e, &p.src0, n, (y0 >> 1) - 1, (x0 >> 1) - 1, &p.PH, &p.PW, 256u, 0, lds0 + (uint32_t)(buf * kS0Bytes));
 #pragma unroll
         for (int m = 0; m < kSkPerWave; ++m) {
             const int e = sk_e[m];
@@ -223,18 +198,11 @@ __global__ __launch_bounds__(512, 2) void dec_halo_f16(const DecHaloParams p)
             } else {
                 wait4<4>(cw[0], cw[1], cw[2], cw[3]);
             }
-            const h8_t a[2][2] = {{__builtin_bit_cast(h8_t, cw[0]), __builtin_bit_cast(h8_t, cw[1])},
-                                  {__builtin_bit_cast(h8_t, cw[2]), __builtin_bit_cast(h8_t, cw[3])}};
+            const h8_t a0k[2] = {__builtin_bit_cast(h8_t, cw[0]), __builtin_bit_cast(h8_t, cw[2])};      // k-half 0 of the two row blocks
+            const h8_t a1k[2] = {__builtin_bit_cast(h8_t, cw[1]), __builtin_bit_cast(h8_t, cw[3])};      // k-half 1
             const h8_t (&x0)[4] = b0[s & 1];
             const h8_t (&x1f)[4] = b1[s & 1];
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[m][ni] = mma(a[m][0], x0[ni], acc[m][ni]);
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[m][ni] = mma(a[m][1], x1f[ni], acc[m][ni]);
+            mma_step<false, 2>(acc, a0k, a1k, x0, x1f);
             // this set's weights are spent: step t + 2 (of the next tile behind the last two; always issued: the counts stay constant)
             wload4(cw[0], cw[1], cw[2], cw[3], wlane + (uint32_t)(((t + 2) % kSteps) * 8192), wrsrc);
             if constexpr (t == 7) {
@@ -276,17 +244,11 @@ __global__ __launch_bounds__(512, 2) void dec_halo_f16(const DecHaloParams p)
 hipError_t launch_dec_halo_f16(const DecHaloParams& p, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     static bool attr_done[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = dynamic_lds_once((const void*)dec_halo_f16, kDecHaloF16LdsBytes, attr_done);
     if (e != hipSuccess) return e;
-    if (!attr_done[dev & 63]) {
-        e = hipFuncSetAttribute((const void*)dec_halo_f16, hipFuncAttributeMaxDynamicSharedMemorySize, kDecHaloF16LdsBytes);
-        if (e != hipSuccess) return e;
-        attr_done[dev & 63] = true;
-    }
     const int n_tiles = p.ttab ? p.n_tab : p.n * (p.PH / 8) * (p.PW / 8);
     if (n_tiles <= 0) return hipSuccess;
-    const int grid = ((n_tiles < num_cus ? n_tiles : num_cus) + 7) & ~7;
+    const int grid = xcd_grid(n_tiles, num_cus);
     launch_rec(rec, SBBSEG_LAUNCH_DEC_HALO, 16 * 16, 64, 1, n_tiles, grid, 1, p.ttab != nullptr);
     hipLaunchKernelGGL(dec_halo_f16, dim3(grid), dim3(512), kDecHaloF16LdsBytes, s, p);
     return hipGetLastError();

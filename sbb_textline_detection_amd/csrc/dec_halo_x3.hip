@@ -25,18 +25,20 @@
 //     wave, duplicates where 25 / 81 do not divide; the last tile re-issues its own halo), so the counts are constants
 //   * pixel rows are 256 B (16 granule slots); granule G of halo pixel (hy, hx) sits at slot (G + 2 hx) & 15 (src0) / (G + hx) & 15
 //     (skip, whose fragments take every second pixel): conflict-free for the 16-lane groups of ds_read_b128
-#include "device_prims.h"
+#include "tile_walk.h"
 
 namespace sbbseg {
 
 namespace {
 
-constexpr int kS0Px = 100, kSkPx = 324;                 // halo pixels: 10 x 10, 18 x 18
-constexpr int kS0Instr = 25, kSkInstr = 81;             // wave-instructions of 4 pixels x 256 B
-constexpr int kS0Bytes = kS0Instr * 1024;               // one src0 piece (two channel groups of every halo pixel)
+constexpr int kSkInstr = 81;                            // wave-instructions of 4 pixels x 256 B: the 18 x 18 skip halo (src0: tile_walk.h, 10 x 10)
+constexpr int kS0Bytes = kHalo10Bytes;                  // one src0 piece (two channel groups of every halo pixel)
 constexpr int kSkBytes = kSkInstr * 1024;
 constexpr int kDecHaloLdsBytes = 2 * kS0Bytes + kSkBytes;      // 134 144
 constexpr int kSteps = 34;                              // 4 groups x 4 taps of src0 + 2 groups x 9 taps of the skip
+constexpr int kS0PerWave = kHalo10PerWave, kSkPerWave = 11;    // DMA instructions per wave: a src0 piece (32 >= 25), the skip halo (88 >= 81: the surplus repeats)
+constexpr int kStores = 8;                              // store instructions of the epilogue per wave
+constexpr int kWLoads = 4;                              // weight loads per wave and K-step
 
 }  // namespace
 
@@ -56,33 +58,24 @@ __global__ __launch_bounds__(512, 2) void dec_halo_x3(const DecHaloParams p)
     const int H = 2 * p.PH, W = 2 * p.PW;
     const int tiles_x = W / 16, tiles_y = H / 16;
     const int tiles_per_patch = tiles_x * tiles_y;
-    // owned-region launch (DecHaloParams::ttab, region.h): the tiles are the table's entries -- (patch, output origin / 2) -- instead of the
-    // 14 x 14 grid of every patch; an origin is any even pixel, tiles of one patch may overlap at its far edge (same values twice)
+    // owned-region launch (DecHaloParams::ttab, region.h): the tiles are the table's entries instead of the 14 x 14 grid of every patch
+    // (tile_walk.h: dec_tile_coords)
     const int n_tiles = p.ttab ? p.n_tab : p.n * tiles_per_patch;
     const __attribute__((address_space(4))) uint32_t* ttab = (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)p.ttab;
-    // XCD-contiguous walk (neighbouring tiles share halo lines in one L2)
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, GX = gridDim.x >> 3;
-    const int per_xcd = (n_tiles + 7) >> 3;
-    const int xcd_lo = xcd * per_xcd, xcd_hi = min(n_tiles, xcd_lo + per_xcd);
-    const int my_tiles = xcd_lo + slot < xcd_hi ? (xcd_hi - xcd_lo - slot + GX - 1) / GX : 0;
+    const XcdWalk walk = xcd_walk(n_tiles, blockIdx, gridDim);      // (neighbouring tiles share halo lines in one L2)
+    const int my_tiles = walk.my_tiles;
     if (my_tiles <= 0) return;
-    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return xcd_lo + slot + (it < my_tiles ? it : my_tiles - 1) * GX; };
+    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return walk.tile_at_clamped(it); };
 
     // ---- halo DMA: tile-invariant part of this lane's pieces.  Instruction k of a piece fills halo pixels 4 k .. 4 k + 3 (256 B each);
     // lane l writes slot l & 15 of pixel 4 k + (l >> 4), i.e. fetches granule (slot - rot(hx)) & 15 of it.  wave w issues k = w, w + 8, ...
-    // -- 4 instructions of a src0 piece, 11 of the skip halo; where 25 / 81 do not divide, the surplus repeats instruction k - 25 /
-    // k - 81 (same bytes to the same place): every wave issues the same number of loads
-    int s0_hyx[4], sk_hyx[11];                                 // hy | hx << 8 | source granule << 16 | instruction << 24
+    // -- kS0PerWave instructions of a src0 piece (tile_walk.h: halo10_*), kSkPerWave of the skip halo; where 25 / 81 do not divide, the surplus
+    // repeats instruction k - 25 / k - 81 (same bytes to the same place): every wave issues the same number of loads
+    int s0_hyx[kS0PerWave], sk_hyx[kSkPerWave];                // hy | hx << 8 | source granule << 16 | instruction << 24
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        int k = wave + 8 * m;
-        k = k < kS0Instr ? k : k - kS0Instr;
-        const int hp = 4 * k + (lane >> 4);
-        const int hy = hp / 10, hx = hp - hy * 10;
-        s0_hyx[m] = hy | (hx << 8) | ((((lane & 15) - 2 * hx) & 15) << 16) | (k << 24);
-    }
+    for (int m = 0; m < kS0PerWave; ++m) s0_hyx[m] = halo10_desc(wave, lane, m);
 #pragma unroll
-    for (int m = 0; m < 11; ++m) {
+    for (int m = 0; m < kSkPerWave; ++m) {
         int k = wave + 8 * m;
         k = k < kSkInstr ? k : k - kSkInstr;
         const int hp = 4 * k + (lane >> 4);
@@ -91,32 +84,15 @@ __global__ __launch_bounds__(512, 2) void dec_halo_x3(const DecHaloParams p)
     }
     // tile -> patch and origin (y0, x0) of its 16 x 16 outputs (wave-uniform: the table entry comes through the scalar cache)
     auto tile_coords = [&](int tile, int& n, int& y0, int& x0) __attribute__((always_inline)) {
-        if (ttab) {
-            const uint32_t code = ttab[tile];
-            n = (int)(code >> 22); y0 = (int)((code >> 11) & 2047u) * 2; x0 = (int)(code & 2047u) * 2;
-        } else {
-            n = tile / tiles_per_patch;
-            const int rem = tile - n * tiles_per_patch;
-            const int ty = rem / tiles_x;
-            y0 = ty * 16;
-            x0 = (rem - ty * tiles_x) * 16;
-        }
+        dec_tile_coords(ttab, tile, tiles_per_patch, tiles_x, n, y0, x0);
     };
-    // src0 piece `pc` (channel groups 2 pc, 2 pc + 1 = bytes 256 pc .. of the 512-byte stored pixel): 4 loads per wave
+    // src0 piece `pc` (channel groups 2 pc, 2 pc + 1 = bytes 256 pc .. of the 512-byte stored pixel): kS0PerWave loads per wave
     auto issue_s0 = [&](int n, int y0, int x0, int pc) __attribute__((always_inline)) {
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const int e = s0_hyx[m];
-            const int Y = (y0 >> 1) - 1 + (e & 255), X = (x0 >> 1) - 1 + ((e >> 8) & 255);
-            const bool ok = (unsigned)Y < (unsigned)p.PH && (unsigned)X < (unsigned)p.PW;
-            const uint32_t off = ok ? (uint32_t)((n * p.PH + Y) * p.PW + X) * 512u + (uint32_t)(pc * 256 + ((e >> 16) & 15) * 16 + kZeroHeaderBytes) : 0u;
-            const uint32_t dst = lds0 + (uint32_t)(pc * kS0Bytes) + (uint32_t)__builtin_amdgcn_readfirstlane(e >> 24) * 1024u;
-            glds16_hidden(p.src0 + off, dst);
-        }
+        halo10_issue(s0_hyx, &p.src0, n, (y0 >> 1) - 1, (x0 >> 1) - 1, &p.PH, &p.PW, 512u, pc * 256, lds0 + (uint32_t)(pc * kS0Bytes));
     };
-    auto issue_sk = [&](int n, int y0, int x0) __attribute__((always_inline)) {        // 11 loads per wave
+    auto issue_sk = [&](int n, int y0, int x0) __attribute__((always_inline)) {        // kSkPerWave loads per wave
 #pragma unroll
-        for (int m = 0; m < 11; ++m) {
+        for (int m = 0; m < kSkPerWave; ++m) {
             const int e = sk_hyx[m];
             const int Y = y0 - 1 + (e & 255), X = x0 - 1 + ((e >> 8) & 255);
             const bool ok = (unsigned)Y < (unsigned)H && (unsigned)X < (unsigned)W;
@@ -226,35 +202,23 @@ __global__ __launch_bounds__(512, 2) void dec_halo_x3(const DecHaloParams p)
             // before this step's MFMAs
             load_b((t + 1) % kSteps, bh[(t + 1) & 1], bl[(t + 1) & 1]);
             // This step's weights (loaded two steps ago) have landed when all but the younger loads of this wave are done.  Younger, in
-            // issue order: a DMA burst at the end of step t - 2, the 4 weight loads of step t - 1, a DMA burst at the end of step t - 1,
-            // and -- behind the burst of step 33 -- the 8 stores of the epilogue.  Bursts: 4 loads after steps 7 and 15, 11 after step 33.
-            // (First tile: the prologue's bursts were drained, nothing but the 4 loads of step t - 1 is younger.)
+            // issue order: a DMA burst at the end of step t - 2, the kWLoads weight loads of step t - 1, a DMA burst at the end of step t - 1,
+            // and -- behind the burst of step 33 -- the kStores stores of the epilogue.  Bursts: kS0PerWave loads after steps 7 and 15,
+            // kSkPerWave after step 33.  (First tile: the prologue's bursts were drained, nothing but the loads of step t - 1 is younger.)
             u4_t (&cw)[4] = w[t & 1];
             if constexpr (t == 0 || t == 1) {
-                if (it == 0) wait4<4>(cw[0], cw[1], cw[2], cw[3]);
-                else wait4<4 + 11 + 8>(cw[0], cw[1], cw[2], cw[3]);
+                if (it == 0) wait4<kWLoads>(cw[0], cw[1], cw[2], cw[3]);
+                else wait4<kWLoads + kSkPerWave + kStores>(cw[0], cw[1], cw[2], cw[3]);
             } else if constexpr (t == 8 || t == 9 || t == 16 || t == 17) {
-                wait4<4 + 4>(cw[0], cw[1], cw[2], cw[3]);
+                wait4<kWLoads + kS0PerWave>(cw[0], cw[1], cw[2], cw[3]);
             } else {
-                wait4<4>(cw[0], cw[1], cw[2], cw[3]);
+                wait4<kWLoads>(cw[0], cw[1], cw[2], cw[3]);
             }
             const h8_t ch[2] = {__builtin_bit_cast(h8_t, cw[0]), __builtin_bit_cast(h8_t, cw[2])};
             const h8_t cl[2] = {__builtin_bit_cast(h8_t, cw[1]), __builtin_bit_cast(h8_t, cw[3])};
             const h8_t (&xh)[4] = bh[t & 1];
             const h8_t (&xl)[4] = bl[t & 1];
-            // three sweeps, small terms first (the order conv_igemm_mfma's split loop uses per accumulator)
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[m][ni] = mma(cl[m], xh[ni], acc[m][ni]);
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[m][ni] = mma(ch[m], xl[ni], acc[m][ni]);
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[m][ni] = mma(ch[m], xh[ni], acc[m][ni]);
+            mma_step<true, 2>(acc, ch, cl, xh, xl);
             // this set's weights are spent: K-step t + 2 (of the next tile behind the last two; always issued: the counts stay constant)
             wload4(cw[0], cw[1], cw[2], cw[3], wlane + (uint32_t)(((t + 2) % kSteps) * 8192), wrsrc);
             // piece boundaries: every wave has taken its last fragment from the piece (the reads of step t + 1 above belong to the NEXT
@@ -271,7 +235,7 @@ __global__ __launch_bounds__(512, 2) void dec_halo_x3(const DecHaloParams p)
         });
 
         // ---- epilogue: y = ReLU(scale * acc + shift) -> hi | lo, 16 bytes each per pixel and 8-channel group (as conv_igemm_mfma's split
-        // path).  EXACTLY 8 store instructions per wave: the wait counts of steps 0 and 1 include them.
+        // path).  EXACTLY kStores store instructions per wave (a pair per pixel block): the wait counts of steps 0 and 1 include them.
         const int n = cn;
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
@@ -300,17 +264,11 @@ __global__ __launch_bounds__(512, 2) void dec_halo_x3(const DecHaloParams p)
 hipError_t launch_dec_halo_x3(const DecHaloParams& p, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     static bool attr_done[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = dynamic_lds_once((const void*)dec_halo_x3, kDecHaloLdsBytes, attr_done);
     if (e != hipSuccess) return e;
-    if (!attr_done[dev & 63]) {
-        e = hipFuncSetAttribute((const void*)dec_halo_x3, hipFuncAttributeMaxDynamicSharedMemorySize, kDecHaloLdsBytes);
-        if (e != hipSuccess) return e;
-        attr_done[dev & 63] = true;
-    }
     const int n_tiles = p.ttab ? p.n_tab : p.n * (p.PH / 8) * (p.PW / 8);
     if (n_tiles <= 0) return hipSuccess;
-    const int grid = ((n_tiles < num_cus ? n_tiles : num_cus) + 7) & ~7;
+    const int grid = xcd_grid(n_tiles, num_cus);
     launch_rec(rec, SBBSEG_LAUNCH_DEC_HALO, 16 * 16, 64, 1, n_tiles, grid, 1, p.ttab != nullptr);
     hipLaunchKernelGGL(dec_halo_x3, dim3(grid), dim3(512), kDecHaloLdsBytes, s, p);
     return hipGetLastError();

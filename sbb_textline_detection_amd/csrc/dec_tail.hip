@@ -1,5 +1,5 @@
 // dec_tail.hip -- the network's last decoder conv and head in one launch: dec_tail_fused (16-bit modes) and dec_tail_fused_x3ps (split mode).
-#include "device_prims.h"
+#include "tile_walk.h"
 
 namespace sbbseg {
 
@@ -63,15 +63,13 @@ __global__ __launch_bounds__(256, 2) void dec_tail_fused(const TailParams p)
             x0 = (rem - ty * tiles_x) * 16;
         }
     };
-    // XCD-contiguous walk (grid = a multiple of 8 blocks): XCD x = block % 8 owns tiles [x * per_xcd, (x + 1) * per_xcd), so the
+    // XCD-contiguous walk (tile_walk.h; grid = a multiple of 8 blocks): XCD x = block % 8 owns a contiguous eighth of the tiles, so the
     // halo pixels neighbouring tiles share are fetched into one L2 once instead of once per XCD (a round-robin walk
     // re-fetched them from HBM: 1.8x the input bytes, L2 hit rate 2 %)
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, GX = gridDim.x >> 3;
-    const int per_xcd = (n_tiles + 7) >> 3;
-    const int xcd_lo = xcd * per_xcd, xcd_hi = min(n_tiles, xcd_lo + per_xcd);
-    const int my_tiles = xcd_lo + slot < xcd_hi ? (xcd_hi - xcd_lo - slot + GX - 1) / GX : 0;
+    const XcdWalk walk = xcd_walk(n_tiles, blockIdx, gridDim);
+    const int my_tiles = walk.my_tiles;
     if (my_tiles <= 0) return;
-    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return xcd_lo + slot + it * GX; };
+    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return walk.tile_at(it); };
     if (tid < 4) ((uint32_t*)zero_gran)[tid] = 0u;
     constexpr int CR = NC <= 2 ? 4 : 8;                        // floats per constant row
     if (tid < 32) {                                            // epilogue constants stay in LDS (VGPRs hold the weights)
@@ -335,12 +333,10 @@ __global__ __launch_bounds__(512, 2) void dec_tail_fused_x3ps(const TailParams p
         }
     };
     // XCD-contiguous walk, as in the other tail kernels
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, GX = gridDim.x >> 3;
-    const int per_xcd = (n_tiles + 7) >> 3;
-    const int xcd_lo = xcd * per_xcd, xcd_hi = min(n_tiles, xcd_lo + per_xcd);
-    const int my_tiles = xcd_lo + slot < xcd_hi ? (xcd_hi - xcd_lo - slot + GX - 1) / GX : 0;
+    const XcdWalk walk = xcd_walk(n_tiles, blockIdx, gridDim);
+    const int my_tiles = walk.my_tiles;
     if (my_tiles <= 0) return;
-    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return xcd_lo + slot + it * GX; };
+    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return walk.tile_at(it); };
     constexpr int CR = NC <= 2 ? 4 : 8;
     if (tid < 32) {
         float* row = cst + ((tid & 7) * 4 + (tid >> 3)) * CR;
@@ -601,20 +597,22 @@ hipError_t launch_tail(const TailParams& p, int precision, int num_cus, hipStrea
 {
     const int n_tiles = p.ttab ? p.n_tab : p.n * (p.PH / 8) * (p.PW / 8);
     if (n_tiles <= 0) return hipSuccess;
-    const int grid = ((n_tiles < 2 * num_cus ? n_tiles : 2 * num_cus) + 7) & ~7;      // (the XCD-contiguous walk: a multiple of 8)
+    const int grid = xcd_grid(n_tiles, 2 * num_cus);
     launch_rec(rec, SBBSEG_LAUNCH_TAIL, 16 * 16, 32, 1, n_tiles, grid, 1, p.ttab != nullptr);
     auto go = [&](auto kern) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kTailLdsBytes);
+        static bool attr_done[64] = {};                         // (one per kernel: the lambda is instantiated per `kern`)
+        hipError_t e = dynamic_lds_once((const void*)kern, kTailLdsBytes, attr_done);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), kTailLdsBytes, s, p);
         return hipSuccess;
     };
     hipError_t e;
     if (precision == kF16X3) {
-        const int grid3 = ((n_tiles < num_cus ? n_tiles : num_cus) + 7) & ~7;
+        const int grid3 = xcd_grid(n_tiles, num_cus);
         if (rec) rec->grid = grid3;
         auto gops = [&](auto kern) -> hipError_t {
-            hipError_t e8 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kT3PsLdsBytes);
+            static bool attr_done[64] = {};
+            hipError_t e8 = dynamic_lds_once((const void*)kern, kT3PsLdsBytes, attr_done);
             if (e8 != hipSuccess) return e8;
             hipLaunchKernelGGL(kern, dim3(grid3), dim3(512), kT3PsLdsBytes, s, p);
             return hipSuccess;

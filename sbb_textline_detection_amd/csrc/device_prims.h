@@ -1,5 +1,6 @@
 // device_prims.h -- the low-level device primitives the gfx950 kernel units of libsbbseg share: vector types, 16-bit packing, the
-// hi | lo split of the label-exact mode, MFMA wrappers, and the inline-asm loads / waits whose counts the kernels keep by hand.
+// hi | lo split of the label-exact mode, MFMA wrappers and the K-step built from them, and the inline-asm loads / waits whose counts the kernels
+// keep by hand.  (The steps built from these that several units run: tile_walk.h, pair_steps.h.)
 // Each exists ONCE, here: a wait or an M0 save that is audited or fixed is audited or fixed for every kernel.  A unit keeps a private
 // variant only where the instructions differ (stem_pool_x3.hip: split1).
 #pragma once
@@ -64,6 +65,34 @@ template <bool F16> __device__ inline float unpack_hi(uint32_t v) { return F16 ?
 __device__ inline f4_t mma(h8_t a, h8_t b, f4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 // w * x with both operands split: small terms first
 __device__ inline f4_t mma3(h8_t wh, h8_t wl, h8_t xh, h8_t xl, f4_t c) { return mma(wh, xh, mma(wh, xl, mma(wl, xh, c))); }
+// One K-step on a wave tile of M row blocks x 4 pixel blocks, one accumulator per output.  Split mode (X3): (ah, al) / (ph, pl) are the hi and lo
+// halves of the weights / pixels, three sweeps, small terms first -- al . ph, ah . pl, ah . ph, the order conv_igemm_mfma's split loop uses per
+// accumulator.  Plain fp16: (ah, al) / (ph, pl) are the two k-halves of a 64-channel step, k-half 0 before k-half 1.
+template <bool X3, int M>
+__device__ __attribute__((always_inline)) inline void mma_step(f4_t (&acc)[M][4], const h8_t (&ah)[M], const h8_t (&al)[M], const h8_t (&ph)[4],
+                                                               const h8_t (&pl)[4])
+{
+    if constexpr (X3) {
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) acc[m][ni] = mma(al[m], ph[ni], acc[m][ni]);
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) acc[m][ni] = mma(ah[m], pl[ni], acc[m][ni]);
+    }
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) acc[m][ni] = mma(ah[m], ph[ni], acc[m][ni]);
+    if constexpr (!X3) {
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) acc[m][ni] = mma(al[m], pl[ni], acc[m][ni]);
+    }
+}
 template <bool F16> __device__ inline f4_t mfma16(bf16x8_t a, bf16x8_t b, f4_t c)
 {
     if constexpr (F16)

@@ -1,6 +1,6 @@
 // direct64.hip -- 3x3 convs with 64 input and 64 output channels as direct convs on LDS halo tiles: conv3x3_c64_direct (16-bit modes)
 // and conv3x3_c64_direct_x3 (split mode).
-#include "device_prims.h"
+#include "tile_walk.h"
 
 namespace sbbseg {
 
@@ -31,12 +31,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_direct(const Direct64Param
     const int tiles_per_patch = tiles_x * tiles_y;
     const int n_tiles = p.n * tiles_per_patch;
     // XCD-contiguous walk (grid = a multiple of 8 blocks), as in the tail kernels
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, GX = gridDim.x >> 3;
-    const int per_xcd = (n_tiles + 7) >> 3;
-    const int xcd_lo = xcd * per_xcd, xcd_hi = min(n_tiles, xcd_lo + per_xcd);
-    const int my_tiles = xcd_lo + slot < xcd_hi ? (xcd_hi - xcd_lo - slot + GX - 1) / GX : 0;
+    const XcdWalk walk = xcd_walk(n_tiles, blockIdx, gridDim);
+    const int my_tiles = walk.my_tiles;
     if (my_tiles <= 0) return;
-    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return xcd_lo + slot + it * GX; };
+    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return walk.tile_at(it); };
     float* cst = (float*)(smem + 2 * kD64BufBytes);
     if (tid < 64) { cst[tid] = p.scale[tid]; cst[64 + tid] = p.shift[tid]; }
 
@@ -170,12 +168,10 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_direct_x3(const Direct64Pa
     const int tiles_per_patch = tiles_x * tiles_y;
     const int n_tiles = p.n * tiles_per_patch;
     // XCD-contiguous walk (grid = a multiple of 8 blocks), as in the tail kernels
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, GX = gridDim.x >> 3;
-    const int per_xcd = (n_tiles + 7) >> 3;
-    const int xcd_lo = xcd * per_xcd, xcd_hi = min(n_tiles, xcd_lo + per_xcd);
-    const int my_tiles = xcd_lo + slot < xcd_hi ? (xcd_hi - xcd_lo - slot + GX - 1) / GX : 0;
+    const XcdWalk walk = xcd_walk(n_tiles, blockIdx, gridDim);
+    const int my_tiles = walk.my_tiles;
     if (my_tiles <= 0) return;
-    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return xcd_lo + slot + it * GX; };
+    auto tile_at = [&](int it) __attribute__((always_inline)) -> int { return walk.tile_at(it); };
     float* cst = (float*)(smem + 2 * kD64x3BufBytes);
     if (tid < 64) { cst[tid] = p.scale[tid] * p.wmul; cst[64 + tid] = p.shift[tid]; }
 
@@ -290,19 +286,13 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_direct_x3(const Direct64Pa
 hipError_t launch_direct64(const Direct64Params& p, int precision, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     const int n_tiles = p.n * ((p.H + 7) / 8) * ((p.W + 15) / 16);
-    const int grid = ((n_tiles < 2 * num_cus ? n_tiles : 2 * num_cus) + 7) & ~7;      // (XCD-contiguous walk: a multiple of 8)
-    launch_rec(rec, SBBSEG_LAUNCH_DIRECT64, 8 * 16, 64, 1, n_tiles, precision == kF16X3 ? ((n_tiles < num_cus ? n_tiles : num_cus) + 7) & ~7 : grid, 1);
+    const int grid = xcd_grid(n_tiles, (precision == kF16X3 ? 1 : 2) * num_cus);      // (the split kernel: one block per CU)
+    launch_rec(rec, SBBSEG_LAUNCH_DIRECT64, 8 * 16, 64, 1, n_tiles, grid, 1);
     if (precision == kF16X3) {
         static bool attr_done[64] = {};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
+        const hipError_t e = dynamic_lds_once((const void*)conv3x3_c64_direct_x3, kD64x3LdsBytes, attr_done);
         if (e != hipSuccess) return e;
-        if (!attr_done[dev & 63]) {
-            e = hipFuncSetAttribute((const void*)conv3x3_c64_direct_x3, hipFuncAttributeMaxDynamicSharedMemorySize, kD64x3LdsBytes);
-            if (e != hipSuccess) return e;
-            attr_done[dev & 63] = true;
-        }
-        hipLaunchKernelGGL(conv3x3_c64_direct_x3, dim3(((n_tiles < num_cus ? n_tiles : num_cus) + 7) & ~7), dim3(256), kD64x3LdsBytes, s, p);
+        hipLaunchKernelGGL(conv3x3_c64_direct_x3, dim3(grid), dim3(256), kD64x3LdsBytes, s, p);
         return hipGetLastError();
     }
     if (precision == kF16) hipLaunchKernelGGL(conv3x3_c64_direct<true>, dim3(grid), dim3(256), kD64LdsBytes, s, p);

@@ -23,11 +23,13 @@
 // (Every asm store ends in `s_nop 1`: the hazard recognizer does not see a store inside inline asm, so it does not insert the wait state the
 // ISA wants between a store of more than 64 bits and a VALU write of its data registers -- lanes 12-15 of the first data register came out
 // as the NEXT pixel block's values in the plain mode, where the compiler reuses the registers at once.)
+// The steps named above -- fragment loads, x / weight requests, the epilogues' arithmetic and stores -- are pair_steps.h's, shared with
+// conv3_expand_reduce.hip; this unit holds the schedule: which step requests what, and the terms of every wait count.
 // Every vector-memory operation of the loop is issued from inline asm and waited for by a hand-counted vmcnt (retirement is in issue
 // order): see dec_halo_x3.hip for why.  Pixel rows in LDS are C * 4 bytes (b) / 1 KB (y chunk); 16-byte slot s of pixel p sits at slot
 // (s + 2 (p & 15)) mod row: conflict-free for the 16-lane groups of ds_read_b128 (64 banks); the epilogue's ds_write_b128 (32 banks, 8-lane
 // groups) lands two lanes on a bank -- PMC: 13-17 % of the LDS-busy cycles are conflict cycles, all from those 16 writes per chunk.
-#include "device_prims.h"
+#include "pair_steps.h"
 
 namespace sbbseg {
 
@@ -38,19 +40,11 @@ namespace sbbseg {
 template <int C, bool X3>
 __global__ __launch_bounds__(512, 2) void expand_reduce(const ExpRedParams p)
 {
-    constexpr int EB = X3 ? 4 : 2;                              // stored bytes per channel
-    constexpr int KCH = X3 ? 32 : 64;                           // channels per K-step
-    constexpr int KS1 = C / KCH;                                // K-steps of GEMM 1
-    constexpr int G2S = 256 / KCH;                              // K-steps of GEMM 2 per chunk
-    constexpr int NCH = C / 64;                                 // 256-channel chunks of y
-    constexpr int MI2 = C / 128;                                // row blocks of a' per wave
-    constexpr int LG2 = 2 * MI2;                                // weight loads per K-step of GEMM 2
-    constexpr int PB = C * EB, PY = 4 * C * EB, PA = C * EB;    // bytes per stored pixel: b, y / x, a'
-    constexpr int YROW = 256 * EB;                              // bytes per pixel of the y chunk's LDS image
-    constexpr int SLB = PB / 16, SLY = YROW / 16;               // 16-byte slots per LDS row
+    using S = PairShape<C, X3>;                                 // the pair's shape (pair_steps.h), under the names the schedule below uses
+    constexpr int EB = S::EB, KS1 = S::KS1, G2S = S::G2S, NCH = S::NCH, MI2 = S::MI2, LG2 = S::LG2, PB = S::PB, PY = S::PY, PA = S::PA, YROW = S::YROW;
+    constexpr int SLB = S::SLB, SLY = S::SLY, kEpi1 = S::kEpi1;
     constexpr int kBBytes = 64 * PB, kYBytes = 64 * YROW;
     constexpr int STEPS = NCH * (KS1 + G2S);                    // K-steps per tile, both GEMMs (even)
-    constexpr int kEpi1 = X3 ? 16 : 8, kEpi2 = X3 ? 8 : 4;      // vector-memory operations of the epilogues: y stores + x loads; a' stores
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const lds_b = smem;
     char* const lds_y = smem + kBBytes;
@@ -108,26 +102,15 @@ __global__ __launch_bounds__(512, 2) void expand_reduce(const ExpRedParams p)
     auto issue_w = [&](int u, u4_t (&d)[4]) __attribute__((always_inline)) {             // u in [0, STEPS)
         const int j = u / (KS1 + G2S), r = u % (KS1 + G2S);
         const uint32_t wm = SBBSEG_PROBE(p.dbg & 1) ? 0u : 1u;                 // (timing probe: every request reads the first step's fragments)
-        if (r < KS1) wload4(d[0], d[1], d[2], d[3], wlane + wm * (uint32_t)((j * KS1 + r) * 8 * 4096), w3rsrc);
-        else if constexpr (MI2 == 2) wload4(d[0], d[1], d[2], d[3], wlane + wm * (uint32_t)((j * G2S + r - KS1) * 8 * 4096), w1rsrc);
-        else wload2(d[0], d[1], wlane + wm * (uint32_t)((j * G2S + r - KS1) * 8 * 2048), w1rsrc);
+        pair_issue_w<S>(j, r, d, wlane, wm, w3rsrc, w1rsrc);
     };
-    auto issue_x = [&](int tile, int j) __attribute__((always_inline)) {                  // 8 loads (plain mode: 4)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            const uint32_t off = (SBBSEG_PROBE(p.dbg & 4) ? 0xf0000000u : 0u) + xlane + (uint32_t)(tile * 64 + ni * 16) * (uint32_t)PY + (uint32_t)(j * YROW);
-            if constexpr (X3) xload2(xh[ni], xl[ni], off, xrsrc);
-            else asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=&v"(xh[ni]) : "v"(off), "s"(xrsrc) : "memory");
-        }
+    auto issue_x = [&](int tile, int j) __attribute__((always_inline)) {                  // kEpi1 / 2 loads
+        pair_issue_x<X3>(xh, xl, xrsrc, [&](int ni) __attribute__((always_inline)) -> uint32_t {
+            return (SBBSEG_PROBE(p.dbg & 4) ? 0xf0000000u : 0u) + xlane + (uint32_t)(tile * 64 + ni * 16) * (uint32_t)PY + (uint32_t)(j * YROW);
+        });
     };
     auto load_frags = [&](const char* base, int row_bytes, int slots, int k, h8_t (&dh)[4], h8_t (&dl)[4]) __attribute__((always_inline)) {
-        const int sh = (rot + 8 * k) & (slots - 1), sl = (rot + 8 * k + 4) & (slots - 1);
-        const char* a = base + frv * row_bytes;
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            dh[ni] = *(const h8_t*)(a + ni * 16 * row_bytes + (sh << 4));
-            dl[ni] = *(const h8_t*)(a + ni * 16 * row_bytes + (sl << 4));
-        }
+        pair_load_frags(base, row_bytes, slots, k, rot, frv, dh, dl);
     };
 
     // ---- prologue: the first tile's b and its first chunk of x
@@ -192,50 +175,12 @@ __global__ __launch_bounds__(512, 2) void expand_reduce(const ExpRedParams p)
             if constexpr (g1) {
                 const h8_t ah[2] = {__builtin_bit_cast(h8_t, cw[0]), __builtin_bit_cast(h8_t, cw[2])};       // (plain mode: k-half 0)
                 const h8_t al[2] = {__builtin_bit_cast(h8_t, cw[1]), __builtin_bit_cast(h8_t, cw[3])};       // (             k-half 1)
-                if constexpr (X3) {
-#pragma unroll
-                    for (int m = 0; m < 2; ++m)
-#pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) acc1[m][ni] = mma(al[m], ph[ni], acc1[m][ni]);
-#pragma unroll
-                    for (int m = 0; m < 2; ++m)
-#pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) acc1[m][ni] = mma(ah[m], pl[ni], acc1[m][ni]);
-                }
-#pragma unroll
-                for (int m = 0; m < 2; ++m)
-#pragma unroll
-                    for (int ni = 0; ni < 4; ++ni) acc1[m][ni] = mma(ah[m], ph[ni], acc1[m][ni]);
-                if constexpr (!X3) {
-#pragma unroll
-                    for (int m = 0; m < 2; ++m)
-#pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) acc1[m][ni] = mma(al[m], pl[ni], acc1[m][ni]);
-                }
+                mma_step<X3, 2>(acc1, ah, al, ph, pl);
             } else {
                 h8_t ah[MI2], al[MI2];
 #pragma unroll
                 for (int m = 0; m < MI2; ++m) { ah[m] = __builtin_bit_cast(h8_t, cw[2 * m]); al[m] = __builtin_bit_cast(h8_t, cw[2 * m + 1]); }
-                if constexpr (X3) {
-#pragma unroll
-                    for (int m = 0; m < MI2; ++m)
-#pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) acc2[m][ni] = mma(al[m], ph[ni], acc2[m][ni]);
-#pragma unroll
-                    for (int m = 0; m < MI2; ++m)
-#pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) acc2[m][ni] = mma(ah[m], pl[ni], acc2[m][ni]);
-                }
-#pragma unroll
-                for (int m = 0; m < MI2; ++m)
-#pragma unroll
-                    for (int ni = 0; ni < 4; ++ni) acc2[m][ni] = mma(ah[m], ph[ni], acc2[m][ni]);
-                if constexpr (!X3) {
-#pragma unroll
-                    for (int m = 0; m < MI2; ++m)
-#pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) acc2[m][ni] = mma(al[m], pl[ni], acc2[m][ni]);
-                }
+                mma_step<X3, MI2>(acc2, ah, al, ph, pl);
             }
             // this set's weights are spent: step u + 2 (of the next tile behind the last two; always issued: the counts stay constant)
             issue_w((u + 2) % STEPS, cw);
@@ -244,49 +189,17 @@ __global__ __launch_bounds__(512, 2) void expand_reduce(const ExpRedParams p)
             if constexpr (g1 && k == KS1 - 1) {
                 // ---- epilogue 1: y = ReLU(s3 * acc + h3 + x) -> hi | lo: to HBM and into the LDS image of the chunk.  x of this chunk was requested
                 // an epilogue ago: older than every weight request already waited for (the wait below only ties the registers to that fact)
-                if constexpr (X3)
-                    asm volatile("s_waitcnt vmcnt(%8)" : "+v"(xh[0]), "+v"(xh[1]), "+v"(xh[2]), "+v"(xh[3]), "+v"(xl[0]), "+v"(xl[1]), "+v"(xl[2]), "+v"(xl[3])
-                                 : "n"(2 * LG2) : "memory");
-                else
-                    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(xh[0]), "+v"(xh[1]), "+v"(xh[2]), "+v"(xh[3]) : "n"(2 * LG2) : "memory");
+                pair_wait_x<X3, 2 * LG2>(xh, xl);
                 const int c0 = j * 256 + wave * 32 + fgv * 8;
-                float sc[8], sh[8];
+                float sc[8], sh[8];                             // (loaded here, where `cst` is a constant address: profiles/kernel_share.md)
                 *(float4*)&sc[0] = *(const float4*)(cst + c0); *(float4*)&sc[4] = *(const float4*)(cst + c0 + 4);
                 *(float4*)&sh[0] = *(const float4*)(cst + 4 * C + c0); *(float4*)&sh[4] = *(const float4*)(cst + 4 * C + c0 + 4);
-                // the wave's 32 channels = granules wave * 4 + fg of the chunk (split mode: group `wave`, hi granules fg, lo granules 4 + fg)
-                // (round 5 timed these writes with a conflict-free rotation -- one slot per pixel, results then wrong -- and found no difference:
-                //  profiles/r05_experiments.md section 6; the probe itself made the compiler add a vmcnt wait to the loop and is not kept)
-                const int s_hi = (wave * (X3 ? 8 : 4) + rot) & (SLY - 1), s_lo = (wave * 8 + 4 + rot) & (SLY - 1);
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) {
-                    float y[8];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        y[q] = __builtin_fmaf(acc1[0][ni][q], sc[q], sh[q]);
-                        y[4 + q] = __builtin_fmaf(acc1[1][ni][q], sc[4 + q], sh[4 + q]);
-                    }
-                    const uint32_t off = (SBBSEG_PROBE(p.dbg & 2) ? 0xf0000000u : 0u) + xlane + (uint32_t)(tile * 64 + ni * 16) * (uint32_t)PY + (uint32_t)(j * YROW);
-                    char* row = lds_y + (ni * 16 + frv) * YROW;
-                    if constexpr (X3) {
-                        const h8_t rh = __builtin_bit_cast(h8_t, xh[ni]), rl = __builtin_bit_cast(h8_t, xl[ni]);
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) y[q] = fmaxf(__fadd_rn(y[q], __fadd_rn((float)rh[q], (float)rl[q])), 0.f);      // (= add_split8 + ReLU, kernels.hip)
-                        h8_t vh, vl;
-                        split_n<8>(y, vh, vl);
-                        asm volatile("buffer_store_dwordx4 %1, %0, %3, 0 offen\n\tbuffer_store_dwordx4 %2, %0, %3, 0 offen offset:64\n\ts_nop 1"
-                                     :: "v"(off), "v"(vh), "v"(vl), "s"(yrsrc) : "memory");
-                        *(h8_t*)(row + (s_hi << 4)) = vh;
-                        *(h8_t*)(row + (s_lo << 4)) = vl;
-                    } else {
-                        const h8_t rr = __builtin_bit_cast(h8_t, xh[ni]);
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) y[q] = fmaxf(__fadd_rn(y[q], (float)rr[q]), 0.f);
-                        u4_t v;
-                        v[0] = pack_h2(y[0], y[1]); v[1] = pack_h2(y[2], y[3]); v[2] = pack_h2(y[4], y[5]); v[3] = pack_h2(y[6], y[7]);
-                        asm volatile("buffer_store_dwordx4 %1, %0, %2, 0 offen\n\ts_nop 1" :: "v"(off), "v"(v), "s"(yrsrc) : "memory");
-                        *(u4_t*)(row + (s_hi << 4)) = v;
-                    }
-                }
+                pair_epilogue1<S, X3>(
+                    acc1, xh, xl, sc, sh, wave, rot, yrsrc,
+                    [&](int ni) __attribute__((always_inline)) -> uint32_t {
+                        return (SBBSEG_PROBE(p.dbg & 2) ? 0xf0000000u : 0u) + xlane + (uint32_t)(tile * 64 + ni * 16) * (uint32_t)PY + (uint32_t)(j * YROW);
+                    },
+                    [&](int ni) __attribute__((always_inline)) -> char* { return lds_y + (ni * 16 + frv) * YROW; });
                 // the residual of the chunk after this one (the next tile's first behind the last)
                 if constexpr (j + 1 < NCH) issue_x(tile, j + 1);
                 else issue_x(tile_next, 0);
@@ -304,16 +217,10 @@ __global__ __launch_bounds__(512, 2) void expand_reduce(const ExpRedParams p)
 
         // ---- epilogue 2: a' = ReLU(s1 * acc + h1) -> hi | lo.  EXACTLY kEpi2 stores per wave.
         {
-            const int c0 = MI2 == 2 ? wave * 32 + fgv * 8 : (wave >> 1) * 32 + fgv * 8 + (wave & 1) * 4;
             float sc[4 * MI2], sh[4 * MI2];
-            *(float4*)&sc[0] = *(const float4*)(cst + 8 * C + c0);
-            *(float4*)&sh[0] = *(const float4*)(cst + 9 * C + c0);
-            if constexpr (MI2 == 2) {
-                *(float4*)&sc[4] = *(const float4*)(cst + 8 * C + c0 + 4);
-                *(float4*)&sh[4] = *(const float4*)(cst + 9 * C + c0 + 4);
-            }
+            pair_bn_consts<MI2>(cst + 8 * C, cst + 9 * C, pair_c0<MI2>(wave, fgv), sc, sh);
 #pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
+            for (int ni = 0; ni < S::kNI; ++ni) {
                 const uint32_t off = alane + (uint32_t)(tile * 64 + ni * 16) * (uint32_t)PA;
                 float y[4 * MI2];
 #pragma unroll
@@ -321,25 +228,7 @@ __global__ __launch_bounds__(512, 2) void expand_reduce(const ExpRedParams p)
                     y[q] = fmaxf(__builtin_fmaf(acc2[0][ni][q], sc[q], sh[q]), 0.f);
                     if constexpr (MI2 == 2) y[4 + q] = fmaxf(__builtin_fmaf(acc2[MI2 - 1][ni][q], sc[4 * (MI2 - 1) + q], sh[4 * (MI2 - 1) + q]), 0.f);
                 }
-                if constexpr (X3 && MI2 == 2) {
-                    h8_t vh, vl;
-                    split_n<8>(y, vh, vl);
-                    asm volatile("buffer_store_dwordx4 %1, %0, %3, 0 offen\n\tbuffer_store_dwordx4 %2, %0, %3, 0 offen offset:64\n\ts_nop 1"
-                                 :: "v"(off), "v"(vh), "v"(vl), "s"(arsrc) : "memory");
-                } else if constexpr (X3) {
-                    h4_t vh, vl;
-                    split_n<4>(y, vh, vl);
-                    asm volatile("buffer_store_dwordx2 %1, %0, %3, 0 offen\n\tbuffer_store_dwordx2 %2, %0, %3, 0 offen offset:64\n\ts_nop 1"
-                                 :: "v"(off), "v"(vh), "v"(vl), "s"(arsrc) : "memory");
-                } else if constexpr (MI2 == 2) {
-                    u4_t v;
-                    v[0] = pack_h2(y[0], y[1]); v[1] = pack_h2(y[2], y[3]); v[2] = pack_h2(y[4 % (4 * MI2)], y[5 % (4 * MI2)]); v[3] = pack_h2(y[6 % (4 * MI2)], y[7 % (4 * MI2)]);
-                    asm volatile("buffer_store_dwordx4 %1, %0, %2, 0 offen\n\ts_nop 1" :: "v"(off), "v"(v), "s"(arsrc) : "memory");
-                } else {
-                    u2_t v;
-                    v[0] = pack_h2(y[0], y[1]); v[1] = pack_h2(y[2], y[3]);
-                    asm volatile("buffer_store_dwordx2 %1, %0, %2, 0 offen\n\ts_nop 1" :: "v"(off), "v"(v), "s"(arsrc) : "memory");
-                }
+                pair_pack_store<X3, MI2>(y, off, arsrc);
             }
         }
     }
@@ -351,14 +240,8 @@ template <int C, bool X3> static hipError_t launch_one(const ExpRedParams& p, in
     constexpr int EB = X3 ? 4 : 2;
     constexpr int lds = 64 * C * EB + 64 * 256 * EB + 10 * C * 4;
     static bool attr_done[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = dynamic_lds_once((const void*)expand_reduce<C, X3>, lds, attr_done);
     if (e != hipSuccess) return e;
-    if (!attr_done[dev & 63]) {
-        e = hipFuncSetAttribute((const void*)expand_reduce<C, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_done[dev & 63] = true;
-    }
     const int n_tiles = (p.M + 63) / 64;
     const int grid = n_tiles < num_cus ? n_tiles : num_cus;
     launch_rec(rec, SBBSEG_LAUNCH_EXPAND_REDUCE, 64, 4 * C, 1, n_tiles, grid, 1, 0, 1);

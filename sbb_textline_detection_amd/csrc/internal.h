@@ -339,6 +339,20 @@ inline void launch_rec(LaunchRec* r, int family, int bp, int bc, int stages, int
     r->table = table; r->residual = residual;
 }
 
+// Raise a kernel's dynamic LDS limit to `bytes`, once per device: the attribute belongs to the device's copy of the kernel, so the caller keeps
+// one flag array per kernel (`static bool done[64] = {}` at the call site) and the current device selects the flag.  THE one call of
+// hipFuncSetAttribute in the library.
+inline hipError_t dynamic_lds_once(const void* kernel, int bytes, bool (&done)[64])
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (done[dev & 63]) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) done[dev & 63] = true;
+    return e;
+}
+
 // launchers, by the unit that defines them ---------------------------------------------------
 // kernels.hip
 hipError_t launch_conv(const ConvParams& p, int precision, hipStream_t s, LaunchRec* rec = nullptr);

@@ -34,16 +34,6 @@ __device__ inline void add_split8(const uint16_t* src, int plane, float (&y)[8])
 // ------------------------------------------------------------------------------------------------
 // conv_igemm_mfma  (16-bit operands: bf16 or fp16, fp32 accumulate)
 // ------------------------------------------------------------------------------------------------
-// blocks per CU a tile family is sized for (LDS budget) -> min waves per SIMD for __launch_bounds__
-constexpr int conv_blocks_per_cu(int bp, int bc, int wp, int wc, int ns)
-{
-    const int waves = wp * wc;
-    const int wrows = bc > 8 * waves ? bc : 8 * waves;
-    const int lds = ns * (bp + wrows) * 128;
-    if (waves != 4) return 1;
-    return 3 * lds <= 160 * 1024 ? 3 : (2 * lds <= 160 * 1024 ? 2 : 1);
-}
-
 template <int BP, int BC, int WP, int WC, int NS, int GS = 8>
 struct ConvTile {
     // GS = 16-byte granules of the contraction axis per LDS stage: 8 (a whole 64-element K-step) or 4
@@ -1185,15 +1175,8 @@ static hipError_t launch_conv_impl(const ConvParams& p, hipStream_t s, LaunchRec
 {
     using T = ConvTile<BP, BC, WP, WC, NS, GS>;
     static bool attr_done[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = dynamic_lds_once((const void*)conv_igemm_mfma<BP, BC, WP, WC, NS, F16, GS, PH8, X3, FG, KS>, T::kLdsBytes, attr_done);
     if (e != hipSuccess) return e;
-    if (!attr_done[dev & 63]) {
-        e = hipFuncSetAttribute((const void*)conv_igemm_mfma<BP, BC, WP, WC, NS, F16, GS, PH8, X3, FG, KS>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, T::kLdsBytes);
-        if (e != hipSuccess) return e;
-        attr_done[dev & 63] = true;
-    }
     const int n_ct = (p.cout + BC - 1) / BC;
     const int n_pt = (p.M + BP - 1) / BP;
     const int n_tiles = (p.n_cls * n_ct * (p.cls_minor ? (n_pt + 7) & ~7 : n_pt)) << (KS ? p.ks_shift : 0);
@@ -1242,9 +1225,7 @@ static hipError_t launch_conv_16(const ConvParams& p, hipStream_t s, LaunchRec* 
 {
     const int bc = conv_tile_bc(p.cout);
     const int variant = p.variant;
-    const long big_blocks = (long)((p.M + 255) / 256) * ((p.cout + bc - 1) / bc);
     const bool big = variant == 2;
-    (void)big_blocks;
     if (p.ks_shift > 0) {                                       // split-K (see launch_conv_x3)
         if (bc != 128 || !p.fast_gather || p.tile_map != 0 || p.cls_minor || (p.total_ksteps & ((1 << p.ks_shift) - 1))) return hipErrorInvalidValue;
         return launch_conv_impl<128, 128, 2, 2, 2, F16, 8, false, false, true, true>(p, s, rec);

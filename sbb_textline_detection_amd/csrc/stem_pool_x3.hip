@@ -350,17 +350,10 @@ __global__ __launch_bounds__(256, 2) void stem_pool(const StemParams p)
 
 hipError_t launch_stem_pool_x3(const StemParams& p, int num_cus, hipStream_t s, LaunchRec* rec)
 {
-    static bool attr_done[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static bool attr_done[2][64] = {};                         // one per kernel
+    hipError_t e = dynamic_lds_once((const void*)stem_pool<true>, kStemPoolLdsBytes, attr_done[0]);
+    if (e == hipSuccess) e = dynamic_lds_once((const void*)stem_pool<false>, kStemPoolF16LdsBytes, attr_done[1]);
     if (e != hipSuccess) return e;
-    if (!attr_done[dev & 63]) {
-        e = hipFuncSetAttribute((const void*)stem_pool<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kStemPoolLdsBytes);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)stem_pool<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kStemPoolF16LdsBytes);
-        if (e != hipSuccess) return e;
-        attr_done[dev & 63] = true;
-    }
     const int n_strips = p.n * (p.Ho / 16);
     // two blocks per CU; 16 blocks = 8 strips x 2 channel halves
     int groups = (n_strips + 7) / 8;
