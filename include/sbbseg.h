@@ -419,6 +419,20 @@ typedef struct sbbseg_run_page_io {
 } sbbseg_run_page_io;
 int sbbseg_run_pages(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline, int n_pages, sbbseg_run_page_io* pages, int channels);
 
+/* What sbbseg_run_pages leaves on the device.  regions[k] / textlines[k] (n_pages entries each, written by the call): the cleaned layout
+ * plane and the textline plane of page k of the LAST successful sbbseg_run_pages that had this handle as `layout`, both h x w of that
+ * page's box (info.box_xywh), one byte per pixel; d_hw = NULL where that page's regions_ok / textlines_ok is 0 (and for a page of status
+ * 1).  The pointers lead into buffers of the layout handle: they stay valid until the next sbbseg_run_page or sbbseg_run_pages that names
+ * one of the three handles, or until sbbseg_destroy, and must not be freed or written.  Status + sbbseg_last_error() when the last
+ * sbbseg_run_pages on the handle failed, when there was none, when an sbbseg_run_page came after it, or when n_pages differs from that
+ * call's.  The handle keeps only the per-page offsets and flags for this; no device memory is added.
+ * STREAMS: when sbbseg_run_pages returns 0, the streams of all three handles have been synchronised behind everything the call queued
+ * (the border handle's at the hand-over to the other two; the layout and textline handles' by the download of every plane they wrote --
+ * the textline planes lie in the layout handle's buffer but are written on the TEXTLINE handle's stream, and their downloads wait for
+ * it).  Any handle of the device may therefore read the planes, e.g. with the sbbseg_planes_* calls below, without synchronising. */
+typedef struct sbbseg_plane { const void* d_hw; int32_t H, W; } sbbseg_plane;   /* dense u8 [H][W] in device memory */
+int sbbseg_run_pages_planes(sbbseg_ctx* layout, int n_pages, sbbseg_plane* regions, sbbseg_plane* textlines);
+
 /* ---- stage glue: the rotate-and-project of the deskew search (return_deskew_slope, main.py:1601-1718; per text region,
  * 80 angles in [-25, 25] and 30 more in [-90, -50] -- the reference spreads the regions over cpu_count() processes,
  * main.py:1760-1799).  The H x W u8 region mask is centred on a zero square of side S = (int)(1.4 * max(H, W))
@@ -573,6 +587,27 @@ int sbbseg_region_line_boxes(sbbseg_ctx* c, const uint8_t* textline_hw, int H, i
                              const double* slopes, const double* rot, const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info,
                              int64_t* line_off, int32_t* lines, int32_t* corners, int32_t* corners_rot);
 
+/* ---- the three per-box calls above for boxes that lie on MANY planes (the textline planes of many pages: sbbseg_run_pages_planes), the
+ * boxes of all planes sharing the launches.  planes: n_planes records; box r = boxes_xywh[4 r ..] lies on planes[box_plane[r]].  Boxes come
+ * in any order; a plane may have no box (its d_hw may then be NULL) or be named by many.  Every per-box result -- slopes; masks, row and
+ * column sums; every field of the line records -- equals bit for bit what the one-plane `_dev` call gives for that box on that plane, and
+ * the outputs are packed in BOX order exactly as there (offsets, capacities, buffers: see the one-plane calls).  Only the row pass of the
+ * crops reads the planes, through one (pointer, width) record per box; every later kernel works on the packed crops.  The number of
+ * launches does not depend on n_planes or n_boxes: per slope sweep 3 + the statistic's 2 or 3 (the second sweep re-crops only the boxes
+ * steeper than 15 degrees, with their planes); line masks 10; line boxes 11 or 12.  Nothing is uploaded but the small tables.
+ * Errors (status + sbbseg_last_error(); checked on the host before anything is queued, the message names the box): box_plane[r] outside
+ * 0 .. n_planes - 1; a box that leaves ITS OWN plane, w or h < 1; a plane named by a box whose d_hw is NULL; n_planes < 1 with n_boxes > 0.
+ * n_boxes = 0 is success.  The limits of the one-plane calls ("too much work for one call ... split the boxes") apply to the totals over
+ * all planes.  Each call synchronises the handle's stream; the planes must be complete when it is called (see sbbseg_run_pages_planes). */
+int sbbseg_planes_deskew_slopes_dev(sbbseg_ctx* c, const sbbseg_plane* planes, int n_planes, const int32_t* boxes_xywh, const int32_t* box_plane,
+                                    int n_boxes, int erode_iterations, const double* weights, int radius, double* slopes);
+int sbbseg_planes_line_masks_dev(sbbseg_ctx* c, const sbbseg_plane* planes, int n_planes, const int32_t* boxes_xywh, const int32_t* box_plane, int n_boxes,
+                                 int erode_iterations, const double* slopes, uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off,
+                                 int64_t* row_off, int64_t* col_off);
+int sbbseg_planes_line_boxes_dev(sbbseg_ctx* c, const sbbseg_plane* planes, int n_planes, const int32_t* boxes_xywh, const int32_t* box_plane, int n_boxes,
+                                 int erode_iterations, const double* slopes, const double* rot, const double* weights, const int64_t* weight_off,
+                                 int sigma_max, int32_t* info, int64_t* line_off, int32_t* lines, int32_t* corners, int32_t* corners_rot);
+
 /* ---- multi-GPU: one process per GPU, one handle per process; tiles (sbbseg_segment_tile_range_dev) or whole
  * pages (sbbseg_segment_pages_dev) are sharded by the caller, and the ONE data-path collective -- the all-gather of the u8
  * label maps -- runs on RCCL inside the library, on the handle's stream, so an integrator needs neither PyTorch nor an MPI:
@@ -678,7 +713,7 @@ int sbbseg_debug_op_launch(sbbseg_ctx* c, int op, int32_t* out, int cap);
  * (-1: none).  One kernel on the handle's stream, waited for (tests: a batch of cyclically repeated patches must come out periodic). */
 int sbbseg_debug_tensor_period_mismatches(sbbseg_ctx* c, int tensor_id, int n, int period, int64_t* count, int64_t* first);
 /* counters: which 0 = how often sbbseg_page_box_dev had to fall back to the host ranking on this handle */
-int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value);      /* which: 0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by sbbseg_region_line_masks(_dev), 3 = ingest + region-table + stitch kernels queued by sbbseg_segment_views_dev, 4 = ingest + label-resize kernels queued by the whole-views calls (sbbseg_segment_whole_views_dev, sbbseg_extract_page_boxes_dev, sbbseg_run_pages: 2 per chunk) */
+int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value);      /* which: 0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by sbbseg_region_line_masks(_dev), sbbseg_region_line_boxes(_dev) and their sbbseg_planes_* forms, 3 = ingest + region-table + stitch kernels queued by sbbseg_segment_views_dev, 4 = ingest + label-resize kernels queued by the whole-views calls (sbbseg_segment_whole_views_dev, sbbseg_extract_page_boxes_dev, sbbseg_run_pages: 2 per chunk), 5 = kernels queued by the deskew slope sweeps (crop 2, profiles 1, statistic 1 or 2, winner 1 per sweep) */
 /* Test hook for the no-abort guarantee: the nth_check-th next internal host-allocation checkpoint throws
  * std::bad_alloc, which every entry point turns into a non-zero status + sbbseg_last_error() instead of
  * terminating the process (main.py:2061-2157 relies on ordinary exceptions).  0 disarms.  Process-global. */

@@ -41,6 +41,7 @@ EXPORTS = [
     "sbbseg_segment_views_dev", "sbbseg_segment_views", "sbbseg_debug_axis_owner",
     "sbbseg_debug_op_launch", "sbbseg_debug_tensor_period_mismatches",
     "sbbseg_segment_whole_views_dev", "sbbseg_extract_page_boxes_dev", "sbbseg_run_pages",
+    "sbbseg_run_pages_planes", "sbbseg_planes_deskew_slopes_dev", "sbbseg_planes_line_masks_dev", "sbbseg_planes_line_boxes_dev",
 ]
 
 
@@ -74,6 +75,11 @@ class RunPageIO(C.Structure):
     _fields_ = [("page", C.c_void_p), ("Hp", C.c_int32), ("Wp", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32),
                 ("page_mask_out", C.c_void_p), ("regions_out", C.c_void_p), ("textlines_out", C.c_void_p), ("info", RunInfo),
                 ("status", C.c_int32)]
+
+
+class Plane(C.Structure):
+    """sbbseg_plane (include/sbbseg.h)"""
+    _fields_ = [("d_hw", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32)]
 
 
 class ConvDesc(C.Structure):
@@ -206,6 +212,10 @@ def load_library(path: Optional[str] = None):
         "sbbseg_line_split_dev": [vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
         "sbbseg_region_line_boxes_dev": [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
         "sbbseg_region_line_boxes": [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
+        "sbbseg_run_pages_planes": [vp, i32, C.POINTER(Plane), C.POINTER(Plane)],
+        "sbbseg_planes_deskew_slopes_dev": [vp, C.POINTER(Plane), i32, vp, vp, i32, i32, vp, i32, vp],
+        "sbbseg_planes_line_masks_dev": [vp, C.POINTER(Plane), i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+        "sbbseg_planes_line_boxes_dev": [vp, C.POINTER(Plane), i32, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -757,11 +767,13 @@ class Context:
                                                      float(multiplier), _ptr(spread), _ptr(state), _ptr(winner)), "sbbseg_profile_statistics_dev")
         return spread, state, winner
 
-    def _slopes_call(self, fn, src, H, W, boxes, erode_iterations, weights):
+    def _slopes_call(self, fn, src, H, W, boxes, erode_iterations, weights, box_plane=None):
+        """``box_plane`` given: the pooled form, ``src`` = the Plane array, ``H`` = its length (``W`` unused)."""
         boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
         w = None if weights is None else np.ascontiguousarray(weights, np.float64).reshape(-1)
         slopes = np.zeros(boxes.shape[0], np.float64)
-        check(fn(self.h, src, int(H), int(W), _ptr(boxes), boxes.shape[0], int(erode_iterations), _ptr(w), 0 if w is None else w.shape[0] - 1, _ptr(slopes)),
+        front = (src, int(H), int(W), _ptr(boxes)) if box_plane is None else (src, int(H), _ptr(boxes), _ptr(box_plane))
+        check(fn(self.h, *front, boxes.shape[0], int(erode_iterations), _ptr(w), 0 if w is None else w.shape[0] - 1, _ptr(slopes)),
               "sbbseg_region_deskew_slopes")
         return [float(v) for v in slopes]
 
@@ -777,7 +789,7 @@ class Context:
             raise ValueError("region_deskew_slopes expects a uint8 plane [H, W]")
         return self._slopes_call(self.lib.sbbseg_region_deskew_slopes, _ptr(plane), plane.shape[0], plane.shape[1], boxes, erode_iterations, weights)
 
-    def _line_masks_call(self, fn, src, H, W, boxes, slopes, erode_iterations, masks):
+    def _line_masks_call(self, fn, src, H, W, boxes, slopes, erode_iterations, masks, box_plane=None):
         boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
         slopes = np.ascontiguousarray(slopes, np.float64).reshape(-1)
         n = boxes.shape[0]
@@ -789,7 +801,8 @@ class Context:
         out_masks = np.empty(int((w * h).sum()), np.uint8) if masks else None
         rows, cols = np.empty(int(h.sum()), np.int32), np.empty(int(w.sum()), np.int32)
         mo, ro, co = (np.zeros(n + 1, np.int64) for _ in range(3))
-        check(fn(self.h, src, int(H), int(W), _ptr(boxes), n, int(erode_iterations), _ptr(slopes), _ptr(out_masks), _ptr(rows), _ptr(cols),
+        front = (src, int(H), int(W), _ptr(boxes)) if box_plane is None else (src, int(H), _ptr(boxes), _ptr(box_plane))
+        check(fn(self.h, *front, n, int(erode_iterations), _ptr(slopes), _ptr(out_masks), _ptr(rows), _ptr(cols),
                  _ptr(mo), _ptr(ro), _ptr(co)), "sbbseg_region_line_masks")
         return [(out_masks[mo[r]:mo[r + 1]].reshape(int(h[r]), int(w[r])) if masks else None,
                  rows[ro[r]:ro[r + 1]].astype(np.int64), cols[co[r]:co[r + 1]].astype(np.int64)) for r in range(n)]
@@ -828,7 +841,8 @@ class Context:
                 records[r] = line_split_host([prof], [geom[r, 1]], [geom[r, 2]], [rots[r]], sigma_max)[0]
         return records
 
-    def _line_boxes_call(self, fn, src, d_src, H, W, boxes, slopes, erode_iterations, sigma_max):
+    def _line_boxes_call(self, fn, src, d_src, H, W, boxes, slopes, erode_iterations, sigma_max, box_plane=None):
+        """``d_src(r)``: (device pointer, H, W) of the plane of box r, for the one-box fallback."""
         boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
         slopes = np.ascontiguousarray(slopes, np.float64).reshape(-1)
         n = boxes.shape[0]
@@ -841,12 +855,13 @@ class Context:
         rots = np.array([line_rotation_terms(int(b[2]), int(b[3]), float(s)) for b, s in zip(boxes, slopes)], np.float64).reshape(n, 6)
         w, w_off = line_weight_table(sigma_max)
         out = _line_split_buffers(geom)
-        check(fn(self.h, src, int(H), int(W), _ptr(boxes), n, int(erode_iterations), _ptr(slopes), _ptr(rots), _ptr(w), _ptr(w_off), int(sigma_max),
+        front = (src, int(H), int(W), _ptr(boxes)) if box_plane is None else (src, int(H), _ptr(boxes), _ptr(box_plane))
+        check(fn(self.h, *front, n, int(erode_iterations), _ptr(slopes), _ptr(rots), _ptr(w), _ptr(w_off), int(sigma_max),
                  *[_ptr(a) for a in out]), "sbbseg_region_line_boxes")
         records = _line_records(*out)
         for r, rec in enumerate(records):
             if rec["status"] == LINES_SIGMA_TOO_LARGE:          # the profile of this one box, then the host twin with its sigma's weights
-                _m, rows, cols = self.region_line_masks_dev(d_src(), H, W, [boxes[r]], [slopes[r]], erode_iterations, False)[0]
+                _m, rows, cols = self.region_line_masks_dev(*d_src(r), [boxes[r]], [slopes[r]], erode_iterations, False)[0]
                 records[r] = line_split_host([cols if vertical[r] else rows], [geom[r, 1]], [geom[r, 2]], [rots[r]], sigma_max)[0]
         return records
 
@@ -854,7 +869,7 @@ class Context:
         """``region_line_masks_dev`` and then the line splitter of every box on its own profile (row sums, or column sums for
         ``abs(slope) > 45``, main.py:1514), the profiles staying on the device: a list of line records (``line_split_host``) -- see
         sbbseg.h.  The x extent of every line is the reference's fallback (0, w): the contour half is not built."""
-        return self._line_boxes_call(self.lib.sbbseg_region_line_boxes_dev, C.c_void_p(d_textlines), lambda: d_textlines, H, W, boxes, slopes,
+        return self._line_boxes_call(self.lib.sbbseg_region_line_boxes_dev, C.c_void_p(d_textlines), lambda r: (d_textlines, H, W), H, W, boxes, slopes,
                                      erode_iterations, sigma_max)
 
     def region_line_boxes(self, textlines: np.ndarray, boxes, slopes, erode_iterations: int = 2, sigma_max: int = LINE_SIGMA_MAX):
@@ -862,8 +877,37 @@ class Context:
         plane = np.ascontiguousarray(textlines, np.uint8)
         if plane.ndim != 2:
             raise ValueError("region_line_boxes expects a uint8 plane [H, W]")
-        return self._line_boxes_call(self.lib.sbbseg_region_line_boxes, _ptr(plane), lambda: self.stage(plane), plane.shape[0], plane.shape[1], boxes,
-                                     slopes, erode_iterations, sigma_max)
+        return self._line_boxes_call(self.lib.sbbseg_region_line_boxes, _ptr(plane), lambda r: (self.stage(plane), plane.shape[0], plane.shape[1]),
+                                     plane.shape[0], plane.shape[1], boxes, slopes, erode_iterations, sigma_max)
+
+    # -- the per-box calls for boxes on many planes (the resident textline planes of many pages: run_pages_planes) -------------
+    def planes_deskew_slopes_dev(self, planes, boxes_per_plane, erode_iterations: int = 2, weights=None):
+        """``region_deskew_slopes_dev`` for the boxes of MANY device planes in one call (``sbbseg_planes_deskew_slopes_dev``): ``planes`` =
+        [(device pointer, H, W)], ``boxes_per_plane`` = one box list per plane.  Returns one list of float per plane; every slope is bit
+        for bit what the one-plane call gives for that box on that plane, and the launches do not grow with the planes."""
+        arr, n_planes, boxes, box_plane, counts = _pool_planes(planes, boxes_per_plane)
+        out = self._slopes_call(self.lib.sbbseg_planes_deskew_slopes_dev, arr, n_planes, 0, boxes, erode_iterations, weights, box_plane)
+        return _unpool(out, counts)
+
+    def planes_line_masks_dev(self, planes, boxes_per_plane, slopes_per_plane, erode_iterations: int = 2, masks: bool = True):
+        """``region_line_masks_dev`` for the boxes of many device planes in one call (``sbbseg_planes_line_masks_dev``): one list of
+        (dst or None, row sums, column sums) per plane."""
+        arr, n_planes, boxes, box_plane, counts = _pool_planes(planes, boxes_per_plane, slopes_per_plane)
+        slopes = [float(v) for sl in slopes_per_plane for v in sl]
+        return _unpool(self._line_masks_call(self.lib.sbbseg_planes_line_masks_dev, arr, n_planes, 0, boxes, slopes, erode_iterations, masks, box_plane), counts)
+
+    def planes_line_boxes_dev(self, planes, boxes_per_plane, slopes_per_plane, erode_iterations: int = 2, sigma_max: int = LINE_SIGMA_MAX):
+        """``region_line_boxes_dev`` for the boxes of many device planes in one call (``sbbseg_planes_line_boxes_dev``): one list of line
+        records per plane.  A box whose sigma exceeds the device's table is finished by the host twin from a one-box call on its plane."""
+        arr, n_planes, boxes, box_plane, counts = _pool_planes(planes, boxes_per_plane, slopes_per_plane)
+        slopes = [float(v) for sl in slopes_per_plane for v in sl]
+        planes = [(int(d or 0), int(H), int(W)) for d, H, W in planes]
+        return _unpool(self._line_boxes_call(self.lib.sbbseg_planes_line_boxes_dev, arr, lambda r: planes[int(box_plane[r])], n_planes, 0, boxes, slopes,
+                                             erode_iterations, sigma_max, box_plane), counts)
+
+    def slope_sweep_launches(self) -> int:
+        """Kernels the deskew slope sweeps have queued on this handle so far (sbbseg_debug_counter 5)."""
+        return self.debug_counter(5)
 
     def line_mask_launches(self) -> int:
         """Kernels the line-mask and line-split calls have queued on this handle so far (sbbseg_debug_counter 2)."""
@@ -966,6 +1010,59 @@ def host_largest_contour(mask: np.ndarray):
     return tuple(int(v) for v in box), int(px.value)
 
 
+def _pool_planes(planes, boxes_per_plane, slopes_per_plane=None):
+    """(Plane array, number of planes, boxes int32 [n, 4], box_plane int32 [n], boxes per plane) of the pooled per-box calls; boxes in plane order."""
+    planes, boxes_per_plane = list(planes), [np.asarray(b, np.int64).reshape(-1, 4) for b in boxes_per_plane]
+    if len(boxes_per_plane) != len(planes):
+        raise ValueError("one box list per plane: %d planes, %d lists" % (len(planes), len(boxes_per_plane)))
+    counts = [b.shape[0] for b in boxes_per_plane]
+    if slopes_per_plane is not None and [len(sl) for sl in slopes_per_plane] != counts:
+        raise ValueError("one slope per box on every plane")
+    arr = (Plane * max(len(planes), 1))()
+    for k, (d, H, W) in enumerate(planes):
+        arr[k].d_hw, arr[k].H, arr[k].W = int(d) if d else None, int(H), int(W)
+    boxes = np.ascontiguousarray(np.concatenate(boxes_per_plane) if planes else np.zeros((0, 4)), np.int32).reshape(-1, 4)
+    box_plane = np.ascontiguousarray(np.repeat(np.arange(len(planes)), np.asarray(counts, np.int64)), np.int32)
+    return arr, len(planes), boxes, box_plane, counts
+
+
+def _unpool(flat, counts):
+    out, at = [], 0
+    for n in counts:
+        out.append(list(flat[at:at + n]))
+        at += n
+    return out
+
+
+def group_pages_for_lines(boxes_per_page, n_angles: int = 80, max_area: int = (1 << 31) - 1, max_counts: int = (1 << 31) - 1):
+    """Greedy grouping of consecutive pages so that every pooled per-box call stays under the library's limits ("too much work for one
+    call ... split the boxes"): the sum of the box areas of a group stays <= ``max_area`` and the sum of ``n_angles * S`` (S = the deskew
+    square's side, int(1.4 * max(h, w)); 80 angles in the first sweep, the larger one) stays <= ``max_counts``.  Returns a list of lists
+    of page indices, in order, every page in exactly one group and no group empty; a single page beyond a limit gets a group of its own
+    (the library then says so).  Pure Python."""
+    groups, area, counts = [], 0, 0
+    for k, boxes in enumerate(boxes_per_page):
+        a = sum(int(b[2]) * int(b[3]) for b in boxes)
+        c = sum(int(n_angles) * int(max(int(b[2]), int(b[3])) * 1.4) for b in boxes)
+        if groups and area + a <= max_area and counts + c <= max_counts:
+            groups[-1].append(k)
+            area, counts = area + a, counts + c
+        else:
+            groups.append([k])
+            area, counts = a, c
+    return groups
+
+
+def run_pages_planes(layout: "Context"):
+    """What the last :func:`run_pages` with ``layout`` as its layout handle left on the device (``sbbseg_run_pages_planes``): two lists, one
+    entry per page, of (device pointer, h, w) -- the cleaned layout plane and the textline plane of the page box; the pointer is 0 where
+    that page has none.  Valid until the next run_page / run_pages on those handles.  Raises after a failed or absent run_pages."""
+    n = getattr(layout, "_run_pages_n", None) or 1
+    regions, textlines = (Plane * n)(), (Plane * n)()
+    check(layout.lib.sbbseg_run_pages_planes(layout.h, n, regions, textlines), "sbbseg_run_pages_planes")
+    return ([(int(p.d_hw or 0), int(p.H), int(p.W)) for p in regions], [(int(p.d_hw or 0), int(p.H), int(p.W)) for p in textlines])
+
+
 def run_page(border: "Context", layout: "Context", textline: "Context", page: np.ndarray, scaled_h: int, scaled_w: int,
              channels: int = 3, want_mask: bool = True):
     """The model-running part of run() (main.py:2056-2107) in one library call (``sbbseg_run_page``): the page is uploaded once and
@@ -1012,7 +1109,9 @@ def run_pages(border: "Context", layout: "Context", textline: "Context", pages, 
         io[k].page, io[k].Hp, io[k].Wp, io[k].Hs, io[k].Ws = page.ctypes.data, page.shape[0], page.shape[1], scaled_h, scaled_w
         io[k].page_mask_out = mask.ctypes.data if want_mask else None
         io[k].regions_out, io[k].textlines_out = regions.ctypes.data, lines.ctypes.data
+    layout._run_pages_n = None
     check(border.lib.sbbseg_run_pages(border.h, layout.h, textline.h, n, io, channels), "sbbseg_run_pages")
+    layout._run_pages_n = n                                     # (run_pages_planes asks for as many)
     out = []
     for k, (_, mask, regions, lines) in enumerate(keep):
         info = RunInfo.from_buffer_copy(io[k].info)

@@ -575,8 +575,8 @@ int sbbseg_debug_inject_alloc_failure(int nth_check)
 int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value)
 {
     API_BEGIN
-    REQUIRE(c && value && which >= 0 && which <= 4, "unknown counter %d (0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by the line-mask calls, 3 = ingest / region-table / stitch kernels queued by sbbseg_segment_views_dev, 4 = ingest / label-resize kernels queued by the whole-views calls)", which);
-    *value = which == 0 ? (int64_t)c->host_contour_calls : which == 1 ? (int64_t)c->forwards : which == 2 ? (int64_t)c->line_launches : which == 3 ? c->views_launches : c->whole_launches;
+    REQUIRE(c && value && which >= 0 && which <= 5, "unknown counter %d (0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by the line-mask calls, 3 = ingest / region-table / stitch kernels queued by sbbseg_segment_views_dev, 4 = ingest / label-resize kernels queued by the whole-views calls, 5 = kernels queued by the deskew slope sweeps)", which);
+    *value = which == 0 ? (int64_t)c->host_contour_calls : which == 1 ? (int64_t)c->forwards : which == 2 ? (int64_t)c->line_launches : which == 3 ? c->views_launches : which == 4 ? c->whole_launches : (int64_t)c->slope_launches;
     return 0;
     API_END
 }

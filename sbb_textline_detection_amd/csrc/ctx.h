@@ -246,6 +246,11 @@ struct sbbseg_ctx {
     // sbbseg_run_pages: all pages' planes one after the other, and the textline planes in the layout handle's d_run_a)
     uint8_t *d_run_page = nullptr, *d_run_mask = nullptr, *d_run_a = nullptr, *d_run_b = nullptr;
     size_t run_page_cap = 0, run_mask_cap = 0, run_a_cap = 0, run_b_cap = 0;
+    // what the last sbbseg_run_pages left resident in this (layout) handle's d_run_b / d_run_a, page by page (sbbseg_run_pages_planes); no
+    // device memory of its own.  Emptied by a failed call and by the next sbbseg_run_page(s) that names the handle.
+    struct RunPlanes { size_t at; int w, h, regions_ok, textlines_ok; };
+    std::vector<RunPlanes> run_planes;
+    bool run_planes_valid = false;
     int *d_cc_parent = nullptr, *d_cc_count = nullptr; size_t cc_parent_cap = 0, cc_count_cap = 0;
     bool force_host_contours = false;     // test hook (conv variant bit 21): always take the exact host ranking
     int host_contour_calls = 0;           // how often the exact host ranking ran (sbbseg_debug_counter)
@@ -257,6 +262,7 @@ struct sbbseg_ctx {
     void* d_rdk = nullptr; size_t rdk_cap = 0;           // sbbseg_region_deskew_profiles_dev: maps | table | geometry | crops | counts
     void* d_pstat = nullptr; size_t pstat_cap = 0;       // sbbseg_profile_statistics_dev: weights | regions | spread | winner | state | workspace
     long long line_launches = 0;                         // kernels queued by sbbseg_region_line_masks_dev (sbbseg_debug_counter 2)
+    long long slope_launches = 0;                        // kernels queued by the slope sweeps: crop, profile, statistic, winner (sbbseg_debug_counter 5)
     void* d_lsplit = nullptr; size_t lsplit_cap = 0;     // sbbseg_line_split_dev: regions | info | lines | corners | rotated corners | workspace
     void* d_line_w = nullptr; size_t line_w_cap = 0;     // ... its table of half Gaussian kernels: offsets | weights, uploaded when it differs from
     std::vector<double> line_w_host;                     // ... this copy of the last one

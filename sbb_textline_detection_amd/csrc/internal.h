@@ -453,9 +453,13 @@ struct DeskewRegion {
     int row_groups;           // blocks per angle: ceil(S / kRegionDeskewRows)
 };
 constexpr int kRegionDeskewRows = 8;      // destination rows per block of region_deskew_profile_kernel (a wave per row, two rounds)
+// the label plane a region is cropped from, one record per region beside its DeskewRegion: the boxes of one call may lie on many planes
+struct DeskewPlane {
+    const uint8_t* base;      // [H][W] label plane (device), dense
+    int W, H;                 // H: for the host's box checks only
+};
 struct RegionDeskewParams {
-    const uint8_t* plane;     // [H][W] label plane (device)
-    int H, W;
+    const DeskewPlane* planes;// [n_regions] the plane of every region (read by the row pass of the crops only)
     const DeskewRegion* geom; // [n_regions]
     int n_regions, n_angles, radius;
     long long total_pix;      // sum of w * h

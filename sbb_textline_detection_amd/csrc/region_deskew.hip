@@ -31,17 +31,30 @@ __device__ __forceinline__ int region_of_pixel(const DeskewRegion* geom, int n, 
 }
 
 // cv2.erode with the 5x5 kernel, n iterations, on the CROP (default border: outside pixels never win) == one (4n+1)-wide minimum over
-// the window clipped to the crop, separable (as launch_morph): pass 0 along x from the plane, pass 1 along y from tmp
+// the window clipped to the crop, separable (as launch_morph): pass 0 along x from the region's plane, pass 1 along y from tmp.
+// Pass 0 is the only kernel that sees a plane: every region brings its own (pointer, width) in p.planes, so the boxes of one call may
+// lie on any number of planes; everything after it works on the packed crops.  Regions are packed one after the other, so a wave
+// usually lies inside one region: its plane record then comes through the scalar cache (loads only), per lane where a wave straddles
+// regions.
 __global__ __launch_bounds__(256) void region_crop_erode_kernel(const RegionDeskewParams p, int vertical)
 {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= p.total_pix) return;
-    const DeskewRegion& g = p.geom[region_of_pixel(p.geom, p.n_regions, idx)];
+    const int r = region_of_pixel(p.geom, p.n_regions, idx);
+    const DeskewRegion& g = p.geom[r];
     const int local = (int)(idx - g.crop_off);
     const int yy = local / g.w, xx = local - yy * g.w;
     int v = 255;
     if (!vertical) {
-        const uint8_t* row = p.plane + (size_t)(g.y + yy) * p.W + g.x;
+        // the record of the first lane's region through the scalar cache (a wave-uniform index; the values are pinned to scalar registers,
+        // or the compiler folds this load and the per-lane one below into one vector load) ...
+        const int r0 = __builtin_amdgcn_readfirstlane(r);
+        const uint64_t b0 = (uint64_t)(uintptr_t)p.planes[r0].base;
+        const uint8_t* base = (const uint8_t*)(uintptr_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b0 >> 32)) << 32) |
+                                                           (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b0));
+        int W = __builtin_amdgcn_readfirstlane(p.planes[r0].W);
+        if (r != r0) { base = p.planes[r].base; W = p.planes[r].W; }      // ... the lanes of a wave that straddles regions read their own
+        const uint8_t* row = base + (size_t)(g.y + yy) * W + g.x;
         const int lo = max(xx - p.radius, 0), hi = min(xx + p.radius, g.w - 1);
         for (int q = lo; q <= hi; ++q) v = min(v, (int)row[q]);
         p.tmp[idx] = (uint8_t)v;

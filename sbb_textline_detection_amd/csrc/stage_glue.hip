@@ -445,16 +445,50 @@ int sbbseg_deskew_profiles(sbbseg_ctx* c, const uint8_t* mask_hw, int H, int W, 
     API_END
 }
 
-// The checks every per-box entry point makes on box r, and the crop part of its DeskewRegion (what launch_region_deskew_crops reads;
-// crop_image_inside_box): the rest of *g is zeroed.
-static int crop_region(const int32_t* boxes_xywh, int r, int H, int W, long long crop_off, DeskewRegion* g)
+// Where the boxes of a per-box call lie: box r on planes[box_plane[r]] (pooled), or every box on planes[0] -- the one-plane entry points'
+// form, a table of one plane.
+struct PlaneSet {
+    const sbbseg_plane* planes;
+    int n_planes;
+    const int32_t* box_plane;
+    bool pooled;
+};
+static PlaneSet one_plane(sbbseg_plane* pl, const void* d_hw, int H, int W)
+{
+    pl->d_hw = d_hw; pl->H = H; pl->W = W;
+    return PlaneSet{pl, 1, nullptr, false};
+}
+
+static int check_plane_set(const PlaneSet& ps, int n_boxes)
+{
+    if (!ps.pooled) {
+        REQUIRE(ps.planes[0].H > 0 && ps.planes[0].W > 0, "bad arguments");
+        return 0;
+    }
+    REQUIRE(n_boxes <= 0 || (ps.planes && ps.box_plane), "bad arguments");
+    REQUIRE(n_boxes <= 0 || ps.n_planes >= 1, "%d boxes but %d planes (at least one plane is needed)", n_boxes, ps.n_planes);
+    return 0;
+}
+
+// The checks every per-box entry point makes on box r, the crop part of its DeskewRegion (what launch_region_deskew_crops reads;
+// crop_image_inside_box; the rest of *g is zeroed) and the record of the plane it is cropped from.
+static int crop_region(const PlaneSet& ps, const int32_t* boxes_xywh, int r, long long crop_off, DeskewRegion* g, DeskewPlane* src)
 {
     const int32_t* b = boxes_xywh + (size_t)r * 4;
+    const int k = ps.pooled ? ps.box_plane[r] : 0;
+    REQUIRE(k >= 0 && k < ps.n_planes, "box %d: plane %d out of range (0 .. %d)", r, k, ps.n_planes - 1);
+    const sbbseg_plane& pl = ps.planes[k];
     REQUIRE(b[2] >= 1 && b[3] >= 1, "box %d: width %d, height %d (both must be at least 1)", r, b[2], b[3]);
-    REQUIRE(b[0] >= 0 && b[1] >= 0 && (long long)b[0] + b[2] <= W && (long long)b[1] + b[3] <= H, "box %d (%d, %d, %d, %d) leaves the %d x %d plane",
-            r, b[0], b[1], b[2], b[3], W, H);
+    const bool inside = b[0] >= 0 && b[1] >= 0 && (long long)b[0] + b[2] <= pl.W && (long long)b[1] + b[3] <= pl.H;
+    if (ps.pooled) {
+        REQUIRE(inside, "box %d (%d, %d, %d, %d) leaves the %d x %d plane %d", r, b[0], b[1], b[2], b[3], pl.W, pl.H, k);
+        REQUIRE(pl.d_hw, "box %d: plane %d has no device pointer", r, k);
+    } else {
+        REQUIRE(inside, "box %d (%d, %d, %d, %d) leaves the %d x %d plane", r, b[0], b[1], b[2], b[3], pl.W, pl.H);
+    }
     memset(g, 0, sizeof(*g));
     g->x = b[0]; g->y = b[1]; g->w = b[2]; g->h = b[3]; g->crop_off = crop_off;
+    src->base = (const uint8_t*)pl.d_hw; src->W = pl.W; src->H = pl.H;
     return 0;
 }
 
@@ -463,19 +497,21 @@ static int crop_region(const int32_t* boxes_xywh, int r, int H, int W, long long
 // ([n_angles][S_r]), offsets[n_boxes] = the total.  size_only: only the offsets are computed (needs no handle).  Otherwise the sweep is
 // queued on the stream and *d_counts points at the packed counts in the handle's buffer: they STAY on the device.  `head` is the host
 // staging buffer of the tables: the caller keeps it alive until it has synchronised the stream.
-static int region_sweep(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+static int region_sweep(sbbseg_ctx* c, const PlaneSet& ps, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
                         const double* angles_deg, int n_angles, int64_t* offsets, bool size_only, std::vector<unsigned char>& head,
                         const int32_t** d_counts)
 {
     *d_counts = nullptr;
-    REQUIRE(H > 0 && W > 0 && n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && offsets && n_angles >= 1 && n_angles <= 4096 &&
+    REQUIRE(n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && offsets && n_angles >= 1 && n_angles <= 4096 &&
                 erode_iterations >= 0 && erode_iterations <= 64, "bad arguments");
+    if (check_plane_set(ps, n_boxes)) return 1;
     alloc_check();
     std::vector<DeskewRegion> geom((size_t)n_boxes);
+    std::vector<DeskewPlane> src((size_t)n_boxes);
     long long total_pix = 0, total_counts = 0, total_blocks = 0;
     for (int r = 0; r < n_boxes; ++r) {
         DeskewRegion& g = geom[r];
-        if (crop_region(boxes_xywh, r, H, W, total_pix, &g)) return 1;
+        if (crop_region(ps, boxes_xywh, r, total_pix, &g, &src[r])) return 1;
         g.S = (int)((double)(g.h > g.w ? g.h : g.w) * 1.4);                               // main.py:1613
         REQUIRE(g.S >= 1 && g.S <= 32767, "box %d: deskew square side %d out of range", r, g.S);
         const int cp = (int)(g.S / 2.0);
@@ -493,10 +529,11 @@ static int region_sweep(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, 
     offsets[n_boxes] = total_counts;
     if (size_only || n_boxes == 0) return 0;                       // (the size query needs no handle)
     if (check_ready(c)) return 1;
-    REQUIRE(d_textline_hw && angles_deg, "bad arguments");
-    // head of the device buffer, built on the host and copied in one piece: inverse maps | bicubic table | geometry
+    REQUIRE((ps.pooled || ps.planes[0].d_hw) && angles_deg, "bad arguments");
+    // head of the device buffer, built on the host and copied in one piece: inverse maps | bicubic table | geometry | planes
     const size_t minv_bytes = (size_t)n_boxes * n_angles * 6 * sizeof(double), tab_bytes = 128 * sizeof(float);
-    const size_t geom_off = minv_bytes + tab_bytes, head_bytes = align16(geom_off + (size_t)n_boxes * sizeof(DeskewRegion));
+    const size_t geom_off = minv_bytes + tab_bytes, src_off = geom_off + (size_t)n_boxes * sizeof(DeskewRegion);
+    const size_t head_bytes = align16(src_off + (size_t)n_boxes * sizeof(DeskewPlane));
     const size_t pix_bytes = align16((size_t)total_pix);
     head.assign(head_bytes, 0);
     double* minv = (double*)head.data();
@@ -508,10 +545,11 @@ static int region_sweep(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, 
         }
     cubic_table((float*)(head.data() + minv_bytes));
     memcpy(head.data() + geom_off, geom.data(), (size_t)n_boxes * sizeof(DeskewRegion));
+    memcpy(head.data() + src_off, src.data(), (size_t)n_boxes * sizeof(DeskewPlane));
     if (ensure(c, &c->d_rdk, &c->rdk_cap, head_bytes + 2 * pix_bytes + (size_t)total_counts * sizeof(int))) return 1;
     unsigned char* d = (unsigned char*)c->d_rdk;
     RegionDeskewParams p;
-    p.plane = (const uint8_t*)d_textline_hw; p.H = H; p.W = W;
+    p.planes = (const DeskewPlane*)(d + src_off);
     p.geom = (const DeskewRegion*)(d + geom_off); p.n_regions = n_boxes; p.n_angles = n_angles; p.radius = 2 * erode_iterations;
     p.total_pix = total_pix;
     p.minv = (const double*)d; p.cubic = (const float*)(d + minv_bytes);
@@ -520,6 +558,7 @@ static int region_sweep(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, 
     HIPCHK(hipMemcpyAsync(d, head.data(), head_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(launch_region_deskew_crops(p, c->stream));
     HIPCHK(launch_region_deskew_profiles(p, c->stream));
+    c->slope_launches += 3;
     *d_counts = p.counts;
     return 0;
 }
@@ -531,7 +570,8 @@ int sbbseg_region_deskew_profiles_dev(sbbseg_ctx* c, const void* d_textline_hw, 
     API_BEGIN
     std::vector<unsigned char> head;
     const int32_t* d_counts = nullptr;
-    if (region_sweep(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, angles_deg, n_angles, offsets, !counts, head, &d_counts)) return 1;
+    sbbseg_plane pl;
+    if (region_sweep(c, one_plane(&pl, d_textline_hw, H, W), boxes_xywh, n_boxes, erode_iterations, angles_deg, n_angles, offsets, !counts, head, &d_counts)) return 1;
     if (!d_counts) return 0;
     HIPCHK(hipMemcpyAsync(counts, d_counts, (size_t)offsets[n_boxes] * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffer lives until here)
@@ -646,6 +686,7 @@ static int profile_stats_queue(sbbseg_ctx* c, const int32_t* d_counts, const int
     p.workspace = (double*)(d + ws_off); p.spread = (double*)(d + spread_off); p.state = d + state_off; p.winner = (int32_t*)(d + winner_off);
     HIPCHK(hipMemcpyAsync(d, head.data(), head_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(launch_profile_statistics(p, ws_doubles > 0, c->stream));
+    c->slope_launches += ws_doubles > 0 ? 3 : 2;
     *out = p;
     return 0;
 }
@@ -672,13 +713,13 @@ int sbbseg_profile_statistics_dev(sbbseg_ctx* c, const void* d_counts, const int
 }
 
 // one sweep of all `boxes`: rotate-and-project, statistic, selection; the winners come back, the counts do not
-static int slopes_sweep(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+static int slopes_sweep(sbbseg_ctx* c, const PlaneSet& ps, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
                         const double* angles, int n_angles, const double* weights, int radius, std::vector<int32_t>& winner)
 {
     std::vector<int64_t> offsets((size_t)n_boxes + 1);
     std::vector<unsigned char> head_sweep, head_stat;
     const int32_t* d_counts = nullptr;
-    if (region_sweep(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, angles, n_angles, offsets.data(), false, head_sweep, &d_counts)) return 1;
+    if (region_sweep(c, ps, boxes_xywh, n_boxes, erode_iterations, angles, n_angles, offsets.data(), false, head_sweep, &d_counts)) return 1;
     ProfileStatParams p;
     if (profile_stats_queue(c, d_counts, offsets.data(), n_boxes, n_angles, weights, radius, 20.3, head_stat, &p)) return 1;      // main.py:1644
     winner.resize((size_t)n_boxes);
@@ -687,35 +728,53 @@ static int slopes_sweep(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, 
     return 0;
 }
 
-int sbbseg_region_deskew_slopes_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
-                                    int erode_iterations, const double* weights, int radius, double* slopes)
+static int region_slopes(sbbseg_ctx* c, const PlaneSet& ps, const int32_t* boxes_xywh, int n_boxes, int erode_iterations, const double* weights,
+                         int radius, double* slopes)
 {
-    API_BEGIN
     if (check_ready(c)) return 1;
-    REQUIRE(H > 0 && W > 0 && n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && (slopes || n_boxes == 0), "bad arguments");
+    REQUIRE(n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && (slopes || n_boxes == 0), "bad arguments");
+    if (check_plane_set(ps, n_boxes)) return 1;
     REQUIRE(radius >= 0 && radius <= (1 << 16), "radius %d out of range (0 .. 65536)", radius);
     if (n_boxes == 0) return 0;
-    REQUIRE(d_textline_hw, "bad arguments");
+    REQUIRE(ps.pooled || ps.planes[0].d_hw, "bad arguments");
     alloc_check();
     double first[kSweeps[0].n], second[kSweeps[1].n];
     sweep_angles(0, first); sweep_angles(1, second);
     std::vector<int32_t> winner;
-    if (slopes_sweep(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, first, kSweeps[0].n, weights, radius, winner)) return 1;
-    std::vector<int32_t> steep, steep_boxes;
+    if (slopes_sweep(c, ps, boxes_xywh, n_boxes, erode_iterations, first, kSweeps[0].n, weights, radius, winner)) return 1;
+    std::vector<int32_t> steep, steep_boxes, steep_plane;              // the steep boxes are cropped again: their planes travel with them
     for (int r = 0; r < n_boxes; ++r) {
         slopes[r] = winner[r] < 0 ? 0.0 : first[winner[r]];
         if (std::fabs(slopes[r]) > 15.0) {                          // main.py:1669-1670
             steep.push_back(r);
             steep_boxes.insert(steep_boxes.end(), boxes_xywh + (size_t)r * 4, boxes_xywh + (size_t)r * 4 + 4);
+            if (ps.pooled) steep_plane.push_back(ps.box_plane[r]);
         }
     }
     if (!steep.empty()) {
-        if (slopes_sweep(c, d_textline_hw, H, W, steep_boxes.data(), (int)steep.size(), erode_iterations, second, kSweeps[1].n, weights, radius, winner)) return 1;
+        const PlaneSet again{ps.planes, ps.n_planes, ps.pooled ? steep_plane.data() : nullptr, ps.pooled};
+        if (slopes_sweep(c, again, steep_boxes.data(), (int)steep.size(), erode_iterations, second, kSweeps[1].n, weights, radius, winner)) return 1;
         for (size_t k = 0; k < steep.size(); ++k) slopes[steep[k]] = winner[k] < 0 ? 0.0 : second[winner[k]];
     }
     for (int r = 0; r < n_boxes; ++r)
         if (std::fabs(slopes[r]) > 120.5) slopes[r] = 0.0;          // main.py:1746-1747
     return 0;
+}
+
+int sbbseg_region_deskew_slopes_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes,
+                                    int erode_iterations, const double* weights, int radius, double* slopes)
+{
+    API_BEGIN
+    sbbseg_plane pl;
+    return region_slopes(c, one_plane(&pl, d_textline_hw, H, W), boxes_xywh, n_boxes, erode_iterations, weights, radius, slopes);
+    API_END
+}
+
+int sbbseg_planes_deskew_slopes_dev(sbbseg_ctx* c, const sbbseg_plane* planes, int n_planes, const int32_t* boxes_xywh, const int32_t* box_plane,
+                                    int n_boxes, int erode_iterations, const double* weights, int radius, double* slopes)
+{
+    API_BEGIN
+    return region_slopes(c, PlaneSet{planes, n_planes, box_plane, true}, boxes_xywh, n_boxes, erode_iterations, weights, radius, slopes);
     API_END
 }
 
@@ -806,20 +865,22 @@ int sbbseg_region_line_masks_host(const uint8_t* crop_hw, int h, int w, int erod
 
 // queues crop / erode / OPEN / CLOSE / warp / sums of all boxes; *out holds the device pointers of the results (in c->d_rdk), out->n_regions
 // == 0 when there is nothing to do.  `need_sums`: what a caller that downloads rows and cols must have passed.
-static int region_line_masks_queue(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+static int region_line_masks_queue(sbbseg_ctx* c, const PlaneSet& ps, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
                                    const double* slopes, bool need_sums, int64_t* mask_off, int64_t* row_off, int64_t* col_off,
                                    std::vector<unsigned char>& head, RegionLinesParams* out, long long* rows_total)
 {
     out->n_regions = 0;
-    REQUIRE(H > 0 && W > 0 && n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && mask_off && row_off && col_off &&
+    REQUIRE(n_boxes >= 0 && n_boxes <= (1 << 20) && (boxes_xywh || n_boxes == 0) && mask_off && row_off && col_off &&
                 erode_iterations >= 0 && erode_iterations <= 64, "bad arguments");
+    if (check_plane_set(ps, n_boxes)) return 1;
     alloc_check();
     std::vector<DeskewRegion> crop_geom((size_t)n_boxes);
+    std::vector<DeskewPlane> src((size_t)n_boxes);
     std::vector<LineRegion> geom((size_t)n_boxes);
     long long total_pix = 0, total_rows = 0, total_cols = 0, total_blocks = 0;
     for (int r = 0; r < n_boxes; ++r) {
         DeskewRegion& cg = crop_geom[r];
-        if (crop_region(boxes_xywh, r, H, W, total_pix, &cg)) return 1;
+        if (crop_region(ps, boxes_xywh, r, total_pix, &cg, &src[r])) return 1;
         LineRegion& g = geom[r];
         g.w = cg.w; g.h = cg.h; g.crop_off = total_pix; g.row_off = (int)total_rows; g.col_off = (int)total_cols; g.block0 = (int)total_blocks; g.pad = 0;
         mask_off[r] = total_pix; row_off[r] = total_rows; col_off[r] = total_cols;
@@ -832,26 +893,28 @@ static int region_line_masks_queue(sbbseg_ctx* c, const void* d_textline_hw, int
     mask_off[n_boxes] = total_pix; row_off[n_boxes] = total_rows; col_off[n_boxes] = total_cols;
     if (n_boxes == 0) return 0;
     if (check_ready(c)) return 1;
-    REQUIRE(d_textline_hw && slopes && need_sums, "bad arguments");
+    REQUIRE((ps.pooled || ps.planes[0].d_hw) && slopes && need_sums, "bad arguments");
     if (!c->d_line_tab) {
         std::vector<int16_t> itab;
         line_table(itab);
         if (upload(c, &c->d_line_tab, itab.data(), itab.size())) return 1;
     }
-    // head of the device buffer, built on the host and copied in one piece: inverse maps | crop geometry | line geometry
+    // head of the device buffer, built on the host and copied in one piece: inverse maps | crop geometry | line geometry | planes
     const size_t minv_bytes = (size_t)n_boxes * 6 * sizeof(double), cgeom_bytes = (size_t)n_boxes * sizeof(DeskewRegion);
-    const size_t lgeom_off = minv_bytes + cgeom_bytes, head_bytes = align16(lgeom_off + (size_t)n_boxes * sizeof(LineRegion));
+    const size_t lgeom_off = minv_bytes + cgeom_bytes, src_off = lgeom_off + (size_t)n_boxes * sizeof(LineRegion);
+    const size_t head_bytes = align16(src_off + (size_t)n_boxes * sizeof(DeskewPlane));
     const size_t pix_bytes = align16((size_t)total_pix);
     head.assign(head_bytes, 0);
     for (int r = 0; r < n_boxes; ++r)
         if (line_inverse_map(geom[r].h, geom[r].w, slopes[r], (double*)head.data() + (size_t)r * 6)) return 1;
     memcpy(head.data() + minv_bytes, crop_geom.data(), cgeom_bytes);
     memcpy(head.data() + lgeom_off, geom.data(), (size_t)n_boxes * sizeof(LineRegion));
+    memcpy(head.data() + src_off, src.data(), (size_t)n_boxes * sizeof(DeskewPlane));
     if (ensure(c, &c->d_rdk, &c->rdk_cap, head_bytes + 3 * pix_bytes + (size_t)(total_rows + total_cols) * sizeof(int))) return 1;
     unsigned char* d = (unsigned char*)c->d_rdk;
     RegionDeskewParams cp;
     memset(&cp, 0, sizeof(cp));
-    cp.plane = (const uint8_t*)d_textline_hw; cp.H = H; cp.W = W;
+    cp.planes = (const DeskewPlane*)(d + src_off);
     cp.geom = (const DeskewRegion*)(d + minv_bytes); cp.n_regions = n_boxes; cp.radius = 2 * erode_iterations; cp.total_pix = total_pix;
     cp.tmp = d + head_bytes; cp.crops = d + head_bytes + pix_bytes;
     RegionLinesParams p;
@@ -869,21 +932,37 @@ static int region_line_masks_queue(sbbseg_ctx* c, const void* d_textline_hw, int
     return 0;
 }
 
-int sbbseg_region_line_masks_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
-                                 const double* slopes, uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off, int64_t* row_off, int64_t* col_off)
+static int region_line_masks(sbbseg_ctx* c, const PlaneSet& ps, const int32_t* boxes_xywh, int n_boxes, int erode_iterations, const double* slopes,
+                             uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off, int64_t* row_off, int64_t* col_off)
 {
-    API_BEGIN
     std::vector<unsigned char> head;
     RegionLinesParams p;
     long long total_rows = 0;
-    if (region_line_masks_queue(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, slopes, rows && cols, mask_off, row_off, col_off, head, &p,
-                                &total_rows)) return 1;
+    if (region_line_masks_queue(c, ps, boxes_xywh, n_boxes, erode_iterations, slopes, rows && cols, mask_off, row_off, col_off, head, &p, &total_rows)) return 1;
     if (p.n_regions == 0) return 0;
     if (masks) HIPCHK(hipMemcpyAsync(masks, p.mask, (size_t)p.total_pix, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(rows, p.rows, (size_t)total_rows * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(cols, p.cols, (size_t)p.total_cols * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffer lives until here)
     return 0;
+}
+
+int sbbseg_region_line_masks_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                                 const double* slopes, uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off, int64_t* row_off, int64_t* col_off)
+{
+    API_BEGIN
+    sbbseg_plane pl;
+    return region_line_masks(c, one_plane(&pl, d_textline_hw, H, W), boxes_xywh, n_boxes, erode_iterations, slopes, masks, rows, cols, mask_off, row_off, col_off);
+    API_END
+}
+
+int sbbseg_planes_line_masks_dev(sbbseg_ctx* c, const sbbseg_plane* planes, int n_planes, const int32_t* boxes_xywh, const int32_t* box_plane, int n_boxes,
+                                 int erode_iterations, const double* slopes, uint8_t* masks, int32_t* rows, int32_t* cols, int64_t* mask_off,
+                                 int64_t* row_off, int64_t* col_off)
+{
+    API_BEGIN
+    return region_line_masks(c, PlaneSet{planes, n_planes, box_plane, true}, boxes_xywh, n_boxes, erode_iterations, slopes, masks, rows, cols, mask_off, row_off,
+                             col_off);
     API_END
 }
 
@@ -1038,11 +1117,10 @@ int sbbseg_line_split_dev(sbbseg_ctx* c, const void* d_profiles, const int64_t* 
     API_END
 }
 
-int sbbseg_region_line_boxes_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
-                                 const double* slopes, const double* rot, const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info,
-                                 int64_t* line_off, int32_t* lines, int32_t* corners, int32_t* corners_rot)
+static int region_line_boxes(sbbseg_ctx* c, const PlaneSet& ps, const int32_t* boxes_xywh, int n_boxes, int erode_iterations, const double* slopes,
+                             const double* rot, const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info, int64_t* line_off,
+                             int32_t* lines, int32_t* corners, int32_t* corners_rot)
 {
-    API_BEGIN
     REQUIRE(n_boxes >= 0 && n_boxes <= (1 << 20) && line_off && ((boxes_xywh && slopes && rot) || n_boxes == 0), "bad arguments");
     alloc_check();
     std::vector<int64_t> mask_off((size_t)n_boxes + 1), row_off((size_t)n_boxes + 1), col_off((size_t)n_boxes + 1), prof_off((size_t)n_boxes + 1);
@@ -1050,7 +1128,7 @@ int sbbseg_region_line_boxes_dev(sbbseg_ctx* c, const void* d_textline_hw, int H
     std::vector<unsigned char> head_masks, head_split;
     RegionLinesParams lp;
     long long total_rows = 0;
-    if (region_line_masks_queue(c, d_textline_hw, H, W, boxes_xywh, n_boxes, erode_iterations, slopes, true, mask_off.data(), row_off.data(), col_off.data(),
+    if (region_line_masks_queue(c, ps, boxes_xywh, n_boxes, erode_iterations, slopes, true, mask_off.data(), row_off.data(), col_off.data(),
                                 head_masks, &lp, &total_rows)) return 1;
     // rows and cols are one device array (cols behind rows): a region's profile is its row sums, or its column sums beyond 45 degrees
     // (main.py:1514)
@@ -1069,6 +1147,26 @@ int sbbseg_region_line_boxes_dev(sbbseg_ctx* c, const void* d_textline_hw, int H
     LineSplitParams p;
     if (line_split_queue(c, lp.rows, prof_off.data(), n_boxes, geom.data(), rot, weights, weight_off, sigma_max, line_off, head_split, &p)) return 1;
     return line_split_download(c, p, line_off, info, lines, corners, corners_rot);
+}
+
+int sbbseg_region_line_boxes_dev(sbbseg_ctx* c, const void* d_textline_hw, int H, int W, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
+                                 const double* slopes, const double* rot, const double* weights, const int64_t* weight_off, int sigma_max, int32_t* info,
+                                 int64_t* line_off, int32_t* lines, int32_t* corners, int32_t* corners_rot)
+{
+    API_BEGIN
+    sbbseg_plane pl;
+    return region_line_boxes(c, one_plane(&pl, d_textline_hw, H, W), boxes_xywh, n_boxes, erode_iterations, slopes, rot, weights, weight_off, sigma_max, info,
+                             line_off, lines, corners, corners_rot);
+    API_END
+}
+
+int sbbseg_planes_line_boxes_dev(sbbseg_ctx* c, const sbbseg_plane* planes, int n_planes, const int32_t* boxes_xywh, const int32_t* box_plane, int n_boxes,
+                                 int erode_iterations, const double* slopes, const double* rot, const double* weights, const int64_t* weight_off,
+                                 int sigma_max, int32_t* info, int64_t* line_off, int32_t* lines, int32_t* corners, int32_t* corners_rot)
+{
+    API_BEGIN
+    return region_line_boxes(c, PlaneSet{planes, n_planes, box_plane, true}, boxes_xywh, n_boxes, erode_iterations, slopes, rot, weights, weight_off, sigma_max, info,
+                             line_off, lines, corners, corners_rot);
     API_END
 }
 

@@ -262,6 +262,7 @@ int sbbseg_run_page(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline
     if (check_ready(border) || check_ready(layout) || check_ready(textline)) return 1;
     REQUIRE(page_hwc && info && regions_out && textlines_out && Hp > 0 && Wp > 0 && Hs > 0 && Ws > 0 && (channels == 1 || channels == 3), "bad arguments");
     REQUIRE(border->device == layout->device && border->device == textline->device, "the three handles must live on one device");
+    border->run_planes_valid = layout->run_planes_valid = textline->run_planes_valid = false;      // (the call rewrites the resident planes)
     memset(info, 0, sizeof(*info));
     const size_t spix = (size_t)Hp * Wp, pix = (size_t)Hs * Ws;
     if (ensure(border, (void**)&border->d_run_page, &border->run_page_cap, spix * 3)) return 1;
@@ -314,14 +315,11 @@ int sbbseg_run_page(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline
 // take all pages' crops in one sbbseg_segment_views_dev call each; masks, region maps and textline maps stay on the device between their
 // model and their glue.  What run() swallows for a page -- a crop that cannot hold a model input -- is decided by geometry before the
 // pooled call; any failure of a library call is a device or allocation error and fails the whole call.
-int sbbseg_run_pages(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline, int n_pages, sbbseg_run_page_io* pages, int channels)
+static int run_pages_impl(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline, int n_pages, sbbseg_run_page_io* pages, int channels,
+                          std::vector<size_t>& crop_at)
 {
-    API_BEGIN
-    if (check_ready(border) || check_ready(layout) || check_ready(textline)) return 1;
-    REQUIRE(n_pages >= 1 && pages && (channels == 1 || channels == 3), "bad arguments");
-    REQUIRE(border->device == layout->device && border->device == textline->device, "the three handles must live on one device");
-    alloc_check();
-    std::vector<size_t> page_at(n_pages), mask_at(n_pages), crop_at(n_pages, 0);
+    std::vector<size_t> page_at(n_pages), mask_at(n_pages);
+    crop_at.assign(n_pages, 0);
     size_t page_bytes = 0, mask_bytes = 0, crop_bytes = 0;
     for (int k = 0; k < n_pages; ++k) {
         sbbseg_run_page_io& pg = pages[k];
@@ -399,6 +397,45 @@ int sbbseg_run_pages(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textlin
         sbbseg_run_page_io& pg = pages[k];
         if (sbbseg_download_labels(textline, pg.textlines_out, layout->d_run_a + crop_at[k], (size_t)pg.info.box_xywh[2] * pg.info.box_xywh[3], 1)) return drain_after_failure(textline);
         pg.info.textlines_ok = 1;
+    }
+    return 0;
+}
+
+// STREAMS: when the call returns 0 the streams of all three handles have been synchronised behind everything it queued -- the border
+// handle's at the hand-over, the other two by the download of every plane they wrote (the textline planes lie in the LAYOUT handle's buffer
+// but are written on the textline handle's stream: their downloads wait for that stream).  So any handle may read the resident planes
+// (sbbseg_run_pages_planes) without a further synchronisation.
+int sbbseg_run_pages(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline, int n_pages, sbbseg_run_page_io* pages, int channels)
+{
+    API_BEGIN
+    if (check_ready(border) || check_ready(layout) || check_ready(textline)) return 1;
+    border->run_planes_valid = layout->run_planes_valid = textline->run_planes_valid = false;
+    REQUIRE(n_pages >= 1 && pages && (channels == 1 || channels == 3), "bad arguments");
+    REQUIRE(border->device == layout->device && border->device == textline->device, "the three handles must live on one device");
+    alloc_check();
+    std::vector<size_t> crop_at;
+    if (run_pages_impl(border, layout, textline, n_pages, pages, channels, crop_at)) return 1;
+    layout->run_planes.resize((size_t)n_pages);
+    for (int k = 0; k < n_pages; ++k) {
+        const sbbseg_run_info& i = pages[k].info;
+        layout->run_planes[k] = {crop_at[k], i.box_xywh[2], i.box_xywh[3], pages[k].status == 0 && i.regions_ok, pages[k].status == 0 && i.textlines_ok};
+    }
+    layout->run_planes_valid = true;
+    return 0;
+    API_END
+}
+
+int sbbseg_run_pages_planes(sbbseg_ctx* layout, int n_pages, sbbseg_plane* regions, sbbseg_plane* textlines)
+{
+    API_BEGIN
+    if (check_ready(layout)) return 1;
+    REQUIRE(regions && textlines && n_pages >= 1, "bad arguments");
+    REQUIRE(layout->run_planes_valid, "no resident planes: the last sbbseg_run_pages on this layout handle failed, was overwritten by a later sbbseg_run_page, or never ran");
+    REQUIRE((size_t)n_pages == layout->run_planes.size(), "%d pages asked for, the last sbbseg_run_pages ran %d", n_pages, (int)layout->run_planes.size());
+    for (int k = 0; k < n_pages; ++k) {
+        const sbbseg_ctx::RunPlanes& rp = layout->run_planes[k];
+        regions[k] = {rp.regions_ok ? layout->d_run_b + rp.at : nullptr, rp.h, rp.w};
+        textlines[k] = {rp.textlines_ok ? layout->d_run_a + rp.at : nullptr, rp.h, rp.w};
     }
     return 0;
     API_END

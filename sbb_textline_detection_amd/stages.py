@@ -646,3 +646,42 @@ class InferenceStages:
         finally:
             for _, session in opened:
                 session.close()
+
+    def run_pages_with_line_boxes(self, images, masks: bool = False):
+        """``[self.run_with_line_boxes(img, masks=masks) for img in images]`` with everything between the stored pages and the text lines
+        resident: ONE ``sbbseg_run_pages`` (``run_pages(resident=True)``: raises what it raises), then, on the planes that call leaves on
+        the device (``_capi.run_pages_planes``), the text-region boxes page by page on the cleaned layout plane (the component
+        labelling works on one plane at a time) and ONE pooled call each for the slopes, the line masks and the line boxes of all pages'
+        boxes (``planes_deskew_slopes_dev`` / ``planes_line_masks_dev`` / ``planes_line_boxes_dev``): no label map is uploaded again and
+        the launches do not grow with the pages.  Pages are grouped (``_capi.group_pages_for_lines``) so that an archive beyond the
+        library's per-call limits becomes several pooled calls.  Returns per page run_with_line_boxes' 8-tuple; boxes, slopes, masks
+        and lines are [] where the textline model did not run.  The line-mask call runs only to return what run_with_lines returns (the
+        line-boxes call repeats its kernels: the C entry points share no outputs).  Foreign model objects take the loop."""
+        images = list(images)
+        opened = [start_new_session_and_model(d, **self.kw) for d in (self.model_page_dir, self.model_region_dir, self.model_textline_dir)]
+        try:
+            if not all(isinstance(m, SegModel) for m, _ in opened):
+                return [self.run_with_line_boxes(img, masks=masks) for img in images]
+            if not images:
+                return []
+            from . import _capi
+            c_region, c_text = opened[1][0].ctx, opened[2][0].ctx
+            runs = self.run_pages(images, resident=True)
+            d_regions, d_textlines = _capi.run_pages_planes(c_region)
+            n = len(runs)
+            has_lines = [runs[k][2] is not None for k in range(n)]
+            boxes = [c_region.text_region_boxes_dev(*d_regions[k], 1, 0.00001, 1.0) if has_lines[k] else [] for k in range(n)]
+            slopes, line_masks, line_boxes = [[] for _ in range(n)], [[] for _ in range(n)], [[] for _ in range(n)]
+            for group in _capi.group_pages_for_lines(boxes):
+                planes, gb = [d_textlines[k] for k in group], [boxes[k] for k in group]
+                if not any(gb):
+                    continue
+                gs = c_text.planes_deskew_slopes_dev(planes, gb, 2)
+                gm = c_text.planes_line_masks_dev(planes, gb, gs, 2, masks)
+                gl = c_text.planes_line_boxes_dev(planes, gb, gs, 2)
+                for q, k in enumerate(group):
+                    slopes[k], line_masks[k], line_boxes[k] = gs[q], gm[q], gl[q]
+            return [runs[k] + (boxes[k], slopes[k], line_masks[k], line_boxes[k]) for k in range(n)]
+        finally:
+            for _, session in opened:
+                session.close()
