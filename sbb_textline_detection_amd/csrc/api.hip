@@ -29,26 +29,13 @@ int set_error(const char* fmt, ...)
     return 1;
 }
 
-int dmalloc(sbbseg_ctx* c, void** p, size_t bytes)
-{
-    HIPCHK(hipMalloc(p, bytes));
-    c->device_bytes += bytes;
-    return 0;
-}
+// The two allocators behind a handle's registries (ctx.h: mem, pinned).  Nothing else in the library allocates or frees device or pinned memory.
+static int hip_device_alloc(void** p, size_t bytes) { HIPCHK(hipMalloc(p, bytes)); return 0; }
+static int hip_device_free(void* p) { HIPCHK(hipFree(p)); return 0; }
+static int hip_pinned_alloc(void** p, size_t bytes) { HIPCHK(hipHostMalloc(p, bytes, hipHostMallocDefault)); return 0; }
+static int hip_pinned_free(void* p) { HIPCHK(hipHostFree(p)); return 0; }
 
-int ensure(sbbseg_ctx* c, void** p, size_t* cap, size_t bytes)
-{
-    if (*cap >= bytes) return 0;
-    if (*p) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipFree(*p));
-        c->device_bytes -= *cap;
-        *p = nullptr; *cap = 0;
-    }
-    if (dmalloc(c, p, bytes)) return 1;
-    *cap = bytes;
-    return 0;
-}
+int dmalloc(sbbseg_ctx* c, void** p, size_t bytes) { return c->mem.alloc(p, bytes); }
 
 int check_ready(sbbseg_ctx* c)
 {
@@ -63,9 +50,9 @@ int check_ready(sbbseg_ctx* c)
 int labels_to_host(sbbseg_ctx* c, const void* d_plane, void* host, size_t pixels, int channels)
 {
     if (channels == 3) {
-        if (ensure(c, (void**)&c->d_page_labels3, &c->page_labels3_cap, (pixels + 3) / 4 * 12)) return 1;
-        HIPCHK(launch_replicate3((const uint8_t*)d_plane, c->d_page_labels3, pixels, c->stream));
-        HIPCHK(hipMemcpyAsync(host, c->d_page_labels3, pixels * 3, hipMemcpyDeviceToHost, c->stream));
+        if (ensure(c, c->page_labels3, (pixels + 3) / 4 * 12)) return 1;
+        HIPCHK(launch_replicate3((const uint8_t*)d_plane, c->page_labels3.p, pixels, c->stream));
+        HIPCHK(hipMemcpyAsync(host, c->page_labels3.p, pixels * 3, hipMemcpyDeviceToHost, c->stream));
     } else {
         HIPCHK(hipMemcpyAsync(host, d_plane, pixels, hipMemcpyDeviceToHost, c->stream));
     }
@@ -102,7 +89,7 @@ int sbbseg_create(int device, int precision, sbbseg_ctx** out)
     HIPCHK(hipGetDeviceProperties(&prop, device));
     REQUIRE(strncmp(prop.gcnArchName, "gfx950", 6) == 0,
             "libsbbseg is built for gfx950 (MI355X) only; device %d is %s", device, prop.gcnArchName);
-    sbbseg_ctx* c = new sbbseg_ctx();
+    sbbseg_ctx* c = new sbbseg_ctx(hip_device_alloc, hip_device_free, hip_pinned_alloc, hip_pinned_free);
     c->device = device;
     c->precision = precision;
     c->elem = precision == SBBSEG_PREC_F32 ? 4 : 2;
@@ -149,46 +136,10 @@ int sbbseg_destroy(sbbseg_ctx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->lane_stream) (void)hipStreamSynchronize(c->lane_stream);
-    for (auto& t : c->tensors) {
-        (void)hipFree(t.lane_buf[0]);
-        (void)hipFree(t.lane_buf[1]);
-    }
-    std::vector<Op*> all_ops;
-    for (auto& op : c->ops) {
-        all_ops.push_back(&op);
-        for (auto& part : op.parts) all_ops.push_back(&part);
-    }
-    for (Op* opp : all_ops) {
-        Op& op = *opp;
-        (void)hipFree(op.block.d_w1); (void)hipFree(op.block.d_w3);
-        for (int q = 0; q < 4; ++q) (void)hipFree(op.conv.d_fgstep_cls[q]);
-        (void)hipFree(op.conv.d_ktab); (void)hipFree(op.conv.d_kstep); (void)hipFree(op.conv.d_w); (void)hipFree(op.conv.d_scale); (void)hipFree(op.conv.d_shift);
-        (void)hipFree(op.conv.d_rscale); (void)hipFree(op.conv.d_rshift);
-        (void)hipFree(op.conv.d_head_w); (void)hipFree(op.conv.d_head_scale); (void)hipFree(op.conv.d_head_shift); (void)hipFree(op.conv.d_stem_wfrag); (void)hipFree(op.conv.d_d64_wfrag);
-        (void)hipFree(op.conv.d_halo_wfrag); (void)hipFree(op.conv.d_halo_taps);
-        (void)hipFree(op.conv.d_er_w3); (void)hipFree(op.conv.d_er_w1);
-        (void)hipFree(op.conv.d_c3_w2); (void)hipFree(op.conv.d_c3_k0);
-        for (int q = 1; q < 4; ++q) { (void)hipFree(op.conv.d_w_cls[q]); (void)hipFree(op.conv.d_kstep_cls[q]); (void)hipFree(op.conv.d_ktab_cls[q]); }
-        (void)hipFree(op.head.d_w); (void)hipFree(op.head.d_scale); (void)hipFree(op.head.d_shift);
-        (void)hipFree(op.pool.d_pre_scale); (void)hipFree(op.pool.d_pre_shift);
-        (void)hipFree(op.tail.d_wfrag); (void)hipFree(op.tail.d_scale); (void)hipFree(op.tail.d_shift); (void)hipFree(op.tail.d_head_w);
-        (void)hipFree(op.tail.d_head_scale); (void)hipFree(op.tail.d_head_shift);
-    }
-    (void)hipFree(c->d_lut); (void)hipFree(c->d_hist); (void)hipFree(c->d_tile_xy); (void)hipFree(c->d_batch_labels); (void)hipFree(c->d_probs); (void)hipFree(c->d_xin); (void)hipFree(c->d_ks_ws);
-    (void)hipFree(c->d_page); (void)hipFree(c->d_page_labels); (void)hipFree(c->d_page_labels3); (void)hipFree(c->d_tile_labels);
-    (void)hipFree(c->d_own_x); (void)hipFree(c->d_own_y); (void)hipFree(c->d_map); (void)hipFree(c->d_wmap);
-    (void)hipFree(c->d_views); (void)hipHostFree(c->h_views);
+    (void)c->mem.release_all();
+    (void)c->pinned.release_all();
     if (c->ev_views) (void)hipEventDestroy(c->ev_views);
-    (void)hipFree(c->d_deskew);
-    (void)hipFree(c->d_cc_bg); (void)hipFree(c->d_cc_roots); (void)hipFree(c->d_rdk); (void)hipFree(c->d_pstat); (void)hipFree(c->d_line_tab);
-    (void)hipFree(c->d_lsplit); (void)hipFree(c->d_line_w);
-    for (int lane = 0; lane < 2; ++lane)
-        for (int L = 0; L < kRegionMaxLevels; ++L) (void)hipFree(c->d_rtab[lane][L]);
-    (void)hipFree(c->d_run_page); (void)hipFree(c->d_run_mask); (void)hipFree(c->d_run_a); (void)hipFree(c->d_run_b);
-    for (auto& ub : c->user_bufs) (void)hipFree(ub.first);
     for (int k = 0; k < 2; ++k) {
-        (void)hipHostFree(c->pp_h_in[k]); (void)hipHostFree(c->pp_h_out[k]);
-        (void)hipFree(c->pp_d_in[k]); (void)hipFree(c->pp_d_out[k]); (void)hipFree(c->pp_d_out3[k]);
         if (c->pp_in[k]) (void)hipEventDestroy(c->pp_in[k]);
         if (c->pp_comp[k]) (void)hipEventDestroy(c->pp_comp[k]);
         if (c->pp_out[k]) (void)hipEventDestroy(c->pp_out[k]);
@@ -196,7 +147,6 @@ int sbbseg_destroy(sbbseg_ctx* c)
     comm_release(c);
     if (c->copy_in) (void)hipStreamDestroy(c->copy_in);
     if (c->copy_out) (void)hipStreamDestroy(c->copy_out);
-    (void)hipFree(c->d_morph_a); (void)hipFree(c->d_morph_b); (void)hipFree(c->d_cc_parent); (void)hipFree(c->d_cc_count); (void)hipFree(c->d_cc_aux); (void)hipFree(c->d_cc_list); (void)hipFree(c->d_cc_small);
     for (auto& pe : c->pending) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
     for (auto e : c->free_events) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -293,9 +243,9 @@ int sbbseg_debug_poison_activations(sbbseg_ctx* c, int byte_value)
             HIPCHK(hipMemset(t.lane_buf[lane] + kZeroHeaderBytes, byte_value & 255, n));
         }
     }
-    if (c->d_tile_labels) HIPCHK(hipMemset(c->d_tile_labels, byte_value & 255, c->tile_labels_cap));
+    if (c->tile_labels.p) HIPCHK(hipMemset(c->tile_labels.p, byte_value & 255, c->tile_labels.cap));
     // the split-K partial sums too: a split that a later pass does not write must not find the last pass's (equal) value there
-    if (c->d_ks_ws) HIPCHK(hipMemset(c->d_ks_ws, byte_value & 255, c->ks_ws_cap));
+    if (c->ks_ws.p) HIPCHK(hipMemset(c->ks_ws.p, byte_value & 255, c->ks_ws.cap));
     HIPCHK(hipDeviceSynchronize());
     return 0;
     API_END
@@ -366,7 +316,7 @@ int sbbseg_device_bytes(sbbseg_ctx* c, size_t* bytes)
 {
     API_BEGIN
     REQUIRE(c && bytes, "bad arguments");
-    *bytes = c->device_bytes;
+    *bytes = c->mem.bytes();
     return 0;
     API_END
 }
@@ -404,12 +354,7 @@ int sbbseg_device_alloc(sbbseg_ctx* c, size_t bytes, void** d_ptr)
     REQUIRE(c != nullptr && d_ptr != nullptr && bytes > 0, "bad arguments");
     HIPCHK(hipSetDevice(c->device));
     alloc_check();
-    void* p = nullptr;
-    c->user_bufs.reserve(c->user_bufs.size() + 1);
-    if (dmalloc(c, &p, bytes)) return 1;
-    c->user_bufs.push_back({p, bytes});
-    *d_ptr = p;
-    return 0;
+    return c->mem.alloc(d_ptr, bytes, /*user=*/true);
     API_END
 }
 
@@ -418,17 +363,12 @@ int sbbseg_device_free(sbbseg_ctx* c, void* d_ptr)
     API_BEGIN
     REQUIRE(c != nullptr, "null handle");
     if (!d_ptr) return 0;
-    for (size_t i = 0; i < c->user_bufs.size(); ++i)
-        if (c->user_bufs[i].first == d_ptr) {
-            HIPCHK(hipSetDevice(c->device));
-            HIPCHK(hipDeviceSynchronize());            // DEVICE-wide on purpose: any handle on the device may use the buffer (sbbseg.h), so
+    const DeviceMem::Block* b = c->mem.find(d_ptr);
+    REQUIRE(b && b->user, "sbbseg_device_free: %p was not allocated by this handle", d_ptr);      // (its own blocks are not the caller's to free)
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());                    // DEVICE-wide on purpose: any handle on the device may use the buffer (sbbseg.h), so
                                                        // other handles' streams may still be reading it; a free is not a hot-path call
-            HIPCHK(hipFree(d_ptr));
-            c->device_bytes -= c->user_bufs[i].second;
-            c->user_bufs.erase(c->user_bufs.begin() + (long)i);
-            return 0;
-        }
-    return set_error("sbbseg_device_free: %p was not allocated by this handle", d_ptr);
+    return c->mem.release(d_ptr) ? 1 : 0;
     API_END
 }
 
@@ -469,6 +409,20 @@ int sbbseg_download_labels(sbbseg_ctx* c, uint8_t* dst, const void* d_labels_hw,
 }
 
 // ----------------------------------------------------------------------------------------- debug
+// n stored elements of tensor t (of the lane in use) -> n floats in host memory, through a temporary of the handle; returns when they are there
+static int tensor_to_host_f32(sbbseg_ctx* c, const Tensor& t, size_t n, float* out)
+{
+    ScopedBlock<float> tmp(c->mem);
+    if (tmp.alloc(n)) return 1;
+    HIPCHK(c->planes == 2 ? launch_split_to_f32(t.data(), tmp.p, n / t.C, t.C, c->stream) : launch_to_f32(t.data(), tmp.p, n, c->precision, c->stream));
+    HIPCHK(hipMemcpyAsync(out, tmp.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->planes == 2 && t.is_input_form && t.form == SBBSEG_INPUT_C8)      // (the hi plane's slots 4..6 repeat lo(ch 0..2) for the fused tail: not channels)
+        for (size_t i = 0; i < n; i += 8)
+            for (int ch = 3; ch < 8; ++ch) out[i + ch] = 0.f;
+    return 0;
+}
+
 int sbbseg_debug_ingest(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, int Wp, const int32_t* tile_xy, int n_tiles,
                         int form, float* out, size_t out_floats)
 {
@@ -481,26 +435,15 @@ int sbbseg_debug_ingest(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, int Wp, 
     const size_t n = t.elems_per_patch * n_tiles;
     REQUIRE(out_floats >= n, "output buffer too small (%zu < %zu)", out_floats, n);
     const size_t pix = (size_t)Hp * Wp;
-    if (ensure(c, (void**)&c->d_page, &c->page_cap, pix * 3)) return 1;
-    HIPCHK(hipMemcpyAsync(c->d_page, page_hwc, pix * 3, hipMemcpyHostToDevice, c->stream));
+    if (ensure(c, c->page, pix * 3)) return 1;
+    HIPCHK(hipMemcpyAsync(c->page.p, page_hwc, pix * 3, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(c->d_tile_xy, tile_xy, sizeof(int) * 2 * n_tiles, hipMemcpyHostToDevice));
     IngestParams ip;
     if (fill_ingest(c, ip)) return 1;
-    ip.page = c->d_page; ip.Hp = Hp; ip.Wp = Wp; ip.src_Hp = Hp; ip.src_Wp = Wp; ip.tile_xy = c->d_tile_xy; ip.n_tiles = n_tiles;
+    ip.page = c->page.p; ip.Hp = Hp; ip.Wp = Wp; ip.src_Hp = Hp; ip.src_Wp = Wp; ip.tile_xy = c->d_tile_xy; ip.n_tiles = n_tiles;
     HIPCHK(launch_ingest_u8(ip, c->precision, c->stream));
-    float* d_tmp = nullptr;
-    HIPCHK(hipMalloc((void**)&d_tmp, n * sizeof(float)));
-    hipError_t e = c->planes == 2 ? launch_split_to_f32(t.data(), d_tmp, n / t.C, t.C, c->stream)
-                                  : launch_to_f32(t.data(), d_tmp, n, c->precision, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_tmp, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_tmp);
-    HIPCHK(e);
-    if (c->planes == 2 && form == SBBSEG_INPUT_C8)      // (the hi plane's slots 4..6 repeat lo(ch 0..2) for the fused tail: not channels)
-        for (size_t i = 0; i < n; i += 8)
-            for (int ch = 3; ch < 8; ++ch) out[i + ch] = 0.f;
-    return 0;
+    return tensor_to_host_f32(c, t, n, out);
     API_END
 }
 
@@ -512,18 +455,7 @@ int sbbseg_debug_read_tensor(sbbseg_ctx* c, int tensor_id, int n, float* out, si
     const Tensor& t = c->tensors[tensor_id];
     const size_t cnt = t.elems_per_patch * n;
     REQUIRE(out_floats >= cnt, "output buffer too small (%zu < %zu)", out_floats, cnt);
-    float* d_tmp = nullptr;
-    HIPCHK(hipMalloc((void**)&d_tmp, cnt * sizeof(float)));
-    hipError_t e = c->planes == 2 ? launch_split_to_f32(t.data(), d_tmp, cnt / t.C, t.C, c->stream)
-                                  : launch_to_f32(t.data(), d_tmp, cnt, c->precision, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_tmp, cnt * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_tmp);
-    HIPCHK(e);
-    if (c->planes == 2 && t.is_input_form && t.form == SBBSEG_INPUT_C8)      // (see sbbseg_debug_ingest)
-        for (size_t i = 0; i < cnt; i += 8)
-            for (int ch = 3; ch < 8; ++ch) out[i + ch] = 0.f;
-    return 0;
+    return tensor_to_host_f32(c, t, cnt, out);
     API_END
 }
 
@@ -549,14 +481,12 @@ int sbbseg_debug_tensor_period_mismatches(sbbseg_ctx* c, int tensor_id, int n, i
     const size_t stride = t.elems_per_patch * (size_t)c->elem * c->planes;          // bytes of one stored patch
     REQUIRE(stride % 16 == 0, "patch stride %zu is not a multiple of 16 bytes", stride);
     unsigned long long h_res[2] = {0ull, ~0ull};
-    unsigned long long* d_res = nullptr;
-    HIPCHK(hipMalloc((void**)&d_res, sizeof(h_res)));
-    hipError_t e = hipMemcpyAsync(d_res, h_res, sizeof(h_res), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_period_mismatches(t.data(), stride * period, stride * (size_t)(n - period), d_res, c->num_cus, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_res, d_res, sizeof(h_res), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_res);
-    HIPCHK(e);
+    ScopedBlock<unsigned long long> res(c->mem);
+    if (res.alloc(2)) return 1;
+    HIPCHK(hipMemcpyAsync(res.p, h_res, sizeof(h_res), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_period_mismatches(t.data(), stride * period, stride * (size_t)(n - period), res.p, c->num_cus, c->stream));
+    HIPCHK(hipMemcpyAsync(h_res, res.p, sizeof(h_res), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     *count = (int64_t)h_res[0];
     *first = h_res[0] ? (int64_t)h_res[1] : -1;
     return 0;

@@ -1,6 +1,7 @@
 // ctx.h -- private, host only: what the translation units behind the C ABI (api.hip, forward.hip, pages.hip, whole.hip, comm.hip -- these five
 // through exec.h, forward.hip and pages.hip through route.h too -- plan_build.hip, stage_glue.hip) share: the error and exception plumbing, the allocation helpers, and the handle
-// (struct sbbseg_ctx) with the plan structs it embeds.
+// (struct sbbseg_ctx) with the plan structs it embeds.  Device and pinned memory belong to the handle's two registries (devmem.h: `mem`, `pinned`);
+// every device pointer below, in the handle and in the plan structs, points at a block one of them owns and sbbseg_destroy frees with the registry.
 #pragma once
 
 #include <new>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "../../include/sbbseg.h"
+#include "devmem.h"
 #include "internal.h"
 #include "region.h"
 
@@ -44,9 +46,11 @@ extern thread_local int g_err_kind;             // kind of the error in g_err: s
 extern int g_alloc_fail_countdown;              // test hook (sbbseg_debug_inject_alloc_failure): the n-th next alloc_check() throws std::bad_alloc
 inline void alloc_check() { if (g_alloc_fail_countdown > 0 && --g_alloc_fail_countdown == 0) throw std::bad_alloc(); }
 
-int dmalloc(sbbseg_ctx* c, void** p, size_t bytes);                    // hipMalloc, counted in c->device_bytes
-int ensure(sbbseg_ctx* c, void** p, size_t* cap, size_t bytes);        // grows *p to `bytes` (waits for the stream before it frees)
+int dmalloc(sbbseg_ctx* c, void** p, size_t bytes);                    // a block of c->mem
 int check_ready(sbbseg_ctx* c);                                        // a finalized handle; makes its device current
+
+template <typename T>
+int ensure(sbbseg_ctx* c, DevBuf<T>& b, size_t bytes);                 // grows b to `bytes` in c->mem (defined below the handle)
 
 template <typename T>
 int upload(sbbseg_ctx* c, T** dptr, const T* host, size_t n)
@@ -192,7 +196,14 @@ struct sbbseg_ctx {
     int form_tensor[2] = {-1, -1};
     int classes = 0, max_batch = 0;
     bool finalized = false;
-    size_t device_bytes = 0;
+    // who owns the handle's memory (devmem.h).  A new buffer: declare a DevBuf here and call ensure() where it is used -- nothing else.
+    // sbbseg_create gives the registries their allocators (api.hip); a handle built without them (the host-only tests) can allocate nothing
+    sbbseg::DeviceMem mem;                        // device memory; sbbseg_device_bytes is its total
+    sbbseg::DeviceMem pinned;                     // pinned host staging
+    typedef sbbseg::DeviceMem::AllocFn AllocFn;
+    typedef sbbseg::DeviceMem::FreeFn FreeFn;
+    explicit sbbseg_ctx(AllocFn dev_alloc = nullptr, FreeFn dev_free = nullptr, AllocFn pin_alloc = nullptr, FreeFn pin_free = nullptr)
+        : mem(dev_alloc, dev_free), pinned(pin_alloc, pin_free) {}
     // run-time buffers
     float* d_lut = nullptr;
     unsigned* d_hist = nullptr;   // [256] channel-0 histogram + [1] Otsu threshold (int) behind it
@@ -200,14 +211,13 @@ struct sbbseg_ctx {
     uint8_t* d_batch_labels = nullptr; // [max_batch][H][W] (predict / whole-image path)
     float* d_probs = nullptr;          // [max_batch][H][W][classes], lazily allocated
     float* d_xin = nullptr;            // predict(): staged float input, lazily allocated
-    float* d_ks_ws = nullptr; size_t ks_ws_cap = 0;      // split-K partial sums (whole-image branch)
+    sbbseg::DevBuf<float> ks_ws;                         // split-K partial sums (whole-image branch)
     bool ksplit = true, ksplit_now = false;              // SBBSEG_KSPLIT=0 switches it off; _now: inside the whole-image branch's run_plan
-    uint8_t* d_page = nullptr; size_t page_cap = 0;
-    uint8_t* d_page_labels = nullptr; size_t page_labels_cap = 0;
-    uint8_t* d_page_labels3 = nullptr; size_t page_labels3_cap = 0;   // 3-channel copy for label_channels == 3
+    sbbseg::DevBuf<uint8_t> page, page_labels;
+    sbbseg::DevBuf<uint8_t> page_labels3;                             // 3-channel copy for label_channels == 3
     int label_channels = 1;
-    uint8_t* d_tile_labels = nullptr; size_t tile_labels_cap = 0;
-    int *d_own_x = nullptr, *d_own_y = nullptr; size_t own_cap = 0;
+    sbbseg::DevBuf<uint8_t> tile_labels;
+    sbbseg::DevBuf<int> own_x, own_y;
     int own_Hp = -1, own_Wp = -1, own_nyf = 0;
     bool own_dedupe = false;          // the cached owner tables index the deduplicated grid (see fused_grid)
     // Duplicate clamped tiles: when extent % mid lies in (0, tile - mid] the inward clamp (main.py:276-281) gives the LAST
@@ -216,55 +226,52 @@ struct sbbseg_ctx {
     // (sbbseg_tile_grid, _segment_tile_range_dev, _stitch_dev: the multi-rank protocol) keep the reference's call list.
     bool dedupe = true;               // sbbseg_set_dedupe / SBBSEG_DEDUPE=0
     int64_t forwards = 0;             // patches run through the plan so far (sbbseg_debug_counter 1)
-    int *d_map = nullptr; size_t map_cap = 0;
-    int *d_wmap = nullptr; size_t wmap_cap = 0;      // gather tables of the whole-image branch, cached per geometry
+    sbbseg::DevBuf<int> map;
+    sbbseg::DevBuf<int> wmap;                        // gather tables of the whole-image branch, cached per geometry
     int wmap_key[6] = {0, 0, 0, 0, 0, 0};            // {Hp, Wp, Hs, Ws, out_h, out_w} (0 = none)
-    int map_key[4] = {0, 0, 0, 0};     // {Hs, Ws, Hp, Wp} the nearest maps in d_map were built for (sbbseg_segment_crop_dev; 0 = none)
+    int map_key[4] = {0, 0, 0, 0};     // {Hs, Ws, Hp, Wp} the nearest maps in `map` were built for (sbbseg_segment_crop_dev; 0 = none)
     // sbbseg_segment_views_dev: the call's view table | fallback threshold ints | nearest maps, staged in pinned memory and uploaded in one
     // asynchronous copy; ev_views marks that copy done (the staging may then be rewritten by the next call)
-    void* d_views = nullptr; size_t views_cap = 0;
-    void* h_views = nullptr; size_t h_views_cap = 0;
+    sbbseg::DevBuf<void> views;
+    sbbseg::DevBuf<void> h_views;                                     // (pinned)
     hipEvent_t ev_views = nullptr; bool views_copy_pending = false;
-    int* d_views_thr = nullptr;       // the last call's threshold ints inside d_views, one per view (sbbseg_segment_views reads them back)
+    int* d_views_thr = nullptr;       // the last call's threshold ints inside `views`, one per view (sbbseg_segment_views reads them back)
     int64_t views_launches = 0;       // ingest + region-build + stitch kernels sbbseg_segment_views_dev has queued (sbbseg_debug_counter 3)
     int64_t whole_launches = 0;       // ingest + label-resize kernels the whole-views calls have queued (sbbseg_debug_counter 4)
     // stage glue scratch (morphology planes, union-find arrays, result words)
-    uint8_t *d_morph_a = nullptr, *d_morph_b = nullptr; size_t morph_a_cap = 0, morph_b_cap = 0;
+    sbbseg::DevBuf<uint8_t> morph_a, morph_b;
     // pipelined multi-page host path (sbbseg_segment_pages): copy streams, two slots of pinned staging + device buffers
     hipStream_t copy_in = nullptr, copy_out = nullptr;
     hipEvent_t pp_in[2] = {nullptr, nullptr}, pp_comp[2] = {nullptr, nullptr}, pp_out[2] = {nullptr, nullptr};
-    uint8_t *pp_h_in[2] = {nullptr, nullptr}, *pp_h_out[2] = {nullptr, nullptr}, *pp_d_in[2] = {nullptr, nullptr}, *pp_d_out[2] = {nullptr, nullptr},
-            *pp_d_out3[2] = {nullptr, nullptr};
-    size_t pp_in_cap = 0, pp_out_cap = 0, pp_out3_cap = 0;        // device buffers (bytes each)
-    size_t pp_hin_cap = 0, pp_hout_cap = 0;                       // pinned host staging (bytes each)
+    sbbseg::DevBuf<uint8_t> pp_h_in[2], pp_h_out[2];              // pinned host staging
+    sbbseg::DevBuf<uint8_t> pp_d_in[2], pp_d_out[2], pp_d_out3[2];      // device buffers
     bool pp_ready = false;                                        // streams + events of the page pipeline exist
     // RCCL communicator of the sharded path (sbbseg_comm_init; librccl is dlopen'ed on first use)
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;
-    void* d_deskew = nullptr; size_t deskew_cap = 0;      // inverse maps | bicubic table | row counts of sbbseg_deskew_profiles
+    sbbseg::DevBuf<void> deskew;                          // inverse maps | bicubic table | row counts of sbbseg_deskew_profiles
     // sbbseg_run_page's / sbbseg_run_pages' resident buffers (owned by the handle passed as `border` / `layout` / `textline` respectively;
-    // sbbseg_run_pages: all pages' planes one after the other, and the textline planes in the layout handle's d_run_a)
-    uint8_t *d_run_page = nullptr, *d_run_mask = nullptr, *d_run_a = nullptr, *d_run_b = nullptr;
-    size_t run_page_cap = 0, run_mask_cap = 0, run_a_cap = 0, run_b_cap = 0;
-    // what the last sbbseg_run_pages left resident in this (layout) handle's d_run_b / d_run_a, page by page (sbbseg_run_pages_planes); no
+    // sbbseg_run_pages: all pages' planes one after the other, and the textline planes in the layout handle's run_a)
+    sbbseg::DevBuf<uint8_t> run_page, run_mask, run_a, run_b;
+    // what the last sbbseg_run_pages left resident in this (layout) handle's run_b / run_a, page by page (sbbseg_run_pages_planes); no
     // device memory of its own.  Emptied by a failed call and by the next sbbseg_run_page(s) that names the handle.
     struct RunPlanes { size_t at; int w, h, regions_ok, textlines_ok; };
     std::vector<RunPlanes> run_planes;
     bool run_planes_valid = false;
-    int *d_cc_parent = nullptr, *d_cc_count = nullptr; size_t cc_parent_cap = 0, cc_count_cap = 0;
+    sbbseg::DevBuf<int> cc_parent, cc_count;
     bool force_host_contours = false;     // test hook (conv variant bit 21): always take the exact host ranking
     int host_contour_calls = 0;           // how often the exact host ranking ran (sbbseg_debug_counter)
     int* d_cc_list = nullptr;             // [6 + kCcMaxRivals]: launch_largest_contour's result record
-    int* d_cc_aux = nullptr; size_t cc_aux_cap = 0;      // five int planes: doubled cell area + bounding boxes per root (sbbseg_page_box_dev)
+    sbbseg::DevBuf<int> cc_aux;                          // five int planes: doubled cell area + bounding boxes per root (sbbseg_page_box_dev)
     unsigned long long* d_cc_small = nullptr;      // [0] best key, [1..2] box (4 ints)
-    int* d_cc_bg = nullptr; size_t cc_bg_cap = 0;        // two int planes: labels of the complement, border flags (sbbseg_text_region_boxes_dev)
-    int* d_cc_roots = nullptr; size_t cc_roots_cap = 0;  // parentless roots, 6 ints each
-    void* d_rdk = nullptr; size_t rdk_cap = 0;           // sbbseg_region_deskew_profiles_dev: maps | table | geometry | crops | counts
-    void* d_pstat = nullptr; size_t pstat_cap = 0;       // sbbseg_profile_statistics_dev: weights | regions | spread | winner | state | workspace
+    sbbseg::DevBuf<int> cc_bg;                           // two int planes: labels of the complement, border flags (sbbseg_text_region_boxes_dev)
+    sbbseg::DevBuf<int> cc_roots;                        // parentless roots, 6 ints each
+    sbbseg::DevBuf<void> rdk;                            // sbbseg_region_deskew_profiles_dev: maps | table | geometry | crops | counts
+    sbbseg::DevBuf<void> pstat;                          // sbbseg_profile_statistics_dev: weights | regions | spread | winner | state | workspace
     long long line_launches = 0;                         // kernels queued by sbbseg_region_line_masks_dev (sbbseg_debug_counter 2)
     long long slope_launches = 0;                        // kernels queued by the slope sweeps: crop, profile, statistic, winner (sbbseg_debug_counter 5)
-    void* d_lsplit = nullptr; size_t lsplit_cap = 0;     // sbbseg_line_split_dev: regions | info | lines | corners | rotated corners | workspace
-    void* d_line_w = nullptr; size_t line_w_cap = 0;     // ... its table of half Gaussian kernels: offsets | weights, uploaded when it differs from
+    sbbseg::DevBuf<void> lsplit;                         // sbbseg_line_split_dev: regions | info | lines | corners | rotated corners | workspace
+    sbbseg::DevBuf<void> line_w;                         // ... its table of half Gaussian kernels: offsets | weights, uploaded when it differs from
     std::vector<double> line_w_host;                     // ... this copy of the last one
     int16_t* d_line_tab = nullptr;                       // sbbseg_region_line_masks_dev: the fixed-point bicubic table, built on first use
     // profiling
@@ -291,10 +298,21 @@ struct sbbseg_ctx {
     int owned_mode = 1;
     int region_levels = 0;                        // decoder levels of the chain found by sbbseg_finalize (0: the plan has none)
     int region_op[sbbseg::kRegionMaxLevels] = {0};        // op index per level (level 0 = the tail)
-    uint32_t* d_rtab[2][sbbseg::kRegionMaxLevels] = {{nullptr}, {nullptr}};     // per lane and level: the chunk's table (allocated on first use)
-    size_t rtab_cap[2][sbbseg::kRegionMaxLevels] = {{0}, {0}};
+    sbbseg::DevBuf<uint32_t> rtab[2][sbbseg::kRegionMaxLevels];                 // per lane and level: the chunk's table (allocated on first use)
     sbbseg::RegionRun rr;                                 // the chunk run_plan is launching (set by tile_range_impl around run_plan)
     double last_exec_frac = 1.0;                  // share of its output grid the op being launched walks (run_plan's accounting; launch_op resets
                                                   // it to 1 when an A/B knob takes a level off its owned-region form)
-    std::vector<std::pair<void*, size_t>> user_bufs;      // sbbseg_device_alloc's buffers still alive (freed by sbbseg_destroy)
 };
+
+namespace sbbseg {
+
+// The one way a run-time buffer of the handle grows.  The handle's stream may still be using the block about to be freed: wait for it first.
+template <typename T>
+int ensure(sbbseg_ctx* c, DevBuf<T>& b, size_t bytes)
+{
+    if (b.cap >= bytes) return 0;
+    if (b.p) HIPCHK(hipStreamSynchronize(c->stream));
+    return ensure(c->mem, b, bytes);
+}
+
+}  // namespace sbbseg

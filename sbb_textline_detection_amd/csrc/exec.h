@@ -14,7 +14,7 @@ int resolve_pending(sbbseg_ctx* c);                                             
 int labels_to_host(sbbseg_ctx* c, const void* d_plane, void* host, size_t pixels, int channels);
 // pages.hip
 void nearest_map(int src_len, int dst_len, std::vector<int>& m);                      // cv2.resize(..., INTER_NEAREST)'s index rule
-int views_staging(sbbseg_ctx* c, size_t bytes);                                       // c->h_views / c->d_views hold `bytes`, the staging is free
+int views_staging(sbbseg_ctx* c, size_t bytes);                                       // c->h_views / c->views hold `bytes`, the staging is free
 // comm.hip
 void comm_release(sbbseg_ctx* c);
 
@@ -80,7 +80,7 @@ int run_chunked(sbbseg_ctx* c, int n_tiles, F&& run_chunk)
             forked = true;
         }
         // (a failure from here on must still join the lanes: earlier chunks of this range are in flight on lane_stream, unordered against
-        //  whatever the caller does next on the handle's stream -- stitch, reuse of d_tile_labels, destroy)
+        //  whatever the caller does next on the handle's stream -- stitch, reuse of c->tile_labels, destroy)
         auto join_on_error = [&]() -> int {
             if (hipEventRecord(c->ev_join, c->lane_stream) != hipSuccess || hipStreamWaitEvent(c->stream, c->ev_join, 0) != hipSuccess)
                 (void)hipStreamSynchronize(c->lane_stream);

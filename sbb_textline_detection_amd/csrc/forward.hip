@@ -222,10 +222,10 @@ int launch_generic_conv(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* 
     }
     if (ks > 0) {
         const size_t split_elems = (size_t)n * p.TH * p.TW * p.cout;
-        if (ensure(c, (void**)&c->d_ks_ws, &c->ks_ws_cap, (split_elems << ks) * sizeof(float))) return 1;
-        p.ks_shift = ks; p.ks_ws = c->d_ks_ws; p.ks_split_elems = (long)split_elems; p.tile_map = 0; p.cls_minor = 0;
+        if (ensure(c, c->ks_ws, (split_elems << ks) * sizeof(float))) return 1;
+        p.ks_shift = ks; p.ks_ws = c->ks_ws.p; p.ks_split_elems = (long)split_elems; p.tile_map = 0; p.cls_minor = 0;
         HIPCHK(launch_conv(p, c->precision, c->stream, &op.last));
-        HIPCHK(launch_splitk_finish(c->d_ks_ws, 1 << ks, (long)split_elems, (long)n * p.TH * p.TW, p.cout, p.scale, p.shift, p.residual,
+        HIPCHK(launch_splitk_finish(c->ks_ws.p, 1 << ks, (long)split_elems, (long)n * p.TH * p.TW, p.cout, p.scale, p.shift, p.residual,
                                     p.relu, p.out, c->precision, c->stream));
     } else {
         HIPCHK(launch_conv(p, c->precision, c->stream, &op.last));

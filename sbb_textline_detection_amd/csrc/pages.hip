@@ -57,7 +57,7 @@ void nearest_map(int src_len, int dst_len, std::vector<int>& m)
 }
 
 // The per-call tables of the many-view entry points (sbbseg_segment_views_dev, sbbseg_segment_whole_views_dev): c->h_views (pinned) and
-// c->d_views hold at least `bytes`, and the staging may be rewritten (the previous call's upload has read it).
+// c->views hold at least `bytes`, and the staging may be rewritten (the previous call's upload has read it).
 int views_staging(sbbseg_ctx* c, size_t bytes)
 {
     if (c->views_copy_pending) {                               // (the previous call's upload still reads the staging)
@@ -65,14 +65,8 @@ int views_staging(sbbseg_ctx* c, size_t bytes)
         c->views_copy_pending = false;
     }
     if (!c->ev_views) HIPCHK(hipEventCreateWithFlags(&c->ev_views, hipEventDisableTiming));
-    if (c->h_views_cap < bytes) {
-        c->h_views_cap = 0;
-        (void)hipHostFree(c->h_views); c->h_views = nullptr;
-        const size_t cap = bytes + bytes / 2;
-        HIPCHK(hipHostMalloc(&c->h_views, cap, hipHostMallocDefault));
-        c->h_views_cap = cap;
-    }
-    if (c->views_cap < bytes && ensure(c, &c->d_views, &c->views_cap, bytes + bytes / 2)) return 1;
+    if (c->h_views.cap < bytes && ensure(c->pinned, c->h_views, bytes + bytes / 2)) return 1;       // (half as much again: view counts creep up)
+    if (c->views.cap < bytes && ensure(c, c->views, bytes + bytes / 2)) return 1;
     return 0;
 }
 
@@ -207,14 +201,12 @@ static int region_level_table(sbbseg_ctx* c, int lane, const RegionGeom& rg, int
     const size_t batch_cap = (size_t)(lane == 0 ? c->max_batch : c->lane1_batch);
     const size_t need = 4 * (rg.kind[L] ? 4 * batch_cap * (size_t)(rg.Rh[L] / 2) * (size_t)(rg.Rw[L] / 2)
                                          : batch_cap * (size_t)(rg.Rh[L] / 16 + 1) * (size_t)(rg.Rw[L] / 16 + 1));
-    if (c->rtab_cap[lane][L] < need) {
+    if (c->rtab[lane][L].cap < need) {
         HIPCHK(hipDeviceSynchronize());                  // (first use / a kind switched by an A/B knob: rare)
-        if (c->d_rtab[lane][L]) { HIPCHK(hipFree(c->d_rtab[lane][L])); c->device_bytes -= c->rtab_cap[lane][L]; c->d_rtab[lane][L] = nullptr; c->rtab_cap[lane][L] = 0; }
-        if (dmalloc(c, (void**)&c->d_rtab[lane][L], need)) return 1;
-        c->rtab_cap[lane][L] = need;
+        if (ensure(c, c->rtab[lane][L], need)) return 1;
     }
     RegionRun& rr = c->rr;
-    rr.kind[L] = rg.kind[L]; rr.total[L] = (int)total; rr.tab[L] = c->d_rtab[lane][L];
+    rr.kind[L] = rg.kind[L]; rr.total[L] = (int)total; rr.tab[L] = c->rtab[lane][L].p;
     rr.frac[L] = (double)total * (rg.kind[L] ? 4.0 : 256.0) / ((double)nb * rg.Rh[L] * rg.Rw[L]);
     return 0;
 }
@@ -264,7 +256,7 @@ static int tile_range_impl(sbbseg_ctx* c, const void* const* d_pages, int n_page
                 total += region_entries(rg, i, j, L);
             }
             if (region_level_table(c, lane, rg, L, nb, total)) return 1;
-            bp.out[L] = c->d_rtab[lane][L]; bp.total[L] = (int)total;
+            bp.out[L] = c->rtab[lane][L].p; bp.total[L] = (int)total;
         }
         HIPCHK(launch_region_build(bp, c->stream));
         c->rr.on = true;
@@ -322,16 +314,10 @@ static int prepare_owner(sbbseg_ctx* c, int Hp, int Wp, bool dedupe)
     axis_owner(Wp, c->in_W, margin, ox, own_x);
     axis_owner(Hp, c->in_H, margin, oy, own_y);
     const size_t need = sizeof(int) * (size_t)(Hp > Wp ? Hp : Wp);
-    if (c->own_cap < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_own_x) { HIPCHK(hipFree(c->d_own_x)); HIPCHK(hipFree(c->d_own_y)); c->device_bytes -= 2 * c->own_cap; }
-        c->d_own_x = c->d_own_y = nullptr;
-        if (dmalloc(c, (void**)&c->d_own_x, need) || dmalloc(c, (void**)&c->d_own_y, need)) return 1;
-        c->own_cap = need;
-    }
+    if (ensure(c, c->own_x, need) || ensure(c, c->own_y, need)) return 1;      // (waits for the stream before it frees a table)
     HIPCHK(hipStreamSynchronize(c->stream));   // tables may still be in use by an earlier stitch
-    HIPCHK(hipMemcpy(c->d_own_x, own_x.data(), sizeof(int) * Wp, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->d_own_y, own_y.data(), sizeof(int) * Hp, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->own_x.p, own_x.data(), sizeof(int) * Wp, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->own_y.p, own_y.data(), sizeof(int) * Hp, hipMemcpyHostToDevice));
     c->own_Hp = Hp; c->own_Wp = Wp; c->own_nyf = ny; c->own_dedupe = dedupe;
     return 0;
 }
@@ -340,7 +326,7 @@ static int stitch_impl(sbbseg_ctx* c, const void* d_tile_labels, int Hp, int Wp,
 {
     REQUIRE(d_tile_labels && d_labels_hw, "bad arguments");
     if (prepare_owner(c, Hp, Wp, dedupe)) return 1;
-    HIPCHK(launch_stitch((const uint8_t*)d_tile_labels, c->in_H, c->in_W, c->d_own_x, c->d_own_y, c->own_nyf, Hp, Wp,
+    HIPCHK(launch_stitch((const uint8_t*)d_tile_labels, c->in_H, c->in_W, c->own_x.p, c->own_y.p, c->own_nyf, Hp, Wp,
                          (uint8_t*)d_labels_hw, c->stream));
     return 0;
 }
@@ -354,21 +340,21 @@ int sbbseg_stitch_dev(sbbseg_ctx* c, const void* d_tile_labels, int Hp, int Wp, 
 }
 
 // The nearest maps "row / column of the Hs x Ws stored image shown at Hp x Wp -> stored row / column" (main.py:214 -> 112-113; the identity
-// where the sizes agree), in c->d_map: built and uploaded once per geometry (map_key).
+// where the sizes agree), in c->map: built and uploaded once per geometry (map_key).
 static int page_maps(sbbseg_ctx* c, int Hs, int Ws, int Hp, int Wp, const int** d_my, const int** d_mx)
 {
-    if (c->map_key[0] != Hs || c->map_key[1] != Ws || c->map_key[2] != Hp || c->map_key[3] != Wp || !c->d_map) {
+    if (c->map_key[0] != Hs || c->map_key[1] != Ws || c->map_key[2] != Hp || c->map_key[3] != Wp || !c->map.p) {
         std::vector<int> my, mx;
         nearest_map(Hs, Hp, my);
         nearest_map(Ws, Wp, mx);
-        if (ensure(c, (void**)&c->d_map, &c->map_cap, sizeof(int) * (size_t)(Hp + Wp))) return 1;
+        if (ensure(c, c->map, sizeof(int) * (size_t)(Hp + Wp))) return 1;
         HIPCHK(hipStreamSynchronize(c->stream));   // the maps may still be in use by an earlier call
-        HIPCHK(hipMemcpy(c->d_map, my.data(), sizeof(int) * Hp, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->d_map + Hp, mx.data(), sizeof(int) * Wp, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(c->map.p, my.data(), sizeof(int) * Hp, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(c->map.p + Hp, mx.data(), sizeof(int) * Wp, hipMemcpyHostToDevice));
         c->map_key[0] = Hs; c->map_key[1] = Ws; c->map_key[2] = Hp; c->map_key[3] = Wp;
     }
-    *d_my = c->d_map;
-    *d_mx = c->d_map + Hp;
+    *d_my = c->map.p;
+    *d_mx = c->map.p + Hp;
     return 0;
 }
 
@@ -387,23 +373,23 @@ static int fused_view(sbbseg_ctx* c, const void* d_page, int Hs, int Ws, int Hp,
     if (d_thr) HIPCHK(launch_otsu((const uint8_t*)d_page, Ws, ch, cw, d_my, d_mx, c->d_hist, d_thr, c->num_cus, c->stream));
     int nx = 0, ny = 0;
     if (fused_grid(c, ch, cw, c->dedupe, &nx, &ny)) return 1;
-    if (ensure(c, (void**)&c->d_tile_labels, &c->tile_labels_cap, (size_t)nx * ny * c->in_H * c->in_W)) return 1;
-    if (tile_range_impl(c, &d_page, 1, Hs, Ws, d_my, d_mx, ch, cw, 0, nx * ny, c->d_tile_labels, d_thr, c->dedupe, c->owned_mode >= 1)) return 1;
-    return stitch_impl(c, c->d_tile_labels, ch, cw, d_labels, c->dedupe);
+    if (ensure(c, c->tile_labels, (size_t)nx * ny * c->in_H * c->in_W)) return 1;
+    if (tile_range_impl(c, &d_page, 1, Hs, Ws, d_my, d_mx, ch, cw, 0, nx * ny, c->tile_labels.p, d_thr, c->dedupe, c->owned_mode >= 1)) return 1;
+    return stitch_impl(c, c->tile_labels.p, ch, cw, d_labels, c->dedupe);
 }
 
-// ... for a page in host memory: up into d_page, fused_view into d_page_labels, the labels (label_channels of them) and, with `binarise`,
+// ... for a page in host memory: up into c->page, fused_view into c->page_labels, the labels (label_channels of them) and, with `binarise`,
 // the Otsu threshold back; returns when both have arrived.
 static int host_view(sbbseg_ctx* c, const uint8_t* page_hwc, int Hs, int Ws, int Hp, int Wp, bool mapped, int cx, int cy, int cw, int ch, bool binarise,
                      uint8_t* labels_hw, int* threshold)
 {
     const size_t spix = (size_t)Hs * Ws, pix = (size_t)ch * cw;
-    if (ensure(c, (void**)&c->d_page, &c->page_cap, spix * 3)) return 1;
-    if (ensure(c, (void**)&c->d_page_labels, &c->page_labels_cap, pix + 4)) return 1;
-    HIPCHK(hipMemcpyAsync(c->d_page, page_hwc, spix * 3, hipMemcpyHostToDevice, c->stream));
+    if (ensure(c, c->page, spix * 3)) return 1;
+    if (ensure(c, c->page_labels, pix + 4)) return 1;
+    HIPCHK(hipMemcpyAsync(c->page.p, page_hwc, spix * 3, hipMemcpyHostToDevice, c->stream));
     int* d_thr = binarise ? (int*)(c->d_hist + 256) : nullptr;
-    if (fused_view(c, c->d_page, Hs, Ws, Hp, Wp, mapped, cx, cy, cw, ch, d_thr, c->d_page_labels)) return 1;
-    if (labels_to_host(c, c->d_page_labels, labels_hw, pix, c->label_channels)) return 1;
+    if (fused_view(c, c->page.p, Hs, Ws, Hp, Wp, mapped, cx, cy, cw, ch, d_thr, c->page_labels.p)) return 1;
+    if (labels_to_host(c, c->page_labels.p, labels_hw, pix, c->label_channels)) return 1;
     int thr = 0;
     if (d_thr) HIPCHK(hipMemcpyAsync(&thr, d_thr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -440,12 +426,12 @@ int sbbseg_segment_pages_dev(sbbseg_ctx* c, int n_pages, const void* const* d_pa
     if (G < 1) G = 1;
     if (G > (size_t)n_pages) G = (size_t)n_pages;
     REQUIRE(tpp * G < (size_t)1 << 30, "page group of %zu tiles is too large", tpp * G);
-    if (ensure(c, (void**)&c->d_tile_labels, &c->tile_labels_cap, tpp * G * per)) return 1;
+    if (ensure(c, c->tile_labels, tpp * G * per)) return 1;
     for (size_t g0 = 0; g0 < (size_t)n_pages; g0 += G) {
         const size_t np = g0 + G <= (size_t)n_pages ? G : (size_t)n_pages - g0;
-        if (tile_range_impl(c, d_pages_hwc + g0, (int)np, Hp, Wp, nullptr, nullptr, Hp, Wp, 0, (int)(tpp * np), c->d_tile_labels, nullptr, c->dedupe, c->owned_mode >= 1)) return 1;
+        if (tile_range_impl(c, d_pages_hwc + g0, (int)np, Hp, Wp, nullptr, nullptr, Hp, Wp, 0, (int)(tpp * np), c->tile_labels.p, nullptr, c->dedupe, c->owned_mode >= 1)) return 1;
         for (size_t k = 0; k < np; ++k)
-            if (stitch_impl(c, c->d_tile_labels + k * tpp * per, Hp, Wp, d_labels_hw[g0 + k], c->dedupe)) return 1;
+            if (stitch_impl(c, c->tile_labels.p + k * tpp * per, Hp, Wp, d_labels_hw[g0 + k], c->dedupe)) return 1;
     }
     return 0;
     API_END
@@ -478,38 +464,20 @@ int sbbseg_segment_pages(sbbseg_ctx* c, int n_pages, const uint8_t* const* pages
         c->pp_ready = true;
     }
     HIPCHK(hipStreamSynchronize(c->stream));                            // (buffers below may be re-allocated)
-    // Every buffer has its own capacity in the units it was allocated in; a capacity is zeroed BEFORE its buffers are
-    // freed and set only after all of them exist again, so a failed allocation leaves "nothing allocated", not a stale size.
-    auto host_pair = [&](uint8_t* (&h)[2], size_t* cap, size_t bytes) -> int {
-        if (*cap >= bytes) return 0;
-        *cap = 0;
-        for (int k = 0; k < 2; ++k) { (void)hipHostFree(h[k]); h[k] = nullptr; }
-        for (int k = 0; k < 2; ++k) HIPCHK(hipHostMalloc((void**)&h[k], bytes, hipHostMallocDefault));
-        *cap = bytes;
-        return 0;
-    };
-    auto dev_pair = [&](uint8_t* (&d)[2], size_t* cap, size_t bytes) -> int {
-        if (*cap >= bytes) return 0;
-        const size_t old = *cap;
-        *cap = 0;
-        for (int k = 0; k < 2; ++k)
-            if (d[k]) { (void)hipFree(d[k]); d[k] = nullptr; c->device_bytes -= old; }
-        for (int k = 0; k < 2; ++k)
-            if (dmalloc(c, (void**)&d[k], bytes)) return 1;
-        *cap = bytes;
-        return 0;
-    };
-    if (host_pair(c->pp_h_in, &c->pp_hin_cap, G * in_b)) return 1;
-    if (dev_pair(c->pp_d_in, &c->pp_in_cap, G * in_b)) return 1;
-    if (host_pair(c->pp_h_out, &c->pp_hout_cap, G * out_b)) return 1;
-    if (dev_pair(c->pp_d_out, &c->pp_out_cap, G * (pix + 4))) return 1;   // one u8 plane (+4 bytes slack) per page, whatever label_channels is
-    if (ch == 3 && dev_pair(c->pp_d_out3, &c->pp_out3_cap, G * out3_b)) return 1;
+    // Every slot has its own capacity, and a pair serves only when BOTH slots hold `bytes`: a failed allocation leaves its slot "nothing
+    // allocated" (devmem.h), which the next call sees and fills.
+    auto pair = [&](DeviceMem& mem, DevBuf<uint8_t> (&b)[2], size_t bytes) -> int { return ensure(mem, b[0], bytes) || ensure(mem, b[1], bytes); };
+    if (pair(c->pinned, c->pp_h_in, G * in_b)) return 1;
+    if (pair(c->mem, c->pp_d_in, G * in_b)) return 1;
+    if (pair(c->pinned, c->pp_h_out, G * out_b)) return 1;
+    if (pair(c->mem, c->pp_d_out, G * (pix + 4))) return 1;               // one u8 plane (+4 bytes slack) per page, whatever label_channels is
+    if (ch == 3 && pair(c->mem, c->pp_d_out3, G * out3_b)) return 1;
     const int n_groups = (n_pages + G - 1) / G;
     auto group_pages = [&](int g) { return g * G + G <= n_pages ? G : n_pages - g * G; };
     auto drain = [&](int g) -> int {                                      // labels of group g: staging -> caller
         const int slot = g & 1;
         HIPCHK(hipEventSynchronize(c->pp_out[slot]));
-        for (int k = 0; k < group_pages(g); ++k) memcpy(labels_hw[g * G + k], c->pp_h_out[slot] + (size_t)k * out_b, out_b);
+        for (int k = 0; k < group_pages(g); ++k) memcpy(labels_hw[g * G + k], c->pp_h_out[slot].p + (size_t)k * out_b, out_b);
         return 0;
     };
     alloc_check();
@@ -518,27 +486,27 @@ int sbbseg_segment_pages(sbbseg_ctx* c, int n_pages, const uint8_t* const* pages
     for (int g = 0; g < n_groups; ++g) {
         const int slot = g & 1, np = group_pages(g);
         if (g >= 2 && drain(g - 2)) return 1;                             // frees this slot's staging and device buffers
-        for (int k = 0; k < np; ++k) memcpy(c->pp_h_in[slot] + (size_t)k * in_b, pages_hwc[g * G + k], in_b);
-        HIPCHK(hipMemcpyAsync(c->pp_d_in[slot], c->pp_h_in[slot], (size_t)np * in_b, hipMemcpyHostToDevice, c->copy_in));
+        for (int k = 0; k < np; ++k) memcpy(c->pp_h_in[slot].p + (size_t)k * in_b, pages_hwc[g * G + k], in_b);
+        HIPCHK(hipMemcpyAsync(c->pp_d_in[slot].p, c->pp_h_in[slot].p, (size_t)np * in_b, hipMemcpyHostToDevice, c->copy_in));
         HIPCHK(hipEventRecord(c->pp_in[slot], c->copy_in));
         HIPCHK(hipStreamWaitEvent(c->stream, c->pp_in[slot], 0));
         for (int k = 0; k < np; ++k) {
-            d_pages[k] = c->pp_d_in[slot] + (size_t)k * in_b;
-            d_labels[k] = c->pp_d_out[slot] + (size_t)k * (pix + 4);
+            d_pages[k] = c->pp_d_in[slot].p + (size_t)k * in_b;
+            d_labels[k] = c->pp_d_out[slot].p + (size_t)k * (pix + 4);
         }
         if (sbbseg_segment_pages_dev(c, np, d_pages.data(), Hp, Wp, d_labels.data())) return 1;
-        const uint8_t* d_src = c->pp_d_out[slot];
+        const uint8_t* d_src = c->pp_d_out[slot].p;
         size_t d_stride = pix + 4;
         if (ch == 3) {
             for (int k = 0; k < np; ++k)
-                HIPCHK(launch_replicate3(c->pp_d_out[slot] + (size_t)k * (pix + 4), c->pp_d_out3[slot] + (size_t)k * out3_b, pix, c->stream));
-            d_src = c->pp_d_out3[slot];
+                HIPCHK(launch_replicate3(c->pp_d_out[slot].p + (size_t)k * (pix + 4), c->pp_d_out3[slot].p + (size_t)k * out3_b, pix, c->stream));
+            d_src = c->pp_d_out3[slot].p;
             d_stride = out3_b;
         }
         HIPCHK(hipEventRecord(c->pp_comp[slot], c->stream));
         HIPCHK(hipStreamWaitEvent(c->copy_out, c->pp_comp[slot], 0));
         for (int k = 0; k < np; ++k)
-            HIPCHK(hipMemcpyAsync(c->pp_h_out[slot] + (size_t)k * out_b, d_src + (size_t)k * d_stride, out_b, hipMemcpyDeviceToHost, c->copy_out));
+            HIPCHK(hipMemcpyAsync(c->pp_h_out[slot].p + (size_t)k * out_b, d_src + (size_t)k * d_stride, out_b, hipMemcpyDeviceToHost, c->copy_out));
         HIPCHK(hipEventRecord(c->pp_out[slot], c->copy_out));
     }
     for (int g = n_groups >= 2 ? n_groups - 2 : 0; g < n_groups; ++g)
@@ -693,15 +661,15 @@ int sbbseg_segment_views_dev(sbbseg_ctx* c, int n_views, const sbbseg_view* view
     const size_t thr_at = sizeof(ViewRec) * (size_t)n_views, maps_at = thr_at + sizeof(int) * (size_t)n_views;
     const size_t bytes = maps_at + sizeof(int) * maps.size();
     if (views_staging(c, bytes)) return 1;
-    if (ensure(c, (void**)&c->d_tile_labels, &c->tile_labels_cap, most * per)) return 1;
-    const ViewRec* d_recs = (const ViewRec*)c->d_views;
-    int* d_thr = (int*)((char*)c->d_views + thr_at);
-    const int* d_maps = (const int*)((char*)c->d_views + maps_at);
+    if (ensure(c, c->tile_labels, most * per)) return 1;
+    const ViewRec* d_recs = (const ViewRec*)c->views.p;
+    int* d_thr = (int*)((char*)c->views.p + thr_at);
+    const int* d_maps = (const int*)((char*)c->views.p + maps_at);
     for (int k = 0; k < n_views; ++k) recs[k].thr = views[k].binarise ? (views[k].d_threshold ? views[k].d_threshold : d_thr + k) : nullptr;
-    memcpy(c->h_views, recs.data(), thr_at);
-    memset((char*)c->h_views + thr_at, 0, maps_at - thr_at);
-    if (!maps.empty()) memcpy((char*)c->h_views + maps_at, maps.data(), sizeof(int) * maps.size());
-    HIPCHK(hipMemcpyAsync(c->d_views, c->h_views, bytes, hipMemcpyHostToDevice, c->stream));
+    memcpy(c->h_views.p, recs.data(), thr_at);
+    memset((char*)c->h_views.p + thr_at, 0, maps_at - thr_at);
+    if (!maps.empty()) memcpy((char*)c->h_views.p + maps_at, maps.data(), sizeof(int) * maps.size());
+    HIPCHK(hipMemcpyAsync(c->views.p, c->h_views.p, bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->ev_views, c->stream));
     c->views_copy_pending = true;
     c->d_views_thr = d_thr;
@@ -734,7 +702,7 @@ int sbbseg_segment_views_dev(sbbseg_ctx* c, int n_views, const sbbseg_view* view
                         total += region_entries(lp.g, view_axis_x(gv[w], c->in_W, margin), view_axis_y(gv[w], c->in_H, margin), i, j, L);
                     }
                     if (region_level_table(c, lane, lp.g, L, nb, total)) return 1;
-                    lp.out[L] = c->d_rtab[lane][L]; lp.total[L] = (int)total;
+                    lp.out[L] = c->rtab[lane][L].p; lp.total[L] = (int)total;
                 }
                 HIPCHK(launch_region_build_views(lp, c->stream));
                 c->views_launches += 1;
@@ -748,10 +716,10 @@ int sbbseg_segment_views_dev(sbbseg_ctx* c, int n_views, const sbbseg_view* view
             ip.H = c->in_H; ip.W = c->in_W; ip.margin = margin; ip.lut = fp.lut; ip.c8 = fp.c8; ip.pairs = fp.pairs; ip.pad = fp.pad; ip.pairs_w = fp.pairs_w;
             HIPCHK(launch_ingest_views(ip, c->precision, c->stream));
             c->views_launches += 1;
-            return run_plan(c, nb, c->d_tile_labels + (size_t)first * per, nullptr);
+            return run_plan(c, nb, c->tile_labels.p + (size_t)first * per, nullptr);
         };
         if (run_chunked(c, g.tiles, run_chunk)) return 1;
-        HIPCHK(launch_stitch_views(c->d_tile_labels, c->in_H, c->in_W, margin, d_recs + g.v0, nv, g.blocks, c->stream));
+        HIPCHK(launch_stitch_views(c->tile_labels.p, c->in_H, c->in_W, margin, d_recs + g.v0, nv, g.blocks, c->stream));
         c->views_launches += 1;
     }
     return 0;
@@ -786,18 +754,18 @@ int sbbseg_segment_views(sbbseg_ctx* c, int n_views, const sbbseg_view* views_ho
         plane_bytes += (pix + 4 + 15) & ~(size_t)15;
         most_pix = most_pix > pix ? most_pix : pix;
     }
-    if (ensure(c, (void**)&c->d_page, &c->page_cap, page_bytes)) return 1;
-    if (ensure(c, (void**)&c->d_page_labels, &c->page_labels_cap, plane_bytes)) return 1;
-    if (c->label_channels == 3 && ensure(c, (void**)&c->d_page_labels3, &c->page_labels3_cap, (most_pix + 3) / 4 * 12)) return 1;
+    if (ensure(c, c->page, page_bytes)) return 1;
+    if (ensure(c, c->page_labels, plane_bytes)) return 1;
+    if (c->label_channels == 3 && ensure(c, c->page_labels3, (most_pix + 3) / 4 * 12)) return 1;
     for (int k = 0; k < n_views; ++k) {
         int same = 0;
         while (dv[same].d_page_hwc != dv[k].d_page_hwc) ++same;
         if (same == k)
-            HIPCHK(hipMemcpyAsync(c->d_page + page_at[k], views_host_pointers[k].d_page_hwc, (size_t)dv[k].Hs * dv[k].Ws * 3, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->page.p + page_at[k], views_host_pointers[k].d_page_hwc, (size_t)dv[k].Hs * dv[k].Ws * 3, hipMemcpyHostToDevice, c->stream));
     }
     for (int k = 0; k < n_views; ++k) {                        // (after the search above: it compares the caller's host pointers)
-        dv[k].d_page_hwc = c->d_page + page_at[k];
-        dv[k].d_labels_hw = c->d_page_labels + plane_at[k];
+        dv[k].d_page_hwc = c->page.p + page_at[k];
+        dv[k].d_labels_hw = c->page_labels.p + plane_at[k];
         dv[k].d_threshold = nullptr;
     }
     if (sbbseg_segment_views_dev(c, n_views, dv.data())) {
@@ -805,7 +773,7 @@ int sbbseg_segment_views(sbbseg_ctx* c, int n_views, const sbbseg_view* views_ho
         return 1;
     }
     for (int k = 0; k < n_views; ++k)
-        if (labels_to_host(c, c->d_page_labels + plane_at[k], views_host_pointers[k].d_labels_hw, (size_t)dv[k].ch * dv[k].cw, c->label_channels)) return 1;
+        if (labels_to_host(c, c->page_labels.p + plane_at[k], views_host_pointers[k].d_labels_hw, (size_t)dv[k].ch * dv[k].cw, c->label_channels)) return 1;
     std::vector<int> thr(n_views, 0);
     HIPCHK(hipMemcpyAsync(thr.data(), c->d_views_thr, sizeof(int) * (size_t)n_views, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -75,6 +75,7 @@ int sbbseg_add_conv(sbbseg_ctx* c, const sbbseg_conv_desc* d, const float* w_src
     API_BEGIN
     REQUIRE(c && !c->finalized && d && w_src0 && scale && shift, "bad arguments");
     HIPCHK(hipSetDevice(c->device));
+    AllocScope uploads(c->mem);                  // a failing return below frees what the call uploaded
     REQUIRE(d->n_src == 1 || d->n_src == 2, "n_src must be 1 or 2");
     REQUIRE(d->n_src == 1 || w_src1, "second source needs its weights");
     REQUIRE(d->cout > 0 && d->cout % 8 == 0, "cout %d must be a positive multiple of 8", d->cout);
@@ -276,9 +277,9 @@ int sbbseg_add_conv(sbbseg_ctx* c, const sbbseg_conv_desc* d, const float* w_src
                 }
             pc.d_w_cls[q] = co.d_w; pc.d_kstep_cls[q] = co.d_kstep; pc.d_ktab_cls[q] = co.d_ktab;
             pc.ooy_cls[q] = d->out_off_y; pc.oox_cls[q] = d->out_off_x; pc.wmul_cls[q] = co.wmul_cls[0];
-            (void)hipFree(co.d_scale); (void)hipFree(co.d_shift); (void)hipFree(co.d_head_w); (void)hipFree(co.d_head_scale); (void)hipFree(co.d_head_shift);
-            c->device_bytes -= 2 * sizeof(float) * co.cout_pad;
-            if (d->head_classes > 0) c->device_bytes -= sizeof(float) * ((size_t)d->cout * d->head_classes + 2 * d->head_classes);
+            for (void* p : {(void*)co.d_scale, (void*)co.d_shift, (void*)co.d_head_w, (void*)co.d_head_scale, (void*)co.d_head_shift})
+                (void)c->mem.release(p);         // (class 0's serve)
+            uploads.commit();
             prev.flops += op.flops;
             prev.issued_flops += op.issued_flops;
             prev.min_bytes += op.min_bytes;
@@ -288,6 +289,7 @@ int sbbseg_add_conv(sbbseg_ctx* c, const sbbseg_conv_desc* d, const float* w_src
         }
     }
     c->ops.push_back(op);
+    uploads.commit();
     return 0;
     API_END
 }
@@ -303,6 +305,7 @@ int sbbseg_add_maxpool(sbbseg_ctx* c, int src_tensor, int dst_tensor, int k, int
     const Tensor& t = c->tensors[dst_tensor];
     const int Ho = (s.H - k) / stride + 1, Wo = (s.W - k) / stride + 1;
     REQUIRE(t.H == Ho && t.W == Wo && t.C == s.C, "maxpool output should be %dx%dx%d", Ho, Wo, s.C);
+    AllocScope uploads(c->mem);
     Op op;
     op.type = kPool;
     op.pool.src = src_tensor; op.pool.dst = dst_tensor; op.pool.k = k; op.pool.stride = stride; op.pool.Ho = Ho; op.pool.Wo = Wo;
@@ -318,6 +321,7 @@ int sbbseg_add_maxpool(sbbseg_ctx* c, int src_tensor, int dst_tensor, int k, int
     op.flops = 0;
     op.min_bytes = ((double)s.H * s.W + (double)Ho * Wo) * s.C * c->elem * c->planes;
     c->ops.push_back(op);
+    uploads.commit();
     return 0;
     API_END
 }
@@ -351,6 +355,7 @@ int sbbseg_add_tail(sbbseg_ctx* c, int src0_tensor, int img_c8_tensor, const flo
         wpre = split_prescale(wmax);
         for (float& v : scale_v) v /= wpre;
     }
+    AllocScope uploads(c->mem);
     Op op;
     op.type = kTail;
     op.tail.src0 = src0_tensor; op.tail.img = img_c8_tensor; op.tail.classes = classes;
@@ -368,6 +373,7 @@ int sbbseg_add_tail(sbbseg_ctx* c, int src0_tensor, int img_c8_tensor, const flo
     op.min_bytes = (double)s0.H * s0.W * 64 * c->elem * c->planes + (double)c->in_H * c->in_W * (8 * c->elem * c->planes + 1);
     c->classes = classes;
     c->ops.push_back(op);
+    uploads.commit();
     return 0;
     API_END
 }
@@ -384,6 +390,7 @@ int sbbseg_add_head(sbbseg_ctx* c, int src_tensor, int cin, int classes, const f
     REQUIRE(classes >= 1 && classes <= 8, "head supports 1..8 classes (got %d)", classes);
     REQUIRE(s.H == c->in_H && s.W == c->in_W, "head runs at input resolution");
     REQUIRE(c->classes == 0, "plan already has a head");
+    AllocScope uploads(c->mem);
     Op op;
     op.type = kHead;
     op.head.src = src_tensor; op.head.cin = cin; op.head.classes = classes;
@@ -398,6 +405,7 @@ int sbbseg_add_head(sbbseg_ctx* c, int src_tensor, int cin, int classes, const f
     op.min_bytes = (double)s.H * s.W * (cin * c->elem * c->planes + 1);
     c->classes = classes;
     c->ops.push_back(op);
+    uploads.commit();
     return 0;
     API_END
 }

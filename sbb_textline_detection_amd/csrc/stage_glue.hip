@@ -97,7 +97,7 @@ extern "C" {
 // ------------------------------------------------------------------------------ stage glue (8f-3)
 static size_t align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
-// The host-plane form of an entry point: the caller's H x W plane goes into c->d_morph_b and the `_dev` twin runs on *d_plane (in place
+// The host-plane form of an entry point: the caller's H x W plane goes into c->morph_b.p and the `_dev` twin runs on *d_plane (in place
 // where the twin writes there too).  needed == false -- a size query, or no boxes -- needs no handle and uploads nothing.
 static int stage_plane(sbbseg_ctx* c, const uint8_t* host_hw, int H, int W, bool needed, const void** d_plane)
 {
@@ -106,9 +106,9 @@ static int stage_plane(sbbseg_ctx* c, const uint8_t* host_hw, int H, int W, bool
     if (!needed) return 0;
     if (check_ready(c)) return 1;
     REQUIRE(host_hw, "bad arguments");
-    if (ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, (size_t)H * W)) return 1;
-    HIPCHK(hipMemcpyAsync(c->d_morph_b, host_hw, (size_t)H * W, hipMemcpyHostToDevice, c->stream));
-    *d_plane = c->d_morph_b;
+    if (ensure(c, c->morph_b, (size_t)H * W)) return 1;
+    HIPCHK(hipMemcpyAsync(c->morph_b.p, host_hw, (size_t)H * W, hipMemcpyHostToDevice, c->stream));
+    *d_plane = c->morph_b.p;
     return 0;
 }
 
@@ -119,8 +119,8 @@ int sbbseg_morph_dev(sbbseg_ctx* c, const void* d_src_hw, int H, int W, int op, 
     REQUIRE(d_src_hw && d_dst_hw && H > 0 && W > 0, "bad arguments");
     REQUIRE((op == SBBSEG_MORPH_ERODE || op == SBBSEG_MORPH_DILATE) && ksize >= 1 && (ksize & 1) && iterations >= 1, "morph: op 0|1, odd kernel, iterations >= 1");
     const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_morph_a, &c->morph_a_cap, pix)) return 1;
-    HIPCHK(launch_morph((const uint8_t*)d_src_hw, c->d_morph_a, (uint8_t*)d_dst_hw, H, W, (ksize - 1) / 2 * iterations, op == SBBSEG_MORPH_DILATE, 0, c->stream));
+    if (ensure(c, c->morph_a, pix)) return 1;
+    HIPCHK(launch_morph((const uint8_t*)d_src_hw, c->morph_a.p, (uint8_t*)d_dst_hw, H, W, (ksize - 1) / 2 * iterations, op == SBBSEG_MORPH_DILATE, 0, c->stream));
     return 0;
     API_END
 }
@@ -132,15 +132,15 @@ int sbbseg_morph(sbbseg_ctx* c, const uint8_t* src_hw, int H, int W, int op, int
     REQUIRE(dst_hw, "bad arguments");
     const void* d_plane;
     if (stage_plane(c, src_hw, H, W, true, &d_plane)) return 1;
-    if (sbbseg_morph_dev(c, d_plane, H, W, op, ksize, iterations, c->d_morph_b)) return 1;          // in place
-    HIPCHK(hipMemcpyAsync(dst_hw, c->d_morph_b, (size_t)H * W, hipMemcpyDeviceToHost, c->stream));
+    if (sbbseg_morph_dev(c, d_plane, H, W, op, ksize, iterations, c->morph_b.p)) return 1;          // in place
+    HIPCHK(hipMemcpyAsync(dst_hw, c->morph_b.p, (size_t)H * W, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
     API_END
 }
 
 // The contour ranking behind sbbseg_page_box_dev and sbbseg_text_regions_present_dev: 8-connected components of the 0 / 255 plane in
-// c->d_morph_b, ranked by the area of their outer contour (cv2.contourArea of cv2.findContours' outer borders).  The device ranks by a
+// c->morph_b.p, ranked by the area of their outer contour (cv2.contourArea of cv2.findContours' outer borders).  The device ranks by a
 // lower bound of that area and checks the winner against every other component's bounding-box bound (launch_largest_contour); when
 // that leaves the ranking open -- or when the caller needs the winner's EXACT area (`exact`) -- the host walks the outer borders of
 // the candidates on the device's label plane (parent[i] = root = the component's first pixel in raster order): 4 bytes per pixel of
@@ -151,13 +151,13 @@ int sbbseg_morph(sbbseg_ctx* c, const uint8_t* src_hw, int H, int W, int op, int
 static int rank_contours(sbbseg_ctx* c, int H, int W, bool exact, int (&box)[5], bool* any, long long* area2, bool* traced, double exact_below2 = -1.0)
 {
     const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_cc_parent, &c->cc_parent_cap, pix * sizeof(int)) || ensure(c, (void**)&c->d_cc_count, &c->cc_count_cap, pix * sizeof(int))) return 1;
-    if (ensure(c, (void**)&c->d_cc_aux, &c->cc_aux_cap, 5 * pix * sizeof(int))) return 1;
+    if (ensure(c, c->cc_parent, pix * sizeof(int)) || ensure(c, c->cc_count, pix * sizeof(int))) return 1;
+    if (ensure(c, c->cc_aux, 5 * pix * sizeof(int))) return 1;
     if (!c->d_cc_small && dmalloc(c, (void**)&c->d_cc_small, 4 * sizeof(unsigned long long))) return 1;
     if (!c->d_cc_list && dmalloc(c, (void**)&c->d_cc_list, (6 + kCcMaxRivals) * sizeof(int))) return 1;
     int* d_out = c->d_cc_list;
-    int* aux = c->d_cc_aux;
-    HIPCHK(launch_largest_contour(c->d_morph_b, H, W, c->d_cc_parent, c->d_cc_count, aux, aux + pix, aux + 2 * pix, aux + 3 * pix, aux + 4 * pix,
+    int* aux = c->cc_aux.p;
+    HIPCHK(launch_largest_contour(c->morph_b.p, H, W, c->cc_parent.p, c->cc_count.p, aux, aux + pix, aux + 2 * pix, aux + 3 * pix, aux + 4 * pix,
                                   c->d_cc_small, d_out, c->stream));
     int out[6 + kCcMaxRivals];
     unsigned long long key = 0;
@@ -171,7 +171,7 @@ static int rank_contours(sbbseg_ctx* c, int H, int W, bool exact, int (&box)[5],
     if (*any && (out[5] > 0 || exact || c->force_host_contours || (double)*area2 < exact_below2)) {
         alloc_check();
         std::vector<int> lab(pix);
-        HIPCHK(hipMemcpy(lab.data(), c->d_cc_parent, pix * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(lab.data(), c->cc_parent.p, pix * sizeof(int), hipMemcpyDeviceToHost));
         std::vector<int> cand;
         cand.push_back((int)((unsigned)(key & 0xffffffffu) - 1u));
         if (out[5] <= kCcMaxRivals && !c->force_host_contours) cand.insert(cand.end(), out + 6, out + 6 + out[5]);
@@ -189,7 +189,7 @@ static int rank_contours(sbbseg_ctx* c, int H, int W, bool exact, int (&box)[5],
                 box[0] = tb[0]; box[1] = tb[1]; box[2] = tb[2]; box[3] = tb[3];
             }
         }
-        HIPCHK(hipMemcpy(&box[4], c->d_cc_count + best_root, sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&box[4], c->cc_count.p + best_root, sizeof(int), hipMemcpyDeviceToHost));
         c->host_contour_calls += 1;
         *area2 = best_area2;
         *traced = true;
@@ -204,9 +204,9 @@ int sbbseg_page_box_dev(sbbseg_ctx* c, const void* d_mask_hw, int H, int W, int3
     REQUIRE(d_mask_hw && box_xywh && H > 0 && W > 0, "bad arguments");
     REQUIRE((size_t)H * W < ((size_t)1 << 31), "mask too large for 32-bit pixel indices");
     const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_morph_a, &c->morph_a_cap, pix) || ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
+    if (ensure(c, c->morph_a, pix) || ensure(c, c->morph_b, pix)) return 1;
     // main.py:394-398: gray > 0 -> 255, dilate with the 5x5 kernel of ones, 6 iterations (= one clipped 25x25 maximum)
-    HIPCHK(launch_morph((const uint8_t*)d_mask_hw, c->d_morph_a, c->d_morph_b, H, W, 12, 1, 1, c->stream));
+    HIPCHK(launch_morph((const uint8_t*)d_mask_hw, c->morph_a.p, c->morph_b.p, H, W, 12, 1, 1, c->stream));
     // main.py:398-404: the contour with the largest cv2.contourArea
     int box[5];
     bool any = false, traced = false;
@@ -236,12 +236,12 @@ int sbbseg_text_regions_present_dev(sbbseg_ctx* c, const void* d_regions_hw, int
     REQUIRE(d_regions_hw && present && H > 0 && W > 0 && label >= 0 && label <= 255 && min_area >= 0.0, "bad arguments");
     REQUIRE((size_t)H * W < ((size_t)1 << 31), "plane too large for 32-bit pixel indices");
     const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_morph_a, &c->morph_a_cap, pix) || ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
+    if (ensure(c, c->morph_a, pix) || ensure(c, c->morph_b, pix)) return 1;
     // OPEN = erode, dilate; CLOSE = dilate, erode (cv2.morphologyEx, one iteration each, default border: outside pixels never win);
     // the two dilations in a row are one clipped 9x9 maximum
-    HIPCHK(launch_morph((const uint8_t*)d_regions_hw, c->d_morph_a, c->d_morph_b, H, W, 2, 0, 0x100 | label, c->stream));
-    HIPCHK(launch_morph(c->d_morph_b, c->d_morph_a, c->d_morph_b, H, W, 4, 1, 0, c->stream));
-    HIPCHK(launch_morph(c->d_morph_b, c->d_morph_a, c->d_morph_b, H, W, 2, 0, 0, c->stream));
+    HIPCHK(launch_morph((const uint8_t*)d_regions_hw, c->morph_a.p, c->morph_b.p, H, W, 2, 0, 0x100 | label, c->stream));
+    HIPCHK(launch_morph(c->morph_b.p, c->morph_a.p, c->morph_b.p, H, W, 4, 1, 0, c->stream));
+    HIPCHK(launch_morph(c->morph_b.p, c->morph_a.p, c->morph_b.p, H, W, 2, 0, 0, c->stream));
     const double need = min_area * (double)((long long)H * W);            // main.py:87: area >= min_area * np.prod(image.shape[:2])
     int box[5];
     bool any = false, traced = false;
@@ -269,23 +269,23 @@ int sbbseg_text_region_boxes_dev(sbbseg_ctx* c, const void* d_regions_hw, int H,
                 (boxes_xywh || cap == 0), "bad arguments");
     REQUIRE((size_t)H * W < ((size_t)1 << 31), "plane too large for 32-bit pixel indices");
     const size_t pix = (size_t)H * W;
-    if (ensure(c, (void**)&c->d_morph_a, &c->morph_a_cap, pix) || ensure(c, (void**)&c->d_morph_b, &c->morph_b_cap, pix)) return 1;
-    if (ensure(c, (void**)&c->d_cc_parent, &c->cc_parent_cap, pix * sizeof(int)) || ensure(c, (void**)&c->d_cc_count, &c->cc_count_cap, pix * sizeof(int))) return 1;
-    if (ensure(c, (void**)&c->d_cc_aux, &c->cc_aux_cap, 5 * pix * sizeof(int)) || ensure(c, (void**)&c->d_cc_bg, &c->cc_bg_cap, 2 * pix * sizeof(int))) return 1;
+    if (ensure(c, c->morph_a, pix) || ensure(c, c->morph_b, pix)) return 1;
+    if (ensure(c, c->cc_parent, pix * sizeof(int)) || ensure(c, c->cc_count, pix * sizeof(int))) return 1;
+    if (ensure(c, c->cc_aux, 5 * pix * sizeof(int)) || ensure(c, c->cc_bg, 2 * pix * sizeof(int))) return 1;
     if (!c->d_cc_small && dmalloc(c, (void**)&c->d_cc_small, 4 * sizeof(unsigned long long))) return 1;
     if (!c->d_cc_list && dmalloc(c, (void**)&c->d_cc_list, (6 + kCcMaxRivals) * sizeof(int))) return 1;
     // after OPEN + CLOSE a component holds a whole 5x5 square (planes narrower than the kernel: no such bound)
     const size_t list_cap = (H >= 5 && W >= 5) ? pix / 25 + 16 : pix;
-    if (ensure(c, (void**)&c->d_cc_roots, &c->cc_roots_cap, list_cap * 6 * sizeof(int))) return 1;
-    HIPCHK(launch_morph((const uint8_t*)d_regions_hw, c->d_morph_a, c->d_morph_b, H, W, 2, 0, 0x100 | label, c->stream));
-    HIPCHK(launch_morph(c->d_morph_b, c->d_morph_a, c->d_morph_b, H, W, 4, 1, 0, c->stream));
-    HIPCHK(launch_morph(c->d_morph_b, c->d_morph_a, c->d_morph_b, H, W, 2, 0, 0, c->stream));
-    int* aux = c->d_cc_aux;
-    HIPCHK(launch_largest_contour(c->d_morph_b, H, W, c->d_cc_parent, c->d_cc_count, aux, aux + pix, aux + 2 * pix, aux + 3 * pix, aux + 4 * pix,
+    if (ensure(c, c->cc_roots, list_cap * 6 * sizeof(int))) return 1;
+    HIPCHK(launch_morph((const uint8_t*)d_regions_hw, c->morph_a.p, c->morph_b.p, H, W, 2, 0, 0x100 | label, c->stream));
+    HIPCHK(launch_morph(c->morph_b.p, c->morph_a.p, c->morph_b.p, H, W, 4, 1, 0, c->stream));
+    HIPCHK(launch_morph(c->morph_b.p, c->morph_a.p, c->morph_b.p, H, W, 2, 0, 0, c->stream));
+    int* aux = c->cc_aux.p;
+    HIPCHK(launch_largest_contour(c->morph_b.p, H, W, c->cc_parent.p, c->cc_count.p, aux, aux + pix, aux + 2 * pix, aux + 3 * pix, aux + 4 * pix,
                                   c->d_cc_small, c->d_cc_list, c->stream));
     int* d_n = (int*)(c->d_cc_small + 2);
-    HIPCHK(launch_parentless_roots(c->d_morph_b, c->d_morph_a, H, W, c->d_cc_parent, c->d_cc_bg, c->d_cc_count, aux, aux + pix, aux + 2 * pix,
-                                   aux + 3 * pix, aux + 4 * pix, d_n, c->d_cc_roots, (int)list_cap, c->stream));
+    HIPCHK(launch_parentless_roots(c->morph_b.p, c->morph_a.p, H, W, c->cc_parent.p, c->cc_bg.p, c->cc_count.p, aux, aux + pix, aux + 2 * pix,
+                                   aux + 3 * pix, aux + 4 * pix, d_n, c->cc_roots.p, (int)list_cap, c->stream));
     int found = 0;
     HIPCHK(hipMemcpyAsync(&found, d_n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -293,7 +293,7 @@ int sbbseg_text_region_boxes_dev(sbbseg_ctx* c, const void* d_regions_hw, int H,
     alloc_check();
     struct Root { int root, x0, y0, x1, y1, lower2; };
     std::vector<Root> roots((size_t)found);
-    if (found) HIPCHK(hipMemcpy(roots.data(), c->d_cc_roots, (size_t)found * sizeof(Root), hipMemcpyDeviceToHost));
+    if (found) HIPCHK(hipMemcpy(roots.data(), c->cc_roots.p, (size_t)found * sizeof(Root), hipMemcpyDeviceToHost));
     std::sort(roots.begin(), roots.end(), [](const Root& a, const Root& b) { return a.root > b.root; });
     // main.py:87: area >= min_area * np.prod(image.shape[:2]) and area <= max_area * np.prod(image.shape[:2])
     const double lo = min_area * (double)((long long)H * W), hi = max_area * (double)((long long)H * W);
@@ -310,7 +310,7 @@ int sbbseg_text_region_boxes_dev(sbbseg_ctx* c, const void* d_regions_hw, int H,
     }
     if (trace) {
         std::vector<int> lab(pix);
-        HIPCHK(hipMemcpy(lab.data(), c->d_cc_parent, pix * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(lab.data(), c->cc_parent.p, pix * sizeof(int), hipMemcpyDeviceToHost));
         for (int k = 0; k < found; ++k) {
             if (state[k] != 2) continue;
             const int root = roots[k].root;
@@ -420,8 +420,8 @@ int sbbseg_deskew_profiles_dev(sbbseg_ctx* c, const void* d_mask_hw, int H, int 
     float tab[128];
     cubic_table(tab);
     const size_t need = (size_t)n_angles * 6 * sizeof(double) + sizeof(tab) + (size_t)n_angles * S * sizeof(int);
-    if (ensure(c, (void**)&c->d_deskew, &c->deskew_cap, need)) return 1;
-    double* d_minv = (double*)c->d_deskew;
+    if (ensure(c, c->deskew, need)) return 1;
+    double* d_minv = (double*)c->deskew.p;
     float* d_tab = (float*)(d_minv + (size_t)n_angles * 6);
     int* d_counts = (int*)(d_tab + 128);
     HIPCHK(hipMemcpyAsync(d_minv, minv.data(), minv.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -546,8 +546,8 @@ static int region_sweep(sbbseg_ctx* c, const PlaneSet& ps, const int32_t* boxes_
     cubic_table((float*)(head.data() + minv_bytes));
     memcpy(head.data() + geom_off, geom.data(), (size_t)n_boxes * sizeof(DeskewRegion));
     memcpy(head.data() + src_off, src.data(), (size_t)n_boxes * sizeof(DeskewPlane));
-    if (ensure(c, &c->d_rdk, &c->rdk_cap, head_bytes + 2 * pix_bytes + (size_t)total_counts * sizeof(int))) return 1;
-    unsigned char* d = (unsigned char*)c->d_rdk;
+    if (ensure(c, c->rdk, head_bytes + 2 * pix_bytes + (size_t)total_counts * sizeof(int))) return 1;
+    unsigned char* d = (unsigned char*)c->rdk.p;
     RegionDeskewParams p;
     p.planes = (const DeskewPlane*)(d + src_off);
     p.geom = (const DeskewRegion*)(d + geom_off); p.n_regions = n_boxes; p.n_angles = n_angles; p.radius = 2 * erode_iterations;
@@ -659,7 +659,7 @@ int sbbseg_profile_statistics_host(const int32_t* counts, const int64_t* offsets
     API_END
 }
 
-// queues the statistic of a sweep whose counts are in device memory; *out holds the device pointers of the results (in c->d_pstat)
+// queues the statistic of a sweep whose counts are in device memory; *out holds the device pointers of the results (in c->pstat.p)
 static int profile_stats_queue(sbbseg_ctx* c, const int32_t* d_counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights,
                                int radius, double multiplier, std::vector<unsigned char>& head, ProfileStatParams* out)
 {
@@ -678,8 +678,8 @@ static int profile_stats_queue(sbbseg_ctx* c, const int32_t* d_counts, const int
     }
     const size_t spread_off = head_bytes, winner_off = spread_off + np * sizeof(double), state_off = winner_off + (size_t)n_regions * sizeof(int32_t);
     const size_t ws_off = align16(state_off + np);
-    if (ensure(c, &c->d_pstat, &c->pstat_cap, ws_off + (size_t)ws_doubles * sizeof(double))) return 1;
-    unsigned char* d = (unsigned char*)c->d_pstat;
+    if (ensure(c, c->pstat, ws_off + (size_t)ws_doubles * sizeof(double))) return 1;
+    unsigned char* d = (unsigned char*)c->pstat.p;
     ProfileStatParams p;
     p.counts = d_counts; p.regions = (const ProfileRegion*)(d + w_bytes); p.n_regions = n_regions; p.n_angles = n_angles;
     p.weights = (const double*)d; p.radius = radius; p.multiplier = multiplier;
@@ -863,7 +863,7 @@ int sbbseg_region_line_masks_host(const uint8_t* crop_hw, int h, int w, int erod
     API_END
 }
 
-// queues crop / erode / OPEN / CLOSE / warp / sums of all boxes; *out holds the device pointers of the results (in c->d_rdk), out->n_regions
+// queues crop / erode / OPEN / CLOSE / warp / sums of all boxes; *out holds the device pointers of the results (in c->rdk.p), out->n_regions
 // == 0 when there is nothing to do.  `need_sums`: what a caller that downloads rows and cols must have passed.
 static int region_line_masks_queue(sbbseg_ctx* c, const PlaneSet& ps, const int32_t* boxes_xywh, int n_boxes, int erode_iterations,
                                    const double* slopes, bool need_sums, int64_t* mask_off, int64_t* row_off, int64_t* col_off,
@@ -910,8 +910,8 @@ static int region_line_masks_queue(sbbseg_ctx* c, const PlaneSet& ps, const int3
     memcpy(head.data() + minv_bytes, crop_geom.data(), cgeom_bytes);
     memcpy(head.data() + lgeom_off, geom.data(), (size_t)n_boxes * sizeof(LineRegion));
     memcpy(head.data() + src_off, src.data(), (size_t)n_boxes * sizeof(DeskewPlane));
-    if (ensure(c, &c->d_rdk, &c->rdk_cap, head_bytes + 3 * pix_bytes + (size_t)(total_rows + total_cols) * sizeof(int))) return 1;
-    unsigned char* d = (unsigned char*)c->d_rdk;
+    if (ensure(c, c->rdk, head_bytes + 3 * pix_bytes + (size_t)(total_rows + total_cols) * sizeof(int))) return 1;
+    unsigned char* d = (unsigned char*)c->rdk.p;
     RegionDeskewParams cp;
     memset(&cp, 0, sizeof(cp));
     cp.planes = (const DeskewPlane*)(d + src_off);
@@ -1033,7 +1033,7 @@ int sbbseg_line_split_host(const int32_t* profiles, const int64_t* offsets, int 
 }
 
 // queues the split of regions whose profiles are in device memory (region r: n ints from d_profiles + prof_off[r]); *out holds the device
-// pointers of the results (in c->d_lsplit)
+// pointers of the results (in c->lsplit.p)
 static int line_split_queue(sbbseg_ctx* c, const int32_t* d_profiles, const int64_t* prof_off, int n_regions, const int32_t* geom, const double* rot,
                             const double* weights, const int64_t* weight_off, int sigma_max, const int64_t* line_off, std::vector<unsigned char>& head,
                             LineSplitParams* out)
@@ -1041,13 +1041,13 @@ static int line_split_queue(sbbseg_ctx* c, const int32_t* d_profiles, const int6
     if (sigma_max > kLineSigmaMax) sigma_max = kLineSigmaMax;      // the device's table ends there; larger sigmas are reported, not computed
     const size_t n_off = (size_t)(sigma_max - kLineSigmaMin + 2), n_w = (size_t)weight_off[n_off - 1];
     const size_t off_bytes = align16(n_off * sizeof(long long));
-    if (c->line_w_host.size() != n_w || !c->d_line_w || memcmp(c->line_w_host.data(), weights, n_w * sizeof(double)) != 0) {
+    if (c->line_w_host.size() != n_w || !c->line_w.p || memcmp(c->line_w_host.data(), weights, n_w * sizeof(double)) != 0) {
         std::vector<unsigned char> tab(off_bytes + n_w * sizeof(double));
         for (size_t i = 0; i < n_off; ++i) ((long long*)tab.data())[i] = (long long)weight_off[i];
         memcpy(tab.data() + off_bytes, weights, n_w * sizeof(double));
         c->line_w_host.clear();
-        if (ensure(c, &c->d_line_w, &c->line_w_cap, tab.size())) return 1;
-        HIPCHK(hipMemcpyAsync(c->d_line_w, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
+        if (ensure(c, c->line_w, tab.size())) return 1;
+        HIPCHK(hipMemcpyAsync(c->line_w.p, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         c->line_w_host.assign(weights, weights + n_w);
     }
@@ -1066,11 +1066,11 @@ static int line_split_queue(sbbseg_ctx* c, const int32_t* d_profiles, const int6
         memcpy(reg[r].rot, rot + (size_t)r * 6, 6 * sizeof(double));
         if (g[0] > kProfileLdsSamples) ws_bytes += line_work_bytes(g[0]);
     }
-    if (ensure(c, &c->d_lsplit, &c->lsplit_cap, ws_off + ws_bytes)) return 1;
-    unsigned char* d = (unsigned char*)c->d_lsplit;
+    if (ensure(c, c->lsplit, ws_off + ws_bytes)) return 1;
+    unsigned char* d = (unsigned char*)c->lsplit.p;
     LineSplitParams p;
     p.profiles = d_profiles; p.regions = (const LineSplitRegion*)d; p.n_regions = n_regions; p.sigma_max = sigma_max;
-    p.weights = (const double*)((unsigned char*)c->d_line_w + off_bytes); p.weight_off = (const long long*)c->d_line_w;
+    p.weights = (const double*)((unsigned char*)c->line_w.p + off_bytes); p.weight_off = (const long long*)c->line_w.p;
     p.workspace = d + ws_off; p.info = (int32_t*)(d + info_off); p.pts = (int32_t*)(d + pts_off); p.box = (int32_t*)(d + box_off);
     p.rot = (int32_t*)(d + rot_off);
     HIPCHK(hipMemcpyAsync(d, head.data(), info_off, hipMemcpyHostToDevice, c->stream));

@@ -30,16 +30,16 @@ static void whole_map(int stored, int page, int model, std::vector<int>& m)
 }
 
 // do_prediction(patches=False) on the page as upscaled to Hs x Ws: the page comes from host memory (page_hwc) or is already on the
-// device (d_page_in); the label plane lands in c->d_page_labels and, if labels_out is given, in host memory too -- or, with d_dst, in that
+// device (d_page_in); the label plane lands in c->page_labels and, if labels_out is given, in host memory too -- or, with d_dst, in that
 // device buffer alone (labels_out is then NULL).
 static int whole_scaled_impl(sbbseg_ctx* c, const uint8_t* page_hwc, const void* d_page_in, int Hp, int Wp, int Hs, int Ws, int out_h, int out_w,
                              uint8_t* labels_out, void* d_dst = nullptr)
 {
     const size_t pix = (size_t)Hp * Wp, opix = (size_t)out_h * out_w;
-    if (!d_page_in && ensure(c, (void**)&c->d_page, &c->page_cap, pix * 3)) return 1;
-    if (!d_dst && ensure(c, (void**)&c->d_page_labels, &c->page_labels_cap, opix + 4)) return 1;
+    if (!d_page_in && ensure(c, c->page, pix * 3)) return 1;
+    if (!d_dst && ensure(c, c->page_labels, opix + 4)) return 1;
     const size_t need = sizeof(int) * (size_t)(c->in_H + c->in_W + out_h + out_w);
-    const bool cached = c->d_wmap && c->wmap_cap >= need && c->wmap_key[0] == Hp && c->wmap_key[1] == Wp && c->wmap_key[2] == Hs &&
+    const bool cached = c->wmap.p && c->wmap.cap >= need && c->wmap_key[0] == Hp && c->wmap_key[1] == Wp && c->wmap_key[2] == Hs &&
                         c->wmap_key[3] == Ws && c->wmap_key[4] == out_h && c->wmap_key[5] == out_w;
     if (!cached) {                         // the four gather tables depend on the sizes only: built and uploaded once per geometry
         std::vector<int> my, mx, oy, ox;
@@ -47,9 +47,9 @@ static int whole_scaled_impl(sbbseg_ctx* c, const uint8_t* page_hwc, const void*
         whole_map(Wp, Ws, c->in_W, mx);
         whole_map(out_h, 0, c->in_H, oy);
         whole_map(out_w, 0, c->in_W, ox);
-        if (ensure(c, (void**)&c->d_wmap, &c->wmap_cap, need)) return 1;
+        if (ensure(c, c->wmap, need)) return 1;
         memset(c->wmap_key, 0, sizeof(c->wmap_key));      // (none while the tables are rewritten: a failed copy must not leave the old key)
-        int* d_my = c->d_wmap; int* d_mx = d_my + c->in_H; int* d_oy = d_mx + c->in_W; int* d_ox = d_oy + out_h;
+        int* d_my = c->wmap.p; int* d_mx = d_my + c->in_H; int* d_oy = d_mx + c->in_W; int* d_ox = d_oy + out_h;
         HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(hipMemcpy(d_my, my.data(), sizeof(int) * c->in_H, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d_mx, mx.data(), sizeof(int) * c->in_W, hipMemcpyHostToDevice));
@@ -57,20 +57,20 @@ static int whole_scaled_impl(sbbseg_ctx* c, const uint8_t* page_hwc, const void*
         HIPCHK(hipMemcpy(d_ox, ox.data(), sizeof(int) * out_w, hipMemcpyHostToDevice));
         c->wmap_key[0] = Hp; c->wmap_key[1] = Wp; c->wmap_key[2] = Hs; c->wmap_key[3] = Ws; c->wmap_key[4] = out_h; c->wmap_key[5] = out_w;
     }
-    int* d_my = c->d_wmap; int* d_mx = d_my + c->in_H; int* d_oy = d_mx + c->in_W; int* d_ox = d_oy + out_h;
-    if (!d_page_in) HIPCHK(hipMemcpyAsync(c->d_page, page_hwc, pix * 3, hipMemcpyHostToDevice, c->stream));
+    int* d_my = c->wmap.p; int* d_mx = d_my + c->in_H; int* d_oy = d_mx + c->in_W; int* d_ox = d_oy + out_h;
+    if (!d_page_in) HIPCHK(hipMemcpyAsync(c->page.p, page_hwc, pix * 3, hipMemcpyHostToDevice, c->stream));
     IngestParams ip;
     if (fill_ingest(c, ip)) return 1;
-    ip.page = d_page_in ? (const uint8_t*)d_page_in : c->d_page; ip.Hp = Hp; ip.Wp = Wp; ip.src_Hp = Hp; ip.src_Wp = Wp; ip.tile_xy = nullptr; ip.n_tiles = 1;
+    ip.page = d_page_in ? (const uint8_t*)d_page_in : c->page.p; ip.Hp = Hp; ip.Wp = Wp; ip.src_Hp = Hp; ip.src_Wp = Wp; ip.tile_xy = nullptr; ip.n_tiles = 1;
     ip.whole = 1; ip.map_y = d_my; ip.map_x = d_mx;
     HIPCHK(launch_ingest_u8(ip, c->precision, c->stream));
     {
         KsplitScope scope(c);
         if (run_plan(c, 1, c->d_batch_labels, nullptr)) return 1;
     }
-    HIPCHK(launch_resize_labels(c->d_batch_labels, c->in_H, c->in_W, d_oy, d_ox, out_h, out_w, d_dst ? (uint8_t*)d_dst : c->d_page_labels, c->stream));
+    HIPCHK(launch_resize_labels(c->d_batch_labels, c->in_H, c->in_W, d_oy, d_ox, out_h, out_w, d_dst ? (uint8_t*)d_dst : c->page_labels.p, c->stream));
     if (labels_out) {
-        if (labels_to_host(c, c->d_page_labels, labels_out, opix, c->label_channels)) return 1;
+        if (labels_to_host(c, c->page_labels.p, labels_out, opix, c->label_channels)) return 1;
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     return 0;
@@ -145,13 +145,13 @@ static int whole_views_impl(sbbseg_ctx* c, int n_views, const sbbseg_whole_view*
     }
     const size_t maps_at = sizeof(WholeViewRec) * (size_t)n_views, bytes = maps_at + sizeof(int) * maps.size();
     if (views_staging(c, bytes)) return 1;
-    memcpy(c->h_views, recs.data(), maps_at);
-    memcpy((char*)c->h_views + maps_at, maps.data(), sizeof(int) * maps.size());
-    HIPCHK(hipMemcpyAsync(c->d_views, c->h_views, bytes, hipMemcpyHostToDevice, c->stream));
+    memcpy(c->h_views.p, recs.data(), maps_at);
+    memcpy((char*)c->h_views.p + maps_at, maps.data(), sizeof(int) * maps.size());
+    HIPCHK(hipMemcpyAsync(c->views.p, c->h_views.p, bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->ev_views, c->stream));
     c->views_copy_pending = true;
-    const WholeViewRec* d_recs = (const WholeViewRec*)c->d_views;
-    const int* d_maps = (const int*)((char*)c->d_views + maps_at);
+    const WholeViewRec* d_recs = (const WholeViewRec*)c->views.p;
+    const int* d_maps = (const int*)((char*)c->views.p + maps_at);
     for (int q = 0, first = 0; first < n_views; ++q, first += chunk) {
         const int nb = n_views - first < chunk ? n_views - first : chunk;
         IngestParams fp;
@@ -185,8 +185,8 @@ int sbbseg_extract_page_box(sbbseg_ctx* c, const uint8_t* page_hwc, int Hp, int 
     // border model on the (virtually) upscaled page, result at the upscaled size (main.py:384-392) ...  (mask_out == NULL: the mask --
     // a local of extract_page in the reference -- stays on the device)
     if (whole_scaled_impl(c, page_hwc, nullptr, Hp, Wp, Hs, Ws, Hs, Ws, mask_out)) return 1;
-    // ... whose label plane is still in d_page_labels: threshold, dilate x 6, largest component, bounding box (main.py:394-404)
-    return sbbseg_page_box_dev(c, c->d_page_labels, Hs, Ws, box_xywh, pixels);
+    // ... whose label plane is still in c->page_labels: threshold, dilate x 6, largest component, bounding box (main.py:394-404)
+    return sbbseg_page_box_dev(c, c->page_labels.p, Hs, Ws, box_xywh, pixels);
     API_END
 }
 
@@ -197,8 +197,8 @@ int sbbseg_extract_page_box_dev(sbbseg_ctx* c, const void* d_page_hwc, int Hp, i
     if (check_ready(c)) return 1;
     REQUIRE(d_page_hwc && box_xywh && Hp > 0 && Wp > 0 && Hs > 0 && Ws > 0, "bad arguments");
     if (whole_scaled_impl(c, nullptr, d_page_hwc, Hp, Wp, Hs, Ws, Hs, Ws, nullptr)) return 1;
-    if (d_mask_out) HIPCHK(hipMemcpyAsync(d_mask_out, c->d_page_labels, (size_t)Hs * Ws, hipMemcpyDeviceToDevice, c->stream));
-    return sbbseg_page_box_dev(c, c->d_page_labels, Hs, Ws, box_xywh, pixels);
+    if (d_mask_out) HIPCHK(hipMemcpyAsync(d_mask_out, c->page_labels.p, (size_t)Hs * Ws, hipMemcpyDeviceToDevice, c->stream));
+    return sbbseg_page_box_dev(c, c->page_labels.p, Hs, Ws, box_xywh, pixels);
     API_END
 }
 
@@ -221,9 +221,9 @@ int sbbseg_extract_page_boxes_dev(sbbseg_ctx* c, int n_pages, const sbbseg_whole
         at[k] = scratch;
         scratch += ((size_t)v[k].page_h * v[k].page_w + 15) & ~(size_t)15;
     }
-    if (scratch && ensure(c, (void**)&c->d_page_labels, &c->page_labels_cap, scratch + 16)) return 1;      // (the masks nobody asked for)
+    if (scratch && ensure(c, c->page_labels, scratch + 16)) return 1;      // (the masks nobody asked for)
     for (int k = 0; k < n_pages; ++k)
-        if (!v[k].d_labels_out) v[k].d_labels_out = c->d_page_labels + at[k];
+        if (!v[k].d_labels_out) v[k].d_labels_out = c->page_labels.p + at[k];
     if (whole_views_impl(c, n_pages, v.data())) return 1;
     for (int k = 0; k < n_pages; ++k) {                        // main.py:394-404 per plane; an empty mask: {0, 0, 0, 0} / 0
         int64_t px = 0;
@@ -265,17 +265,17 @@ int sbbseg_run_page(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline
     border->run_planes_valid = layout->run_planes_valid = textline->run_planes_valid = false;      // (the call rewrites the resident planes)
     memset(info, 0, sizeof(*info));
     const size_t spix = (size_t)Hp * Wp, pix = (size_t)Hs * Ws;
-    if (ensure(border, (void**)&border->d_run_page, &border->run_page_cap, spix * 3)) return 1;
-    if (page_mask_out && ensure(border, (void**)&border->d_run_mask, &border->run_mask_cap, pix)) return 1;
-    HIPCHK(hipMemcpyAsync(border->d_run_page, page_hwc, spix * 3, hipMemcpyHostToDevice, border->stream));      // the one upload of the page
+    if (ensure(border, border->run_page, spix * 3)) return 1;
+    if (page_mask_out && ensure(border, border->run_mask, pix)) return 1;
+    HIPCHK(hipMemcpyAsync(border->run_page.p, page_hwc, spix * 3, hipMemcpyHostToDevice, border->stream));      // the one upload of the page
     int64_t pixels = 0;
-    if (sbbseg_extract_page_box_dev(border, border->d_run_page, Hp, Wp, Hs, Ws, page_mask_out ? border->d_run_mask : nullptr, info->box_xywh, &pixels)) return 1;
+    if (sbbseg_extract_page_box_dev(border, border->run_page.p, Hp, Wp, Hs, Ws, page_mask_out ? border->run_mask.p : nullptr, info->box_xywh, &pixels)) return 1;
     info->box_pixels = pixels;                                  // (extract_page_box_dev has synchronised the border handle's stream)
     REQUIRE(pixels > 0, "attempt to get argmax of an empty sequence (the border model found no page: main.py:399-401 raises here)");
-    if (page_mask_out && sbbseg_download_labels(border, page_mask_out, border->d_run_mask, pix, channels)) return 1;
+    if (page_mask_out && sbbseg_download_labels(border, page_mask_out, border->run_mask.p, pix, channels)) return 1;
     const int x = info->box_xywh[0], y = info->box_xywh[1], w = info->box_xywh[2], h = info->box_xywh[3];
     const size_t cpix = (size_t)w * h;
-    // A failed stage: wait for whatever it had queued (its kernels read border->d_run_page and the handle's d_run_a / d_run_b, which the next
+    // A failed stage: wait for whatever it had queued (its kernels read border->run_page and the handle's run_a / run_b, which the next
     // call overwrites / may reallocate), then decide what the failure is.  Only a crop that cannot hold one model input -- what makes the
     // reference's own loop raise inside its bare try / except (main.py:278-281 under 2069-2091 / 2152-2157) -- degrades to "no regions" /
     // "no lines"; a device or allocation error fails the call with its message in sbbseg_last_error(): a fault must not look like an empty page.
@@ -283,14 +283,14 @@ int sbbseg_run_page(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline
     int present = 0;
     bool ok = false;
     do {
-        if (ensure(layout, (void**)&layout->d_run_a, &layout->run_a_cap, cpix + 4) || ensure(layout, (void**)&layout->d_run_b, &layout->run_b_cap, cpix + 4)) break;
+        if (ensure(layout, layout->run_a, cpix + 4) || ensure(layout, layout->run_b, cpix + 4)) break;
         int* d_thr = (int*)(layout->d_hist + 256);
-        if (sbbseg_segment_crop_dev(layout, border->d_run_page, Hp, Wp, Hs, Ws, x, y, w, h, 1, layout->d_run_a, d_thr)) break;
-        if (sbbseg_morph_dev(layout, layout->d_run_a, h, w, SBBSEG_MORPH_ERODE, 5, 3, layout->d_run_b)) break;          // main.py:2074
-        if (sbbseg_morph_dev(layout, layout->d_run_b, h, w, SBBSEG_MORPH_DILATE, 5, 4, layout->d_run_b)) break;         // main.py:2075
-        if (sbbseg_text_regions_present_dev(layout, layout->d_run_b, h, w, 1, 0.00001, &present)) break;                 // main.py:2083, 2096
+        if (sbbseg_segment_crop_dev(layout, border->run_page.p, Hp, Wp, Hs, Ws, x, y, w, h, 1, layout->run_a.p, d_thr)) break;
+        if (sbbseg_morph_dev(layout, layout->run_a.p, h, w, SBBSEG_MORPH_ERODE, 5, 3, layout->run_b.p)) break;          // main.py:2074
+        if (sbbseg_morph_dev(layout, layout->run_b.p, h, w, SBBSEG_MORPH_DILATE, 5, 4, layout->run_b.p)) break;         // main.py:2075
+        if (sbbseg_text_regions_present_dev(layout, layout->run_b.p, h, w, 1, 0.00001, &present)) break;                 // main.py:2083, 2096
         if (sbbseg_download(layout, &info->otsu_threshold, d_thr, sizeof(int))) break;
-        if (sbbseg_download_labels(layout, regions_out, layout->d_run_b, cpix, channels)) break;
+        if (sbbseg_download_labels(layout, regions_out, layout->run_b.p, cpix, channels)) break;
         info->regions_ok = 1;
         ok = true;
     } while (0);
@@ -299,9 +299,9 @@ int sbbseg_run_page(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* textline
     if (info->text_present) {                                  // main.py:2096-2107; a failure = the outer except (2152-2157): no lines
         ok = false;
         do {
-            if (ensure(textline, (void**)&textline->d_run_a, &textline->run_a_cap, cpix + 4)) break;
-            if (sbbseg_segment_crop_dev(textline, border->d_run_page, Hp, Wp, Hs, Ws, x, y, w, h, 0, textline->d_run_a, nullptr)) break;
-            if (sbbseg_download_labels(textline, textlines_out, textline->d_run_a, cpix, 1)) break;
+            if (ensure(textline, textline->run_a, cpix + 4)) break;
+            if (sbbseg_segment_crop_dev(textline, border->run_page.p, Hp, Wp, Hs, Ws, x, y, w, h, 0, textline->run_a.p, nullptr)) break;
+            if (sbbseg_download_labels(textline, textlines_out, textline->run_a.p, cpix, 1)) break;
             info->textlines_ok = 1;
             ok = true;
         } while (0);
@@ -329,19 +329,19 @@ static int run_pages_impl(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* te
         page_at[k] = page_bytes; page_bytes += ((size_t)pg.Hp * pg.Wp * 3 + 15) & ~(size_t)15;
         mask_at[k] = mask_bytes; mask_bytes += ((size_t)pg.Hs * pg.Ws + 15) & ~(size_t)15;
     }
-    if (ensure(border, (void**)&border->d_run_page, &border->run_page_cap, page_bytes)) return 1;
-    if (ensure(border, (void**)&border->d_run_mask, &border->run_mask_cap, mask_bytes)) return 1;
+    if (ensure(border, border->run_page, page_bytes)) return 1;
+    if (ensure(border, border->run_mask, mask_bytes)) return 1;
     // (a failed step: drain_after_failure -- the uploads read the caller's pages, kernels read buffers the next call may reallocate)
     std::vector<sbbseg_whole_view> wv(n_pages);
     std::vector<int32_t> boxes(4 * (size_t)n_pages);
     std::vector<int64_t> px(n_pages);
     for (int k = 0; k < n_pages; ++k) {
         const sbbseg_run_page_io& pg = pages[k];
-        if (hipMemcpyAsync(border->d_run_page + page_at[k], pg.page_hwc, (size_t)pg.Hp * pg.Wp * 3, hipMemcpyHostToDevice, border->stream) != hipSuccess) {
+        if (hipMemcpyAsync(border->run_page.p + page_at[k], pg.page_hwc, (size_t)pg.Hp * pg.Wp * 3, hipMemcpyHostToDevice, border->stream) != hipSuccess) {
             set_error("upload of page %d failed", k);
             return drain_after_failure(border);
         }
-        wv[k] = {border->d_run_page + page_at[k], pg.Hp, pg.Wp, pg.Hs, pg.Ws, pg.Hs, pg.Ws, border->d_run_mask + mask_at[k]};
+        wv[k] = {border->run_page.p + page_at[k], pg.Hp, pg.Wp, pg.Hs, pg.Ws, pg.Hs, pg.Ws, border->run_mask.p + mask_at[k]};
     }
     if (sbbseg_extract_page_boxes_dev(border, n_pages, wv.data(), boxes.data(), px.data())) return drain_after_failure(border);
     HIPCHK(hipStreamSynchronize(border->stream));              // the hand-over: the other two handles read the pages from here on
@@ -350,14 +350,14 @@ static int run_pages_impl(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* te
         memcpy(pg.info.box_xywh, &boxes[4 * (size_t)k], sizeof(pg.info.box_xywh));
         pg.info.box_pixels = px[k];
         if (px[k] <= 0) { pg.status = 1; continue; }            // main.py:399-401 raises for this page: nothing else of it is written
-        if (pg.page_mask_out && sbbseg_download_labels(border, pg.page_mask_out, border->d_run_mask + mask_at[k], (size_t)pg.Hs * pg.Ws, channels)) return drain_after_failure(border);
+        if (pg.page_mask_out && sbbseg_download_labels(border, pg.page_mask_out, border->run_mask.p + mask_at[k], (size_t)pg.Hs * pg.Ws, channels)) return drain_after_failure(border);
         crop_at[k] = crop_bytes;
         crop_bytes += ((size_t)pg.info.box_xywh[2] * pg.info.box_xywh[3] + 4 + 15) & ~(size_t)15;
     }
     auto fits = [](const sbbseg_ctx* h, const sbbseg_run_page_io& pg) { return pg.info.box_xywh[3] >= h->in_H && pg.info.box_xywh[2] >= h->in_W; };
     auto crop_view = [&](const sbbseg_run_page_io& pg, int k, int binarise) -> sbbseg_view {
         const int32_t* b = pg.info.box_xywh;
-        return {border->d_run_page + page_at[k], pg.Hp, pg.Wp, pg.Hs, pg.Ws, b[0], b[1], b[2], b[3], binarise, layout->d_run_a + crop_at[k], nullptr};
+        return {border->run_page.p + page_at[k], pg.Hp, pg.Wp, pg.Hs, pg.Ws, b[0], b[1], b[2], b[3], binarise, layout->run_a.p + crop_at[k], nullptr};
     };
     // layout stage (main.py:2069-2091): every page that has a box and whose crop holds one input of the layout model
     std::vector<int> todo;
@@ -365,7 +365,7 @@ static int run_pages_impl(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* te
     for (int k = 0; k < n_pages; ++k)
         if (pages[k].status == 0 && fits(layout, pages[k])) todo.push_back(k);
     if (todo.empty()) return 0;
-    if (ensure(layout, (void**)&layout->d_run_a, &layout->run_a_cap, crop_bytes) || ensure(layout, (void**)&layout->d_run_b, &layout->run_b_cap, crop_bytes)) return 1;
+    if (ensure(layout, layout->run_a, crop_bytes) || ensure(layout, layout->run_b, crop_bytes)) return 1;
     for (int k : todo) lv.push_back(crop_view(pages[k], k, 1));
     if (sbbseg_segment_views_dev(layout, (int)lv.size(), lv.data())) return drain_after_failure(layout);
     std::vector<int> thr(lv.size(), 0);
@@ -374,8 +374,8 @@ static int run_pages_impl(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* te
         const int k = todo[q];
         sbbseg_run_page_io& pg = pages[k];
         const int w = pg.info.box_xywh[2], h = pg.info.box_xywh[3];
-        uint8_t* raw = layout->d_run_a + crop_at[k];
-        uint8_t* clean = layout->d_run_b + crop_at[k];
+        uint8_t* raw = layout->run_a.p + crop_at[k];
+        uint8_t* clean = layout->run_b.p + crop_at[k];
         int present = 0;
         if (sbbseg_morph_dev(layout, raw, h, w, SBBSEG_MORPH_ERODE, 5, 3, clean) ||                                         // main.py:2074
             sbbseg_morph_dev(layout, clean, h, w, SBBSEG_MORPH_DILATE, 5, 4, clean) ||                                      // main.py:2075
@@ -395,7 +395,7 @@ static int run_pages_impl(sbbseg_ctx* border, sbbseg_ctx* layout, sbbseg_ctx* te
     if (sbbseg_segment_views_dev(textline, (int)lv.size(), lv.data())) return drain_after_failure(textline);
     for (int k : todo) {
         sbbseg_run_page_io& pg = pages[k];
-        if (sbbseg_download_labels(textline, pg.textlines_out, layout->d_run_a + crop_at[k], (size_t)pg.info.box_xywh[2] * pg.info.box_xywh[3], 1)) return drain_after_failure(textline);
+        if (sbbseg_download_labels(textline, pg.textlines_out, layout->run_a.p + crop_at[k], (size_t)pg.info.box_xywh[2] * pg.info.box_xywh[3], 1)) return drain_after_failure(textline);
         pg.info.textlines_ok = 1;
     }
     return 0;
@@ -434,8 +434,8 @@ int sbbseg_run_pages_planes(sbbseg_ctx* layout, int n_pages, sbbseg_plane* regio
     REQUIRE((size_t)n_pages == layout->run_planes.size(), "%d pages asked for, the last sbbseg_run_pages ran %d", n_pages, (int)layout->run_planes.size());
     for (int k = 0; k < n_pages; ++k) {
         const sbbseg_ctx::RunPlanes& rp = layout->run_planes[k];
-        regions[k] = {rp.regions_ok ? layout->d_run_b + rp.at : nullptr, rp.h, rp.w};
-        textlines[k] = {rp.textlines_ok ? layout->d_run_a + rp.at : nullptr, rp.h, rp.w};
+        regions[k] = {rp.regions_ok ? layout->run_b.p + rp.at : nullptr, rp.h, rp.w};
+        textlines[k] = {rp.textlines_ok ? layout->run_a.p + rp.at : nullptr, rp.h, rp.w};
     }
     return 0;
     API_END

@@ -152,3 +152,27 @@ def test_shipped_library_has_no_wrong_answer_probes(lib):
                 depth -= 1
             if re.search(r'getenv\("SBBSEG_(CONV_PROBE|BLOCK_DBG|ER_DBG)', line):
                 assert depth > 0, (src, line.strip())
+
+
+def test_device_memory_is_allocated_and_freed_in_one_place():
+    """Every device and pinned allocation of a handle belongs to one of its two registries (csrc/devmem.h), so sbbseg_destroy frees it and
+    sbbseg_device_bytes counts it without a list kept by hand: the four HIP calls appear once each in the library's sources, in the
+    registries' backends in api.hip, and no byte count is kept beside the registry's."""
+    csrc = os.path.join(ROOT, "sbb_textline_detection_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".cpp")))
+    assert "api.hip" in files and "devmem.h" in files and set(_build.SOURCES) <= set(files)
+    backend = {"hipMalloc(": "static int hip_device_alloc(void** p, size_t bytes)", "hipFree(": "static int hip_device_free(void* p)",
+               "hipHostMalloc(": "static int hip_pinned_alloc(void** p, size_t bytes)", "hipHostFree(": "static int hip_pinned_free(void* p)"}
+    for name in files:
+        for no, line in enumerate(open(os.path.join(csrc, name)).read().splitlines(), 1):
+            for call, definition in backend.items():
+                if re.search(r"\b" + re.escape(call), line):
+                    assert name == "api.hip" and line.startswith(definition + " {"), (name, no, line.strip())
+            assert not re.search(r"(?<!sbbseg_)device_bytes", line), (name, no, line.strip())
+    api = open(os.path.join(csrc, "api.hip")).read()
+    for call, definition in backend.items():
+        assert len(re.findall(r"\b" + re.escape(call), api)) == 1 and api.count(definition + " {") == 1, call
+    # the handle's registries are built on exactly these backends, and only sbbseg_create builds a handle
+    assert "new sbbseg_ctx(hip_device_alloc, hip_device_free, hip_pinned_alloc, hip_pinned_free);" in api
+    assert sum(len(re.findall(r"\bnew sbbseg_ctx\b", open(os.path.join(csrc, name)).read())) for name in files) == 1
+    assert os.path.join(_build.CSRC, "devmem.h") in _build.HEADERS
