@@ -346,7 +346,7 @@ int sbbseg_extract_page_boxes_dev(sbbseg_ctx* c, int n_pages, const sbbseg_whole
  * the textline model at all (main.py:2083-2096): pixels == label -> 255, cv2.morphologyEx MORPH_OPEN then MORPH_CLOSE with the 5x5
  * kernel, cv2.findContours(RETR_TREE), keep parentless contours whose polygon area >= min_area * H * W (the reference: min_area =
  * 0.00001, max_area = 1).  *present = 1 when at least one contour is kept.  Decided from the largest outer-contour area of the
- * opened / closed plane (the ranking of sbbseg_page_box_dev); the polygons themselves are not produced (their boxes: sbbseg_text_region_boxes_dev below).  Synchronises the stream. */
+ * opened / closed plane (the ranking of sbbseg_page_box_dev); the polygons: sbbseg_text_region_contours_dev below.  Synchronises the stream. */
 int sbbseg_text_regions_present_dev(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, double min_area, int* present);
 
 /* The boxes of those contours (main.py:474-478, `self.boxes`): the same class mask, MORPH_OPEN and MORPH_CLOSE, then cv2.boundingRect
@@ -354,12 +354,35 @@ int sbbseg_text_regions_present_dev(sbbseg_ctx* c, const void* d_regions_hw, int
  * another component's hole is dropped) and whose outer-contour area lies in [min_area, max_area] x H x W (the reference: 0.00001, 1).
  * *n_boxes = the number found; at most `cap` boxes are written (cap = 0 and boxes_xywh = NULL: count only, then call again).
  * Order [EXT, unpinned]: the component's first pixel in raster order, DESCENDING -- the reverse discovery order assumed for
- * cv2.findContours' list; slopes are per box, nothing downstream depends on it.  The polygons are not produced.  Synchronises the
- * stream.  The second form takes a HOST plane. */
+ * cv2.findContours' list; slopes are per box, nothing downstream depends on it.  The polygons: sbbseg_text_region_contours_dev.
+ * Synchronises the stream.  The second form takes a HOST plane. */
 int sbbseg_text_region_boxes_dev(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, double min_area, double max_area,
                                  int32_t* boxes_xywh, int cap, int* n_boxes);
 int sbbseg_text_region_boxes(sbbseg_ctx* c, const uint8_t* regions_hw, int H, int W, int label, double min_area, double max_area,
                              int32_t* boxes_xywh, int cap, int* n_boxes);
+
+/* The CONTOURS themselves (main.py:471-481, what get_text_region_contours_and_boxes returns), traced on the device: the same front end,
+ * then the outer border of every parentless component as cv2.findContours(CHAIN_APPROX_SIMPLE) lists it [EXT, restated from OpenCV's
+ * border follower, unpinned] -- first point = the component's first pixel in raster order, counter-clockwise on the screen, a point
+ * kept where the direction changes.  A contour is kept when it has at least three points (main.py:82-83) and its polygon area -- the
+ * exact doubled shoelace sum of the traced chain; no bounds, no host tracing -- lies in [min_area, max_area] x H x W.  Order as the boxes
+ * call: descending first pixel.  *n_contours / *n_points = contours kept and their points in all.  The result -- boxes {x, y, w, h},
+ * doubled areas, point offsets, points -- stays in device memory the handle owns until the next contour call on the handle; read it with
+ * sbbseg_text_region_contours_read.  No label plane leaves the device.  A walk that does not close within 8 x (box pixels) + 8 steps (a
+ * damaged label plane) is an error.  Synchronises the stream.  The second form takes a HOST plane. */
+int sbbseg_text_region_contours_dev(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, double min_area, double max_area,
+                                    int* n_contours, int64_t* n_points);
+int sbbseg_text_region_contours(sbbseg_ctx* c, const uint8_t* regions_hw, int H, int W, int label, double min_area, double max_area,
+                                int* n_contours, int64_t* n_points);
+/* Copies the handle's last contour result out: boxes_xywh [n][4], area2 [n] (TWICE cv2.contourArea), point_off [n + 1] (contour k owns
+ * points point_off[k] .. point_off[k + 1]), points_xy [points][2].  cap_contours / cap_points: room in the caller's arrays; too little of
+ * either is an error that writes nothing.  Synchronises the stream. */
+int sbbseg_text_region_contours_read(sbbseg_ctx* c, int32_t* boxes_xywh, int64_t* area2, int64_t* point_off, int cap_contours, int32_t* points_xy,
+                                     int64_t cap_points);
+/* The host twin of the tracer (no GPU, no handle): the contour of EVERY 8-connected component of mask != 0 -- no morphology, no filter --
+ * by descending first pixel, in the same tables.  All four tables NULL: only *n_contours / *n_points are set (call again with room). */
+int sbbseg_mask_contours_host(const uint8_t* mask_hw, int H, int W, int32_t* boxes_xywh, int64_t* area2, int64_t* point_off, int cap_contours,
+                              int32_t* points_xy, int64_t cap_points, int* n_contours, int64_t* n_points);
 
 /* ---- device buffers for callers without a device runtime of their own.  The reference's environment is Keras/TF (requirements.txt),
  * not PyTorch: what run() keeps resident across its three stages (main.py:2056-2107: the stored page, the border mask, the region
@@ -712,6 +735,17 @@ int sbbseg_debug_op_launch(sbbseg_ctx* c, int op, int32_t* out, int cap);
  * stored (every plane, padding included): *count = differing bytes, *first = offset of the first one from the start of patch `period`
  * (-1: none).  One kernel on the handle's stream, waited for (tests: a batch of cyclically repeated patches must come out periodic). */
 int sbbseg_debug_tensor_period_mismatches(sbbseg_ctx* c, int tensor_id, int n, int period, int64_t* count, int64_t* first);
+/* the device tracer on a raw device mask (!= 0): labels it and traces EVERY root, no morphology and no filter -- shapes OPEN and CLOSE can
+ * never leave behind (tests).  The result is read with sbbseg_text_region_contours_read. */
+int sbbseg_debug_mask_contours_dev(sbbseg_ctx* c, const void* d_mask_hw, int H, int W, int* n_contours, int64_t* n_points);
+/* a contour whose bit map (box + ring, 32-bit words) exceeds `bytes` is traced on the label plane in global memory instead of LDS
+ * (0 .. 65536, the default; tests lower it so that small planes reach the global form) */
+int sbbseg_debug_set_contour_lds_limit(sbbseg_ctx* c, int bytes);
+/* tracer + packing kernels the contour calls have queued on this handle so far */
+int sbbseg_debug_contour_launches(sbbseg_ctx* c, int64_t* value);
+/* sbbseg_mask_contours_host gives up after `steps` steps per contour instead of 8 x (box pixels) + 8 (0 restores that).  Process-global;
+ * tests of the failure path only. */
+int sbbseg_debug_set_contour_host_step_bound(int64_t steps);
 /* counters: which 0 = how often sbbseg_page_box_dev had to fall back to the host ranking on this handle */
 int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value);      /* which: 0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by sbbseg_region_line_masks(_dev), sbbseg_region_line_boxes(_dev) and their sbbseg_planes_* forms, 3 = ingest + region-table + stitch kernels queued by sbbseg_segment_views_dev, 4 = ingest + label-resize kernels queued by the whole-views calls (sbbseg_segment_whole_views_dev, sbbseg_extract_page_boxes_dev, sbbseg_run_pages: 2 per chunk), 5 = kernels queued by the deskew slope sweeps (crop 2, profiles 1, statistic 1 or 2, winner 1 per sweep) */
 /* Test hook for the no-abort guarantee: the nth_check-th next internal host-allocation checkpoint throws

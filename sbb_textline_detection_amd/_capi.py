@@ -42,6 +42,8 @@ EXPORTS = [
     "sbbseg_debug_op_launch", "sbbseg_debug_tensor_period_mismatches",
     "sbbseg_segment_whole_views_dev", "sbbseg_extract_page_boxes_dev", "sbbseg_run_pages",
     "sbbseg_run_pages_planes", "sbbseg_planes_deskew_slopes_dev", "sbbseg_planes_line_masks_dev", "sbbseg_planes_line_boxes_dev",
+    "sbbseg_text_region_contours_dev", "sbbseg_text_region_contours", "sbbseg_text_region_contours_read", "sbbseg_mask_contours_host",
+    "sbbseg_debug_mask_contours_dev", "sbbseg_debug_set_contour_lds_limit", "sbbseg_debug_contour_launches", "sbbseg_debug_set_contour_host_step_bound",
 ]
 
 
@@ -216,6 +218,14 @@ def load_library(path: Optional[str] = None):
         "sbbseg_planes_deskew_slopes_dev": [vp, C.POINTER(Plane), i32, vp, vp, i32, i32, vp, i32, vp],
         "sbbseg_planes_line_masks_dev": [vp, C.POINTER(Plane), i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
         "sbbseg_planes_line_boxes_dev": [vp, C.POINTER(Plane), i32, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
+        "sbbseg_text_region_contours_dev": [vp, vp, i32, i32, i32, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int64)],
+        "sbbseg_text_region_contours": [vp, vp, i32, i32, i32, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int64)],
+        "sbbseg_text_region_contours_read": [vp, vp, vp, vp, i32, vp, C.c_int64],
+        "sbbseg_mask_contours_host": [vp, i32, i32, vp, vp, vp, i32, vp, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int64)],
+        "sbbseg_debug_mask_contours_dev": [vp, vp, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int64)],
+        "sbbseg_debug_set_contour_lds_limit": [vp, i32],
+        "sbbseg_debug_contour_launches": [vp, C.POINTER(C.c_int64)],
+        "sbbseg_debug_set_contour_host_step_bound": [C.c_int64],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -730,6 +740,54 @@ class Context:
                 return [[int(v) for v in b] for b in boxes[:n.value]]
             cap = n.value
 
+    def text_region_contours_dev(self, d_regions: int, H: int, W: int, label: int = 1, min_area: float = 0.00001, max_area: float = 1.0):
+        """get_text_region_contours_and_boxes (main.py:456-481) from a device label plane, traced on the device: ``(boxes, contours)`` --
+        ``self.boxes`` as :meth:`text_region_boxes_dev` gives it and, per box, the contour's CHAIN_APPROX_SIMPLE points as an int32
+        [N, 2] array of (x, y).  Order [EXT, unpinned]: first pixel in raster order, descending.  The tables stay on the device
+        (:meth:`contour_tables` reads them as they are)."""
+        n, npts = C.c_int(0), C.c_int64(0)
+        check(self.lib.sbbseg_text_region_contours_dev(self.h, C.c_void_p(d_regions), int(H), int(W), int(label), float(min_area), float(max_area),
+                                                       C.byref(n), C.byref(npts)), "sbbseg_text_region_contours_dev")
+        return contours_from_tables(*self.contour_tables(n.value, npts.value))
+
+    def text_region_contours(self, regions: np.ndarray, label: int = 1, min_area: float = 0.00001, max_area: float = 1.0):
+        """The same from a host label map ([H, W] or [H, W, 3]: all channels must equal ``label``, main.py:458)."""
+        regions = np.asarray(regions)
+        if regions.ndim == 3:
+            plane = np.where(np.all(regions == label, axis=-1), label, (label + 1) & 255).astype(np.uint8)      # any value but the label
+        else:
+            plane = np.ascontiguousarray(regions, np.uint8)
+        n, npts = C.c_int(0), C.c_int64(0)
+        check(self.lib.sbbseg_text_region_contours(self.h, _ptr(plane), plane.shape[0], plane.shape[1], int(label), float(min_area), float(max_area),
+                                                   C.byref(n), C.byref(npts)), "sbbseg_text_region_contours")
+        return contours_from_tables(*self.contour_tables(n.value, npts.value))
+
+    def debug_mask_contours_dev(self, d_mask: int, H: int, W: int):
+        """The device tracer on a raw device mask (!= 0): every 8-connected component, no morphology, no filter; ``(boxes, contours)``."""
+        n, npts = C.c_int(0), C.c_int64(0)
+        check(self.lib.sbbseg_debug_mask_contours_dev(self.h, C.c_void_p(d_mask), int(H), int(W), C.byref(n), C.byref(npts)),
+              "sbbseg_debug_mask_contours_dev")
+        return contours_from_tables(*self.contour_tables(n.value, npts.value))
+
+    def contour_tables(self, n_contours: int, n_points: int):
+        """The handle's last contour result as the library keeps it: (boxes int32 [n, 4], area2 int64 [n], point_off int64 [n + 1],
+        points int32 [points, 2]).  Arrays smaller than the result are an error that writes nothing."""
+        boxes, area2 = np.zeros((n_contours, 4), np.int32), np.zeros(n_contours, np.int64)
+        off, pts = np.zeros(n_contours + 1, np.int64), np.zeros((n_points, 2), np.int32)
+        check(self.lib.sbbseg_text_region_contours_read(self.h, _ptr(boxes), _ptr(area2), _ptr(off), int(n_contours), _ptr(pts), int(n_points)),
+              "sbbseg_text_region_contours_read")
+        return boxes, area2, off, pts
+
+    def set_contour_lds_limit(self, nbytes: int):
+        """Test hook: contours whose bit map exceeds ``nbytes`` are traced on the label plane in global memory (default 65536)."""
+        check(self.lib.sbbseg_debug_set_contour_lds_limit(self.h, int(nbytes)), "sbbseg_debug_set_contour_lds_limit")
+
+    def contour_launches(self) -> int:
+        """Tracer and packing kernels the contour calls have queued on this handle so far."""
+        v = C.c_int64(0)
+        check(self.lib.sbbseg_debug_contour_launches(self.h, C.byref(v)), "sbbseg_debug_contour_launches")
+        return int(v.value)
+
     def _region_profiles_call(self, fn, src, H, W, boxes, angles_deg, erode_iterations):
         boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
         angles_deg = np.ascontiguousarray(angles_deg, np.float64).reshape(-1)
@@ -1008,6 +1066,36 @@ def host_largest_contour(mask: np.ndarray):
     px = C.c_int64(0)
     check(load_library().sbbseg_debug_largest_contour(_ptr(mask), mask.shape[0], mask.shape[1], _ptr(box), C.byref(px)), "sbbseg_debug_largest_contour")
     return tuple(int(v) for v in box), int(px.value)
+
+
+def contours_from_tables(boxes, area2, point_off, points):
+    """(boxes, contours) of the contour calls from the library's tables: [[x, y, w, h], ...] and one int32 [N, 2] array per contour."""
+    return ([[int(v) for v in b] for b in boxes], [points[int(point_off[k]):int(point_off[k + 1])].copy() for k in range(len(boxes))])
+
+
+def mask_contours_host_tables(mask: np.ndarray):
+    """The library's HOST tracer (no GPU) on a raw u8 mask (!= 0): the contour of every 8-connected component, by descending first pixel,
+    as the tables of :meth:`Context.contour_tables`."""
+    mask = np.ascontiguousarray(mask, np.uint8)
+    lib = load_library()
+    n, npts = C.c_int(0), C.c_int64(0)
+    check(lib.sbbseg_mask_contours_host(_ptr(mask), mask.shape[0], mask.shape[1], None, None, None, 0, None, 0, C.byref(n), C.byref(npts)),
+          "sbbseg_mask_contours_host")
+    boxes, area2 = np.zeros((n.value, 4), np.int32), np.zeros(n.value, np.int64)
+    off, pts = np.zeros(n.value + 1, np.int64), np.zeros((max(npts.value, 1), 2), np.int32)
+    check(lib.sbbseg_mask_contours_host(_ptr(mask), mask.shape[0], mask.shape[1], _ptr(boxes), _ptr(area2), _ptr(off), n.value, _ptr(pts), npts.value,
+                                        C.byref(n), C.byref(npts)), "sbbseg_mask_contours_host")
+    return boxes, area2, off, pts[:npts.value]
+
+
+def mask_contours_host(mask: np.ndarray):
+    """``(boxes, contours)`` of :func:`mask_contours_host_tables`."""
+    return contours_from_tables(*mask_contours_host_tables(mask))
+
+
+def set_contour_host_step_bound(steps: int):
+    """Test hook (process-global): the host tracer gives up after ``steps`` steps per contour; 0 restores 8 x box pixels + 8."""
+    check(load_library().sbbseg_debug_set_contour_host_step_bound(int(steps)), "sbbseg_debug_set_contour_host_step_bound")
 
 
 def _pool_planes(planes, boxes_per_plane, slopes_per_plane=None):

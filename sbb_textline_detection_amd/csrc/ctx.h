@@ -265,7 +265,16 @@ struct sbbseg_ctx {
     sbbseg::DevBuf<int> cc_aux;                          // five int planes: doubled cell area + bounding boxes per root (sbbseg_page_box_dev)
     unsigned long long* d_cc_small = nullptr;      // [0] best key, [1..2] box (4 ints)
     sbbseg::DevBuf<int> cc_bg;                           // two int planes: labels of the complement, border flags (sbbseg_text_region_boxes_dev)
-    sbbseg::DevBuf<int> cc_roots;                        // parentless roots, 6 ints each
+    sbbseg::DevBuf<int> cc_roots;                        // parentless roots (or all roots), 6 ints each: sbbseg::ContourCand
+    // sbbseg_text_region_contours_dev / sbbseg_debug_mask_contours_dev: the last call's result stays here until the next one
+    // (sbbseg_text_region_contours_read; the next device steps read it in place)
+    sbbseg::DevBuf<void> contour_tab;                    // candidates | records | slots | boxes | doubled areas | point offsets | totals
+    sbbseg::DevBuf<int32_t> contour_pts;                 // [points][2] x, y, packed in contour order
+    int contour_n = -1;                                  // contours of the resident result (-1: none)
+    long long contour_np = 0;                            // ... and its points
+    size_t contour_boxes_at = 0, contour_area2_at = 0, contour_off_at = 0;      // byte offsets of the result tables inside contour_tab
+    int contour_lds_limit = 64 * 1024;                   // kContourLdsBytes, or less (sbbseg_debug_set_contour_lds_limit)
+    long long contour_launches = 0;                      // tracer and packing kernels queued so far (sbbseg_debug_contour_launches)
     sbbseg::DevBuf<void> rdk;                            // sbbseg_region_deskew_profiles_dev: maps | table | geometry | crops | counts
     sbbseg::DevBuf<void> pstat;                          // sbbseg_profile_statistics_dev: weights | regions | spread | winner | state | workspace
     long long line_launches = 0;                         // kernels queued by sbbseg_region_line_masks_dev (sbbseg_debug_counter 2)

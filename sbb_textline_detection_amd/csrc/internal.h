@@ -441,6 +441,38 @@ hipError_t launch_parentless_roots(const uint8_t* mask, uint8_t* inv, int H, int
                                    const int* bx0, const int* by0, const int* bx1, const int* by1, int* d_n, int* list, int cap, hipStream_t s);
 hipError_t launch_deskew_profiles(const uint8_t* mask, int H, int W, int S, int top, int left, const double* minv, const float* cubic,
                                   int n_angles, int* counts, hipStream_t s);
+// the outer contour polygons of listed roots of a labelled plane (contours.hip, contour_walk.h): one wave per candidate
+struct ContourCand { int root, x0, y0, x1, y1, lower2; };     // launch_parentless_roots' record: root, box, lower bound of the doubled area
+struct ContourRec {           // what the counting launch leaves per candidate
+    long long area2;          // exact doubled area of the outer contour
+    int n_points, status;     // CHAIN_APPROX_SIMPLE points; kContourOk or why the walk ended early (contour_walk.h)
+    int x, y, w, h;           // cv2.boundingRect of the contour
+};
+struct ContourParams {
+    const int* parent;        // label plane: root per foreground pixel, -1 elsewhere
+    int H, W;
+    const ContourCand* cand;  // [n_cand] in the order of the result
+    int n_cand;
+    int lds_limit;            // bytes: a bit map beyond it takes the global form
+    ContourRec* rec;          // [n_cand], written by the counting launch
+    const int* slot;          // [n_cand] writing launch: the candidate's contour, or -1
+    const long long* point_off;   // [contours + 1] writing launch: first point of every contour
+    int32_t* points;          // [points][2] x, y; nullptr = the counting launch
+};
+struct ContourPackParams {
+    const ContourRec* rec;
+    int n_cand, filter;       // filter: keep contours of at least three points whose area lies in [lo, hi] (main.py:82-88); 0: keep all
+    double lo, hi;
+    int* slot;                // [n_cand]
+    int32_t* boxes;           // [contours][4] x, y, w, h
+    long long* area2;         // [contours]
+    long long* point_off;     // [contours + 1]
+    long long* totals;        // [4] contours, points, candidates whose walk failed, the first such candidate's status
+};
+hipError_t launch_contour_all_roots(const int* parent, const int* bx0, const int* by0, const int* bx1, const int* by1, long n, int* d_n,
+                                    ContourCand* list, int cap, hipStream_t s);
+hipError_t launch_contour_trace(const ContourParams& p, bool any_lds, bool any_global, hipStream_t s);      // 1 launch per form in use
+hipError_t launch_contour_pack(const ContourPackParams& q, hipStream_t s);
 // batched per-region deskew profiles (region_deskew.hip): crop + erode every box of a label plane, then rotate-and-project all
 // (region, angle, row) of a sweep in one launch
 struct DeskewRegion {

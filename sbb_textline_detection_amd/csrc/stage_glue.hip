@@ -9,6 +9,7 @@
 #include "profile_stat.h"
 #include "line_mask.h"
 #include "line_split.h"
+#include "contour_walk.h"
 
 using namespace sbbseg;
 
@@ -260,14 +261,10 @@ int sbbseg_text_regions_present_dev(sbbseg_ctx* c, const void* d_regions_hw, int
 // host (trace_outer_area2 on the label plane, as rank_contours does).  Order [EXT, unpinned]: the component's first pixel in raster order,
 // DESCENDING -- the reverse discovery order that OpenCV's contour list is assumed to have (see host_largest_contour).  Nothing downstream
 // of the boxes depends on it: slopes are per box.
-int sbbseg_text_region_boxes_dev(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, double min_area, double max_area,
-                                 int32_t* boxes_xywh, int cap, int* n_boxes)
+// The front end the boxes and the contours share: class mask, OPEN, CLOSE (into c->morph_b.p), labelling (c->cc_parent.p), and the records of
+// the components without a parent, sorted by DESCENDING root.
+static int parentless_roots(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, std::vector<ContourCand>& roots)
 {
-    API_BEGIN
-    if (check_ready(c)) return 1;
-    REQUIRE(d_regions_hw && n_boxes && H > 0 && W > 0 && label >= 0 && label <= 255 && min_area >= 0.0 && max_area >= min_area && cap >= 0 &&
-                (boxes_xywh || cap == 0), "bad arguments");
-    REQUIRE((size_t)H * W < ((size_t)1 << 31), "plane too large for 32-bit pixel indices");
     const size_t pix = (size_t)H * W;
     if (ensure(c, c->morph_a, pix) || ensure(c, c->morph_b, pix)) return 1;
     if (ensure(c, c->cc_parent, pix * sizeof(int)) || ensure(c, c->cc_count, pix * sizeof(int))) return 1;
@@ -276,7 +273,7 @@ int sbbseg_text_region_boxes_dev(sbbseg_ctx* c, const void* d_regions_hw, int H,
     if (!c->d_cc_list && dmalloc(c, (void**)&c->d_cc_list, (6 + kCcMaxRivals) * sizeof(int))) return 1;
     // after OPEN + CLOSE a component holds a whole 5x5 square (planes narrower than the kernel: no such bound)
     const size_t list_cap = (H >= 5 && W >= 5) ? pix / 25 + 16 : pix;
-    if (ensure(c, c->cc_roots, list_cap * 6 * sizeof(int))) return 1;
+    if (ensure(c, c->cc_roots, list_cap * sizeof(ContourCand))) return 1;
     HIPCHK(launch_morph((const uint8_t*)d_regions_hw, c->morph_a.p, c->morph_b.p, H, W, 2, 0, 0x100 | label, c->stream));
     HIPCHK(launch_morph(c->morph_b.p, c->morph_a.p, c->morph_b.p, H, W, 4, 1, 0, c->stream));
     HIPCHK(launch_morph(c->morph_b.p, c->morph_a.p, c->morph_b.p, H, W, 2, 0, 0, c->stream));
@@ -291,16 +288,30 @@ int sbbseg_text_region_boxes_dev(sbbseg_ctx* c, const void* d_regions_hw, int H,
     HIPCHK(hipStreamSynchronize(c->stream));
     REQUIRE(found >= 0 && (size_t)found <= list_cap, "internal error: %d parentless components, room for %zu", found, list_cap);
     alloc_check();
-    struct Root { int root, x0, y0, x1, y1, lower2; };
-    std::vector<Root> roots((size_t)found);
-    if (found) HIPCHK(hipMemcpy(roots.data(), c->cc_roots.p, (size_t)found * sizeof(Root), hipMemcpyDeviceToHost));
-    std::sort(roots.begin(), roots.end(), [](const Root& a, const Root& b) { return a.root > b.root; });
+    roots.resize((size_t)found);
+    if (found) HIPCHK(hipMemcpy(roots.data(), c->cc_roots.p, (size_t)found * sizeof(ContourCand), hipMemcpyDeviceToHost));
+    std::sort(roots.begin(), roots.end(), [](const ContourCand& a, const ContourCand& b) { return a.root > b.root; });
+    return 0;
+}
+
+int sbbseg_text_region_boxes_dev(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, double min_area, double max_area,
+                                 int32_t* boxes_xywh, int cap, int* n_boxes)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    REQUIRE(d_regions_hw && n_boxes && H > 0 && W > 0 && label >= 0 && label <= 255 && min_area >= 0.0 && max_area >= min_area && cap >= 0 &&
+                (boxes_xywh || cap == 0), "bad arguments");
+    REQUIRE((size_t)H * W < ((size_t)1 << 31), "plane too large for 32-bit pixel indices");
+    const size_t pix = (size_t)H * W;
+    std::vector<ContourCand> roots;
+    if (parentless_roots(c, d_regions_hw, H, W, label, roots)) return 1;
+    const int found = (int)roots.size();
     // main.py:87: area >= min_area * np.prod(image.shape[:2]) and area <= max_area * np.prod(image.shape[:2])
     const double lo = min_area * (double)((long long)H * W), hi = max_area * (double)((long long)H * W);
     std::vector<int> state((size_t)found);                     // 1 keep, 0 drop, 2 undecided
     bool trace = false;
     for (int k = 0; k < found; ++k) {
-        const Root& r = roots[k];
+        const ContourCand& r = roots[k];
         const double lower = (double)r.lower2 * 0.5, upper = (double)(r.x1 - r.x0) * (double)(r.y1 - r.y0);
         if (c->force_host_contours) state[k] = 2;
         else if (upper < lo || lower > hi) state[k] = 0;
@@ -325,7 +336,7 @@ int sbbseg_text_region_boxes_dev(sbbseg_ctx* c, const void* d_regions_hw, int H,
     for (int k = 0; k < found; ++k) {
         if (state[k] != 1) continue;
         if (kept < cap) {
-            const Root& r = roots[k];
+            const ContourCand& r = roots[k];
             int32_t* o = boxes_xywh + (size_t)kept * 4;
             o[0] = r.x0; o[1] = r.y0; o[2] = r.x1 - r.x0 + 1; o[3] = r.y1 - r.y0 + 1;                  // cv2.boundingRect
         }
@@ -344,6 +355,252 @@ int sbbseg_text_region_boxes(sbbseg_ctx* c, const uint8_t* regions_hw, int H, in
     const void* d_plane;
     if (stage_plane(c, regions_hw, H, W, true, &d_plane)) return 1;
     return sbbseg_text_region_boxes_dev(c, d_plane, H, W, label, min_area, max_area, boxes_xywh, cap, n_boxes);
+    API_END
+}
+
+// ---- get_text_region_contours_and_boxes' CONTOURS (main.py:471-481): the outer border of every kept component as
+// cv2.findContours(CHAIN_APPROX_SIMPLE) lists it (contour_walk.h), traced on the device (contours.hip) on the label plane in
+// c->cc_parent.p.  cand: the candidates in the order of the result.  filter: filter_contours_area_of_image's test on the EXACT area of the
+// traced chain (no bounds, no host tracing).  The tables stay in c->contour_tab / c->contour_pts until the next call.
+static int trace_contours(sbbseg_ctx* c, int H, int W, const std::vector<ContourCand>& cand, bool filter, double lo, double hi, int* n_contours,
+                          int64_t* n_points)
+{
+    c->contour_n = -1;
+    c->contour_np = 0;
+    const size_t n = cand.size();
+    *n_contours = 0;
+    *n_points = 0;
+    if (n == 0) {
+        c->contour_n = 0;
+        return 0;
+    }
+    const size_t rec_at = align16(n * sizeof(ContourCand)), slot_at = rec_at + align16(n * sizeof(ContourRec));
+    const size_t boxes_at = slot_at + align16(n * sizeof(int)), area2_at = boxes_at + align16(n * 4 * sizeof(int32_t));
+    const size_t off_at = area2_at + align16(n * sizeof(long long)), totals_at = off_at + align16((n + 1) * sizeof(long long));
+    if (ensure(c, c->contour_tab, totals_at + 4 * sizeof(long long))) return 1;
+    unsigned char* d = (unsigned char*)c->contour_tab.p;
+    bool any_lds = false, any_global = false;
+    for (const ContourCand& k : cand) {
+        const bool lds = contour_form(k.root, k.x0, k.y0, k.x1, k.y1, H, W, c->contour_lds_limit) == kContourFormLds;
+        any_lds = any_lds || lds;
+        any_global = any_global || !lds;
+    }
+    ContourParams p;
+    p.parent = c->cc_parent.p; p.H = H; p.W = W;
+    p.cand = (const ContourCand*)d; p.n_cand = (int)n; p.lds_limit = c->contour_lds_limit;
+    p.rec = (ContourRec*)(d + rec_at); p.slot = (const int*)(d + slot_at); p.point_off = (const long long*)(d + off_at); p.points = nullptr;
+    ContourPackParams q;
+    q.rec = p.rec; q.n_cand = (int)n; q.filter = filter ? 1 : 0; q.lo = lo; q.hi = hi;
+    q.slot = (int*)(d + slot_at); q.boxes = (int32_t*)(d + boxes_at); q.area2 = (long long*)(d + area2_at);
+    q.point_off = (long long*)(d + off_at); q.totals = (long long*)(d + totals_at);
+    long long totals[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(d, cand.data(), n * sizeof(ContourCand), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_contour_trace(p, any_lds, any_global, c->stream));
+    HIPCHK(launch_contour_pack(q, c->stream));
+    HIPCHK(hipMemcpyAsync(totals, q.totals, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                       // (the caller's candidate list lives until here)
+    c->contour_launches += (any_lds ? 1 : 0) + (any_global ? 1 : 0) + 1;
+    REQUIRE(totals[2] == 0, "contour tracing failed for %lld of %zu components (%s): the label plane is damaged", totals[2], n,
+            totals[3] == kContourStepBound ? "the walk did not close within 8 x box pixels + 8 steps"
+                                           : totals[3] == kContourBroken ? "the walk lost its component" : "the component's box does not hold its first pixel");
+    REQUIRE(totals[0] >= 0 && (size_t)totals[0] <= n && totals[1] >= 0, "internal error: %lld contours of %zu candidates", totals[0], n);
+    if (totals[1] > 0) {
+        if (ensure(c, c->contour_pts, (size_t)totals[1] * 2 * sizeof(int32_t))) return 1;
+        p.points = c->contour_pts.p;
+        HIPCHK(launch_contour_trace(p, any_lds, any_global, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->contour_launches += (any_lds ? 1 : 0) + (any_global ? 1 : 0);
+    }
+    c->contour_boxes_at = boxes_at; c->contour_area2_at = area2_at; c->contour_off_at = off_at;
+    c->contour_n = (int)totals[0];
+    c->contour_np = totals[1];
+    *n_contours = c->contour_n;
+    *n_points = (int64_t)c->contour_np;
+    return 0;
+}
+
+int sbbseg_text_region_contours_dev(sbbseg_ctx* c, const void* d_regions_hw, int H, int W, int label, double min_area, double max_area,
+                                    int* n_contours, int64_t* n_points)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    REQUIRE(d_regions_hw && n_contours && n_points && H > 0 && W > 0 && label >= 0 && label <= 255 && min_area >= 0.0 && max_area >= min_area,
+            "bad arguments");
+    REQUIRE((size_t)H * W < ((size_t)1 << 28), "plane too large: a contour's point count must fit 32 bits");
+    c->contour_n = -1;
+    std::vector<ContourCand> roots;
+    if (parentless_roots(c, d_regions_hw, H, W, label, roots)) return 1;
+    // main.py:87: area >= min_area * np.prod(image.shape[:2]) and area <= max_area * np.prod(image.shape[:2])
+    const double lo = min_area * (double)((long long)H * W), hi = max_area * (double)((long long)H * W);
+    return trace_contours(c, H, W, roots, true, lo, hi, n_contours, n_points);
+    API_END
+}
+
+int sbbseg_text_region_contours(sbbseg_ctx* c, const uint8_t* regions_hw, int H, int W, int label, double min_area, double max_area,
+                                int* n_contours, int64_t* n_points)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    const void* d_plane;
+    if (stage_plane(c, regions_hw, H, W, true, &d_plane)) return 1;
+    return sbbseg_text_region_contours_dev(c, d_plane, H, W, label, min_area, max_area, n_contours, n_points);
+    API_END
+}
+
+int sbbseg_debug_mask_contours_dev(sbbseg_ctx* c, const void* d_mask_hw, int H, int W, int* n_contours, int64_t* n_points)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    REQUIRE(d_mask_hw && n_contours && n_points && H > 0 && W > 0, "bad arguments");
+    REQUIRE((size_t)H * W < ((size_t)1 << 28), "plane too large: a contour's point count must fit 32 bits");
+    c->contour_n = -1;
+    const size_t pix = (size_t)H * W;
+    if (ensure(c, c->cc_parent, pix * sizeof(int)) || ensure(c, c->cc_count, pix * sizeof(int)) || ensure(c, c->cc_aux, 5 * pix * sizeof(int))) return 1;
+    if (!c->d_cc_small && dmalloc(c, (void**)&c->d_cc_small, 4 * sizeof(unsigned long long))) return 1;
+    if (!c->d_cc_list && dmalloc(c, (void**)&c->d_cc_list, (6 + kCcMaxRivals) * sizeof(int))) return 1;
+    const size_t list_cap = (size_t)((H + 1) / 2) * (size_t)((W + 1) / 2);         // 8-connected components of an H x W plane, at most
+    if (ensure(c, c->cc_roots, list_cap * sizeof(ContourCand))) return 1;
+    int* aux = c->cc_aux.p;
+    HIPCHK(launch_largest_contour((const uint8_t*)d_mask_hw, H, W, c->cc_parent.p, c->cc_count.p, aux, aux + pix, aux + 2 * pix, aux + 3 * pix,
+                                  aux + 4 * pix, c->d_cc_small, c->d_cc_list, c->stream));
+    int* d_n = (int*)(c->d_cc_small + 2);
+    HIPCHK(launch_contour_all_roots(c->cc_parent.p, aux + pix, aux + 2 * pix, aux + 3 * pix, aux + 4 * pix, (long)pix, d_n, (ContourCand*)c->cc_roots.p,
+                                    (int)list_cap, c->stream));
+    int found = 0;
+    HIPCHK(hipMemcpyAsync(&found, d_n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    REQUIRE(found >= 0 && (size_t)found <= list_cap, "internal error: %d components, room for %zu", found, list_cap);
+    alloc_check();
+    std::vector<ContourCand> roots((size_t)found);
+    if (found) HIPCHK(hipMemcpy(roots.data(), c->cc_roots.p, (size_t)found * sizeof(ContourCand), hipMemcpyDeviceToHost));
+    std::sort(roots.begin(), roots.end(), [](const ContourCand& a, const ContourCand& b) { return a.root > b.root; });
+    return trace_contours(c, H, W, roots, false, 0.0, 0.0, n_contours, n_points);
+    API_END
+}
+
+int sbbseg_text_region_contours_read(sbbseg_ctx* c, int32_t* boxes_xywh, int64_t* area2, int64_t* point_off, int cap_contours, int32_t* points_xy,
+                                     int64_t cap_points)
+{
+    API_BEGIN
+    if (check_ready(c)) return 1;
+    REQUIRE(c->contour_n >= 0, "no contours on this handle: the last contour call failed, or there was none");
+    REQUIRE(cap_contours >= 0 && cap_points >= 0 && point_off && (boxes_xywh || cap_contours == 0) && (area2 || cap_contours == 0) &&
+                (points_xy || cap_points == 0), "bad arguments");
+    const int n = c->contour_n;
+    const long long np = c->contour_np;
+    REQUIRE(cap_contours >= n && cap_points >= np, "room for %d contours and %lld points, the handle holds %d and %lld", cap_contours,
+            (long long)cap_points, n, np);
+    if (n == 0) {
+        point_off[0] = 0;
+        return 0;
+    }
+    static_assert(sizeof(int64_t) == sizeof(long long), "the tables are copied out as they are");
+    const unsigned char* d = (const unsigned char*)c->contour_tab.p;
+    HIPCHK(hipMemcpyAsync(boxes_xywh, d + c->contour_boxes_at, (size_t)n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(area2, d + c->contour_area2_at, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(point_off, d + c->contour_off_at, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (np) HIPCHK(hipMemcpyAsync(points_xy, c->contour_pts.p, (size_t)np * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+    API_END
+}
+
+int sbbseg_debug_set_contour_lds_limit(sbbseg_ctx* c, int bytes)
+{
+    API_BEGIN
+    REQUIRE(c && bytes >= 0 && bytes <= kContourLdsBytes, "contour LDS limit: 0 .. %d bytes", kContourLdsBytes);
+    c->contour_lds_limit = bytes;
+    return 0;
+    API_END
+}
+
+int sbbseg_debug_contour_launches(sbbseg_ctx* c, int64_t* value)
+{
+    API_BEGIN
+    REQUIRE(c && value, "bad arguments");
+    *value = (int64_t)c->contour_launches;
+    return 0;
+    API_END
+}
+
+// The host twin: every 8-connected component of mask != 0 (no morphology, no filter), by descending first pixel, through the same walk.
+static long long g_contour_host_step_bound = 0;          // test hook: > 0 replaces contour_step_bound (sbbseg_debug_set_contour_host_step_bound)
+
+int sbbseg_debug_set_contour_host_step_bound(int64_t steps)
+{
+    API_BEGIN
+    REQUIRE(steps >= 0, "steps must be >= 0 (0 restores the bound of 8 x box pixels + 8)");
+    g_contour_host_step_bound = steps;
+    return 0;
+    API_END
+}
+
+int sbbseg_mask_contours_host(const uint8_t* mask_hw, int H, int W, int32_t* boxes_xywh, int64_t* area2, int64_t* point_off, int cap_contours,
+                              int32_t* points_xy, int64_t cap_points, int* n_contours, int64_t* n_points)
+{
+    API_BEGIN
+    REQUIRE(mask_hw && H > 0 && W > 0 && n_contours && n_points && cap_contours >= 0 && cap_points >= 0, "bad arguments");
+    REQUIRE((size_t)H * W < ((size_t)1 << 28), "plane too large: a contour's point count must fit 32 bits");
+    const bool count_only = !boxes_xywh && !area2 && !point_off && !points_xy;
+    REQUIRE(count_only || (boxes_xywh && area2 && point_off && points_xy), "give every output table, or none (to get the counts)");
+    alloc_check();
+    // the device's label plane: root (first pixel in raster order) per foreground pixel, -1 elsewhere
+    const long n = (long)H * W;
+    std::vector<int> lab((size_t)n, -1);
+    std::vector<ContourCand> comps;
+    std::vector<long> stack;
+    for (long s = 0; s < n; ++s) {
+        if (!mask_hw[s] || lab[s] >= 0) continue;
+        ContourCand k = {(int)s, W, H, -1, -1, 0};
+        stack.assign(1, s);
+        lab[s] = (int)s;
+        while (!stack.empty()) {
+            const long i = stack.back();
+            stack.pop_back();
+            const int y = (int)(i / W), x = (int)(i - (long)y * W);
+            k.x0 = x < k.x0 ? x : k.x0; k.x1 = x > k.x1 ? x : k.x1; k.y0 = y < k.y0 ? y : k.y0; k.y1 = y > k.y1 ? y : k.y1;
+            for (int d = 0; d < 8; ++d) {
+                const int yy = y + dy8[d], xx = x + dx8[d];
+                if ((unsigned)yy >= (unsigned)H || (unsigned)xx >= (unsigned)W) continue;
+                const long j = (long)yy * W + xx;
+                if (mask_hw[j] && lab[j] < 0) { lab[j] = (int)s; stack.push_back(j); }
+            }
+        }
+        comps.push_back(k);
+    }
+    std::vector<int32_t> boxes, pts;
+    std::vector<int64_t> areas, offs(1, 0);
+    for (size_t q = comps.size(); q-- > 0;) {                      // descending first pixel
+        const ContourCand& k = comps[q];
+        const int root = k.root;
+        auto nb = [&](int x, int y) {
+            unsigned m = 0;
+            for (int d = 0; d < 8; ++d) {
+                const int xx = x + contour_step_x(d), yy = y + contour_step_y(d);
+                if ((unsigned)xx < (unsigned)W && (unsigned)yy < (unsigned)H && lab[(size_t)yy * W + xx] == root) m |= 1u << d;
+            }
+            return m;
+        };
+        auto emit = [&](int, int x, int y) { pts.push_back(x); pts.push_back(y); };
+        const long long bound = g_contour_host_step_bound > 0 ? g_contour_host_step_bound
+                                                              : contour_step_bound((long long)(k.x1 - k.x0 + 1) * (k.y1 - k.y0 + 1));
+        const ContourResult r = contour_walk(nb, root % W, root / W, bound, emit);
+        REQUIRE(r.status == kContourOk, "the contour of the component at (%d, %d) did not close within %lld steps", root % W, root / W, bound);
+        const int32_t b[4] = {r.x0, r.y0, r.x1 - r.x0 + 1, r.y1 - r.y0 + 1};
+        boxes.insert(boxes.end(), b, b + 4);
+        areas.push_back((int64_t)r.area2);
+        offs.push_back((int64_t)(pts.size() / 2));
+    }
+    *n_contours = (int)comps.size();
+    *n_points = offs.back();
+    if (count_only) return 0;
+    REQUIRE((size_t)cap_contours >= comps.size() && cap_points >= offs.back(), "room for %d contours and %lld points, the mask has %zu and %lld",
+            cap_contours, (long long)cap_points, comps.size(), (long long)offs.back());
+    if (!boxes.empty()) memcpy(boxes_xywh, boxes.data(), boxes.size() * sizeof(int32_t));
+    if (!areas.empty()) memcpy(area2, areas.data(), areas.size() * sizeof(int64_t));
+    memcpy(point_off, offs.data(), offs.size() * sizeof(int64_t));
+    if (!pts.empty()) memcpy(points_xy, pts.data(), pts.size() * sizeof(int32_t));
+    return 0;
     API_END
 }
 

@@ -117,13 +117,10 @@ def host_text_regions_present(regions: np.ndarray, label: int = 1, min_area: flo
     return _capi.host_largest_contour_area2(p) * 0.5 >= min_area * float(p.shape[0] * p.shape[1])
 
 
-def host_text_region_boxes(regions: np.ndarray, label: int = 1, min_area: float = 0.00001, max_area: float = 1.0):
-    """Host mirror of sbbseg_text_region_boxes_dev (foreign model objects, CPU-only checks; main.py:456-480): class mask -> OPEN -> CLOSE ->
-    [x, y, w, h] of every 8-connected component that is 4-adjacent to the background connected to the frame (no parent) and whose
-    outer-contour area (the library's host tracer, no GPU) lies in [min_area, max_area] x H x W.  Order [EXT, unpinned]: first pixel in
-    raster order, descending -- the reverse discovery order assumed for cv2.findContours' list."""
+def _host_parentless_components(regions: np.ndarray, label: int):
+    """The front end of the two host mirrors below: class mask -> OPEN -> CLOSE, scipy's 8-connected labels (numbered by first pixel in
+    raster order), which of them have no parent (4-adjacent to the background connected to the frame), and their slices."""
     from scipy import ndimage
-    from . import _capi
     a = np.asarray(regions)
     m = np.all(a == label, axis=-1) if a.ndim == 3 else a == label
     p = np.where(m, 255, 0).astype(np.uint8)
@@ -135,15 +132,50 @@ def host_text_region_boxes(regions: np.ndarray, label: int = 1, min_area: float 
     beside = outer[1:-1, :-2] | outer[1:-1, 2:] | outer[:-2, 1:-1] | outer[2:, 1:-1]
     parentless = np.zeros(n + 1, bool)
     parentless[np.unique(lab[beside & (lab > 0)])] = True
-    lo, hi = min_area * float(p.shape[0] * p.shape[1]), max_area * float(p.shape[0] * p.shape[1])
+    return lab, parentless, ndimage.find_objects(lab)
+
+
+def host_text_region_boxes(regions: np.ndarray, label: int = 1, min_area: float = 0.00001, max_area: float = 1.0):
+    """Host mirror of sbbseg_text_region_boxes_dev (foreign model objects, CPU-only checks; main.py:456-480): class mask -> OPEN -> CLOSE ->
+    [x, y, w, h] of every 8-connected component that is 4-adjacent to the background connected to the frame (no parent) and whose
+    outer-contour area (the library's host tracer, no GPU) lies in [min_area, max_area] x H x W.  Order [EXT, unpinned]: first pixel in
+    raster order, descending -- the reverse discovery order assumed for cv2.findContours' list."""
+    from . import _capi
+    lab, parentless, slices = _host_parentless_components(regions, label)
+    lo, hi = min_area * float(lab.shape[0] * lab.shape[1]), max_area * float(lab.shape[0] * lab.shape[1])
     boxes = []
-    for k, sl in reversed(list(enumerate(ndimage.find_objects(lab), start=1))):
+    for k, sl in reversed(list(enumerate(slices, start=1))):
         if not parentless[k]:
             continue
         area = _capi.host_largest_contour_area2(np.where(lab[sl] == k, 255, 0).astype(np.uint8)) * 0.5
         if lo <= area <= hi:
             boxes.append([sl[1].start, sl[0].start, sl[1].stop - sl[1].start, sl[0].stop - sl[0].start])
     return boxes
+
+
+def host_text_region_contours(regions: np.ndarray, label: int = 1, min_area: float = 0.00001, max_area: float = 1.0):
+    """Host mirror of sbbseg_text_region_contours_dev (foreign model objects, CPU-only checks; main.py:456-481): the same components as
+    ``host_text_region_boxes``, each traced by the library's host tracer (``sbbseg_mask_contours_host``, no GPU) and kept when it has at
+    least three points and its area lies in the window.  Returns ``(boxes, contours)``: [[x, y, w, h], ...] and one int32 [N, 2] array of
+    (x, y) per box, CHAIN_APPROX_SIMPLE points in OpenCV's order."""
+    from . import _capi
+    lab, parentless, slices = _host_parentless_components(regions, label)
+    lo, hi = min_area * float(lab.shape[0] * lab.shape[1]), max_area * float(lab.shape[0] * lab.shape[1])
+    boxes, contours = [], []
+    for k, sl in reversed(list(enumerate(slices, start=1))):
+        if not parentless[k]:
+            continue
+        (box,), area2, _, pts = _capi.mask_contours_host_tables(np.where(lab[sl] == k, 255, 0).astype(np.uint8))
+        if len(pts) >= 3 and lo <= int(area2[0]) * 0.5 <= hi:
+            boxes.append([int(box[0]) + sl[1].start, int(box[1]) + sl[0].start, int(box[2]), int(box[3])])
+            contours.append(pts + np.array([sl[1].start, sl[0].start], np.int32))
+    return boxes, contours
+
+
+def closed_rings(contours):
+    """The contours as the reference's filter_contours_area_of_image returns them (main.py:85-90): ``np.uint`` [N + 1, 1, 2], the ring
+    of ``polygon.exterior.coords`` -- the first point repeated at the end."""
+    return [np.concatenate([c, c[:1]]).astype(np.uint).reshape(-1, 1, 2) for c in contours]
 
 
 def _profile_statistics(y: np.ndarray, sigma: float, multiplier: float):
@@ -467,6 +499,20 @@ class InferenceStages:
         finally:
             session.close()
 
+    def get_text_region_contours(self, regions: np.ndarray):
+        """get_text_region_contours_and_boxes (main.py:456-481) for the cleaned layout map: returns what the reference returns -- a list
+        of ``np.uint`` arrays [N + 1, 1, 2], each the closed ring of one kept contour -- and sets ``self.boxes``.  Traced on the device
+        for a SegModel (``sbbseg_text_region_contours``); foreign model objects get the host mirror."""
+        model, session = start_new_session_and_model(self.model_region_dir, **self.kw)
+        try:
+            if isinstance(model, SegModel):
+                self.boxes, contours = model.ctx.text_region_contours(regions, 1, 0.00001, 1.0)
+            else:
+                self.boxes, contours = host_text_region_contours(regions)
+            return closed_rings(contours)
+        finally:
+            session.close()
+
     def get_slopes(self, textlines: np.ndarray, boxes, statistics: str = "device"):
         """One deskew slope per box (``get_slopes``: main.py:1728-1748) on the textline model's handle."""
         model, session = start_new_session_and_model(self.model_textline_dir, **self.kw)
@@ -657,11 +703,25 @@ class InferenceStages:
         library's per-call limits becomes several pooled calls.  Returns per page run_with_line_boxes' 8-tuple; boxes, slopes, masks
         and lines are [] where the textline model did not run.  The line-mask call runs only to return what run_with_lines returns (the
         line-boxes call repeats its kernels: the C entry points share no outputs).  Foreign model objects take the loop."""
+        return self._run_pages_lines(images, masks, False)
+
+    def run_pages_with_contours(self, images, masks: bool = False):
+        """``run_pages_with_line_boxes`` plus, per page, the text-region contours (``get_text_region_contours``'s list; [] where the
+        textline model did not run): a 9-tuple per page.  The per-page boxes call on the resident cleaned layout plane is replaced by the
+        contours call (``text_region_contours_dev``): boxes and contours come out of the same launches, and no label plane leaves the
+        device.  Foreign model objects take the loop."""
+        return self._run_pages_lines(images, masks, True)
+
+    def _run_pages_lines(self, images, masks: bool, contours: bool):
         images = list(images)
         opened = [start_new_session_and_model(d, **self.kw) for d in (self.model_page_dir, self.model_region_dir, self.model_textline_dir)]
         try:
             if not all(isinstance(m, SegModel) for m, _ in opened):
-                return [self.run_with_line_boxes(img, masks=masks) for img in images]
+                out = []
+                for img in images:
+                    page = self.run_with_line_boxes(img, masks=masks)
+                    out.append(page + ((self.get_text_region_contours(page[1]) if page[2] is not None else []),) if contours else page)
+                return out
             if not images:
                 return []
             from . import _capi
@@ -670,7 +730,12 @@ class InferenceStages:
             d_regions, d_textlines = _capi.run_pages_planes(c_region)
             n = len(runs)
             has_lines = [runs[k][2] is not None for k in range(n)]
-            boxes = [c_region.text_region_boxes_dev(*d_regions[k], 1, 0.00001, 1.0) if has_lines[k] else [] for k in range(n)]
+            rings = [[] for _ in range(n)]
+            if contours:
+                traced = [c_region.text_region_contours_dev(*d_regions[k], 1, 0.00001, 1.0) if has_lines[k] else ([], []) for k in range(n)]
+                boxes, rings = [t[0] for t in traced], [closed_rings(t[1]) for t in traced]
+            else:
+                boxes = [c_region.text_region_boxes_dev(*d_regions[k], 1, 0.00001, 1.0) if has_lines[k] else [] for k in range(n)]
             slopes, line_masks, line_boxes = [[] for _ in range(n)], [[] for _ in range(n)], [[] for _ in range(n)]
             for group in _capi.group_pages_for_lines(boxes):
                 planes, gb = [d_textlines[k] for k in group], [boxes[k] for k in group]
@@ -681,7 +746,7 @@ class InferenceStages:
                 gl = c_text.planes_line_boxes_dev(planes, gb, gs, 2)
                 for q, k in enumerate(group):
                     slopes[k], line_masks[k], line_boxes[k] = gs[q], gm[q], gl[q]
-            return [runs[k] + (boxes[k], slopes[k], line_masks[k], line_boxes[k]) for k in range(n)]
+            return [runs[k] + (boxes[k], slopes[k], line_masks[k], line_boxes[k]) + ((rings[k],) if contours else ()) for k in range(n)]
         finally:
             for _, session in opened:
                 session.close()
