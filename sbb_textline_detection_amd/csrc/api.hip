@@ -1,7 +1,7 @@
 // api.hip -- host side of libsbbseg: the error and allocation plumbing every host unit uses (ctx.h), the handle's life cycle, setters and queries,
 // seam 2 (sbbseg_predict), the device buffers handed to callers, and the debug entry points.  The rest of the C ABI declared in include/sbbseg.h:
 // forward.hip (the forward pass over a plan), pages.hip (the tile and page paths), whole.hip (the whole-image branch, sbbseg_run_page(s)), comm.hip
-// (the RCCL collective), plan_build.hip (plan building) and stage_glue.hip (the stage glue).  All of them sit on ctx.h; those that run a plan share exec.h.
+// (the RCCL collective), plan_build.hip (plan building), stage_glue.hip (the stage glue) and contour_glue.hip (components and contours).  All of them sit on ctx.h; those that run a plan share exec.h.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>

@@ -1,5 +1,5 @@
 // ctx.h -- private, host only: what the translation units behind the C ABI (api.hip, forward.hip, pages.hip, whole.hip, comm.hip -- these five
-// through exec.h, forward.hip and pages.hip through route.h too -- plan_build.hip, stage_glue.hip) share: the error and exception plumbing, the allocation helpers, and the handle
+// through exec.h, forward.hip and pages.hip through route.h too -- plan_build.hip, stage_glue.hip, contour_glue.hip) share: the error and exception plumbing, the allocation helpers, and the handle
 // (struct sbbseg_ctx) with the plan structs it embeds.  Device and pinned memory belong to the handle's two registries (devmem.h: `mem`, `pinned`);
 // every device pointer below, in the handle and in the plan structs, points at a block one of them owns and sbbseg_destroy frees with the registry.
 #pragma once
@@ -322,6 +322,24 @@ int ensure(sbbseg_ctx* c, DevBuf<T>& b, size_t bytes)
     if (b.cap >= bytes) return 0;
     if (b.p) HIPCHK(hipStreamSynchronize(c->stream));
     return ensure(c->mem, b, bytes);
+}
+
+// ---- what the stage-glue units (stage_glue.hip, contour_glue.hip) share
+inline size_t align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+// The host-plane form of an entry point: the caller's H x W plane goes into c->morph_b.p and the `_dev` twin runs on *d_plane (in place
+// where the twin writes there too).  needed == false -- a size query, or no boxes -- needs no handle and uploads nothing.
+inline int stage_plane(sbbseg_ctx* c, const uint8_t* host_hw, int H, int W, bool needed, const void** d_plane)
+{
+    *d_plane = nullptr;
+    REQUIRE(H > 0 && W > 0, "bad arguments");
+    if (!needed) return 0;
+    if (check_ready(c)) return 1;
+    REQUIRE(host_hw, "bad arguments");
+    if (ensure(c, c->morph_b, (size_t)H * W)) return 1;
+    HIPCHK(hipMemcpyAsync(c->morph_b.p, host_hw, (size_t)H * W, hipMemcpyHostToDevice, c->stream));
+    *d_plane = c->morph_b.p;
+    return 0;
 }
 
 }  // namespace sbbseg

@@ -1,4 +1,4 @@
-// internal.h -- structures shared by the host side (api.hip, forward.hip, pages.hip, whole.hip, comm.hip, plan_build.hip and stage_glue.hip
+// internal.h -- structures shared by the host side (api.hip, forward.hip, pages.hip, whole.hip, comm.hip, plan_build.hip, stage_glue.hip and contour_glue.hip
 // through ctx.h; wpack.h) and the gfx950 kernel units (kernels.hip and the other *.hip around it).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -394,7 +394,7 @@ __global__ __launch_bounds__(256) void cc_box_kernel(const int* parent, int* bx0
     wave_minmax_by_root(by0, by1, cur, loy, hiy);
 }
 // best = max over roots of (area2 lower bound, then LARGEST root index: the reference's np.argmax over OpenCV's contour list, which
-// runs in reverse discovery order, keeps the last-discovered of equal areas -- api.hip host_largest_contour); key = area2 << 32 | root + 1
+// runs in reverse discovery order, keeps the last-discovered of equal areas -- contour_host.h host_largest_contour); key = area2 << 32 | root + 1
 __global__ __launch_bounds__(256) void cc_best_area_kernel(const int* parent, const int* area2, long n, unsigned long long* best)
 {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;

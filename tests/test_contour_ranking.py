@@ -89,6 +89,27 @@ def test_equal_areas_go_to_the_last_discovered():
     assert _capi.host_largest_contour(by_name["equal_blocks"])[0] == (50, 30, 30, 20)
 
 
+def test_largest_contour_is_the_argmax_of_the_contour_tables():
+    """The host ranking (sbbseg_debug_largest_contour[_area2]) and the host twin's tables (sbbseg_mask_contours_host) state the same
+    contours: the ranking's winner is the tables' entry at np.argmax(area2), in area and in box.  The tables run by descending first
+    pixel, so numpy's first maximum is the later root: the reference's own tie rule."""
+    import cc_planes
+    import contour_shapes
+    masks = list(contour_shapes.hand_shapes().values()) + contour_shapes.random_masks(400, seed=11, max_side=24)
+    masks += [cc_planes.region_mask(p) for planes in cc_planes.region_families().values() for p in planes.values()]
+    checked = ties = 0
+    for k, m in enumerate(masks):
+        if not np.any(m):
+            continue
+        boxes, area2, _, _ = _capi.mask_contours_host_tables(m)
+        best = int(np.argmax(area2))
+        assert _capi.host_largest_contour_area2(m) == int(area2[best]), k
+        assert list(_capi.host_largest_contour(m)[0]) == boxes[best].tolist(), k
+        checked += 1
+        ties += int((area2 == area2[best]).sum() > 1)
+    assert checked >= 440 and ties >= 50, (checked, ties)
+
+
 def test_frame_beats_block_unlike_pixel_count():
     name, m = cases()[0]
     (x, y, w, h), px = sg.largest_component_box(m)
