@@ -746,6 +746,15 @@ int sbbseg_debug_contour_launches(sbbseg_ctx* c, int64_t* value);
 /* sbbseg_mask_contours_host gives up after `steps` steps per contour instead of 8 x (box pixels) + 8 (0 restores that).  Process-global;
  * tests of the failure path only. */
 int sbbseg_debug_set_contour_host_step_bound(int64_t steps);
+/* sbbseg_profile_statistics_host / _dev behind one signature, with two more outputs (tests).  counts is a HOST array.  c = NULL: the serial
+ * host twin.  A handle: the counts are uploaded and the product's kernels run through the product's launch.  Optional outputs: smooth = z of
+ * every profile, packed like counts; below [n_regions][n_angles] = the level a deep minimum must lie below, mean(maxima > 10) * (1 - 1 /
+ * multiplier) as the reference writes it, NaN without such maxima -- the only place where the ORDER of the compacted maxima shows. */
+int sbbseg_debug_profile_statistics(sbbseg_ctx* c, const int32_t* counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights,
+                                    int radius, double multiplier, double* spread, uint8_t* state, int32_t* winner, double* smooth, double* below);
+/* The statistic's own float64 divide (op 0: out[i] = a[i] / b[i]) and square root (op 1: out[i] = sqrt(a[i]), b unused), which claim IEEE
+ * round-to-nearest-even for every class of operand (tests).  Host arrays of n <= 2^24 doubles.  c = NULL: on the host; a handle: one kernel. */
+int sbbseg_debug_soft_arith(sbbseg_ctx* c, int op, const double* a, const double* b, int64_t n, double* out);
 /* counters: which 0 = how often sbbseg_page_box_dev had to fall back to the host ranking on this handle */
 int sbbseg_debug_counter(sbbseg_ctx* c, int which, int64_t* value);      /* which: 0 = exact host contour rankings, 1 = patches run through the plan, 2 = kernels queued by sbbseg_region_line_masks(_dev), sbbseg_region_line_boxes(_dev) and their sbbseg_planes_* forms, 3 = ingest + region-table + stitch kernels queued by sbbseg_segment_views_dev, 4 = ingest + label-resize kernels queued by the whole-views calls (sbbseg_segment_whole_views_dev, sbbseg_extract_page_boxes_dev, sbbseg_run_pages: 2 per chunk), 5 = kernels queued by the deskew slope sweeps (crop 2, profiles 1, statistic 1 or 2, winner 1 per sweep) */
 /* Test hook for the no-abort guarantee: the nth_check-th next internal host-allocation checkpoint throws

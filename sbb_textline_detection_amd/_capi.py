@@ -44,6 +44,7 @@ EXPORTS = [
     "sbbseg_run_pages_planes", "sbbseg_planes_deskew_slopes_dev", "sbbseg_planes_line_masks_dev", "sbbseg_planes_line_boxes_dev",
     "sbbseg_text_region_contours_dev", "sbbseg_text_region_contours", "sbbseg_text_region_contours_read", "sbbseg_mask_contours_host",
     "sbbseg_debug_mask_contours_dev", "sbbseg_debug_set_contour_lds_limit", "sbbseg_debug_contour_launches", "sbbseg_debug_set_contour_host_step_bound",
+    "sbbseg_debug_profile_statistics", "sbbseg_debug_soft_arith",
 ]
 
 
@@ -226,6 +227,8 @@ def load_library(path: Optional[str] = None):
         "sbbseg_debug_set_contour_lds_limit": [vp, i32],
         "sbbseg_debug_contour_launches": [vp, C.POINTER(C.c_int64)],
         "sbbseg_debug_set_contour_host_step_bound": [C.c_int64],
+        "sbbseg_debug_profile_statistics": [vp, vp, vp, i32, i32, vp, i32, C.c_double, vp, vp, vp, vp, vp],
+        "sbbseg_debug_soft_arith": [vp, i32, vp, vp, C.c_int64, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -1305,6 +1308,34 @@ def profile_statistics_host(counts, offsets, n_angles: int, weights=None, multip
                                                         float(multiplier), _ptr(spread), _ptr(state), _ptr(winner), _ptr(smooth)),
           "sbbseg_profile_statistics_host")
     return (spread, state, winner, smooth) if want_smooth else (spread, state, winner)
+
+
+def debug_profile_statistics(ctx, counts, offsets, n_angles: int, weights=None, multiplier: float = 20.3):
+    """(spread, state, winner, smooth, below) of sbbseg_debug_profile_statistics from packed int32 HOST counts: ``ctx`` None = the serial host
+    twin, a ``Context`` = the product's kernels.  ``smooth``: z packed like ``counts``; ``below`` float64 [n_regions, n_angles]."""
+    counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+    offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+    n = offsets.shape[0] - 1
+    w = None if weights is None else np.ascontiguousarray(weights, np.float64).reshape(-1)
+    spread, state, winner = np.zeros((n, n_angles), np.float64), np.zeros((n, n_angles), np.uint8), np.zeros(n, np.int32)
+    smooth, below = np.zeros(counts.shape[0], np.float64), np.zeros((n, n_angles), np.float64)
+    check(load_library().sbbseg_debug_profile_statistics(None if ctx is None else ctx.h, _ptr(counts), _ptr(offsets), n, int(n_angles), _ptr(w),
+                                                         0 if w is None else w.shape[0] - 1, float(multiplier), _ptr(spread), _ptr(state), _ptr(winner),
+                                                         _ptr(smooth), _ptr(below)), "sbbseg_debug_profile_statistics")
+    return spread, state, winner, smooth, below
+
+
+def debug_soft_arith(ctx, op: int, a, b=None) -> np.ndarray:
+    """csrc/profile_stat.h's soft_div(a, b) (``op`` 0) or soft_sqrt(a) (``op`` 1) element by element: ``ctx`` None = on the host, a ``Context`` =
+    one kernel.  float64 in, float64 out (compare bit patterns)."""
+    a = np.ascontiguousarray(a, np.float64).reshape(-1)
+    b = None if b is None else np.ascontiguousarray(b, np.float64).reshape(-1)
+    if op == 0 and (b is None or b.shape != a.shape):
+        raise ValueError("debug_soft_arith: the divide takes two arrays of one length")
+    out = np.zeros(a.shape[0], np.float64)
+    check(load_library().sbbseg_debug_soft_arith(None if ctx is None else ctx.h, int(op), _ptr(a), _ptr(b), a.shape[0], _ptr(out)),
+          "sbbseg_debug_soft_arith")
+    return out
 
 
 _LINE_TABLES = {}

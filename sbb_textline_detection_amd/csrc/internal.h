@@ -549,8 +549,12 @@ struct ProfileStatParams {
     double* spread;           // [n_regions][n_angles]
     uint8_t* state;           // [n_regions][n_angles]: 0 appended, 1 skipped, 2 exception
     int32_t* winner;          // [n_regions]
+    double* smooth;           // null, or (sbbseg_debug_profile_statistics) z of every profile, packed like counts
+    double* below;            // null, or (the same) [n_regions][n_angles]: what deep_level returned
 };
 hipError_t launch_profile_statistics(const ProfileStatParams& p, bool any_long, hipStream_t s);
+// out[i] = soft_div(a[i], b[i]) (op 0) or soft_sqrt(a[i]) (op 1) of profile_stat.h on the device (sbbseg_debug_soft_arith)
+hipError_t launch_soft_arith(int op, const double* a, const double* b, long long n, double* out, hipStream_t s);
 // the text lines of every region from its row or column sums (line_split.hip, line_split.h): one wave per region
 struct LineSplitRegion {
     long long prof_off;       // first int of the region's profile

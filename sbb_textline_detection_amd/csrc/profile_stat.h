@@ -209,12 +209,12 @@ SBB_HD double pairwise_block(const F& f, int o, int n)
 }
 
 template <class F>
-SBB_HD double pairwise_sum(const F& f, int n, PairwiseStack* st)
+SBB_HD double pairwise_range(const F& f, int first, int n, PairwiseStack* st)
 {
 #pragma clang fp contract(off)
-    if (n <= 128) return pairwise_block(f, 0, n);
+    if (n <= 128) return pairwise_block(f, first, n);
     int top = 0, vtop = 0;
-    st->off[0] = 0; st->len[0] = n; top = 1;
+    st->off[0] = first; st->len[0] = n; top = 1;
     while (top > 0) {
         --top;
         const int o = st->off[top], l = st->len[top];
@@ -232,6 +232,24 @@ SBB_HD double pairwise_sum(const F& f, int n, PairwiseStack* st)
         }
     }
     return st->val[0];
+}
+
+// np.add.reduce of f(0) .. f(n - 1) (what np.sum, np.mean and np.std call): numpy hands its add loop at most one ufunc buffer (8192
+// elements, numpy's default bufsize) at a time, so the pairwise sum is taken per stretch of 8192 and the stretches are added up in order,
+// starting from 0.  Up to 8192 elements that is the pairwise sum of the whole.
+constexpr int kNumpySumStretch = 8192;
+
+template <class F>
+SBB_HD double pairwise_sum(const F& f, int n, PairwiseStack* st)
+{
+#pragma clang fp contract(off)
+    if (n <= kNumpySumStretch) return pairwise_range(f, 0, n, st);
+    double res = 0.0;
+    for (int first = 0; first < n; first += kNumpySumStretch) {
+        const int len = n - first < kNumpySumStretch ? n - first : kNumpySumStretch;
+        res = res + pairwise_range(f, first, len, st);
+    }
+    return res;
 }
 
 template <class Ptr>
@@ -291,9 +309,9 @@ SBB_HD int classify_minimum(Ptr z, int n, int mid, double below)
 
 // The whole statistic of one profile, serially (the CPU entry point; the kernels of profile_stats.hip deal the same steps out to the lanes
 // of a wave).  z: n doubles, g: n + 40 doubles of workspace; z holds the smoothed profile afterwards.  Returns the state, *spread = np.std(z)
-// for kProfileAppended and 0 otherwise.
+// for kProfileAppended and 0 otherwise.  Optional (debug entry point): smooth_out = a copy of z, *below_out = what deep_level returned.
 inline int profile_statistic_serial(const int32_t* y, int n, const double* w, int radius, double multiplier, double* z, double* g,
-                                    PairwiseStack* st, double* spread)
+                                    PairwiseStack* st, double* spread, double* smooth_out = nullptr, double* below_out = nullptr)
 {
     int top = 0;
     for (int i = 0; i < n; ++i) top = y[i] > top ? y[i] : top;
@@ -305,6 +323,8 @@ inline int profile_statistic_serial(const int32_t* y, int n, const double* w, in
         if (peak_starts_at(z, n, i, &mid) && z[mid] >= 0.0 && z[mid] > 10.0) g[m++] = z[mid];
     }
     const double below = deep_level(g, m, multiplier, st);
+    if (smooth_out) memcpy(smooth_out, z, (size_t)n * sizeof(double));
+    if (below_out) *below_out = below;
     const FlippedSamples fs{y, n, (double)top};
     const int nf = n + kProfileFlipExtra;
     for (int k = 0; k < nf; ++k) g[k] = smooth_sample(fs, nf, w, radius, k);

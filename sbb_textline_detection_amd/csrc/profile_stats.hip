@@ -91,6 +91,11 @@ __global__ __launch_bounds__(64) void profile_stat_kernel(const ProfileStatParam
         if (state == kProfileAppended) spread = std_of(z, n, &stack);
         p.spread[blockIdx.x] = spread;
         p.state[blockIdx.x] = (uint8_t)state;
+        if (p.below) p.below[blockIdx.x] = below;
+    }
+    if (p.smooth) {                                                 // (debug entry point only: z is not written after the first smoothing)
+        double* out = p.smooth + reg.count_off + (size_t)a * n;
+        for (int i = lane; i < n; i += 64) out[i] = z[i];
     }
 }
 
@@ -102,7 +107,21 @@ __global__ __launch_bounds__(64) void profile_winner_kernel(const ProfileStatPar
     p.winner[r] = sweep_winner(p.spread + (size_t)r * p.n_angles, p.state + (size_t)r * p.n_angles, p.n_angles);
 }
 
+// soft_div / soft_sqrt on operands of any class, one per thread (sbbseg_debug_soft_arith)
+__global__ __launch_bounds__(256) void soft_arith_kernel(int op, const double* a, const double* b, long long n, double* out)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = op == 0 ? soft_div(a[i], b[i]) : soft_sqrt(a[i]);
+}
+
 }  // namespace
+
+hipError_t launch_soft_arith(int op, const double* a, const double* b, long long n, double* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(soft_arith_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op, a, b, n, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_profile_statistics(const ProfileStatParams& p, bool any_long, hipStream_t s)
 {

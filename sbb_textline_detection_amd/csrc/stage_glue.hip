@@ -330,13 +330,10 @@ static int check_profile_tables(const int64_t* offsets, int n_regions, int n_ang
     return 0;
 }
 
-int sbbseg_profile_statistics_host(const int32_t* counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights, int radius,
-                                   double multiplier, double* spread, uint8_t* state, int32_t* winner, double* smooth)
+// the serial host twin on every profile of a sweep (checked arguments); smooth and below are optional
+static void profile_stats_serial(const int32_t* counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights, int radius,
+                                 double multiplier, double* spread, uint8_t* state, int32_t* winner, double* smooth, double* below)
 {
-    API_BEGIN
-    if (check_profile_tables(offsets, n_regions, n_angles, radius)) return 1;
-    REQUIRE((counts && spread && state && winner) || n_regions == 0, "bad arguments");
-    alloc_check();
     if (!weights) { weights = kSigma2Weights; radius = kSigma2Radius; }
     std::vector<double> z, g;
     PairwiseStack stack;
@@ -346,18 +343,29 @@ int sbbseg_profile_statistics_host(const int32_t* counts, const int64_t* offsets
         for (int a = 0; a < n_angles; ++a) {
             const size_t k = (size_t)r * n_angles + a;
             const size_t at = (size_t)offsets[r] + (size_t)a * S;
-            state[k] = (uint8_t)profile_statistic_serial(counts + at, S, weights, radius, multiplier, z.data(), g.data(), &stack, &spread[k]);
-            if (smooth) memcpy(smooth + at, z.data(), (size_t)S * sizeof(double));
+            state[k] = (uint8_t)profile_statistic_serial(counts + at, S, weights, radius, multiplier, z.data(), g.data(), &stack, &spread[k],
+                                                         smooth ? smooth + at : nullptr, below ? below + k : nullptr);
         }
         winner[r] = sweep_winner(spread + (size_t)r * n_angles, state + (size_t)r * n_angles, n_angles);
     }
+}
+
+int sbbseg_profile_statistics_host(const int32_t* counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights, int radius,
+                                   double multiplier, double* spread, uint8_t* state, int32_t* winner, double* smooth)
+{
+    API_BEGIN
+    if (check_profile_tables(offsets, n_regions, n_angles, radius)) return 1;
+    REQUIRE((counts && spread && state && winner) || n_regions == 0, "bad arguments");
+    alloc_check();
+    profile_stats_serial(counts, offsets, n_regions, n_angles, weights, radius, multiplier, spread, state, winner, smooth, nullptr);
     return 0;
     API_END
 }
 
 // queues the statistic of a sweep whose counts are in device memory; *out holds the device pointers of the results (in c->pstat.p)
 static int profile_stats_queue(sbbseg_ctx* c, const int32_t* d_counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights,
-                               int radius, double multiplier, std::vector<unsigned char>& head, ProfileStatParams* out)
+                               int radius, double multiplier, std::vector<unsigned char>& head, ProfileStatParams* out, double* d_smooth = nullptr,
+                               double* d_below = nullptr)
 {
     if (!weights) { weights = kSigma2Weights; radius = kSigma2Radius; }
     const size_t np = (size_t)n_regions * n_angles;
@@ -380,6 +388,7 @@ static int profile_stats_queue(sbbseg_ctx* c, const int32_t* d_counts, const int
     p.counts = d_counts; p.regions = (const ProfileRegion*)(d + w_bytes); p.n_regions = n_regions; p.n_angles = n_angles;
     p.weights = (const double*)d; p.radius = radius; p.multiplier = multiplier;
     p.workspace = (double*)(d + ws_off); p.spread = (double*)(d + spread_off); p.state = d + state_off; p.winner = (int32_t*)(d + winner_off);
+    p.smooth = d_smooth; p.below = d_below;                         // (null in the product's calls)
     HIPCHK(hipMemcpyAsync(d, head.data(), head_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(launch_profile_statistics(p, ws_doubles > 0, c->stream));
     c->slope_launches += ws_doubles > 0 ? 3 : 2;
@@ -404,6 +413,59 @@ int sbbseg_profile_statistics_dev(sbbseg_ctx* c, const void* d_counts, const int
     if (state) HIPCHK(hipMemcpyAsync(state, p.state, np, hipMemcpyDeviceToHost, c->stream));
     if (winner) HIPCHK(hipMemcpyAsync(winner, p.winner, (size_t)n_regions * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));                       // (the host staging buffer lives until here)
+    return 0;
+    API_END
+}
+
+int sbbseg_debug_profile_statistics(sbbseg_ctx* c, const int32_t* counts, const int64_t* offsets, int n_regions, int n_angles, const double* weights,
+                                    int radius, double multiplier, double* spread, uint8_t* state, int32_t* winner, double* smooth, double* below)
+{
+    API_BEGIN
+    if (c && check_ready(c)) return 1;
+    if (check_profile_tables(offsets, n_regions, n_angles, radius)) return 1;
+    REQUIRE((counts && spread && state && winner) || n_regions == 0, "bad arguments");
+    if (n_regions == 0) return 0;
+    alloc_check();
+    if (!c) {
+        profile_stats_serial(counts, offsets, n_regions, n_angles, weights, radius, multiplier, spread, state, winner, smooth, below);
+        return 0;
+    }
+    const size_t np = (size_t)n_regions * n_angles, total = (size_t)offsets[n_regions];
+    ScopedBlock<int32_t> d_counts(c->mem);
+    ScopedBlock<double> d_smooth(c->mem), d_below(c->mem);
+    if (d_counts.alloc(total) || (smooth && d_smooth.alloc(total)) || (below && d_below.alloc(np))) return 1;
+    HIPCHK(hipMemcpyAsync(d_counts.p, counts, total * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    std::vector<unsigned char> head;
+    ProfileStatParams p;
+    if (profile_stats_queue(c, d_counts.p, offsets, n_regions, n_angles, weights, radius, multiplier, head, &p, d_smooth.p, d_below.p)) return 1;
+    HIPCHK(hipMemcpyAsync(spread, p.spread, np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(state, p.state, np, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(winner, p.winner, (size_t)n_regions * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (smooth) HIPCHK(hipMemcpyAsync(smooth, p.smooth, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (below) HIPCHK(hipMemcpyAsync(below, p.below, np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+    API_END
+}
+
+int sbbseg_debug_soft_arith(sbbseg_ctx* c, int op, const double* a, const double* b, int64_t n, double* out)
+{
+    API_BEGIN
+    if (c && check_ready(c)) return 1;
+    REQUIRE((op == 0 || op == 1) && n >= 0 && n <= (1ll << 24) && ((a && out && (b || op == 1)) || n == 0), "bad arguments");
+    if (n == 0) return 0;
+    if (!c) {
+        for (int64_t i = 0; i < n; ++i) out[i] = op == 0 ? soft_div(a[i], b[i]) : soft_sqrt(a[i]);
+        return 0;
+    }
+    alloc_check();
+    ScopedBlock<double> d_a(c->mem), d_b(c->mem), d_out(c->mem);
+    if (d_a.alloc((size_t)n) || (op == 0 && d_b.alloc((size_t)n)) || d_out.alloc((size_t)n)) return 1;
+    HIPCHK(hipMemcpyAsync(d_a.p, a, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (op == 0) HIPCHK(hipMemcpyAsync(d_b.p, b, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_soft_arith(op, d_a.p, d_b.p, n, d_out.p, c->stream));
+    HIPCHK(hipMemcpyAsync(out, d_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
     API_END
 }

@@ -199,3 +199,49 @@ def load_golden():
                     "peaks": g["peaks"][ls], "point_up": g["boxes"][ls][:, 0, 1], "point_down": g["boxes"][ls][:, 2, 1], "boxes": g["boxes"][ls],
                     "boxes_rot": g["boxes_rot"][ls], "page": int(g["page"][k]), "box": int(g["box"][k])})
     return out
+
+
+# ---- cases the CPU and the device tests share: each gives (profiles, others, slopes) ----
+
+def _random_profiles(count=200, seed=5):
+    rng = np.random.RandomState(seed)
+    profiles, others, slopes = [], [], []
+    for _ in range(count):
+        n, period, other = int(rng.randint(1, 401)), int(rng.randint(4, 121)), int(rng.randint(1, 300))
+        i = np.arange(n)
+        y = (((i + rng.randint(0, period)) % period) < rng.uniform(0.2, 0.8) * period) * rng.randint(1, other + 1)
+        y = (y + rng.randint(0, 3, n) * (rng.rand() < 0.5)).clip(0, other)
+        if rng.rand() < 0.2:
+            y[rng.randint(0, n):] = 0
+        profiles.append(y.astype(np.int32))
+        others.append(other)
+        slopes.append(float(rng.choice([0, 2.0, -9.5, 21, 44, 46, -70, 90, rng.uniform(-90, 90)])))
+    return profiles, others, slopes
+
+
+def both_ends_profiles():
+    """Mass at both ends only, each profile once beyond 45 degrees and once below."""
+    profiles, others, slopes = [], [], []
+    for n in (300, 400, 600):
+        y = np.zeros(n, np.int32)
+        y[:3] = y[-3:] = 50
+        profiles += [y, y]
+        others += [50, 50]
+        slopes += [80.0, 2.0]
+    return profiles, others, slopes
+
+
+def long_zero_constant_profiles():
+    """2100 samples (beyond what the device keeps in LDS), all zeros, a constant and a single sample."""
+    long = ((np.arange(2100) % 70) < 30).astype(np.int32) * 55
+    return ([long, long, np.zeros(57, np.int32), np.zeros(57, np.int32), np.full(80, 9, np.int32), np.full(80, 9, np.int32), np.array([4], np.int32)],
+            [60, 60, 31, 31, 9, 9, 4], [1.5, -80.0, 0.0, 90.0, 3.0, 60.0, 0.0])
+
+
+STRIPED = ((2049, 20), (3000, 24), (1500, 16), (2048, 12))       # (samples, period): more than 64 lines each
+STRIPED_LINES = (103, 125, 94, 171)
+
+
+def striped_profiles():
+    """Half-period stripes of height 40 over the whole profile, slope 1."""
+    return [(((np.arange(n) % period) < period // 2) * 40).astype(np.int32) for n, period in STRIPED], [40] * len(STRIPED), [1.0] * len(STRIPED)

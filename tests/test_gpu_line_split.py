@@ -104,6 +104,47 @@ def test_dev_equals_the_host_twin_in_batches_of_1_2_and_37_and_permuted(model):
         assert lr.same(a, lr.line_split(*r))
 
 
+def _as_regions(profiles, others, slopes):
+    """(y, other, vertical, rotation terms) per profile, as the CPU tests form them from (profiles, others, slopes)."""
+    out = []
+    for y, other, slope in zip(profiles, others, slopes):
+        vertical = abs(slope) > 45
+        w, h = (len(y), other) if vertical else (other, len(y))
+        out.append((y, other, vertical, _capi.line_rotation_terms(w, h, slope)))
+    return out
+
+
+def test_dev_equals_the_host_twin_on_the_cpu_tests_seeded_sweep(model):
+    """The 200 seeded profiles that hold the host twin to the restatement (test_line_split_cpu.py), in one batch."""
+    regions = _as_regions(*lr._random_profiles())
+    info = _assert_dev_equals_host(model.ctx, regions)[0]
+    assert len(regions) == 200 and {0, 2, 3, 4} <= set(info[:, 3].tolist()) and info[:, 2].any() and {lr.OK, lr.NONE} <= set(info[:, 0].tolist())
+    assert (info[:, 1] > 12).any()
+
+
+def test_dev_equals_the_host_twin_on_the_cpu_tests_edge_profiles(model):
+    """Mass at both ends only; a long, a zero, a constant and a one-sample profile."""
+    ctx = model.ctx
+    info = _assert_dev_equals_host(ctx, _as_regions(*lr.both_ends_profiles()))[0]
+    for k in range(0, 6, 2):
+        assert info[k, [0, 3, 4]].tolist() == [lr.OK, 1, 0] and info[k, 1] > 5 and info[k + 1, [0, 3]].tolist() == [lr.NONE, -1]
+    info = _assert_dev_equals_host(ctx, _as_regions(*lr.long_zero_constant_profiles()))[0]
+    assert info[0, 4] == 30 and info[1, 4] == 30 and info[2, 0] == lr.NONE and info[3, 2] == 1
+
+
+def test_dev_equals_the_host_twin_beyond_64_lines(model):
+    """More than 64 peaks in one profile and more than 64 lines in one region (the line kernel walks its lines 64 at a time), on the LDS form
+    (1500, 2048) and on the global-workspace form (2049, 3000)."""
+    ctx = model.ctx
+    regions = _as_regions(*lr.striped_profiles())
+    info = _assert_dev_equals_host(ctx, regions)[0]
+    print("[test_gpu_line_split] striped profiles: lines per region", info[:, 4].tolist())
+    assert (info[:, 0] == lr.OK).all() and (info[:, 4] > 64).all()
+    assert info[:, 4].tolist() == list(lr.STRIPED_LINES)
+    vertical = _as_regions(lr.striped_profiles()[0], [40] * 4, [80.0] * 4)
+    assert (_assert_dev_equals_host(ctx, vertical)[0][:, 4] > 64).all()
+
+
 def test_sigma_beyond_the_table_is_reported_by_the_device_and_finished_on_the_host(model):
     """SBBSEG_LINES_SIGMA_TOO_LARGE: info only, nothing else written; the Python layer finishes the region with the host twin."""
     ctx = model.ctx

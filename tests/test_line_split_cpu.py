@@ -50,24 +50,8 @@ def test_host_twin_equals_the_restatement_on_the_fixture():
         assert lr.same(a, c), (c["page"], c["box"], {f: (a[f], c[f]) for f in lr.FIELDS})
 
 
-def _random_profiles(count=200, seed=5):
-    rng = np.random.RandomState(seed)
-    profiles, others, slopes = [], [], []
-    for _ in range(count):
-        n, period, other = int(rng.randint(1, 401)), int(rng.randint(4, 121)), int(rng.randint(1, 300))
-        i = np.arange(n)
-        y = (((i + rng.randint(0, period)) % period) < rng.uniform(0.2, 0.8) * period) * rng.randint(1, other + 1)
-        y = (y + rng.randint(0, 3, n) * (rng.rand() < 0.5)).clip(0, other)
-        if rng.rand() < 0.2:
-            y[rng.randint(0, n):] = 0
-        profiles.append(y.astype(np.int32))
-        others.append(other)
-        slopes.append(float(rng.choice([0, 2.0, -9.5, 21, 44, 46, -70, 90, rng.uniform(-90, 90)])))
-    return profiles, others, slopes
-
-
 def test_host_twin_equals_the_restatement_on_a_seeded_sweep():
-    want = _check(*_random_profiles())
+    want = _check(*lr._random_profiles())
     assert {0, 2, 3, 4} <= {w["branch"] for w in want} and any(w["raised"] for w in want) and any(w["clusters"] for w in want)
     assert any(w["status"] == lr.NONE for w in want) and any(w["sigma"] > 12 for w in want)
 
@@ -75,23 +59,14 @@ def test_host_twin_equals_the_restatement_on_a_seeded_sweep():
 def test_host_twin_on_profiles_with_mass_at_both_ends_only():
     """No interior maximum after the second smoothing (its radius exceeds the pads and scipy reflects at the ends): the vertical splitter
     falls into ``len(peaks) < 1`` (main.py:1288), the horizontal one raises in main.py:646."""
-    profiles, others, slopes = [], [], []
-    for n in (300, 400, 600):
-        y = np.zeros(n, np.int32)
-        y[:3] = y[-3:] = 50
-        profiles += [y, y]
-        others += [50, 50]
-        slopes += [80.0, 2.0]
-    want = _check(profiles, others, slopes)
+    want = _check(*lr.both_ends_profiles())
     for k in range(0, 6, 2):
         assert (want[k]["status"], want[k]["branch"], len(want[k]["peaks"])) == (lr.OK, 1, 0) and want[k]["sigma"] > 5
         assert (want[k + 1]["status"], want[k + 1]["branch"]) == (lr.NONE, -1)
 
 
 def test_host_twin_on_a_long_a_zero_and_a_constant_profile():
-    long = ((np.arange(2100) % 70) < 30).astype(np.int32) * 55
-    want = _check([long, long, np.zeros(57, np.int32), np.zeros(57, np.int32), np.full(80, 9, np.int32), np.full(80, 9, np.int32), np.array([4], np.int32)],
-                  [60, 60, 31, 31, 9, 9, 4], [1.5, -80.0, 0.0, 90.0, 3.0, 60.0, 0.0])
+    want = _check(*lr.long_zero_constant_profiles())
     assert len(want[0]["peaks"]) == 30 and len(want[1]["peaks"]) == 30 and want[2]["status"] == lr.NONE and want[3]["raised"]
 
 

@@ -9,60 +9,15 @@ import re
 import numpy as np
 import pytest
 from scipy.ndimage import gaussian_filter1d
-from scipy.signal import find_peaks
 
 from sbb_textline_detection_amd import _capi, stages
 
 import slopes_ref
+from profile_cases import MULTIPLIER, bits, five_configurations, text_lines, yardstick_below, yardstick_profile, yardstick_sweep, yardstick_tops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_EXPORTS = ["sbbseg_profile_statistics_host", "sbbseg_profile_statistics_dev", "sbbseg_deskew_sweep_angles", "sbbseg_region_deskew_slopes_dev",
                "sbbseg_region_deskew_slopes"]
-MULTIPLIER = 20.3                                                # main.py:1644
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
-def yardstick_profile(y, sigma, multiplier=MULTIPLIER):
-    """stages._profile_statistics with its caller's bookkeeping (stages._deskew_sweep), statement for statement, plus what the tests want
-    to know about the case: (state, spread, z, facts)."""
-    y = np.asarray(y, np.float64)
-    padded = np.zeros(len(y) + 20)
-    padded[10:10 + len(y)] = y
-    flipped = np.zeros(len(padded) + 20)
-    flipped[10:10 + len(padded)] = padded.max() - padded
-    z = gaussian_filter1d(y, sigma)
-    minima = find_peaks(gaussian_filter1d(flipped, sigma), height=0)[0] - 20
-    maxima, props = find_peaks(z, height=0, plateau_size=1)
-    assert np.array_equal(maxima, find_peaks(z, height=0)[0])
-    facts = {"wrapped": bool(((minima < 0) & (minima >= -len(y))).any()), "plateau": bool((props["plateau_sizes"] > 1).any())}
-    tops = z[maxima]
-    tops = tops[tops > 10]
-    try:
-        lows = z[minima]
-    except IndexError:
-        return 2, 0.0, z, facts
-    with np.errstate(all="ignore"):
-        level = np.mean(tops) if tops.size else np.float64("nan")
-    if lows[lows < level - level / multiplier].size == 0:
-        return 1, 0.0, z, facts
-    return 0, np.std(z), z, facts
-
-
-def yardstick_sweep(profiles, sigma):
-    """(states, spreads, winner index or -1, the index of the maximum in the FULL list or -1, z per angle, facts)."""
-    states, spreads, zs, facts = [], [], [], {"wrapped": False, "plateau": False}
-    for y in profiles:
-        st, sd, z, f = yardstick_profile(y, sigma)
-        states.append(st); spreads.append(sd); zs.append(z)
-        facts = {k: facts[k] or f[k] for k in facts}
-    appended = [k for k, st in enumerate(states) if st != 1]
-    if not appended:
-        return states, spreads, -1, -1, zs, facts
-    pos = int(np.argmax(np.array([spreads[k] for k in appended])))
-    return states, spreads, pos, appended[pos], zs, facts
 
 
 def compare_sweeps(regions, n_angles, sigma, weights):
@@ -90,50 +45,6 @@ def compare_sweeps(regions, n_angles, sigma, weights):
     return seen
 
 
-def text_lines(rng, n, period, thick, height, phase=0, noise=0):
-    x = np.arange(n)
-    y = np.where((x + phase) % period < thick, height, 0)
-    if noise:
-        y = y + rng.randint(0, noise + 1, n) * (y > 0)
-    return y
-
-
-def synthetic_regions(rng, n_angles, lengths):
-    """One region per length; the kinds cycle so that every kind meets short and long profiles."""
-    regions = []
-    for q, n in enumerate(lengths):
-        kind = q % 8
-        if kind == 0:                                            # random counts
-            p = rng.randint(0, 400, (n_angles, n))
-        elif kind == 1:                                          # runs of equal values (plateaus survive the smoothing when they are long)
-            run = int(rng.choice([7, 23, 40]))
-            p = np.repeat(rng.randint(0, 60, (n_angles, n // run + 1)), run, axis=1)[:, :n]
-        elif kind == 2:                                          # all zeros
-            p = np.zeros((n_angles, n), np.int64)
-        elif kind == 3:                                          # constants
-            p = np.repeat(rng.randint(1, 900, (n_angles, 1)), n, axis=1)
-        elif kind == 4:                                          # single spikes
-            p = np.zeros((n_angles, n), np.int64)
-            p[np.arange(n_angles), rng.randint(0, n, n_angles)] = rng.randint(1, 5000, n_angles)
-        elif kind == 5:                                          # text-line-like: sharp at some angles, washed out (no deep minimum) at others
-            p = np.stack([text_lines(rng, n, 30, 12, int(rng.randint(60, 300)), int(rng.randint(30)), 5) if rng.rand() < 0.6 else
-                          np.full(n, int(rng.randint(20, 90))) + rng.randint(0, 3, n) for _ in range(n_angles)])
-            p[:, :min(25, n // 4)] = 0
-            p[:, n - min(25, n // 4):] = 0
-        elif kind == 6:                                          # the mass at the right end: a minimum lands in the right-hand padding
-            p = np.zeros((n_angles, n), np.int64)
-            k = max(1, n // 8)
-            p[:, n - k:] = rng.randint(20, 500, (n_angles, k))
-        else:                                                    # the mass at the left end: a minimum before sample 0 wraps
-            p = np.zeros((n_angles, n), np.int64)
-            k = max(1, n // 8)
-            p[:, :k] = rng.randint(20, 500, (n_angles, k))
-            if n > 60:
-                p[:, n // 2:n // 2 + 12] = 300                    # (and a line further in, so that there is a deep minimum as well)
-        regions.append(np.ascontiguousarray(p, np.int32))
-    return regions
-
-
 def test_weight_and_angle_tables_equal_numpy_and_scipy():
     from scipy.ndimage._filters import _gaussian_kernel1d
     for sigma in (0.7, 1, 2, 3, 5.5):
@@ -159,20 +70,33 @@ def test_weight_and_angle_tables_equal_numpy_and_scipy():
 
 def test_host_mirror_equals_scipy_on_synthetic_profiles():
     """Several hundred int32 profiles of 1 .. 2 100 samples in regions of 80 and of 30 angles: smoothed profile, state, spread and winner."""
-    rng = np.random.RandomState(2024)
-    lengths80 = [1, 2, 3, 7, 8, 9, 17, 19, 20, 21, 22, 39, 40, 41, 64, 100, 127, 128, 129, 130, 136, 255, 257, 300, 511, 700, 1031, 1300, 1500, 2100]
-    lengths30 = [1, 5, 16, 18, 25, 33, 60, 90, 120, 131, 200, 260, 333, 512, 640, 801, 1024, 1111, 1600, 2049, 2100, 45, 77, 150]
     seen = set()
     n_profiles = 0
-    for n_angles, lengths, sigma, weights in ((80, lengths80, 2, None), (30, lengths30, 2, _capi.gaussian_weights(2)),
-                                              (30, lengths30[3::4], 0.7, _capi.gaussian_weights(0.7)), (30, lengths30[1::5], 5.5, _capi.gaussian_weights(5.5)),
-                                              (30, [3, 12, 400], 3, _capi.gaussian_weights(3))):
-        regions = synthetic_regions(rng, n_angles, lengths)
+    for n_angles, sigma, weights, regions in five_configurations():
         n_profiles += n_angles * len(regions)
         seen |= compare_sweeps(regions, n_angles, sigma, weights)
     assert n_profiles >= 300
     missing = {"state0", "state1", "state2", "wrapped", "plateau", "quirk", "nothing"} - seen
     assert not missing, "the generators no longer produce: %s" % sorted(missing)
+
+
+def test_host_mirror_equals_numpy_beyond_one_sum_buffer():
+    """np.mean and np.std add stretches of 8192 elements (numpy's ufunc buffer) up one after the other, each summed pairwise: a profile or a
+    list of maxima longer than that is not one pairwise sum.  Lengths around one and two stretches and the longest the tables admit; the
+    second profile of each region has a maximum at every other sample, so the mean of the maxima crosses a stretch as well."""
+    rng = np.random.RandomState(8)
+    most = 0
+    for n in (8191, 8192, 8193, 8200, 16383, 16384, 16385, 20000, 32767):
+        prof = np.stack([text_lines(rng, n, 30, 12, 250, 7, 9), rng.randint(150, 400, n) * (np.arange(n) % 2)]).astype(np.int32)
+        prof[:, :25] = 0
+        prof[:, -25:] = 0
+        assert "state0" in compare_sweeps([prof], 2, 0.1, np.array([1.0]))       # (radius 0: z = y)
+        below = _capi.debug_profile_statistics(None, prof, [0, prof.size], 2, np.array([1.0]))[4]
+        for k in range(2):
+            tops = yardstick_tops(yardstick_profile(prof[k], 0.1)[2])
+            assert bits(below[0, k]) == bits(yardstick_below(tops)), (n, k)
+            most = max(most, tops.size)
+    assert most > 2 * 8192 - 100
 
 
 def test_multiplier_and_radius_zero():
@@ -257,6 +181,30 @@ def test_bad_arguments_are_a_status_and_a_message():
     assert lib.sbbseg_deskew_sweep_angles(2, None, 0, C.byref(n)) != 0
     assert lib.sbbseg_deskew_sweep_angles(1, None, 0, C.byref(n)) == 0 and n.value == 30
     assert lib.sbbseg_deskew_sweep_angles(0, p(np.zeros(10)), 10, C.byref(n)) != 0 and b"80" in lib.sbbseg_last_error()
+
+
+def test_debug_entry_points_without_a_handle():
+    """sbbseg_debug_profile_statistics with a null handle is the host entry point plus `below`; sbbseg_debug_soft_arith checks its arguments."""
+    lib = _capi.load_library()
+    rng = np.random.RandomState(11)
+    prof = np.stack([text_lines(rng, 300, 30, 12, 200, k, 5) for k in range(4)]).astype(np.int32)
+    prof[2] = 0                                                  # no maximum: the level is NaN
+    want = _capi.profile_statistics_host(prof, [0, prof.size], 4, None, want_smooth=True)
+    got = _capi.debug_profile_statistics(None, prof, [0, prof.size], 4)
+    assert all(np.array_equal(bits(a) if a.dtype == np.float64 else a, bits(b) if b.dtype == np.float64 else b) for a, b in zip(got[:4], want))
+    for k in range(4):
+        level = yardstick_below(yardstick_tops(yardstick_profile(prof[k], 2)[2]))
+        assert np.isnan(level) == np.isnan(got[4][0, k]) == (k == 2) and (k == 2 or bits(got[4][0, k]) == bits(level))
+    with pytest.raises(RuntimeError, match="n_angles"):
+        _capi.debug_profile_statistics(None, prof, [0, prof.size], 0)
+    assert _capi.debug_soft_arith(None, 0, [1.0, 0.0, 7.0], [3.0, 0.0, -0.0]).view(np.uint64).tolist() == [0x3fd5555555555555, 0x7ff8000000000000,
+                                                                                                            0xfff0000000000000]
+    assert _capi.debug_soft_arith(None, 1, [2.0, -1.0]).view(np.uint64).tolist() == [0x3ff6a09e667f3bcd, 0x7ff8000000000000]
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    a, out = np.ones(2), np.zeros(2)
+    assert lib.sbbseg_debug_soft_arith(None, 2, p(a), p(a), 2, p(out)) != 0 and b"bad arguments" in lib.sbbseg_last_error()
+    assert lib.sbbseg_debug_soft_arith(None, 0, p(a), None, 2, p(out)) != 0 and lib.sbbseg_debug_soft_arith(None, 1, p(a), None, 2, p(out)) == 0
+    assert lib.sbbseg_debug_soft_arith(None, 0, None, None, 0, None) == 0
 
 
 def test_get_slopes_checks_its_keyword():
