@@ -746,6 +746,45 @@ int sbbseg_debug_contour_launches(sbbseg_ctx* c, int64_t* value);
 /* sbbseg_mask_contours_host gives up after `steps` steps per contour instead of 8 x (box pixels) + 8 (0 restores that).  Process-global;
  * tests of the failure path only. */
 int sbbseg_debug_set_contour_host_step_bound(int64_t steps);
+
+/* ---- reading order of the text regions (order_of_regions / order_and_id_of_texts, main.py:1802-1906; csrc/order.h) ----
+ * Contours: n lists of int (x, y) points, contour r = points point_off[r] .. point_off[r + 1] of points_xy (point_off[0] = 0).  The
+ * repeated closing point of a ring adds zero terms: closed and unclosed lists give the same bits.  In the `_dev` calls points_xy = NULL
+ * names the handle's resident contour result (sbbseg_text_region_contours_dev / sbbseg_debug_mask_contours_dev), read in place: n must
+ * be its contour count and point_off is ignored.
+ *
+ * Moments: OpenCV's contourMoments for integer points [EXT: restated, unpinned] -- float64, serial, starting from the last point:
+ * dxy = x' y - x y', a00 += dxy, a10 += dxy (x' + x), a01 += dxy (y' + y), every multiply and add rounded on its own; if
+ * fabs(a00) > FLT_EPSILON, m00 = a00 * (s / 2), m10 = a10 * (s * 0.16666666666666666), m01 likewise (s = sign of a00), else all 0;
+ * cx = m10 / (m00 + 1e-32), cy likewise.  moments [n][3] = m00, m10, m01; centroids [n][2] = cx, cy.  The device sums exact integers
+ * with a wave scan where that is the float64 sum (coordinates below 32768 in magnitude, every prefix below 2^53) and redoes any other
+ * contour serially in float64: serial [n] (optional) = 1 for those.  The host twin is the serial loop and reports the same flags.
+ * n = 0 is success and needs no handle. */
+int sbbseg_contour_moments_dev(sbbseg_ctx* c, const int32_t* points_xy, const int64_t* point_off, int n, double* moments, double* centroids,
+                               int32_t* serial);
+int sbbseg_contour_moments_host(const int32_t* points_xy, const int64_t* point_off, int n, double* moments, double* centroids, int32_t* serial);
+/* The order.  plane: the textline plane, uint8 [H][W]; its rows are summed as stored (not `!= 0`).  weights: the 33 doubles of
+ * scipy's half Gaussian kernel of sigma 8 (_gaussian_kernel1d(8, 0, 32)[32:]); the library does not reproduce libm.
+ *   edges [cap], *n_edges: [0] + (find_peaks(gaussian_filter1d(zneg, 8), height=0) - 40) + [H]; cap >= (H + 80) / 2 + 2.  Edges below 0
+ *     and at or above H occur and are not clamped.
+ *   centroids [n][2]: cx, cy as above.  band [n]: the i with edges[i] <= cy < edges[i + 1] (at most one; exactly one for 0 <= cy < H), or -1.
+ *   sorted_index [n]: the regions by (band, cx, index) -- the reference's list; cx ties [EXT: np.argsort's default sort is unstable] by
+ *     ascending index; regions of band -1, which the reference leaves out, stand behind all others.  order [n]: the region's position in
+ *     that list, -1 for band -1.
+ * The region order is that of the contour list.  The plane may belong to another handle on the same device.  n = 0 is success (the edges
+ * are still computed).  sbbseg_region_order_host takes the int32 row sums instead of the plane and needs no GPU. */
+int sbbseg_region_order_dev(sbbseg_ctx* c, const void* d_plane_hw, int H, int W, const double* weights, const int32_t* points_xy,
+                            const int64_t* point_off, int n, int32_t* sorted_index, int32_t* order, int32_t* band, double* centroids, int32_t* edges,
+                            int cap, int* n_edges);
+int sbbseg_region_order(sbbseg_ctx* c, const uint8_t* plane_hw, int H, int W, const double* weights, const int32_t* points_xy,
+                        const int64_t* point_off, int n, int32_t* sorted_index, int32_t* order, int32_t* band, double* centroids, int32_t* edges,
+                        int cap, int* n_edges);
+int sbbseg_region_order_host(const int32_t* row_sums, int H, const double* weights, const int32_t* points_xy, const int64_t* point_off, int n,
+                             int32_t* sorted_index, int32_t* order, int32_t* band, double* centroids, int32_t* edges, int cap, int* n_edges);
+/* the row-sum kernel alone on a host plane (tests): row_sums int32 [H] */
+int sbbseg_debug_row_sums(sbbseg_ctx* c, const uint8_t* plane_hw, int H, int W, int32_t* row_sums);
+/* kernels the reading-order calls have queued on this handle so far (4 per order call with regions, 2 without) */
+int sbbseg_debug_order_launches(sbbseg_ctx* c, int64_t* value);
 /* sbbseg_profile_statistics_host / _dev behind one signature, with two more outputs (tests).  counts is a HOST array.  c = NULL: the serial
  * host twin.  A handle: the counts are uploaded and the product's kernels run through the product's launch.  Optional outputs: smooth = z of
  * every profile, packed like counts; below [n_regions][n_angles] = the level a deep minimum must lie below, mean(maxima > 10) * (1 - 1 /

@@ -45,6 +45,8 @@ EXPORTS = [
     "sbbseg_text_region_contours_dev", "sbbseg_text_region_contours", "sbbseg_text_region_contours_read", "sbbseg_mask_contours_host",
     "sbbseg_debug_mask_contours_dev", "sbbseg_debug_set_contour_lds_limit", "sbbseg_debug_contour_launches", "sbbseg_debug_set_contour_host_step_bound",
     "sbbseg_debug_profile_statistics", "sbbseg_debug_soft_arith",
+    "sbbseg_contour_moments_dev", "sbbseg_contour_moments_host", "sbbseg_region_order_dev", "sbbseg_region_order", "sbbseg_region_order_host",
+    "sbbseg_debug_row_sums", "sbbseg_debug_order_launches",
 ]
 
 
@@ -229,6 +231,13 @@ def load_library(path: Optional[str] = None):
         "sbbseg_debug_set_contour_host_step_bound": [C.c_int64],
         "sbbseg_debug_profile_statistics": [vp, vp, vp, i32, i32, vp, i32, C.c_double, vp, vp, vp, vp, vp],
         "sbbseg_debug_soft_arith": [vp, i32, vp, vp, C.c_int64, vp],
+        "sbbseg_contour_moments_dev": [vp, vp, vp, i32, vp, vp, vp],
+        "sbbseg_contour_moments_host": [vp, vp, i32, vp, vp, vp],
+        "sbbseg_region_order_dev": [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_int)],
+        "sbbseg_region_order": [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_int)],
+        "sbbseg_region_order_host": [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_int)],
+        "sbbseg_debug_row_sums": [vp, vp, i32, i32, vp],
+        "sbbseg_debug_order_launches": [vp, C.POINTER(C.c_int64)],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -791,6 +800,47 @@ class Context:
         check(self.lib.sbbseg_debug_contour_launches(self.h, C.byref(v)), "sbbseg_debug_contour_launches")
         return int(v.value)
 
+    def contour_moments_dev(self, contours=None, n: int = 0):
+        """cv2.moments' m00, m10, m01 and the centroids of main.py:1835-1836 per contour, on the device (``sbbseg_contour_moments_dev``):
+        (moments float64 [n, 3], centroids float64 [n, 2], serial int32 [n]).  ``contours``: a list of int (x, y) point arrays ([N, 2] or
+        the reference's [N, 1, 2] rings), or None for the ``n`` contours of the handle's resident contour result, read in place."""
+        pts, off, n = (None, None, int(n)) if contours is None else pack_contours(contours)
+        moments, centroids, serial = np.zeros((n, 3), np.float64), np.zeros((n, 2), np.float64), np.zeros(n, np.int32)
+        check(self.lib.sbbseg_contour_moments_dev(self.h, _ptr(pts), _ptr(off), n, _ptr(moments), _ptr(centroids), _ptr(serial)),
+              "sbbseg_contour_moments_dev")
+        return moments, centroids, serial
+
+    def _region_order_call(self, fn, what, src, H, W, contours, n):
+        pts, off, n = (None, None, int(n)) if contours is None else pack_contours(contours)
+        out = _region_order_buffers(H, n)
+        ne = C.c_int(0)
+        check(fn(self.h, src, int(H), int(W), _ptr(order_weights()), _ptr(pts), _ptr(off), n, *[_ptr(a) for a in out], out[-1].shape[0], C.byref(ne)), what)
+        return _region_order_record(out, ne.value)
+
+    def region_order_dev(self, d_textlines: int, H: int, W: int, contours=None, n: int = 0):
+        """order_of_regions (main.py:1802-1889) for a textline plane in device memory (``sbbseg_region_order_dev``): the record of
+        :func:`host_region_order`.  ``contours`` None: the ``n`` contours of the handle's resident contour result, read in place -- nothing
+        but the record's few ints and doubles crosses the bus.  The plane may belong to another handle on the same device."""
+        return self._region_order_call(self.lib.sbbseg_region_order_dev, "sbbseg_region_order_dev", C.c_void_p(d_textlines), H, W, contours, n)
+
+    def region_order(self, textlines: np.ndarray, contours=None, n: int = 0):
+        """The same from a host plane (uint8 [H, W]), uploaded once."""
+        plane = np.ascontiguousarray(textlines, np.uint8)
+        return self._region_order_call(self.lib.sbbseg_region_order, "sbbseg_region_order", _ptr(plane), plane.shape[0], plane.shape[1], contours, n)
+
+    def debug_row_sums(self, plane: np.ndarray) -> np.ndarray:
+        """``plane.sum(axis=1)`` of a uint8 [H, W] plane by the reading order's row-sum kernel: int32 [H]."""
+        plane = np.ascontiguousarray(plane, np.uint8)
+        out = np.zeros(plane.shape[0], np.int32)
+        check(self.lib.sbbseg_debug_row_sums(self.h, _ptr(plane), plane.shape[0], plane.shape[1], _ptr(out)), "sbbseg_debug_row_sums")
+        return out
+
+    def order_launches(self) -> int:
+        """Kernels the reading-order calls have queued on this handle so far."""
+        v = C.c_int64(0)
+        check(self.lib.sbbseg_debug_order_launches(self.h, C.byref(v)), "sbbseg_debug_order_launches")
+        return int(v.value)
+
     def _region_profiles_call(self, fn, src, H, W, boxes, angles_deg, erode_iterations):
         boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
         angles_deg = np.ascontiguousarray(angles_deg, np.float64).reshape(-1)
@@ -1350,6 +1400,60 @@ def line_weight_table(sigma_max: int = LINE_SIGMA_MAX):
         offsets = np.concatenate([[0], np.cumsum([h.shape[0] for h in halves])]).astype(np.int64)
         _LINE_TABLES[sigma_max] = (np.ascontiguousarray(np.concatenate(halves), np.float64), offsets)
     return _LINE_TABLES[sigma_max]
+
+ORDER_SIGMA = 8                                                  # order_of_regions' sigma_gaus (main.py:1814; csrc/order.h)
+
+
+def order_weights() -> np.ndarray:
+    """The 33 doubles the reading-order calls take from their caller: the sigma 8 slice of :func:`line_weight_table`."""
+    w, off = line_weight_table()
+    return np.ascontiguousarray(w[int(off[ORDER_SIGMA - 2]):int(off[ORDER_SIGMA - 1])])
+
+
+def pack_contours(contours):
+    """(points int32 [total, 2], point_off int64 [n + 1], n) of a list of int (x, y) point arrays ([N, 2], or [N, 1, 2] rings)."""
+    arrays = [np.asarray(c).reshape(-1, 2) for c in contours]
+    for a in arrays:
+        if a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
+            raise ValueError("contour coordinates must fit 32 bits")
+    off = np.concatenate([[0], np.cumsum([a.shape[0] for a in arrays])]).astype(np.int64)
+    pts = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0, 2)), np.int32).reshape(-1, 2)
+    if pts.shape[0] == 0:
+        pts = np.zeros((1, 2), np.int32)                         # (a pointer to pass; no point of it is read)
+    return pts, off, len(arrays)
+
+
+def _region_order_buffers(H: int, n: int):
+    return (np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 2), np.float64),
+            np.zeros((int(H) + 80) // 2 + 2, np.int32))
+
+
+def _region_order_record(out, n_edges: int):
+    sorted_index, order, band, centroids, edges = out
+    return dict(sorted_index=sorted_index, order=order, band=band, centroids=centroids, edges=edges[:n_edges].copy())
+
+
+def host_region_order(textline_mask: np.ndarray, contours):
+    """``Context.region_order_dev`` on the CPU (serial, no handle, no GPU): the same bits.  A record: ``edges`` int32 (the band edges, [0] +
+    peaks_neg + [H], unclamped), ``centroids`` float64 [n, 2] (cx, cy), ``band`` int32 [n] (-1: in no band), ``sorted_index`` int32 [n]
+    (the regions by band, cx, index; those of band -1 last) and ``order`` int32 [n] (position in that list; -1 for band -1)."""
+    mask = np.asarray(textline_mask)
+    sums = np.ascontiguousarray(mask.sum(axis=1, dtype=np.int64), np.int32)
+    pts, off, n = pack_contours(contours)
+    out = _region_order_buffers(mask.shape[0], n)
+    ne = C.c_int(0)
+    check(load_library().sbbseg_region_order_host(_ptr(sums), mask.shape[0], _ptr(order_weights()), _ptr(pts), _ptr(off), n, *[_ptr(a) for a in out],
+                                                  out[-1].shape[0], C.byref(ne)), "sbbseg_region_order_host")
+    return _region_order_record(out, ne.value)
+
+
+def host_contour_moments(contours):
+    """``Context.contour_moments_dev`` on the CPU (the literal serial float64 loop): (moments [n, 3], centroids [n, 2], serial [n])."""
+    pts, off, n = pack_contours(contours)
+    moments, centroids, serial = np.zeros((n, 3), np.float64), np.zeros((n, 2), np.float64), np.zeros(n, np.int32)
+    check(load_library().sbbseg_contour_moments_host(_ptr(pts), _ptr(off), n, _ptr(moments), _ptr(centroids), _ptr(serial)),
+          "sbbseg_contour_moments_host")
+    return moments, centroids, serial
 
 
 def line_rotation_terms(w: int, h: int, slope: float):

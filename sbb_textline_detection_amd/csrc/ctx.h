@@ -1,5 +1,5 @@
 // ctx.h -- private, host only: what the translation units behind the C ABI (api.hip, forward.hip, pages.hip, whole.hip, comm.hip -- these five
-// through exec.h, forward.hip and pages.hip through route.h too -- plan_build.hip, stage_glue.hip, contour_glue.hip) share: the error and exception plumbing, the allocation helpers, and the handle
+// through exec.h, forward.hip and pages.hip through route.h too -- plan_build.hip, stage_glue.hip, contour_glue.hip, order_glue.hip) share: the error and exception plumbing, the allocation helpers, and the handle
 // (struct sbbseg_ctx) with the plan structs it embeds.  Device and pinned memory belong to the handle's two registries (devmem.h: `mem`, `pinned`);
 // every device pointer below, in the handle and in the plan structs, points at a block one of them owns and sbbseg_destroy frees with the registry.
 #pragma once
@@ -283,6 +283,11 @@ struct sbbseg_ctx {
     sbbseg::DevBuf<void> line_w;                         // ... its table of half Gaussian kernels: offsets | weights, uploaded when it differs from
     std::vector<double> line_w_host;                     // ... this copy of the last one
     int16_t* d_line_tab = nullptr;                       // sbbseg_region_line_masks_dev: the fixed-point bicubic table, built on first use
+    // sbbseg_region_order_dev / sbbseg_contour_moments_dev (order_glue.hip): point offsets | edges | ranks | bands | flags | centroids | moments |
+    // row sums | smoothed profile | weights, and the points of a contour list the caller passed in
+    sbbseg::DevBuf<void> order_buf;
+    sbbseg::DevBuf<int32_t> order_pts;
+    long long order_launches = 0;                        // kernels queued by the two calls above (sbbseg_debug_order_launches)
     // profiling
     bool profiling = false;
     int conv_variant = 0;
@@ -324,7 +329,7 @@ int ensure(sbbseg_ctx* c, DevBuf<T>& b, size_t bytes)
     return ensure(c->mem, b, bytes);
 }
 
-// ---- what the stage-glue units (stage_glue.hip, contour_glue.hip) share
+// ---- what the stage-glue units (stage_glue.hip, contour_glue.hip, order_glue.hip) share
 inline size_t align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
 // The host-plane form of an entry point: the caller's H x W plane goes into c->morph_b.p and the `_dev` twin runs on *d_plane (in place

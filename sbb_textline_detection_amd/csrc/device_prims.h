@@ -135,6 +135,30 @@ __device__ inline uint32_t row_ror8(uint32_t v)
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false);
 }
 
+// ---- wave-wide (64 lanes) reductions and scans of integers: every lane returns the result of the whole wave (reductions) or of lanes
+// 0 .. its own (inclusive scans).  Integer sums are exact in any order, so these never decide a bit.
+__device__ inline int wave_sum(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ inline int wave_max(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
+    return v;
+}
+__device__ inline long long wave_scan_sum(long long v, int lane)
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const long long below = __shfl_up(v, off, 64);
+        if (lane >= off) v += below;
+    }
+    return v;
+}
+
 // ---- vector memory.  The wload / xload / glds16_hidden loads are invisible to the compiler's own wait insertion: a kernel that issues
 // them counts its vmcnt by hand (retirement is in issue order) and ties the destination registers to the wait (wait4).
 // buffer resource over [base, base + bytes): wave-uniform words, out-of-range lanes read zeros

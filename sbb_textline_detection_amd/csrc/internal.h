@@ -576,6 +576,31 @@ struct LineSplitParams {
     int32_t* rot;             // [lines][4][2]
 };
 hipError_t launch_line_split(const LineSplitParams& p, bool any_long, hipStream_t s);      // 1 launch, 2 with a profile beyond kProfileLdsSamples
+// the reading order of a page's text regions (order.hip, order.h)
+struct OrderParams {
+    const uint8_t* plane;     // [H][W] textline plane, or null: row_sums are given
+    int H, W;
+    const double* weights;    // [radius + 1] half Gaussian kernel of sigma 8
+    int radius;               // kOrderRadius
+    const int32_t* points;    // [points][2] x, y, packed in contour order
+    const long long* point_off;       // [n + 1]
+    int n;                    // contours
+    int32_t* row_sums;        // [H]
+    double* smooth;           // [H + 80] workspace: the smoothed, flipped profile
+    int32_t* n_edges;         // [1]
+    int32_t* edges;           // [order_edge_capacity(H)]
+    double* moments;          // [n][3] m00, m10, m01
+    double* centroids;        // [n][2] cx, cy
+    int32_t* serial;          // [n] 1: the contour's sums were redone in float64, serially
+    int32_t* sorted_index;    // [n]
+    int32_t* order;           // [n]
+    int32_t* band;            // [n]
+};
+hipError_t launch_row_sums(const OrderParams& p, hipStream_t s);                 // 1 launch
+hipError_t launch_order_edges(const OrderParams& p, hipStream_t s);              // 1 launch
+hipError_t launch_contour_moments(const OrderParams& p, hipStream_t s);          // 1 launch
+hipError_t launch_order_rank(const OrderParams& p, hipStream_t s);               // 1 launch
+constexpr int kOrderLaunches = 4;         // of a whole reading-order call, whatever n and H are
 
 // channel-tile width the bf16 conv kernel uses for `cout` (weights are padded to it)
 inline int conv_tile_bc(int cout) { return cout >= 128 ? 128 : (cout > 32 ? 64 : 32); }

@@ -335,6 +335,47 @@ def get_slopes_and_line_boxes(textline_mask: np.ndarray, boxes, ctx=None, sigma_
     return slopes, ctx.region_line_boxes_dev(d_plane, plane.shape[0], plane.shape[1], boxes, slopes, 2)
 
 
+def _order_result(rec):
+    """(indexes_sorted, matrix_of_orders) of order_of_regions from the library's record (``_capi.host_region_order``)."""
+    n = rec["band"].shape[0]
+    matrix = np.zeros((n, 5))
+    matrix[:, 0] = np.arange(n)
+    matrix[:, 1] = 1
+    matrix[:, 2:4] = rec["centroids"]
+    matrix[:, 4] = np.arange(n)
+    kept = int(np.count_nonzero(rec["band"] >= 0))               # a region in no band is left out, as the reference's masks leave it out
+    return [int(v) for v in rec["sorted_index"][:kept]], matrix
+
+
+def order_of_regions(textline_mask: np.ndarray, contours, ctx=None):
+    """order_of_regions (main.py:1802-1889): ``(indexes_sorted, matrix_of_orders)`` as the reference returns them -- the region indices
+    band by band (bands: between the minima of the smoothed row profile of ``textline_mask``), by ascending cx inside a band, and the
+    float64 [n, 5] matrix {m, 1, cx, cy, m}.  ``contours``: the reference's rings ([N, 1, 2]) or [N, 2] point arrays; the region order is
+    that of the list.  cx ties [EXT] by ascending index.  On the device with a ``ctx`` (``sbbseg_region_order``), else the library's
+    serial host twin: the same bits."""
+    from . import _capi
+    mask = np.asarray(textline_mask)
+    rec = ctx.region_order(mask, contours) if ctx is not None else _capi.host_region_order(mask, contours)
+    return _order_result(rec)
+
+
+def order_and_id_of_texts(found_polygons_text_region, matrix_of_orders, indexes_sorted):
+    """order_and_id_of_texts (main.py:1894-1906): ``(order_of_texts, id_of_texts)`` -- per region its position in ``indexes_sorted`` and
+    'r' + its index.  A region ``indexes_sorted`` does not hold raises IndexError, as the reference's ``np.where(...)[0][0]`` does."""
+    matrix_of_orders = np.asarray(matrix_of_orders)
+    position = {}
+    for at, index in enumerate(indexes_sorted):
+        position.setdefault(int(index), at)
+    order_of_texts, id_of_texts = [], []
+    for mm in range(len(found_polygons_text_region)):
+        id_of_texts.append('r' + str(mm))
+        rows = matrix_of_orders[:, 0][(matrix_of_orders[:, 1] == 1) & (matrix_of_orders[:, 4] == mm)]
+        if rows.shape[0] != 1 or int(rows[0]) not in position:
+            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+        order_of_texts.append(position[int(rows[0])])
+    return order_of_texts, id_of_texts
+
+
 class InferenceStages:
     """The model-running part of ``textline_detector.run()`` (main.py:2056-2107)."""
 
@@ -712,7 +753,24 @@ class InferenceStages:
         device.  Foreign model objects take the loop."""
         return self._run_pages_lines(images, masks, True)
 
-    def _run_pages_lines(self, images, masks: bool, contours: bool):
+    def get_region_order(self, textlines: np.ndarray, contours):
+        """``(order_of_texts, id_of_texts)`` of the text regions (order_of_regions + order_and_id_of_texts, main.py:2118-2119) on the
+        textline model's handle; foreign model objects get the library's serial host twin."""
+        model, session = start_new_session_and_model(self.model_textline_dir, **self.kw)
+        try:
+            indexes_sorted, matrix = order_of_regions(textlines, contours, model.ctx if isinstance(model, SegModel) else None)
+            return order_and_id_of_texts(contours, matrix, indexes_sorted)
+        finally:
+            session.close()
+
+    def run_pages_with_reading_order(self, images, masks: bool = False):
+        """``run_pages_with_contours`` plus, per page, the reading order of its text regions (main.py:2118-2119): the 9-tuple +
+        ``(order_of_texts, id_of_texts)``; ([], []) where the textline model did not run.  The order call for a page
+        (``region_order_dev``) is made right after that page's contour call, while its contour table is resident, on the page's resident
+        textline plane: neither a plane nor a polygon crosses the bus for it.  Foreign model objects take the loop with the host twin."""
+        return self._run_pages_lines(images, masks, True, True)
+
+    def _run_pages_lines(self, images, masks: bool, contours: bool, order: bool = False):
         images = list(images)
         opened = [start_new_session_and_model(d, **self.kw) for d in (self.model_page_dir, self.model_region_dir, self.model_textline_dir)]
         try:
@@ -720,7 +778,11 @@ class InferenceStages:
                 out = []
                 for img in images:
                     page = self.run_with_line_boxes(img, masks=masks)
-                    out.append(page + ((self.get_text_region_contours(page[1]) if page[2] is not None else []),) if contours else page)
+                    if contours:
+                        page = page + ((self.get_text_region_contours(page[1]) if page[2] is not None else []),)
+                    if order:
+                        page = page + (self.get_region_order(page[2], page[8]) if page[2] is not None else ([], []))
+                    out.append(page)
                 return out
             if not images:
                 return []
@@ -730,10 +792,18 @@ class InferenceStages:
             d_regions, d_textlines = _capi.run_pages_planes(c_region)
             n = len(runs)
             has_lines = [runs[k][2] is not None for k in range(n)]
-            rings = [[] for _ in range(n)]
+            rings, orders = [[] for _ in range(n)], [([], []) for _ in range(n)]
             if contours:
-                traced = [c_region.text_region_contours_dev(*d_regions[k], 1, 0.00001, 1.0) if has_lines[k] else ([], []) for k in range(n)]
-                boxes, rings = [t[0] for t in traced], [closed_rings(t[1]) for t in traced]
+                boxes = [[] for _ in range(n)]
+                for k in range(n):
+                    if not has_lines[k]:
+                        continue
+                    boxes[k], traced = c_region.text_region_contours_dev(*d_regions[k], 1, 0.00001, 1.0)
+                    rings[k] = closed_rings(traced)
+                    if order:                                    # while page k's contour table is resident
+                        rec = c_region.region_order_dev(*d_textlines[k], None, len(traced))
+                        indexes_sorted, matrix = _order_result(rec)
+                        orders[k] = order_and_id_of_texts(traced, matrix, indexes_sorted)
             else:
                 boxes = [c_region.text_region_boxes_dev(*d_regions[k], 1, 0.00001, 1.0) if has_lines[k] else [] for k in range(n)]
             slopes, line_masks, line_boxes = [[] for _ in range(n)], [[] for _ in range(n)], [[] for _ in range(n)]
@@ -746,7 +816,7 @@ class InferenceStages:
                 gl = c_text.planes_line_boxes_dev(planes, gb, gs, 2)
                 for q, k in enumerate(group):
                     slopes[k], line_masks[k], line_boxes[k] = gs[q], gm[q], gl[q]
-            return [runs[k] + (boxes[k], slopes[k], line_masks[k], line_boxes[k]) + ((rings[k],) if contours else ()) for k in range(n)]
+            return [runs[k] + (boxes[k], slopes[k], line_masks[k], line_boxes[k]) + ((rings[k],) if contours else ()) + (orders[k] if order else ()) for k in range(n)]
         finally:
             for _, session in opened:
                 session.close()
