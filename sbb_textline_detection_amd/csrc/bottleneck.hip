@@ -26,6 +26,14 @@ namespace sbbseg {
 //   * W1 and W3 stay in LDS for the whole kernel (A-fragment order, linear 16-byte reads); a (halo, 192 rows x 128 B)
 //     and b (128 rows x 128 B) are XOR-swizzled rows; halo pixels outside the image are ZERO (the 3x3 conv pads a, not x).
 //   * tiles are walked so that every XCD owns one contiguous range of them: vertical halo neighbours share an L2.
+//   * DUMP (conv variant bit 26, the step check of tests/test_gpu_steps_blocks.py; never a product launch): what phase A packs for the
+//     lane's two inner pixels and what phase B packs also go to the plan tensors of a and b (BlockParams::dump_a / dump_b, the [n][H][W][64]
+//     layout the three-conv route writes), under the in-image predicate of phase C's store.  The halo copies of a are not stored: b's
+//     reference is built from the dumped a, so a halo that disagrees with its neighbour's inner pixels puts b over its bound.
+//     bottleneck_fused_pq's P waves have no register for a second store of a group next to its LDS store (the identity block's product
+//     instantiation uses 253 of 256), so its DUMP form stores the same groups where they are read back: a from phase B's centre-tap read
+//     of each inner pixel, b from LDS behind B2 in the 16-byte groups the Q waves read for phase C; it also requests the next tile's x
+//     behind phase B instead of behind phase A.  No DUMP instantiation may spill (tests/test_build_resources.py).
 // ------------------------------------------------------------------------------------------------
 constexpr int kBlkHaloW = 18;
 constexpr int kBlkABytes = 192 * 128;                           // a: 180 halo rows (+12 dummy rows)
@@ -33,7 +41,15 @@ constexpr int kBlkBBytes = 128 * 128;                           // b: 8 x 16 pix
 constexpr int kBlkCstBytes = (4 * 64 + 2 * 256) * 4;            // s1, b1, s2, b2 [64]; s3, b3 [256]
 constexpr int block_lds_bytes(int cin, bool proj) { return (cin / 32) * 4 * 1024 + (proj ? 4 : 2) * 16 * 1024 + kBlkABytes + kBlkBBytes + kBlkCstBytes; }
 
-template <bool F16, int CIN, bool PROJ>
+// DUMP: the start of the 16 pixels (x0 .. x0 + 15) of row oy of patch n in the plan tensor of a or b, [n][H][W][64] 16-bit = 128 bytes a pixel.
+// Wave-uniform, so it costs scalar registers only; a lane adds dump_lane = frow * 128 + fg * 16 (its pixel and 8-channel group) and the
+// uniform byte offset of the 32-channel group it is packing.
+__device__ __attribute__((always_inline)) inline char* dump_row(void* base, int n, int H, int W, int oy, int x0)
+{
+    return (char*)base + (((size_t)n * H + oy) * W + x0) * 128;
+}
+
+template <bool F16, int CIN, bool PROJ, bool DUMP>
 __global__ __launch_bounds__(256, 1) void bottleneck_fused(const BlockParams p)
 {
     static_assert((CIN == 256 && !PROJ) || (CIN == 64 && PROJ), "identity blocks read 256 channels, the projection block 64");
@@ -51,6 +67,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_fused(const BlockParams p)
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int frow = lane & 15, fg = lane >> 4;
+    const int dump_lane = frow * 128 + fg * 16;                 // (DUMP only)
     const int tiles_x = (p.W + 15) / 16, tiles_y = (p.H + 7) / 8;
     const int tiles_per_patch = tiles_x * tiles_y;
     const int n_tiles = p.n * tiles_per_patch;
@@ -125,6 +142,12 @@ __global__ __launch_bounds__(256, 1) void bottleneck_fused(const BlockParams p)
             locate(tile_at(it + 1), in_next, off_next);
             fetch(off_next, xnext);
         }
+        int dn = 0, dty = 0, dtx = 0;                           // DUMP: patch and tile origin of this tile
+        if constexpr (DUMP) {
+            dn = tile / tiles_per_patch;
+            const int rem = tile - dn * tiles_per_patch;
+            dty = rem / tiles_x; dtx = rem - dty * tiles_x;
+        }
 
         // ---- phase A: a[halo pixel][64] = ReLU(s1 * (W1 . x) + b1), zero outside the image
         {
@@ -161,6 +184,13 @@ __global__ __launch_bounds__(256, 1) void bottleneck_fused(const BlockParams p)
                     r.x = pack2<F16>(y[0], y[1]); r.y = pack2<F16>(y[2], y[3]); r.z = pack2<F16>(y[4], y[5]); r.w = pack2<F16>(y[6], y[7]);
                     if (!inimg[j]) r = make_uint4(0u, 0u, 0u, 0u);
                     *(uint4*)(lds_a + hr[j] * 128 + (((s2 * 4 + fg) ^ (hr[j] & 7)) << 4)) = r;
+                    if constexpr (DUMP) {
+                        if (j < 2) {                            // the lane's inner pixels: rows 2w, 2w+1 of the tile, column frow
+                            const int oy = dty * 8 + 2 * wave + j;
+                            if (oy < p.H && dtx * 16 + frow < p.W)
+                                *(uint4*)(dump_row(p.dump_a, dn, p.H, p.W, oy, dtx * 16) + s2 * 64 + dump_lane) = r;
+                        }
+                    }
                 }
             }
         }
@@ -193,6 +223,11 @@ __global__ __launch_bounds__(256, 1) void bottleneck_fused(const BlockParams p)
                     r.x = pack2<F16>(fmaxf(acc[i][0] * sc.x + sh.x, 0.f), fmaxf(acc[i][1] * sc.y + sh.y, 0.f));
                     r.y = pack2<F16>(fmaxf(acc[i][2] * sc.z + sh.z, 0.f), fmaxf(acc[i][3] * sc.w + sh.w, 0.f));
                     *(uint2*)(lds_b + row * 128 + (((sB * 4 + fg) ^ (row & 7)) << 4) + half * 8) = r;
+                    if constexpr (DUMP) {
+                        const int oy = dty * 8 + g4 * 4 + i;
+                        if (oy < p.H && dtx * 16 + frow < p.W)
+                            *(uint2*)(dump_row(p.dump_b, dn, p.H, p.W, oy, dtx * 16) + sB * 64 + half * 8 + dump_lane) = r;
+                    }
                 }
             }
         }
@@ -283,7 +318,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_fused(const BlockParams p)
 // ------------------------------------------------------------------------------------------------
 constexpr int block_pq_lds_bytes(int cin, bool proj) { return block_lds_bytes(cin, proj) + kBlkBBytes; }
 
-template <bool F16, int CIN, bool PROJ>
+template <bool F16, int CIN, bool PROJ, bool DUMP>
 __global__ __launch_bounds__(512, 1) void bottleneck_fused_pq(const BlockParams p)
 {
     static_assert((CIN == 256 && !PROJ) || (CIN == 64 && PROJ), "identity blocks read 256 channels, the projection block 64");
@@ -367,6 +402,30 @@ __global__ __launch_bounds__(512, 1) void bottleneck_fused_pq(const BlockParams 
 
         for (int it = 0; it <= my_tiles; ++it) {
             bool in_cur[3] = {inimg[0], inimg[1], inimg[2]};
+            if constexpr (DUMP) {
+                // b of tile it - 1, complete since B2: the 16-byte groups of this wave's rows 2w, 2w+1 exactly as the Q waves read them for phase C
+                // (a second store of phase B's 8-byte groups costs registers that wave does not have, above; here the accumulators are dead)
+                if (it >= 1) {
+                    const int tile = tile_at(it - 1);
+                    const int pn = tile / tiles_per_patch;
+                    const int rem = tile - pn * tiles_per_patch;
+                    const int pty = rem / tiles_x, ptx = rem - pty * tiles_x;
+                    const char* pb = lds_b + ((it - 1) & 1) * kBlkBBytes;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const int oy = pty * 8 + 2 * wave + j;
+                        if (oy < p.H && ptx * 16 + frow < p.W) {
+                            int lane_now = lane;
+                            asm volatile("" : "+v"(lane_now));  // (opaque copy: the addresses below are worked out here per tile, not held in registers across the phases)
+                            const int row = (2 * wave + j) * 16 + (lane_now & 15);
+#pragma unroll
+                            for (int kk = 0; kk < 2; ++kk)
+                                *(uint4*)(dump_row(p.dump_b, pn, p.H, p.W, oy, ptx * 16) + kk * 64 + ((lane_now & 15) * 128 + (lane_now >> 4) * 16)) =
+                                    *(const uint4*)(pb + row * 128 + (((kk * 4 + (lane_now >> 4)) ^ (row & 7)) << 4));
+                        }
+                    }
+                }
+            }
             if (it < my_tiles) {
                 // ---- phase A of tile `it`, 32 output channels (two MFMA row blocks) at a time: 24 accumulator registers
                 // instead of 48 -- with 96 registers of x fragments and 72 of 3x3 weights this wave has no more to give
@@ -405,7 +464,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck_fused_pq(const BlockParams 
                         *(uint4*)(lds_a + hr[j] * 128 + (((s2 * 4 + fg) ^ (hr[j] & 7)) << 4)) = r;
                     }
                 }
-                if (it + 1 < my_tiles) {                        // x of the next tile into the registers phase A just freed
+                if (!DUMP && it + 1 < my_tiles) {               // x of the next tile into the registers phase A just freed
                     locate(tile_at(it + 1));
                     fetch();
                 }
@@ -414,6 +473,13 @@ __global__ __launch_bounds__(512, 1) void bottleneck_fused_pq(const BlockParams 
             if (it < my_tiles) {
                 // ---- phase B of tile `it` -> b[it & 1]
                 char* bb = lds_b + (it & 1) * kBlkBBytes;
+                int dn = 0, dty = 0, dtx = 0;                   // DUMP: patch and tile origin of tile `it`
+                if constexpr (DUMP) {
+                    const int tile = tile_at(it);
+                    dn = tile / tiles_per_patch;
+                    const int rem = tile - dn * tiles_per_patch;
+                    dty = rem / tiles_x; dtx = rem - dty * tiles_x;
+                }
                 const int sB = wave >> 1, half = wave & 1;
                 const int cB = sB * 32 + fg * 8 + half * 4;
                 const float4 sc = *(const float4*)(cst + 128 + cB), sh = *(const float4*)(cst + 192 + cB);
@@ -431,6 +497,16 @@ __global__ __launch_bounds__(512, 1) void bottleneck_fused_pq(const BlockParams 
                                 const int row = (g4 * 4 + i + t / 3) * kBlkHaloW + frow + t % 3;
                                 const bf16x8_t bq = *(const bf16x8_t*)(lds_a + row * 128 + (((kk * 4 + fg) ^ (row & 7)) << 4));
                                 acc[i] = mfma16<F16>(wf[t][kk], bq, acc[i]);
+                                if constexpr (DUMP) {
+                                    // the centre tap of output row g4 * 4 + i IS a's inner pixel (that row, column frow), channel group kk * 4 + fg:
+                                    // what phase A packed, as phase B reads it (phase A itself has no register left for a second store, above).
+                                    // All four waves read it; the one that owns the row in phase A stores it
+                                    if (t == 4 && wave == ((g4 * 4 + i) >> 1)) {
+                                        const int oy = dty * 8 + g4 * 4 + i;
+                                        if (oy < p.H && dtx * 16 + frow < p.W)
+                                            *(uint4*)(dump_row(p.dump_a, dn, p.H, p.W, oy, dtx * 16) + kk * 64 + (frow * 128 + fg * 16)) = __builtin_bit_cast(uint4, bq);
+                                    }
+                                }
                             }
                         __builtin_amdgcn_sched_barrier(0);      // (keeps later taps' reads from being hoisted: registers)
                     }
@@ -442,6 +518,14 @@ __global__ __launch_bounds__(512, 1) void bottleneck_fused_pq(const BlockParams 
                         r.y = pack2<F16>(fmaxf(acc[i][2] * sc.z + sh.z, 0.f), fmaxf(acc[i][3] * sc.w + sh.w, 0.f));
                         *(uint2*)(bb + row * 128 + (((sB * 4 + fg) ^ (row & 7)) << 4) + half * 8) = r;
                     }
+                }
+            }
+            if constexpr (DUMP) {
+                // the dump stores of phase B take registers this wave does not have while the next tile's x is in flight (the P waves' budget,
+                // above): here that request goes out behind phase B.  Later, not different: in_cur was taken at the top of the iteration
+                if (it + 1 < my_tiles) {
+                    locate(tile_at(it + 1));
+                    fetch();
                 }
             }
             __syncthreads();                                    // B2: b[it & 1] complete; a and b[(it-1) & 1] free
@@ -546,33 +630,39 @@ __global__ __launch_bounds__(512, 1) void bottleneck_fused_pq(const BlockParams 
     }
 }
 
+// One instantiation per (precision, block kind); DUMP (BlockParams::dump_a set) selects the step check's form of the same kernel.
+template <bool DUMP>
+static hipError_t launch_bottleneck_form(const BlockParams& p, int precision, int grid, hipStream_t s)
+{
+    const int slot = (precision == kF16 ? 0 : 1) + (p.proj ? 2 : 0);
+    auto go = [&](auto kernel, int lds, int threads, bool (&done)[64]) -> hipError_t {
+        const hipError_t e = dynamic_lds_once((const void*)kernel, lds, done);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, s, p);
+        return hipGetLastError();
+    };
+    if (p.pq) {
+        static bool attr_done8[4][64] = {};
+        bool (&done)[64] = attr_done8[slot];
+        if (p.proj) return precision == kF16 ? go(bottleneck_fused_pq<true, 64, true, DUMP>, block_pq_lds_bytes(64, true), 512, done) : go(bottleneck_fused_pq<false, 64, true, DUMP>, block_pq_lds_bytes(64, true), 512, done);
+        return precision == kF16 ? go(bottleneck_fused_pq<true, 256, false, DUMP>, block_pq_lds_bytes(256, false), 512, done) : go(bottleneck_fused_pq<false, 256, false, DUMP>, block_pq_lds_bytes(256, false), 512, done);
+    }
+    static bool attr_done[4][64] = {};
+    bool (&done)[64] = attr_done[slot];
+    if (p.proj) return precision == kF16 ? go(bottleneck_fused<true, 64, true, DUMP>, block_lds_bytes(64, true), 256, done) : go(bottleneck_fused<false, 64, true, DUMP>, block_lds_bytes(64, true), 256, done);
+    return precision == kF16 ? go(bottleneck_fused<true, 256, false, DUMP>, block_lds_bytes(256, false), 256, done) : go(bottleneck_fused<false, 256, false, DUMP>, block_lds_bytes(256, false), 256, done);
+}
+
 hipError_t launch_bottleneck(const BlockParams& p, int precision, int num_cus, hipStream_t s, LaunchRec* rec)
 {
     const int n_tiles = p.n * ((p.H + 7) / 8) * ((p.W + 15) / 16);
     const int grid = xcd_grid(n_tiles, num_cus);
     launch_rec(rec, p.pq ? SBBSEG_LAUNCH_BOTTLENECK_PQ : SBBSEG_LAUNCH_BOTTLENECK, 8 * 16, 256, 1, n_tiles, grid, 1, 0, !p.proj);
-    auto go = [&](auto kernel, int lds) -> hipError_t {
-        static bool attr_done[4][64] = {};
-        const int slot = (precision == kF16 ? 0 : 1) + (p.proj ? 2 : 0);
-        const hipError_t e = dynamic_lds_once((const void*)kernel, lds, attr_done[slot]);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, s, p);
-        return hipGetLastError();
-    };
-    if (p.pq) {
-        auto go8 = [&](auto kernel, int lds) -> hipError_t {
-            static bool attr_done8[4][64] = {};
-            const int slot = (precision == kF16 ? 0 : 1) + (p.proj ? 2 : 0);
-            const hipError_t e = dynamic_lds_once((const void*)kernel, lds, attr_done8[slot]);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, s, p);
-            return hipGetLastError();
-        };
-        if (p.proj) return precision == kF16 ? go8(bottleneck_fused_pq<true, 64, true>, block_pq_lds_bytes(64, true)) : go8(bottleneck_fused_pq<false, 64, true>, block_pq_lds_bytes(64, true));
-        return precision == kF16 ? go8(bottleneck_fused_pq<true, 256, false>, block_pq_lds_bytes(256, false)) : go8(bottleneck_fused_pq<false, 256, false>, block_pq_lds_bytes(256, false));
+    if (p.dump_a || p.dump_b) {
+        if (!p.dump_a || !p.dump_b) return hipErrorInvalidValue;
+        return launch_bottleneck_form<true>(p, precision, grid, s);
     }
-    if (p.proj) return precision == kF16 ? go(bottleneck_fused<true, 64, true>, block_lds_bytes(64, true)) : go(bottleneck_fused<false, 64, true>, block_lds_bytes(64, true));
-    return precision == kF16 ? go(bottleneck_fused<true, 256, false>, block_lds_bytes(256, false)) : go(bottleneck_fused<false, 256, false>, block_lds_bytes(256, false));
+    return launch_bottleneck_form<false>(p, precision, grid, s);
 }
 
 }  // namespace sbbseg

@@ -297,7 +297,9 @@ struct sbbseg_ctx {
     bool ranged_walk = false;    // A/B: grouped launches walk XCD-contiguous tile ranges (conv variant bit 19)
     bool block_pq = true;        // fused bottleneck blocks run the producer / consumer form (conv variant bit 20: the one-group form)
     bool unfuse_blocks = false;  // A/B: run a fused bottleneck block as its three convs (conv variant bit 18)
-    bool unfuse_stem_pool = false;     // A/B: stem and max-pool as two launches (conv variant bit 22)
+    bool dump_blocks = false;    // step check: the fused 16-bit bottleneck blocks also store a and b to their plan tensors (conv variant bit 26;
+                                 // nothing in the split mode, whose block_x3 is held bit-identical to its three convs)
+    bool unfuse_stem_pool = false;    // A/B: stem and max-pool as two launches (conv variant bit 22)
     bool no_dec_halo = false;          // A/B: the 224 x 224 decoder conv on the generic kernel (conv variant bit 23)
     bool no_expand_reduce = false;     // A/B: expand + next reduce 1x1 convs as two launches (conv variant bit 24)
     bool no_c3er = false;              // A/B: the 3x3 conv of a stage-3 identity block as its own launch in front of expand_reduce (conv variant bit 25)

@@ -40,7 +40,13 @@ int launch_block(sbbseg_ctx* c, Op& op, int n)
     { static const int blk_dbg = getenv("SBBSEG_BLOCK_DBG") ? atoi(getenv("SBBSEG_BLOCK_DBG")) : 0; bp.dbg = blk_dbg; }
 #endif
     if (c->precision == kF16X3) HIPCHK(launch_block_x3(bp, c->num_cus, c->stream, &op.last));
-    else HIPCHK(launch_bottleneck(bp, c->precision, c->num_cus, c->stream, &op.last));
+    else {
+        if (c->dump_blocks) {         // the parts stay alive, so the plan tensors of a and b exist
+            bp.dump_a = c->tensors[op.parts[0].conv.d.out_tensor].data();
+            bp.dump_b = c->tensors[op.parts[1].conv.d.out_tensor].data();
+        }
+        HIPCHK(launch_bottleneck(bp, c->precision, c->num_cus, c->stream, &op.last));
+    }
     return 0;
 }
 

@@ -209,6 +209,10 @@ struct BlockParams {
     // w2 = [hi | lo][9][2][4 mi][64 lanes] x 16 B, every conv's weights pre-scaled by a power of two; wmulN = 2^-s undoes it in sN
     float wmul1 = 1.f, wmul2 = 1.f, wmul3 = 1.f;
     int dbg = 0;              // timing probes (SBBSEG_BLOCK_DBG; results are WRONG with any bit set): 1 = LDS rows rotated by 1 slot per row on the WRITE side only
+    // conv variant bit 26 (16-bit modes only; null otherwise): data pointers [n][H][W][64] of the plan tensors of a and b.  Non-null selects the
+    // DUMP instantiation of bottleneck_fused*, which also stores what phases A and B pack for the pixels inside the image (tests/test_gpu_steps_blocks.py)
+    void* dump_a = nullptr;
+    void* dump_b = nullptr;
 };
 
 // The decoder conv at 224 x 224 in the split mode with LDS-resident source halos (dec_halo_x3.hip): the grouped launch of the four

@@ -42,11 +42,11 @@ def _is_conv(s, kh, cin, cout, n_src=1):
             and g.channels == cin and s.out_stride == (1, 1))
 
 
-def expected_unwritten(plan, precision, ops):
-    """{plan tensor id} the default plan keeps in LDS: the two 64-channel tensors of every fused stage-2 block and the 3x3 output b of
-    every stage-3 identity block that runs as conv3_expand_reduce (128 channels, map sides multiples of 8)."""
+def fused_block_tensors(plan):
+    """({plan tensor id: "a" | "b"}, number of blocks): the two 64-channel tensors of every stage-2 bottleneck block the library fuses
+    (csrc/plan_build.hip fuse_bottlenecks)."""
     st = plan.steps
-    keep = set()
+    keep = {}
     blocks = 0
     for i in range(len(st) - 2):
         a, b, c = st[i], st[i + 1], st[i + 2]
@@ -60,9 +60,20 @@ def expected_unwritten(plan, precision, ops):
         ident = len(c.srcs) == 1 and c.srcs[0].tensor == b.out and c.residual == x and cin == 256
         proj = len(c.srcs) == 2 and c.residual < 0 and cin == 64 and {g.tensor for g in c.srcs} == {b.out, x}
         if ident or proj:
-            keep |= {a.out, b.out}
+            keep[a.out], keep[b.out] = "a", "b"
             blocks += 1
+    return keep, blocks
+
+
+def expected_unwritten(plan, precision, ops, dump_blocks=False):
+    """{plan tensor id} the default plan keeps in LDS: the two 64-channel tensors of every fused stage-2 block and the 3x3 output b of
+    every stage-3 identity block that runs as conv3_expand_reduce (128 channels, map sides multiples of 8).  `dump_blocks`: the form
+    under conv variant bit 26, where bottleneck_fused* stores a and b too -- in the f16 / bf16 modes the block tensors leave the set; the
+    split mode's block_x3 has no such form and keeps them."""
+    st = plan.steps
+    ab, blocks = fused_block_tensors(plan)
     assert blocks == sum(1 for o in ops if o["name"].startswith("block")), [o["name"] for o in ops]
+    keep = set() if dump_blocks and precision in ("f16", "bf16") else set(ab)
     for i in range(1, len(st) - 1):
         k3, e, r = st[i - 1], st[i], st[i + 1]
         if not (_is_conv(k3, 3, 128, 128) and k3.relu and k3.residual < 0 and _is_conv(e, 1, 128, 512) and e.relu and e.residual >= 0
