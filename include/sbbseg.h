@@ -572,9 +572,9 @@ int sbbseg_region_line_table(int16_t* itab, int capacity);
  * kernels and this step.  Every float64 result equals scipy's gaussian_filter1d / find_peaks and numpy's mean / std bit for bit, on the
  * device and in the serial host twin (csrc/line_split.h is shared by both).
  *   SCOPE: the contour enters the reference only through cv2.pointPolygonTest (x_min / x_max of the horizontal splitter; the vertical
- *   splitter computes it and never uses it).  The contour half of textline_contours_postprocessing (main.py:1492-1511) is NOT built and
- *   not approximated: every line gets the reference's own fallback extent x_min_cont = 0, x_max_cont = w (main.py:786-788).  The rotation
- *   terms are inputs, so a caller that has the contour re-rotates with its own x extent.  return_contours_of_image /
+ *   splitter computes it and never uses it).  These calls do not take it: every line gets the reference's own fallback extent
+ *   x_min_cont = 0, x_max_cont = w (main.py:786-788), and sbbseg_region_line_extents_dev (below) then cuts the lines to the region's filled,
+ *   rotated contour (main.py:1492-1511) and rewrites the corners.  return_contours_of_image /
  *   filter_contours_area_of_image inside the first `try` (main.py:608-609) are treated as dead and non-raising [EXT] unpinned.
  * Inputs per region r: geom[r] = {length of the profile, the other extent of dst, vertical (0 / 1)}; rot[r] = {cos, -sin, sin, cos, x_d,
  * y_d}: numpy's cos / sin of thetha / 180. * np.pi (thetha = slope, + 90 first for the vertical splitter) and M[0, 2], M[1, 2] of
@@ -630,6 +630,68 @@ int sbbseg_planes_line_masks_dev(sbbseg_ctx* c, const sbbseg_plane* planes, int 
 int sbbseg_planes_line_boxes_dev(sbbseg_ctx* c, const sbbseg_plane* planes, int n_planes, const int32_t* boxes_xywh, const int32_t* box_plane, int n_boxes,
                                  int erode_iterations, const double* slopes, const double* rot, const double* weights, const int64_t* weight_off,
                                  int sigma_max, int32_t* info, int64_t* line_off, int32_t* lines, int32_t* corners, int32_t* corners_rot);
+
+/* ---- stage glue: the x extent of every text line from its region's filled, rotated contour -- the contour half of
+ * textline_contours_postprocessing (main.py:1492-1511) and cv2.pointPolygonTest inside seperate_lines (main.py:780-791, 878-889, 945-956);
+ * csrc/line_extent.h is shared by the device step and the serial host twin.  Every cv2 rule is [EXT]: restated from the OpenCV 4.5.1
+ * text, unpinned (no cv2 to hold it against), reduced to integer predicates:
+ *   R1 cv2.fillPoly(zeros (h, w), ring - (x, y), 255).  Scope: rings whose edges between consecutive points (the closing edge included; a
+ *      repeated closing point is a zero-length edge) are horizontal, vertical or exact diagonals and whose points lie inside the box --
+ *      what CHAIN_APPROX_SIMPLE lists are.  A pixel is set when it lies on an edge, or when an odd number of edges cross its row strictly
+ *      left of it (an edge crosses row py when min(y0, y1) <= py < max(y0, y1)).  Any other ring is an error that names the region.
+ *   R2 rotate_image on float64: the matrix, inverse map and 5-bit table indices of sbbseg_region_line_masks_dev, the FLOAT bicubic path:
+ *      the weight of a tap is the float32 product tab[ay][r] * tab[ax][c]; all of them are multiples of 2^-34, so with a 0 / 255 source
+ *      the float64 sum is exact in any order: v = 255 * S / 2^34, S = the integer sum of weight * 2^34 over the taps on set pixels.
+ *   R3 .astype(np.uint8) truncates toward zero and keeps the low 8 bits (numpy on x86-64); BGR2GRAY of equal channels is the value;
+ *      threshold(., 0, 255, 0): a pixel of threshrot is set iff (trunc(v) & 255) != 0 -- the negative overshoot outside the outline IS set,
+ *      |v| < 1 and 256 <= v < 257 are holes.
+ *   R4 cv2.findContours(threshrot, RETR_TREE, CHAIN_APPROX_SIMPLE) and np.argmax of the point counts: ALL borders compete, outer borders
+ *      and hole borders.  Raster scan over the image padded with zeros; at a position with pixel p and west neighbour q: p set and
+ *      unmarked, q background -- an outer border starts there, first search clockwise from west; p background, q set and not marked
+ *      "right" -- a hole border starts at q, first search clockwise from east; then the walk of sbbseg_mask_contours_host.  A step marks
+ *      the pixel it leaves "right" if its east neighbour was examined as background during the step, "visited" otherwise.  The winner has
+ *      the most kept points; among equals the LAST discovered (OpenCV lists borders in reverse discovery order: assumed, as everywhere
+ *      in this library) -- `tie` reports that there were equals.  No border: np.argmax([]) raises, the region's lines are [] (status NONE).
+ *   R5 per line of the HORIZONTAL splitter (|slope| <= 45): xv = np.linspace(0, w, 1000) (k * (w / 999), the last exactly w); sample k is
+ *      inside iff pointPolygonTest(winner, (float32(xv[k]), float32(peak)), True) >= 0: some edge's dist_num is 0, or the crossing
+ *      counter is odd; pt.x - v.x is a float32 subtraction, all else float64 signs of sums of two exact products.  x_min = int(min inside
+ *      xv), x_max = int(max inside xv); none inside: 0, w.
+ *   R6 branches 0, 3 and 4 of the line record take x_min / x_max: corners and corners_rot are rewritten through the writer of
+ *      sbbseg_line_split_dev.  Branch 2 and the vertical splitter keep 0 .. w and their corners.
+ * sbbseg_region_line_extents_dev: n regions.  Rings: packed int (x, y) points in page coordinates, region r = points point_off[r] ..
+ * point_off[r + 1] (closed or not); points_xy = NULL names the handle's resident contour result (sbbseg_text_region_contours_dev), read in
+ * place: n must be its contour count.  boxes_xywh [n][4], slopes [n], rot [n][6], info [n][5], line_off [n + 1], lines [total][3]: as
+ * passed to and written by sbbseg_region_line_boxes_dev.  Outputs (host): extent [total][2] = x_min, x_max for the first `count` lines of
+ * every region with status SBBSEG_LINES_OK (0, w where the step does not apply); corners / corners_rot [total][4][2]: IN / OUT, only the
+ * lines R6 names are rewritten; rec [n][8] = {status (SBBSEG_EXTENT_OK, SBBSEG_EXTENT_NONE: the region has no lines), borders found,
+ * the winner's points, 1 = the winner is a hole border, 1 = tie, the winner's start pixel x, y, hole borders found}.  The step reads no
+ * label plane: the boxes of many pages share one call.  Launches, whatever n is: fill 1, warp + threshold 1, border scan 2 per form in use
+ * (bit maps + marks within 60 KB of LDS: the LDS form, else a global workspace -- chosen, not measured; so is one wave per region), extents
+ * 1.  No atomics: the results are bit-identical from run to run.  n = 0 is success.  Synchronises the stream.
+ * sbbseg_region_line_extents_read: threshrot (uint8 [h][w], 0 / 255) and the winner's points of region `region` of the handle's last
+ * extent (or debug mask) call; either may be NULL.  sbbseg_region_line_extents_host: ONE region, serial, no GPU, no handle: the same
+ * statements; lines [n_lines][3], branch = info[3]; threshrot / winner_xy optional.  sbbseg_region_line_extent_weights: the int64
+ * [32][32][16] table of R2 (host only). */
+#define SBBSEG_EXTENT_OK 0
+#define SBBSEG_EXTENT_NONE 1
+#define SBBSEG_EXTENT_REC_INTS 8
+int sbbseg_region_line_extents_dev(sbbseg_ctx* c, const int32_t* points_xy, const int64_t* point_off, int n, const int32_t* boxes_xywh,
+                                   const double* slopes, const double* rot, const int32_t* info, const int64_t* line_off, const int32_t* lines,
+                                   int32_t* extent, int32_t* corners, int32_t* corners_rot, int32_t* rec);
+int sbbseg_region_line_extents_read(sbbseg_ctx* c, int region, uint8_t* threshrot_hw, int32_t* winner_xy, int cap);
+int sbbseg_region_line_extents_host(const int32_t* ring_xy, int n_points, const int32_t* box_xywh, double slope, const double* rot, int branch,
+                                    const int32_t* lines, int n_lines, int32_t* extent, int32_t* corners, int32_t* corners_rot, int32_t* rec,
+                                    uint8_t* threshrot, int32_t* winner_xy, int winner_cap);
+int sbbseg_region_line_extent_weights(int64_t* wtab, int capacity);
+/* the border scan of R4 alone on raw masks (!= 0; tests): n masks packed one after the other, mask r = wh[2 r] x wh[2 r + 1] bytes; rec as
+ * above; winners through sbbseg_region_line_extents_read.  _host: one mask, serially, no GPU. */
+int sbbseg_debug_mask_border_winner_dev(sbbseg_ctx* c, const uint8_t* masks, const int32_t* wh, int n, int32_t* rec);
+int sbbseg_debug_mask_border_winner_host(const uint8_t* mask, int w, int h, int32_t* rec, int32_t* winner_xy, int cap);
+/* a region whose three bit maps (box + ring, 32-bit words) exceed `bytes` is scanned on a global workspace instead of LDS (0 .. 61440, the
+ * default; tests lower it so that small shapes reach the global form) */
+int sbbseg_debug_set_extent_lds_limit(sbbseg_ctx* c, int bytes);
+/* kernels the extent calls have queued on this handle so far */
+int sbbseg_debug_extent_launches(sbbseg_ctx* c, int64_t* value);
 
 /* ---- multi-GPU: one process per GPU, one handle per process; tiles (sbbseg_segment_tile_range_dev) or whole
  * pages (sbbseg_segment_pages_dev) are sharded by the caller, and the ONE data-path collective -- the all-gather of the u8

@@ -47,6 +47,8 @@ EXPORTS = [
     "sbbseg_debug_profile_statistics", "sbbseg_debug_soft_arith",
     "sbbseg_contour_moments_dev", "sbbseg_contour_moments_host", "sbbseg_region_order_dev", "sbbseg_region_order", "sbbseg_region_order_host",
     "sbbseg_debug_row_sums", "sbbseg_debug_order_launches",
+    "sbbseg_region_line_extents_dev", "sbbseg_region_line_extents_read", "sbbseg_region_line_extents_host", "sbbseg_region_line_extent_weights",
+    "sbbseg_debug_mask_border_winner_dev", "sbbseg_debug_mask_border_winner_host", "sbbseg_debug_set_extent_lds_limit", "sbbseg_debug_extent_launches",
 ]
 
 
@@ -238,6 +240,14 @@ def load_library(path: Optional[str] = None):
         "sbbseg_region_order_host": [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_int)],
         "sbbseg_debug_row_sums": [vp, vp, i32, i32, vp],
         "sbbseg_debug_order_launches": [vp, C.POINTER(C.c_int64)],
+        "sbbseg_region_line_extents_dev": [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "sbbseg_region_line_extents_read": [vp, i32, vp, vp, i32],
+        "sbbseg_region_line_extents_host": [vp, i32, vp, C.c_double, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32],
+        "sbbseg_region_line_extent_weights": [vp, i32],
+        "sbbseg_debug_mask_border_winner_dev": [vp, vp, vp, i32, vp],
+        "sbbseg_debug_mask_border_winner_host": [vp, i32, i32, vp, vp, i32],
+        "sbbseg_debug_set_extent_lds_limit": [vp, i32],
+        "sbbseg_debug_extent_launches": [vp, C.POINTER(C.c_int64)],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -841,6 +851,73 @@ class Context:
         check(self.lib.sbbseg_debug_order_launches(self.h, C.byref(v)), "sbbseg_debug_order_launches")
         return int(v.value)
 
+    def region_line_extents_raw(self, boxes, slopes, records, contours=None, fill: int = 0):
+        """``sbbseg_region_line_extents_dev`` as the library packs it: (line_off int64 [n + 1], extent int32 [total, 2], corners and
+        corners_rot int32 [total, 4, 2], rec int32 [n, 8]).  ``fill``: what ``extent`` and the line slots beyond every record's count hold
+        before the call (tests: the call writes nothing there)."""
+        boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        slopes = np.ascontiguousarray(slopes, np.float64).reshape(-1)
+        n = boxes.shape[0]
+        if slopes.shape[0] != n or len(records) != n:
+            raise ValueError("one slope and one record per box: %d boxes, %d slopes, %d records" % (n, slopes.shape[0], len(records)))
+        pts, off, nc = (None, None, n) if contours is None else pack_contours(contours)
+        if nc != n:
+            raise ValueError("one ring per box: %d boxes, %d rings" % (n, nc))
+        rots = np.array([line_rotation_terms(int(b[2]), int(b[3]), float(s)) for b, s in zip(boxes, slopes)], np.float64).reshape(n, 6)
+        info, line_off, lines, corners, corners_rot = _extent_tables(boxes, slopes, records, fill)
+        extent, rec = np.full((lines.shape[0], 2), fill, np.int32), np.zeros((n, EXTENT_REC_INTS), np.int32)
+        check(self.lib.sbbseg_region_line_extents_dev(self.h, _ptr(pts), _ptr(off), n, _ptr(boxes), _ptr(slopes), _ptr(rots), _ptr(info), _ptr(line_off),
+                                                      _ptr(lines), _ptr(extent), _ptr(corners), _ptr(corners_rot), _ptr(rec)),
+              "sbbseg_region_line_extents_dev")
+        return line_off, extent, corners, corners_rot, rec
+
+    def region_line_extents_dev(self, boxes, slopes, records, contours=None):
+        """The x extent of every text line from its region's filled, rotated contour (``sbbseg_region_line_extents_dev``; the contour half
+        of textline_contours_postprocessing, main.py:1492-1511, and cv2.pointPolygonTest inside seperate_lines).  ``records``: the line
+        records of ``region_line_boxes_dev`` for ``boxes`` / ``slopes``; ``contours``: one ring per box (int (x, y) points in page
+        coordinates, [N, 2] or [N, 1, 2]), or None for the handle's resident contour result, read in place.  Returns the records with
+        ``boxes`` / ``boxes_rot`` rewritten where the reference takes x_min / x_max (branches 0, 3, 4 of the horizontal splitter), plus
+        ``extent`` int32 [lines, 2] and ``contour`` = the region's record of :func:`host_region_line_extents`.  A region without any border
+        in its rotated contour has status LINES_NONE and no lines, as the reference's bare except leaves it."""
+        if len(records) == 0:
+            return []
+        return _extent_records(records, *self.region_line_extents_raw(boxes, slopes, records, contours))
+
+    def region_line_extents_read(self, region: int, w: int, h: int, n_points: int):
+        """(threshrot uint8 [h, w] of 0 / 255, the winner's points int32 [n_points, 2]) of region ``region`` of the handle's last extent or
+        border-winner call."""
+        thresh, winner = np.zeros((int(h), int(w)), np.uint8), np.zeros((max(int(n_points), 1), 2), np.int32)
+        check(self.lib.sbbseg_region_line_extents_read(self.h, int(region), _ptr(thresh), _ptr(winner), winner.shape[0]), "sbbseg_region_line_extents_read")
+        return thresh, winner[:int(n_points)].copy()
+
+    def debug_mask_border_winner(self, masks):
+        """The border scan of the extent step alone on raw masks (``sbbseg_debug_mask_border_winner_dev``): per mask the record of
+        :func:`host_mask_border_winner`."""
+        masks = [np.ascontiguousarray(np.asarray(m) != 0, np.uint8) for m in masks]
+        n = len(masks)
+        if n == 0:
+            return []
+        wh = np.ascontiguousarray([[m.shape[1], m.shape[0]] for m in masks], np.int32)
+        packed = np.ascontiguousarray(np.concatenate([m.reshape(-1) for m in masks]), np.uint8)
+        rec = np.zeros((n, EXTENT_REC_INTS), np.int32)
+        check(self.lib.sbbseg_debug_mask_border_winner_dev(self.h, _ptr(packed), _ptr(wh), n, _ptr(rec)), "sbbseg_debug_mask_border_winner_dev")
+        out = []
+        for r in range(n):
+            d = _extent_rec(rec[r])
+            d["winner"] = self.region_line_extents_read(r, wh[r, 0], wh[r, 1], d["points"])[1]
+            out.append(d)
+        return out
+
+    def set_extent_lds_limit(self, nbytes: int):
+        """Test hook: regions whose three bit maps exceed ``nbytes`` are scanned on a global workspace (default 61440)."""
+        check(self.lib.sbbseg_debug_set_extent_lds_limit(self.h, int(nbytes)), "sbbseg_debug_set_extent_lds_limit")
+
+    def extent_launches(self) -> int:
+        """Kernels the extent calls have queued on this handle so far."""
+        v = C.c_int64(0)
+        check(self.lib.sbbseg_debug_extent_launches(self.h, C.byref(v)), "sbbseg_debug_extent_launches")
+        return int(v.value)
+
     def _region_profiles_call(self, fn, src, H, W, boxes, angles_deg, erode_iterations):
         boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
         angles_deg = np.ascontiguousarray(angles_deg, np.float64).reshape(-1)
@@ -934,7 +1011,7 @@ class Context:
     def line_split_dev(self, d_profiles: int, offsets, others, verticals, rots, sigma_max: int = LINE_SIGMA_MAX):
         """The text lines of every region from its projection (``seperate_lines`` / ``seperate_lines_vertical`` after ``img_patch.sum``,
         main.py:516-1457) for packed int32 profiles in device memory, one call: a list of line records (``line_split_host``).  The x
-        extent of every line is the reference's fallback (0, w): the contour is not built (sbbseg.h).  A region whose sigma_gaus exceeds
+        extent of every line is the reference's fallback (0, w); ``region_line_extents_dev`` cuts the lines to the contour (sbbseg.h).  A region whose sigma_gaus exceeds
         the device's table is finished by the host twin with that sigma's weights."""
         offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
         n = offsets.shape[0] - 1
@@ -979,7 +1056,7 @@ class Context:
     def region_line_boxes_dev(self, d_textlines: int, H: int, W: int, boxes, slopes, erode_iterations: int = 2, sigma_max: int = LINE_SIGMA_MAX):
         """``region_line_masks_dev`` and then the line splitter of every box on its own profile (row sums, or column sums for
         ``abs(slope) > 45``, main.py:1514), the profiles staying on the device: a list of line records (``line_split_host``) -- see
-        sbbseg.h.  The x extent of every line is the reference's fallback (0, w): the contour half is not built."""
+        sbbseg.h.  The x extent of every line is the reference's fallback (0, w); ``region_line_extents_dev`` cuts the lines to the contour."""
         return self._line_boxes_call(self.lib.sbbseg_region_line_boxes_dev, C.c_void_p(d_textlines), lambda r: (d_textlines, H, W), H, W, boxes, slopes,
                                      erode_iterations, sigma_max)
 
@@ -1509,8 +1586,8 @@ def line_split_host(profiles, others, verticals, rots, sigma_max: int = LINE_SIG
     of dst, or column sums for the vertical splitter); ``others``: the other extent of dst; ``rots``: ``line_rotation_terms``.  Returns
     one record per region: status (LINES_OK, or LINES_NONE where the reference returns []), sigma (sigma_gaus), raised (the first
     estimate's ``try`` raised), branch (0 .. 4: main.py:744, 822, 825, 864, 919; -1 not reached), peaks, point_up, point_down (int32
-    [lines]), boxes and boxes_rot (int32 [lines, 4, 2]: main.py:817-820 and 812-815).  The x extent is the reference's fallback (0, w):
-    the contour is not built.  A region whose sigma_gaus is beyond the table is run again with that sigma's weights."""
+    [lines]), boxes and boxes_rot (int32 [lines, 4, 2]: main.py:817-820 and 812-815).  The x extent is the reference's fallback (0, w);
+    ``host_region_line_extents`` cuts the lines to the contour.  A region whose sigma_gaus is beyond the table is run again with that sigma's weights."""
     raw = line_split_host_raw(profiles, others, verticals, rots, sigma_max)
     records = _line_records(*raw)
     for r, rec in enumerate(records):
@@ -1518,6 +1595,86 @@ def line_split_host(profiles, others, verticals, rots, sigma_max: int = LINE_SIG
             one = line_split_host_raw([profiles[r]], [others[r]], [verticals[r]], [np.asarray(rots, np.float64).reshape(-1, 6)[r]], sigma_max, rec["sigma"])
             records[r] = _line_records(*one)[0]
     return records
+
+
+EXTENT_OK, EXTENT_NONE, EXTENT_REC_INTS = 0, 1, 8
+
+
+def _extent_rec(rec) -> dict:
+    return {"status": int(rec[0]), "borders": int(rec[1]), "points": int(rec[2]), "is_hole": bool(rec[3]), "tie": bool(rec[4]),
+            "start": (int(rec[5]), int(rec[6])), "holes": int(rec[7])}
+
+
+def _extent_tables(boxes, slopes, records, fill: int = 0):
+    """Line records back in the packed form of ``sbbseg_region_line_boxes_dev``: (info, line_off, lines, corners, corners_rot); slots
+    beyond a record's count hold ``fill``."""
+    vertical = np.abs(slopes) > 45
+    geom = _line_geom(np.where(vertical, boxes[:, 2], boxes[:, 3]).clip(1), np.where(vertical, boxes[:, 3], boxes[:, 2]), vertical)
+    info, line_off, lines, corners, corners_rot = _line_split_buffers(geom)
+    line_off[1:] = np.cumsum((geom[:, 0].astype(np.int64) + 40) // 2)
+    for a in (lines, corners, corners_rot):
+        a[...] = fill
+    for r, rec in enumerate(records):
+        at, cnt = int(line_off[r]), len(rec["peaks"])
+        info[r] = (rec["status"], rec["sigma"], int(rec["raised"]), rec["branch"], cnt)
+        lines[at:at + cnt, 0], lines[at:at + cnt, 1], lines[at:at + cnt, 2] = rec["peaks"], rec["point_up"], rec["point_down"]
+        corners[at:at + cnt], corners_rot[at:at + cnt] = rec["boxes"], rec["boxes_rot"]
+    return info, line_off, lines, corners, corners_rot
+
+
+def _extent_records(records, line_off, extent, corners, corners_rot, rec):
+    out = []
+    for r, old in enumerate(records):
+        at, cnt = int(line_off[r]), len(old["peaks"])
+        new = dict(old, boxes=corners[at:at + cnt].copy(), boxes_rot=corners_rot[at:at + cnt].copy(), extent=extent[at:at + cnt].copy(),
+                   contour=_extent_rec(rec[r]))
+        if new["contour"]["status"] == EXTENT_NONE:              # np.argmax([]) raised: the bare except returns [] (main.py:1520)
+            new.update(status=LINES_NONE, peaks=old["peaks"][:0], point_up=old["point_up"][:0], point_down=old["point_down"][:0],
+                       boxes=new["boxes"][:0], boxes_rot=new["boxes_rot"][:0], extent=new["extent"][:0])
+        out.append(new)
+    return out
+
+
+def host_region_line_extents(contour, box, slope: float, record, want_masks: bool = False):
+    """``Context.region_line_extents_dev`` for ONE region on the CPU (serial, no handle, no GPU; the same statements, csrc/line_extent.h).
+    Returns the record with ``boxes`` / ``boxes_rot`` rewritten, ``extent`` int32 [lines, 2] and ``contour`` = {status (EXTENT_OK /
+    EXTENT_NONE), borders, points, is_hole, tie, start, holes} of the border that wins np.argmax in the rotated contour image;
+    ``want_masks`` adds ``threshrot`` (uint8 [h, w] of 0 / 255) and ``winner`` (int32 [points, 2]) to ``contour``."""
+    box = np.ascontiguousarray(box, np.int32).reshape(4)
+    ring = np.ascontiguousarray(np.asarray(contour).reshape(-1, 2), np.int32)
+    w, h = int(box[2]), int(box[3])
+    slopes = np.array([float(slope)], np.float64)
+    info, line_off, lines, corners, corners_rot = _extent_tables(box.reshape(1, 4), slopes, [record])
+    rot = np.array(line_rotation_terms(w, h, float(slope)), np.float64)
+    cnt = len(record["peaks"])
+    extent, rec = np.zeros((lines.shape[0], 2), np.int32), np.zeros((1, EXTENT_REC_INTS), np.int32)
+    thresh = np.zeros((max(h, 1), max(w, 1)), np.uint8)
+    winner = np.zeros((4 * (max(h, 1) * max(w, 1)) + 8, 2), np.int32)
+    check(load_library().sbbseg_region_line_extents_host(_ptr(ring), ring.shape[0], _ptr(box), float(slope), _ptr(rot), int(record["branch"]), _ptr(lines),
+                                                         cnt if record["status"] == LINES_OK else 0, _ptr(extent), _ptr(corners), _ptr(corners_rot),
+                                                         _ptr(rec), _ptr(thresh), _ptr(winner), winner.shape[0]), "sbbseg_region_line_extents_host")
+    out = _extent_records([record], line_off, extent, corners, corners_rot, rec)[0]
+    if want_masks:
+        out["contour"].update(threshrot=thresh, winner=winner[:out["contour"]["points"]].copy())
+    return out
+
+
+def host_mask_border_winner(mask: np.ndarray) -> dict:
+    """The serial border scan of the extent step on a raw mask (!= 0): {status, borders, points, is_hole, tie, start, holes, winner}."""
+    m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+    rec, winner = np.zeros(EXTENT_REC_INTS, np.int32), np.zeros((4 * m.size + 8, 2), np.int32)
+    check(load_library().sbbseg_debug_mask_border_winner_host(_ptr(m), m.shape[1], m.shape[0], _ptr(rec), _ptr(winner), winner.shape[0]),
+          "sbbseg_debug_mask_border_winner_host")
+    d = _extent_rec(rec)
+    d["winner"] = winner[:d["points"]].copy()
+    return d
+
+
+def region_line_extent_weights() -> np.ndarray:
+    """int64 [32][32][4][4]: the float32 bicubic products of the contour rotation times 2^34, indexed [ay][ax][row][column] (sbbseg.h)."""
+    out = np.empty(32 * 32 * 16, np.int64)
+    check(load_library().sbbseg_region_line_extent_weights(_ptr(out), out.shape[0]), "sbbseg_region_line_extent_weights")
+    return out.reshape(32, 32, 4, 4)
 
 
 def host_region_line_mask(crop: np.ndarray, slope: float, erode_iterations: int = 2, mask: bool = True):

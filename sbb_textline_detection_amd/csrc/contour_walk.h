@@ -61,20 +61,32 @@ struct ContourResult {
 };
 
 // nb(x, y): bit d set <=> the neighbour of (x, y) in direction d belongs to the component.  emit(k, x, y): kept point k.
-template <typename Nb, typename Emit>
-SBB_CW_HD ContourResult contour_walk(Nb nb, int sx, int sy, long long max_steps, Emit emit)
+//
+// contour_walk_from is the same walk with two more parameters, for the callers that follow EVERY border of a mask (line_extent.h):
+//   * first: the direction after which the clockwise search for the predecessor begins -- 4 (west) for an outer border, 0 (east) for the
+//     border of a hole, whose start pixel is the pixel WEST of the hole's first background pixel;
+//   * mark(x, y, right): called once per step with the pixel the step leaves; right = the pixel's east neighbour was examined during this
+//     step's search and was background (OpenCV writes -nbd there, nbd otherwise).  A one-pixel border is marked right.
+// contour_walk is contour_walk_from(first = 4, no marks): the outer-border callers' results do not change.
+struct ContourNoMark {
+    SBB_CW_HD void operator()(int, int, bool) const {}
+};
+
+template <typename Nb, typename Emit, typename Mark>
+SBB_CW_HD ContourResult contour_walk_from(Nb nb, int sx, int sy, int first, long long max_steps, Emit emit, Mark mark)
 {
     ContourResult r;
     r.area2 = 0; r.steps = 1; r.n_points = 0; r.status = kContourOk;
     r.x0 = r.x1 = sx; r.y0 = r.y1 = sy;
     unsigned m = nb(sx, sy);
-    m = (((m | (m << 8)) >> 4) & 0xfeu);                     // bit j = the neighbour in direction 4 + j: clockwise from west, west itself left out
+    m = (((m | (m << 8)) >> first) & 0xfeu);                 // bit j = the neighbour in direction first + j: clockwise from `first`, itself left out
     if (!m) {                                                // a one-pixel component
         emit(0, sx, sy);
+        mark(sx, sy, true);
         r.n_points = 1;
         return r;
     }
-    const int to_pred = (4 + __builtin_ctz(m)) & 7;          // from the start pixel to its predecessor
+    const int to_pred = (first + __builtin_ctz(m)) & 7;          // from the start pixel to its predecessor
     const int px = sx + contour_step_x(to_pred), py = sy + contour_step_y(to_pred);
     int cx = sx, cy = sy, back = to_pred, entered = to_pred ^ 4;
     long long sum = 0, steps = 0;
@@ -83,7 +95,9 @@ SBB_CW_HD ContourResult contour_walk(Nb nb, int sx, int sy, long long max_steps,
         m = nb(cx, cy);
         m = ((m | (m << 8)) >> back) & 0xffu;                // bit j = direction back + j; counter-clockwise from `back`: j = 7, 6, ..., 0
         if (!m) { r.status = kContourBroken; break; }        // (the pixel the walk came from has gone: the plane is damaged)
-        const int d = (back + 31 - __builtin_clz(m)) & 7;
+        const int found = 31 - __builtin_clz(m);
+        const int d = (back + found) & 7;
+        mark(cx, cy, ((8 - back) & 7) > found);              // east = direction back + ((8 - back) & 7): examined iff that offset lies above `found`
         if (d != entered) { emit(r.n_points, cx, cy); ++r.n_points; }
         const int nx = cx + contour_step_x(d), ny = cy + contour_step_y(d);
         sum += (long long)cx * ny - (long long)nx * cy;
@@ -99,6 +113,12 @@ SBB_CW_HD ContourResult contour_walk(Nb nb, int sx, int sy, long long max_steps,
     r.area2 = sum < 0 ? -sum : sum;
     r.steps = steps;
     return r;
+}
+
+template <typename Nb, typename Emit>
+SBB_CW_HD ContourResult contour_walk(Nb nb, int sx, int sy, long long max_steps, Emit emit)
+{
+    return contour_walk_from(nb, sx, sy, 4, max_steps, emit, ContourNoMark{});
 }
 
 }  // namespace sbbseg

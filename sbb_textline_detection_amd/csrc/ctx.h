@@ -1,5 +1,5 @@
 // ctx.h -- private, host only: what the translation units behind the C ABI (api.hip, forward.hip, pages.hip, whole.hip, comm.hip -- these five
-// through exec.h, forward.hip and pages.hip through route.h too -- plan_build.hip, stage_glue.hip, contour_glue.hip, order_glue.hip) share: the error and exception plumbing, the allocation helpers, and the handle
+// through exec.h, forward.hip and pages.hip through route.h too -- plan_build.hip, stage_glue.hip, contour_glue.hip, order_glue.hip, line_extent_glue.hip) share: the error and exception plumbing, the allocation helpers, and the handle
 // (struct sbbseg_ctx) with the plan structs it embeds.  Device and pinned memory belong to the handle's two registries (devmem.h: `mem`, `pinned`);
 // every device pointer below, in the handle and in the plan structs, points at a block one of them owns and sbbseg_destroy frees with the registry.
 #pragma once
@@ -288,6 +288,16 @@ struct sbbseg_ctx {
     sbbseg::DevBuf<void> order_buf;
     sbbseg::DevBuf<int32_t> order_pts;
     long long order_launches = 0;                        // kernels queued by the two calls above (sbbseg_debug_order_launches)
+    // sbbseg_region_line_extents_dev / sbbseg_debug_mask_border_winner_dev (line_extent_glue.hip); the last call's bit maps, records and
+    // winners stay here until the next one (sbbseg_region_line_extents_read)
+    sbbseg::DevBuf<void> extent_tab;                     // regions | point offsets | records | line tables
+    sbbseg::DevBuf<uint32_t> extent_bits, extent_marks;  // filled + threshrot bit maps; mark planes of the scan's global form
+    sbbseg::DevBuf<int32_t> extent_pts, extent_win;      // a ring list the caller passed in; the winners' points
+    int64_t* d_extent_wtab = nullptr;                    // float32 bicubic products * 2^34, built on first use
+    int extent_lds_limit = 60 * 1024;                    // kExtentLdsBytes, or less (sbbseg_debug_set_extent_lds_limit)
+    long long extent_launches = 0;                       // kernels queued by the two calls (sbbseg_debug_extent_launches)
+    std::vector<int32_t> extent_geom;                    // per region of the resident result: w, h, first word of threshrot, winner offset, points
+    int extent_n = -1;                                   // regions of the resident result (-1: none)
     // profiling
     bool profiling = false;
     int conv_variant = 0;
@@ -331,8 +341,11 @@ int ensure(sbbseg_ctx* c, DevBuf<T>& b, size_t bytes)
     return ensure(c->mem, b, bytes);
 }
 
-// ---- what the stage-glue units (stage_glue.hip, contour_glue.hip, order_glue.hip) share
+// ---- what the stage-glue units (stage_glue.hip, contour_glue.hip, order_glue.hip, line_extent_glue.hip) share
 inline size_t align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+// (stage_glue.hip) the float bicubic table [32][4] of cv2.warpAffine, and rotate_image's inverse map for an h x w crop
+void cubic_table(float* tab);
+int line_inverse_map(int h, int w, double slope, double* minv6);
 
 // The host-plane form of an entry point: the caller's H x W plane goes into c->morph_b.p and the `_dev` twin runs on *d_plane (in place
 // where the twin writes there too).  needed == false -- a size query, or no boxes -- needs no handle and uploads nothing.

@@ -605,6 +605,38 @@ hipError_t launch_order_edges(const OrderParams& p, hipStream_t s);             
 hipError_t launch_contour_moments(const OrderParams& p, hipStream_t s);          // 1 launch
 hipError_t launch_order_rank(const OrderParams& p, hipStream_t s);               // 1 launch
 constexpr int kOrderLaunches = 4;         // of a whole reading-order call, whatever n and H are
+// the x extents of the text lines of every region from its filled, rotated contour (line_extent.hip, line_extent.h)
+struct ExtentRegion {
+    long long win_off;        // first point of the region's winner in ExtentParams::winner (second scan pass, extents)
+    long long mark_off;       // global form of the scan: first word of the region's two mark planes in ExtentParams::marks
+    int ox, oy, w, h;         // the box
+    int src_off, dst_off;     // first word of the filled bit map / of threshrot's bit map (box + ring) in ExtentParams::bits
+    int block0;               // first work item (8 rows) of the fill and warp kernels
+    int line_off, vertical;   // first line of the region in the packed line tables; 1 = |slope| > 45
+    int pad;
+    double minv[6];           // rotate_image's inverse map for the box
+    double rot[6];            // cos, -sin, sin, cos, x_d, y_d as sbbseg_line_split_dev takes them
+    double step;              // w / 999.0 (np.linspace's step; divided on the host)
+};
+struct ExtentParams {
+    const ExtentRegion* regions;
+    int n_regions, total_blocks, total_lines, lds_limit;
+    const int32_t* points;    // [points][2] the rings, page coordinates
+    const long long* point_off;       // [n_regions + 1]
+    uint32_t* bits;
+    uint32_t* marks;
+    const int64_t* wtab;      // [kExtentTabEntries] float32 bicubic products * 2^34
+    int32_t* rec;             // [n_regions][kExtentRecInts]
+    int32_t* winner;          // [points][2]; null in the counting pass of the scan
+    const int32_t* info;      // [n_regions][kLineInfoInts] as sbbseg_line_split_dev wrote them
+    const int32_t* lines;     // [total_lines][3] peak, point_up, point_down
+    int32_t* extent;          // [total_lines][2]
+    int32_t* box;             // [total_lines][4][2] rewritten corners
+    int32_t* rot;             // [total_lines][4][2]
+};
+hipError_t launch_extent_masks(const ExtentParams& p, hipStream_t s);                               // 2 launches: fill, warp + threshold
+hipError_t launch_extent_scan(const ExtentParams& p, bool any_lds, bool any_global, hipStream_t s);  // 1 launch per form in use
+hipError_t launch_extent_lines(const ExtentParams& p, hipStream_t s);                                // 1 launch
 
 // channel-tile width the bf16 conv kernel uses for `cout` (weights are padded to it)
 inline int conv_tile_bc(int cout) { return cout >= 128 ? 128 : (cout > 32 ? 64 : 32); }

@@ -5,9 +5,9 @@
 // soft_div / soft_sqrt), so find_peaks' exact comparisons, the ratio tests and the int() truncations decide the same.
 //
 // Scope.  The contour the reference passes in enters only through cv2.pointPolygonTest (x_min / x_max of the horizontal splitter; computed
-// and never used by the vertical one).  It is NOT part of this file: every line gets the reference's own fallback extent x_min_cont = 0,
-// x_max_cont = w (main.py:786-788, the `len(xvinside) == 0` case).  The rotation terms come in per region, so a caller that has the
-// contour can rotate corners with its own x extent.  return_contours_of_image / filter_contours_area_of_image inside the first `try`
+// and never used by the vertical one).  It is not part of this file: every line gets the reference's own fallback extent x_min_cont = 0,
+// x_max_cont = w (main.py:786-788, the `len(xvinside) == 0` case); line_extent.h computes x_min / x_max from the region's filled, rotated
+// contour and rewrites the corners through line_box_with_extent below.  return_contours_of_image / filter_contours_area_of_image inside the first `try`
 // (main.py:608-609) produce values nobody reads; they are treated as dead and non-raising [EXT] unpinned.  point_down_narrow
 // (main.py:759-778) is computed by the reference and read by nothing; it is not computed here.
 //
@@ -226,7 +226,20 @@ SBB_HD int line_rot(double a, double b, double d, int x, int y, bool clamp)
     return (int)v;
 }
 
-// line jj of a region (main.py:744-988): pts = {peak, point_up, point_down}, box = the unrotated corners [4][2] (main.py:817-820), rot =
+// the four rotated corners (main.py:793-815): p1 and p4 clamp x, p1 and p2 clamp y
+SBB_HD void line_rot_corners(const LineGeom& g, const int* px, const int* py, int32_t* rot)
+{
+    rot[0] = line_rot(g.r00, g.r01, g.xd, px[0], py[0], true);      // x_min_rot1
+    rot[1] = line_rot(g.r10, g.r11, g.yd, px[0], py[0], true);      // point_up_rot1
+    rot[2] = line_rot(g.r00, g.r01, g.xd, px[1], py[1], false);
+    rot[3] = line_rot(g.r10, g.r11, g.yd, px[1], py[1], true);      // point_up_rot2
+    rot[4] = line_rot(g.r00, g.r01, g.xd, px[2], py[2], false);
+    rot[5] = line_rot(g.r10, g.r11, g.yd, px[2], py[2], false);
+    rot[6] = line_rot(g.r00, g.r01, g.xd, px[3], py[3], true);      // x_min_rot4
+    rot[7] = line_rot(g.r10, g.r11, g.yd, px[3], py[3], false);
+}
+
+// line jj of a region (main.py:744-988): pts ={peak, point_up, point_down}, box = the unrotated corners [4][2] (main.py:817-820), rot =
 // the rotated corners [4][2]
 SBB_HD void line_box(const LineWork& k, const LineGeom& g, const LineSummary& s, int jj, int32_t* pts, int32_t* box, int32_t* rot)
 {
@@ -281,14 +294,16 @@ SBB_HD void line_box(const LineWork& k, const LineGeom& g, const LineSummary& s,
     } else {
         px[0] = 0; py[0] = up; px[1] = x_max; py[1] = up; px[2] = x_max; py[2] = down; px[3] = 0; py[3] = down;
     }
-    rot[0] = line_rot(g.r00, g.r01, g.xd, px[0], py[0], true);      // x_min_rot1
-    rot[1] = line_rot(g.r10, g.r11, g.yd, px[0], py[0], true);      // point_up_rot1
-    rot[2] = line_rot(g.r00, g.r01, g.xd, px[1], py[1], false);
-    rot[3] = line_rot(g.r10, g.r11, g.yd, px[1], py[1], true);      // point_up_rot2
-    rot[4] = line_rot(g.r00, g.r01, g.xd, px[2], py[2], false);
-    rot[5] = line_rot(g.r10, g.r11, g.yd, px[2], py[2], false);
-    rot[6] = line_rot(g.r00, g.r01, g.xd, px[3], py[3], true);      // x_min_rot4
-    rot[7] = line_rot(g.r10, g.r11, g.yd, px[3], py[3], false);
+    line_rot_corners(g, px, py, rot);
+}
+
+// The corners of a line of the HORIZONTAL splitter for an x extent other than 0 .. x_max_cont (line_extent.h: x_min / x_max from
+// cv2.pointPolygonTest, main.py:780-820): box and rot as line_box writes them, with x_min / x_max in place of 0 / x_max_cont.
+SBB_HD void line_box_with_extent(const LineGeom& g, int x_min, int x_max, int up, int down, int32_t* box, int32_t* rot)
+{
+    box[0] = x_min; box[1] = up; box[2] = x_max; box[3] = up; box[4] = x_max; box[5] = down; box[6] = x_min; box[7] = down;
+    const int px[4] = {x_min, x_max, x_max, x_min}, py[4] = {up, up, down, down};
+    line_rot_corners(g, px, py, rot);
 }
 
 // both smoothings and both scans of one pass, serially; returns through *P, *Q

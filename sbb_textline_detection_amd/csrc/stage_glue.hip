@@ -81,7 +81,9 @@ static void invert_affine(const double* M, double* o)
     for (int i = 0; i < 6; ++i) o[i] = m[i];
 }
 
-static void cubic_table(float* tab)
+extern "C++" {
+namespace sbbseg {
+void cubic_table(float* tab)
 {
 #pragma clang fp contract(off)
     // interpolateCubic of imgwarp.cpp, A = -0.75, float arithmetic
@@ -95,6 +97,8 @@ static void cubic_table(float* tab)
         c[3] = 1.f - c[0] - c[1] - c[2];
     }
 }
+}  // namespace sbbseg
+}  // extern "C++"
 
 int sbbseg_deskew_profiles_dev(sbbseg_ctx* c, const void* d_mask_hw, int H, int W, const double* matrices, const double* angles_deg,
                                int n_angles, int32_t* counts)
@@ -558,13 +562,17 @@ static void line_table(std::vector<int16_t>& itab)
 }
 
 // rotate_image's inverse map for an h x w crop (main.py:159-163: center = (w // 2, h // 2))
-static int line_inverse_map(int h, int w, double slope, double* minv6)
+extern "C++" {
+namespace sbbseg {
+int line_inverse_map(int h, int w, double slope, double* minv6)
 {
     double M[6];
     if (sbbseg_rotation_matrix((double)(w / 2), (double)(h / 2), slope, M)) return 1;
     invert_affine(M, minv6);
     return 0;
 }
+}  // namespace sbbseg
+}  // extern "C++"
 
 int sbbseg_region_line_table(int16_t* itab, int capacity)
 {

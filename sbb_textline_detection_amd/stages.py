@@ -310,17 +310,40 @@ def get_slopes_and_line_masks(textline_mask: np.ndarray, boxes, ctx=None, sigma_
     return slopes, ctx.region_line_masks_dev(d_plane, plane.shape[0], plane.shape[1], boxes, slopes, 2, masks)
 
 
-def get_line_boxes(textline_mask: np.ndarray, boxes, slopes, ctx=None):
+def get_line_extents(boxes, slopes, records, contours, ctx=None):
+    """The contour half of ``textline_contours_postprocessing`` (main.py:1492-1511) and its consumer, ``cv2.pointPolygonTest`` inside
+    ``seperate_lines``: per box its ring (``get_text_region_contours``'s, page coordinates) is filled, rotated by the box's slope, cast and
+    thresholded as the reference does it, the border with the most points is found among ALL borders of that image, and every line of
+    the horizontal splitter is cut to it: x_min / x_max of the 1000 samples of the peak row that lie inside.  ``records``: what
+    ``get_line_boxes`` returned for these boxes.  Returns the records with ``boxes`` / ``boxes_rot`` rewritten (branches 0, 3, 4; branch 2
+    and the vertical splitter keep 0 .. w), ``extent`` int32 [lines, 2] and ``contour`` (the winner's record); a region whose rotated
+    contour has no border at all has no lines, as the reference's bare except leaves it.  All boxes share the launches on the device with
+    a ``ctx`` (``sbbseg_region_line_extents_dev``); without one the library's serial host twin runs box by box: the same bits."""
+    from . import _capi
+    boxes = [[int(v) for v in b] for b in boxes]
+    if not (len(boxes) == len(slopes) == len(records) == len(contours)):
+        raise ValueError("one slope, one record and one ring per box: %d boxes, %d slopes, %d records, %d rings"
+                         % (len(boxes), len(slopes), len(records), len(contours)))
+    if not boxes:
+        return []
+    if ctx is not None:
+        return ctx.region_line_extents_dev(boxes, [float(s) for s in slopes], records, contours)
+    return [_capi.host_region_line_extents(c, b, float(s), r) for c, b, s, r in zip(contours, boxes, slopes, records)]
+
+
+def get_line_boxes(textline_mask: np.ndarray, boxes, slopes, ctx=None, contours=None):
     """What ``textline_contours_postprocessing`` (main.py:1472-1524) gets from ``seperate_lines`` / ``seperate_lines_vertical`` for all
     boxes of a page: ``get_line_masks``' steps and then the splitter of every box on its own projection, the projections staying on the
     device (``sbbseg_region_line_boxes_dev``).  One record per box (``_capi.line_split_host``): status, sigma, raised, branch, peaks,
     point_up, point_down, boxes, boxes_rot; ``boxes_rot`` is the reference's ``textline_boxes_rot``, [] where it returns [].
-    CAVEAT: the contour half (main.py:1492-1511) is not built, so every line has the reference's fallback x extent 0 .. w
-    (main.py:786-788), not the extent of the region's contour at the peak row; nothing approximates the contour."""
+    ``contours``: one ring per box (``get_text_region_contours``) -- the lines are then cut to the region's filled, rotated contour
+    (``get_line_extents``), which is what the reference returns.  Without it (the default) every line has the reference's FALLBACK x
+    extent 0 .. w (main.py:786-788)."""
     plane, boxes = _line_masks_args(textline_mask, boxes, slopes, ctx, "get_line_boxes")
     if not boxes:
         return []
-    return ctx.region_line_boxes_dev(ctx.stage(plane), plane.shape[0], plane.shape[1], boxes, [float(s) for s in slopes], 2)
+    records = ctx.region_line_boxes_dev(ctx.stage(plane), plane.shape[0], plane.shape[1], boxes, [float(s) for s in slopes], 2)
+    return records if contours is None else get_line_extents(boxes, slopes, records, contours, ctx)
 
 
 def get_slopes_and_line_boxes(textline_mask: np.ndarray, boxes, ctx=None, sigma_des: float = 2):
@@ -770,11 +793,21 @@ class InferenceStages:
         textline plane: neither a plane nor a polygon crosses the bus for it.  Foreign model objects take the loop with the host twin."""
         return self._run_pages_lines(images, masks, True, True)
 
-    def _run_pages_lines(self, images, masks: bool, contours: bool, order: bool = False):
+    def run_pages_with_text_lines(self, images, masks: bool = False):
+        """``run_pages_with_reading_order`` plus, per page, what ``do_work_of_slopes`` collects as ``all_found_texline_polygons``
+        (main.py:1750-1756): per text region the list of its lines' 4 x 2 polygons (``textline_boxes_rot``, int32), [] for a region the
+        reference leaves without lines -- a 12-tuple per page.  The lines of all pages' regions are cut to their regions' contours in ONE
+        pooled call per page group (``region_line_extents_dev``), after the pooled line-box call; the line records in the tuple (index 7)
+        are the cut ones.  Needs the library's own model objects: there is no loop for foreign ones."""
+        return self._run_pages_lines(images, masks, True, True, True)
+
+    def _run_pages_lines(self, images, masks: bool, contours: bool, order: bool = False, text_lines: bool = False):
         images = list(images)
         opened = [start_new_session_and_model(d, **self.kw) for d in (self.model_page_dir, self.model_region_dir, self.model_textline_dir)]
         try:
             if not all(isinstance(m, SegModel) for m, _ in opened):
+                if text_lines:
+                    raise RuntimeError("run_pages_with_text_lines needs the library's own models: there is no CPU fallback")
                 out = []
                 for img in images:
                     page = self.run_with_line_boxes(img, masks=masks)
@@ -814,9 +847,17 @@ class InferenceStages:
                 gs = c_text.planes_deskew_slopes_dev(planes, gb, 2)
                 gm = c_text.planes_line_masks_dev(planes, gb, gs, 2, masks)
                 gl = c_text.planes_line_boxes_dev(planes, gb, gs, 2)
+                if text_lines:                                   # the step reads no label plane: the boxes of the whole group share one call
+                    cut = c_text.region_line_extents_dev([b for pb in gb for b in pb], [s for ps in gs for s in ps], [r for pr in gl for r in pr],
+                                                         [ring for k in group for ring in rings[k]])
+                    at = 0
+                    for q in range(len(group)):
+                        gl[q], at = cut[at:at + len(gb[q])], at + len(gb[q])
                 for q, k in enumerate(group):
                     slopes[k], line_masks[k], line_boxes[k] = gs[q], gm[q], gl[q]
-            return [runs[k] + (boxes[k], slopes[k], line_masks[k], line_boxes[k]) + ((rings[k],) if contours else ()) + (orders[k] if order else ()) for k in range(n)]
+            polygons = [[[p for p in rec["boxes_rot"]] if rec["status"] == _capi.LINES_OK else [] for rec in line_boxes[k]] for k in range(n)]
+            return [runs[k] + (boxes[k], slopes[k], line_masks[k], line_boxes[k]) + ((rings[k],) if contours else ()) + (orders[k] if order else ())
+                    + ((polygons[k],) if text_lines else ()) for k in range(n)]
         finally:
             for _, session in opened:
                 session.close()
