@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ_DIR = os.path.join(HERE, "_obj")          # package-local (git- and gpurun-ignored): an installed copy never writes outside itself
 LIB = os.path.join(HERE, "libsbbseg.so")
 SOURCES = ["kernels.hip", "dec_tail.hip", "stem.hip", "direct64.hip", "bottleneck.hip", "pixel_ops.hip", "page_glue.hip", "block_x3.hip", "stem_pool_x3.hip", "dec_halo_x3.hip", "dec_halo_f16.hip", "expand_reduce_x3.hip", "conv3_expand_reduce.hip", "region.hip", "region_deskew.hip", "profile_stats.hip", "region_lines.hip", "line_split.hip", "contours.hip", "order.hip", "line_extent.hip", "api.hip", "forward.hip", "pages.hip", "whole.hip", "comm.hip", "plan_build.hip", "stage_glue.hip", "contour_glue.hip", "order_glue.hip", "line_extent_glue.hip", "loader.cpp"]
-HEADERS = [os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "device_prims.h"), os.path.join(CSRC, "pair_steps.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "devmem.h"), os.path.join(CSRC, "exec.h"), os.path.join(CSRC, "route.h"), os.path.join(CSRC, "wpack.h"), os.path.join(CSRC, "region.h"), os.path.join(CSRC, "profile_stat.h"), os.path.join(CSRC, "line_mask.h"), os.path.join(CSRC, "line_split.h"), os.path.join(CSRC, "contour_walk.h"), os.path.join(CSRC, "contour_host.h"), os.path.join(CSRC, "order.h"), os.path.join(CSRC, "line_extent.h"), os.path.join(HERE, "..", "include", "sbbseg.h")]
+HEADERS = [os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "device_prims.h"), os.path.join(CSRC, "pair_steps.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "devmem.h"), os.path.join(CSRC, "exec.h"), os.path.join(CSRC, "route.h"), os.path.join(CSRC, "conv_choice.h"), os.path.join(CSRC, "wpack.h"), os.path.join(CSRC, "region.h"), os.path.join(CSRC, "profile_stat.h"), os.path.join(CSRC, "line_mask.h"), os.path.join(CSRC, "line_split.h"), os.path.join(CSRC, "contour_walk.h"), os.path.join(CSRC, "contour_host.h"), os.path.join(CSRC, "order.h"), os.path.join(CSRC, "line_extent.h"), os.path.join(HERE, "..", "include", "sbbseg.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 
 

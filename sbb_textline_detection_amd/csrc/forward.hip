@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "conv_choice.h"
 #include "exec.h"
 #include "route.h"
 
@@ -138,63 +139,45 @@ int launch_dec_halo(sbbseg_ctx* c, Op& op, int n)
     return 0;
 }
 
-// conv_igemm_mfma.  What depends on the call and not on the plan is decided here: the tile walk, whether an owned-region level gets its
-// pixel map, split-K.
+// conv_igemm_mfma.  The form of the launch -- tile, gather, tile walk, owned-region table, split-K -- is choose_conv's (conv_choice.h); here
+// ConvParams is filled from the op and that form.
 int launch_generic_conv(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* d_probs)
 {
     const ConvOp& co = op.conv;
+    const int region_entries = conv_region_entries(c, op);
+    const ConvForm form = choose_conv(c, co, n, region_entries, conv_env());
     ConvParams p;
     memset(&p, 0, sizeof(p));
     p.n_src = co.d.n_src;
-    // (short-K layers keep the plain gather: the per-tile mask set-up costs them 1-10 %; from ~9 K-steps on the fast
-    // gather wins 2-10 %, profiles/r02_experiments.md)
-    bool fg = co.d_fgstep_cls[0] && !c->plain_gather;
     for (int s = 0; s < co.d.n_src; ++s) {
         const Tensor& t = c->tensors[co.d.src[s].tensor];
         SrcDesc& sd = p.src[s];
         sd.base = t.buf;
         sd.PH = t.H; sd.PW = t.W;
-        sd.pix_bytes = t.C * c->elem * c->planes;
+        sd.pix_bytes = conv_src_pix_bytes(c, t);
         sd.lo_off = c->planes == 2 ? split_group(t.C) * c->elem : 64;       // split mode: hi -> lo inside a channel group
         sd.shift = co.d.src[s].up_shift;
         sd.lim_y = t.H << sd.shift; sd.lim_x = t.W << sd.shift;
         sd.ksteps = co.ksteps[s];
         sd.sy_shift = co.d.src[s].stride_y == 2; sd.sx_shift = co.d.src[s].stride_x == 2;
-        const size_t bytes = kZeroHeaderBytes + t.elems_per_patch * (size_t)n * c->elem * c->planes;
-        sd.bytes = (uint32_t)bytes;
-        // fast gather: bit 31 of a lane offset marks an out-of-bounds tap, so every real offset must stay below 2^31
+        sd.bytes = (uint32_t)conv_src_bytes(c, t, n);
         sd.tap_lo_y = co.tap_lo[s][0]; sd.tap_lo_x = co.tap_lo[s][1];
-        if (bytes + (size_t)kFgBiasPixels(t.W) * sd.pix_bytes >= ((size_t)1 << 31)) fg = false;
     }
-    p.fast_gather = fg ? (co.fg_pointwise ? 2 : 1) : 0;
+    p.fast_gather = form.fast_gather;
     p.ktab = co.d_ktab; p.kstep = co.d_kstep; p.half_stages = (c->conv_variant & 16) ? 1 : 0;
     p.variant = c->conv_variant & 3; p.persist_blocks = (c->conv_variant & 4) ? 0 : c->num_cus;
     p.M = n * co.Ho * co.Wo;
-    p.variant_flags = ((c->conv_variant & 64) ? 1 : 0) | ((c->conv_variant & 128) ? 2 : 0) | (c->ph8 ? 4 : 0);
+    p.variant_flags = form.variant_flags;
 #ifdef SBBSEG_PROBES
     { static const int probe_local = getenv("SBBSEG_CONV_PROBE_LOCAL") ? atoi(getenv("SBBSEG_CONV_PROBE_LOCAL")) : 0; if (probe_local) p.variant_flags |= 32; }
     { static const int probe_whot = getenv("SBBSEG_CONV_PROBE_WHOT") ? atoi(getenv("SBBSEG_CONV_PROBE_WHOT")) : 0; if (probe_whot) p.variant_flags |= 64; }
 #endif
-    // XCD-grouped walk for single-class layers: measured neutral-to-slower (it removes the n_ct-fold
-    // re-fetch of the pixel operand, but those layers are not bound by fetch bytes) -> opt-in, bit 5
-    // (split mode: on by default -- twice the pixel bytes; +0.7 % page throughput in two runs, profiles/r03_experiments.md)
-    // (SBBSEG_PSHARE_MAX_MB: weight-matrix size up to which the pixel-sharing walk is taken; round 6 experiment -- the K >= 768 merge / reduce
-    //  convs of stages 4 / 5 and dec0 re-fetch their pixel operand once per channel tile under map 0: PMC FETCH = n_ct x the input)
-    static const size_t pshare_max = (size_t)(getenv("SBBSEG_PSHARE_MAX_MB") ? atoi(getenv("SBBSEG_PSHARE_MAX_MB")) : 2) << 20;
-    p.tile_map = (((c->conv_variant & 32) || c->precision == kF16X3) && !(c->conv_variant & 8) && (c->conv_variant & 4) == 0 && co.d.cout > conv_tile_bc(co.d.cout) && p.M >= 256 * 128 &&
-                  (size_t)co.cout_pad * co.Ktot * c->elem <= pshare_max) ? 1 : 0;
-    if (p.tile_map == 1 && co.n_cls == 1 && co.Ktot <= c->contig_max_k) p.tile_map = 2;
+    p.tile_map = form.tile_map; p.cls_minor = form.cls_minor;
     p.w = co.d_w; p.Ktot = co.Ktot; p.total_ksteps = co.total_ksteps;
     p.Ho = co.Ho; p.Wo = co.Wo;
     p.TH = co.TH; p.TW = co.TW; p.osy = co.d.out_stride_y; p.osx = co.d.out_stride_x;
     p.ooy = co.d.out_off_y; p.oox = co.d.out_off_x;
     p.n_cls = co.n_cls;
-    p.cls_minor = 0;
-    if (co.n_cls > 1 && (co.n_cls & (co.n_cls - 1)) == 0 && !(c->conv_variant & 8) && !(c->conv_variant & 4) &&
-        (size_t)co.cout_pad * co.Ktot * c->elem <= ((size_t)16 << 20)) {     // (dec1/dec2 too: fetch -30 / -53 %, time unchanged)
-        p.cls_minor = 1;      // small weights: let the classes share their source pixels in one L2
-        p.tile_map = c->ranged_walk ? 3 : 1;
-    }
     for (int q = 0; q < 4; ++q) {
         p.w_cls[q] = co.d_w_cls[q]; p.kstep_cls[q] = co.d_kstep_cls[q]; p.ktab_cls[q] = co.d_ktab_cls[q]; p.fgstep_cls[q] = co.d_fgstep_cls[q];
         p.ooy_cls[q] = co.ooy_cls[q]; p.oox_cls[q] = co.oox_cls[q]; p.wmul_cls[q] = co.wmul_cls[q];
@@ -206,36 +189,19 @@ int launch_generic_conv(sbbseg_ctx* c, Op& op, int n, uint8_t* d_labels, float* 
     p.residual = co.d.residual_tensor >= 0 ? c->tensors[co.d.residual_tensor].data() : nullptr;
     p.raw_out = co.d.raw_out_tensor >= 0 ? c->tensors[co.d.raw_out_tensor].data() : nullptr;
     p.raw_scale = co.d_rscale; p.raw_shift = co.d_rshift; p.relu = co.d.relu;
-    // owned-region launch of a decoder level (region.h): the chunk's table replaces the walk over the whole output grid
-    const int rlv = c->rr.on ? op.region_level : -1;
-    if (rlv >= 0 && c->rr.kind[rlv] == 1) {
-        // the pixel table is read by the fast-gather form of conv_igemm_mfma, 2-stage whole-K-step tiles only (what every decoder conv
-        // runs by default); under an A/B knob that takes the level elsewhere it is launched whole -- a superset, same results
-        if (p.fast_gather && !p.half_stages && p.variant != 2 && !(p.variant_flags & 4)) { p.rmap = c->rr.tab[rlv]; p.M = c->rr.total[rlv]; }
-        else c->last_exec_frac = 1.0;
-    }
-    // One patch through a long-K conv = 2-32 tiles of 100-400 K-steps at ~1 us a step on as many CUs: the whole-image branch
-    // (extract_page's border model, 1 forward per page) splits the K range over the idle CUs -- up to 16 blocks per tile, each
-    // at least 4 K-steps, fp32 partial sums added in split order by splitk_finish.  Only there: a split launch differs from
-    // the unsplit one in the last bits, and seam 2 / the patch paths promise batch-size-independent results.
-    int ks = 0;
-    if (c->ksplit_now && n == 1 && c->precision != kF32 && p.fast_gather && conv_tile_bc(p.cout) == 128 && !p.raw_out && !p.head_classes &&
-        p.out && p.cout % 8 == 0 &&
-        ((p.n_cls == 1 && p.osy == 1 && p.osx == 1 && p.ooy == 0 && p.oox == 0 && p.TH == p.Ho && p.TW == p.Wo) ||
-         (p.n_cls == 4 && p.osy == 2 && p.osx == 2 && p.TH == 2 * p.Ho && p.TW == 2 * p.Wo))) {
-        const long tiles = (long)p.n_cls * ((p.M + 127) / 128) * ((p.cout + 127) / 128);
-        while (ks < 4 && (tiles << (ks + 1)) <= 512 && p.total_ksteps % (2 << ks) == 0 && (p.total_ksteps >> (ks + 1)) >= 4) ++ks;
-    }
-    if (ks > 0) {
+    // owned-region launch of a decoder level (region.h): the chunk's table replaces the walk over the whole output grid; a level whose table
+    // is withheld runs whole and counts as whole
+    if (form.table) { p.rmap = c->rr.tab[op.region_level]; p.M = region_entries; }
+    else if (region_entries >= 0) c->last_exec_frac = 1.0;
+    if (form.ks_shift > 0) {
         const size_t split_elems = (size_t)n * p.TH * p.TW * p.cout;
-        if (ensure(c, c->ks_ws, (split_elems << ks) * sizeof(float))) return 1;
-        p.ks_shift = ks; p.ks_ws = c->ks_ws.p; p.ks_split_elems = (long)split_elems; p.tile_map = 0; p.cls_minor = 0;
-        HIPCHK(launch_conv(p, c->precision, c->stream, &op.last));
-        HIPCHK(launch_splitk_finish(c->ks_ws.p, 1 << ks, (long)split_elems, (long)n * p.TH * p.TW, p.cout, p.scale, p.shift, p.residual,
-                                    p.relu, p.out, c->precision, c->stream));
-    } else {
-        HIPCHK(launch_conv(p, c->precision, c->stream, &op.last));
+        if (ensure(c, c->ks_ws, (split_elems << form.ks_shift) * sizeof(float))) return 1;
+        p.ks_shift = form.ks_shift; p.ks_ws = c->ks_ws.p; p.ks_split_elems = (long)split_elems;
     }
+    HIPCHK(launch_conv(p, form, c->precision, c->stream, &op.last));
+    if (form.ks_shift > 0)
+        HIPCHK(launch_splitk_finish(c->ks_ws.p, 1 << form.ks_shift, p.ks_split_elems, (long)n * p.TH * p.TW, p.cout, p.scale, p.shift, p.residual,
+                                    p.relu, p.out, c->precision, c->stream));
     return 0;
 }
 

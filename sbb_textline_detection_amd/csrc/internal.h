@@ -357,9 +357,47 @@ inline hipError_t dynamic_lds_once(const void* kernel, int bytes, bool (&done)[6
     return e;
 }
 
+// The tile forms conv_igemm_mfma is instantiated in: one value per (BP, BC, WP, WC, NS, GS, PH8).  conv_choice.h picks one per launch,
+// launch_conv (kernels.hip) maps it to the instantiation; the split mode has the five forms marked x3.
+enum ConvTileForm {
+    kTile128x128 = 0,       // 4 waves, 2 blocks per CU: the default of 128-channel tiles; the split-K launches (x3)
+    kTile256x256,           // 8 waves, wave tile 128 px x 64 ch (x3)
+    kTile256x256Ph8,        // ... on the staggered 8-phase schedule (conv variant bit 16)
+    kTile512x128,           // 8 waves (x3)
+    kTile512x64,            // 8 waves, forced by variant 3 only
+    kTile256x128S3,         // variant 2: the 8-wave 3-stage tiles
+    kTile256x64S3,
+    kTile256x32S3,
+    kTile256x64,            // 4 waves: the default of 64-channel tiles (x3)
+    kTile256x32,            // ... of 32-channel tiles (x3)
+    kTile256x256Half,       // conv variant bit 4: half-K-step stages in a 4-deep ring
+    kTile128x128Half,
+    kTile256x64Half,
+    kConvTiles
+};
+struct ConvTileDims { int bp, bc, wp, wc, ns, gs; bool ph8; };
+constexpr ConvTileDims kConvTileDims[kConvTiles] = {
+    {128, 128, 2, 2, 2, 8, false}, {256, 256, 2, 4, 2, 8, false}, {256, 256, 2, 4, 2, 8, true}, {512, 128, 4, 2, 2, 8, false},
+    {512, 64, 8, 1, 2, 8, false},  {256, 128, 4, 2, 3, 8, false}, {256, 64, 8, 1, 3, 8, false}, {256, 32, 8, 1, 3, 8, false},
+    {256, 64, 4, 1, 2, 8, false},  {256, 32, 4, 1, 2, 8, false},  {256, 256, 2, 4, 4, 4, false}, {128, 128, 2, 2, 4, 4, false},
+    {256, 64, 4, 1, 4, 4, false}};
+// a fast-gather instantiation exists only for whole-K-step, 2-stage, non-8-phase tiles (the others keep the plain gather)
+constexpr bool conv_tile_has_fg(const ConvTileDims& d) { return d.ns == 2 && d.gs == 8 && !d.ph8; }
+
+// The form of one conv_igemm_mfma launch, chosen by conv_choice.h's choose_conv -- here, because kernels.hip reads it without ctx.h.
+struct ConvForm {
+    int tile;             // ConvTileForm (split-K: kTile128x128)
+    int fg;               // 1: the fast-gather instantiation runs
+    int fast_gather;      // ConvParams::fast_gather: 0 = plain gather, 1 = masked fast gather, 2 = pointwise (no masks)
+    int ks_shift;         // split-K: 2^ks_shift blocks per tile; 0 = off
+    int tile_map, cls_minor;      // ConvParams
+    int table;            // 1: the owned-region level's pixel table is handed over (ConvParams::rmap, M = its entries)
+    int variant_flags;    // ConvParams::variant_flags, but for the probe bits
+};
+
 // launchers, by the unit that defines them ---------------------------------------------------
 // kernels.hip
-hipError_t launch_conv(const ConvParams& p, int precision, hipStream_t s, LaunchRec* rec = nullptr);
+hipError_t launch_conv(const ConvParams& p, const ConvForm& form, int precision, hipStream_t s, LaunchRec* rec = nullptr);
 hipError_t launch_splitk_finish(const float* ws, int splits, long split_elems, long pixels, int cout, const float* scale, const float* shift,
                                 const void* residual, int relu, void* out, int precision, hipStream_t s);
 // dec_tail.hip, stem.hip, direct64.hip, bottleneck.hip

@@ -1198,106 +1198,64 @@ static hipError_t launch_conv_impl(const ConvParams& p, hipStream_t s, LaunchRec
     return hipGetLastError();
 }
 
-template <int BP, int BC, int WP, int WC, int NS, bool F16, int GS = 8, bool PH8 = false, bool X3 = false>
-static hipError_t launch_conv_t(const ConvParams& p, hipStream_t s, LaunchRec* rec)
+// One tile form in one precision mode: its fast-gather instantiation where the form has one and the launch takes it, else the plain gather's.
+template <int BP, int BC, int WP, int WC, int NS, int GS, bool PH8, bool F16, bool X3>
+static hipError_t launch_conv_tile(const ConvParams& p, const ConvForm& f, hipStream_t s, LaunchRec* rec)
 {
-    if constexpr (!PH8 && GS == 8 && NS == 2) {        // (the opt-in half-stage, 3-stage and 8-phase forms keep the plain gather)
-        if (p.fast_gather) return launch_conv_impl<BP, BC, WP, WC, NS, F16, GS, PH8, X3, true>(p, s, rec);
+    if constexpr (conv_tile_has_fg({BP, BC, WP, WC, NS, GS, PH8})) {
+        if (f.fg) return launch_conv_impl<BP, BC, WP, WC, NS, F16, GS, PH8, X3, true>(p, s, rec);
     }
-    if (p.rmap) return hipErrorInvalidValue;           // an owned-region table needs the fast-gather form (launch_op checks before it sets one)
     return launch_conv_impl<BP, BC, WP, WC, NS, F16, GS, PH8, X3, false>(p, s, rec);
 }
 
-// Tile choice.  Measured on MI355X (profiles/r01_conv_variants.md): with two 4-wave blocks per CU the
-// 2-stage tiles already hide the staging latency (dec1-3 at 925-980 TFLOP/s); the 8-wave / 3-stage /
-// counted-vmcnt tiles (1 block per CU) are 5-25 % slower on every layer, so they are opt-in only.
-// the 8-phase schedule of the 256x256 tile: regular K-steps only (>= 64-channel sources), at least 2 K-steps
-static bool ph8_ok(const ConvParams& p)
-{
-    if (!(p.variant_flags & 4) || p.total_ksteps < 2 || p.half_stages || p.rmap) return false;      // opt-in: conv variant bit 16; never with an owned-region table
-    for (int i = 0; i < p.n_src; ++i)
-        if (p.src[i].pix_bytes < 128) return false;
-    return true;
-}
+// ConvTileForm -> template arguments, checked against kConvTileDims (internal.h) at compile time
+#define SBBSEG_CONV_TILE(T, BP, BC, WP, WC, NS, GS, PH8)                                                                                         \
+    case T: {                                                                                                                                    \
+        constexpr ConvTileDims d = kConvTileDims[T];                                                                                             \
+        static_assert(d.bp == BP && d.bc == BC && d.wp == WP && d.wc == WC && d.ns == NS && d.gs == GS && d.ph8 == PH8, #T);                     \
+        return launch_conv_tile<BP, BC, WP, WC, NS, GS, PH8, F16, X3>(p, f, s, rec);                                                             \
+    }
 
+// the plain 16-bit modes: all 13 tile forms (here and below in the order the ladders they replace named them: the instantiations keep their
+// order in the code object)
 template <bool F16>
-static hipError_t launch_conv_16(const ConvParams& p, hipStream_t s, LaunchRec* rec)
+static hipError_t launch_conv_form_16(const ConvParams& p, const ConvForm& f, hipStream_t s, LaunchRec* rec)
 {
-    const int bc = conv_tile_bc(p.cout);
-    const int variant = p.variant;
-    const bool big = variant == 2;
-    if (p.ks_shift > 0) {                                       // split-K (see launch_conv_x3)
-        if (bc != 128 || !p.fast_gather || p.tile_map != 0 || p.cls_minor || (p.total_ksteps & ((1 << p.ks_shift) - 1))) return hipErrorInvalidValue;
-        return launch_conv_impl<128, 128, 2, 2, 2, F16, 8, false, false, true, true>(p, s, rec);
+    constexpr bool X3 = false;
+    if (p.ks_shift > 0) return launch_conv_impl<128, 128, 2, 2, 2, F16, 8, false, X3, true, true>(p, s, rec);
+    switch (f.tile) {
+    SBBSEG_CONV_TILE(kTile256x256Half, 256, 256, 2, 4, 4, 4, false)
+    SBBSEG_CONV_TILE(kTile128x128Half, 128, 128, 2, 2, 4, 4, false)
+    SBBSEG_CONV_TILE(kTile256x64Half, 256, 64, 4, 1, 4, 4, false)
+    SBBSEG_CONV_TILE(kTile256x256Ph8, 256, 256, 2, 4, 2, 8, true)
+    SBBSEG_CONV_TILE(kTile256x256, 256, 256, 2, 4, 2, 8, false)
+    SBBSEG_CONV_TILE(kTile512x128, 512, 128, 4, 2, 2, 8, false)
+    SBBSEG_CONV_TILE(kTile512x64, 512, 64, 8, 1, 2, 8, false)
+    SBBSEG_CONV_TILE(kTile256x128S3, 256, 128, 4, 2, 3, 8, false)
+    SBBSEG_CONV_TILE(kTile128x128, 128, 128, 2, 2, 2, 8, false)
+    SBBSEG_CONV_TILE(kTile256x64S3, 256, 64, 8, 1, 3, 8, false)
+    SBBSEG_CONV_TILE(kTile256x64, 256, 64, 4, 1, 2, 8, false)
+    SBBSEG_CONV_TILE(kTile256x32S3, 256, 32, 8, 1, 3, 8, false)
+    SBBSEG_CONV_TILE(kTile256x32, 256, 32, 4, 1, 2, 8, false)
     }
-    if (p.half_stages) {   // A/B: half-K-step stages, 4-deep ring (3 stages in flight across the barriers)
-        const long t256 = (long)p.n_cls * ((p.M + 255) / 256) * (p.cout / 256);
-        if (bc == 128 && !p.residual && p.cout % 256 == 0 && p.Ktot >= 512 && t256 >= 200) return launch_conv_t<256, 256, 2, 4, 4, F16, 4>(p, s, rec);
-        if (bc == 128) return launch_conv_t<128, 128, 2, 2, 4, F16, 4>(p, s, rec);
-        if (bc == 64) return launch_conv_t<256, 64, 4, 1, 4, F16, 4>(p, s, rec);
-    }
-    if (variant == 3) {   // force: 8 waves, wave tile 128 px x 64 ch (64x64 for cout 64), 2 LDS stages, 1 block per CU
-        if (bc == 128 && p.cout % 256 == 0) return ph8_ok(p) ? launch_conv_t<256, 256, 2, 4, 2, F16, 8, true>(p, s, rec) : launch_conv_t<256, 256, 2, 4, 2, F16>(p, s, rec);
-        if (bc == 128) return launch_conv_t<512, 128, 4, 2, 2, F16>(p, s, rec);
-        if (bc == 64) return launch_conv_t<512, 64, 8, 1, 2, F16>(p, s, rec);
-    }
-    {   // round 5 (plain modes; profiles/r05_experiments.md section 13): residual layers on the 256 x 256 tile from this K on (0 = never) --
-        // the stage-4 / stage-5 expands the fused pair kernel does not take, -3..-4 % each (the K = 128 one of stage 3 loses 1.5 %: left out)
-        static const int kres256 = getenv("SBBSEG_F16_RES256_MINK") ? atoi(getenv("SBBSEG_F16_RES256_MINK")) : 256;
-        if (variant == 0 && bc == 128 && p.residual && kres256 > 0 && p.cout % 256 == 0 && p.Ktot >= kres256 &&
-            (long)p.n_cls * ((p.M + 255) / 256) * (p.cout / 256) >= 200)
-            return launch_conv_t<256, 256, 2, 4, 2, F16>(p, s, rec);
-    }
-    // (384 since round 5: the stage-3 projection merge, K = 384 channels, on the 256 x 256 tile: 0.40 -> 0.31 ms per 160 patches in fp16)
-    static const int k256_16 = getenv("SBBSEG_F16_T256_MINK") ? atoi(getenv("SBBSEG_F16_T256_MINK")) : 384;
-    if (variant == 0 && bc == 128 && !p.residual) {
-        // auto (measured per layer, profiles/r01_conv_variants.md): the 8-wave tiles with 128x64 wave
-        // tiles (LDS bytes per MFMA x0.75, L2 bytes per MFMA x0.5) win on long-K layers that still
-        // give every CU a block; short-K / residual (HBM-bound) layers and small grids stay on 128x128
-        const long t256 = (long)p.n_cls * ((p.M + 255) / 256) * (p.cout / 256);
-        const long t512 = (long)p.n_cls * ((p.M + 511) / 512) * ((p.cout + 127) / 128);
-        if (p.cout % 256 == 0 && p.Ktot >= k256_16 && t256 >= 200) return ph8_ok(p) ? launch_conv_t<256, 256, 2, 4, 2, F16, 8, true>(p, s, rec) : launch_conv_t<256, 256, 2, 4, 2, F16>(p, s, rec);
-        if (p.Ktot >= 1024 && t512 >= 200) return launch_conv_t<512, 128, 4, 2, 2, F16>(p, s, rec);
-    }
-    if (bc == 128) return big ? launch_conv_t<256, 128, 4, 2, 3, F16>(p, s, rec) : launch_conv_t<128, 128, 2, 2, 2, F16>(p, s, rec);
-    if (bc == 64) return big ? launch_conv_t<256, 64, 8, 1, 3, F16>(p, s, rec) : launch_conv_t<256, 64, 4, 1, 2, F16>(p, s, rec);
-    return big ? launch_conv_t<256, 32, 8, 1, 3, F16>(p, s, rec) : launch_conv_t<256, 32, 4, 1, 2, F16>(p, s, rec);
+    return hipErrorInvalidValue;
 }
 
-// split mode: the 4-wave tiles at 2 blocks per CU (3 MFMAs per product for the same LDS bytes: the matrix pipe, not the
-// staging path, is what fills first here)
-static hipError_t launch_conv_x3(const ConvParams& p, hipStream_t s, LaunchRec* rec)
+// the split mode: the five forms choose_conv takes there
+static hipError_t launch_conv_form_x3(const ConvParams& p, const ConvForm& f, hipStream_t s, LaunchRec* rec)
 {
-    const int bc = conv_tile_bc(p.cout);
-    if (p.ks_shift > 0) {                                       // split-K (the caller has checked: 128-channel tiles, fast gather, whole K ranges)
-        if (bc != 128 || !p.fast_gather || p.tile_map != 0 || p.cls_minor || (p.total_ksteps & ((1 << p.ks_shift) - 1))) return hipErrorInvalidValue;
-        return launch_conv_impl<128, 128, 2, 2, 2, true, 8, false, true, true, true>(p, s, rec);
+    constexpr bool F16 = true, X3 = true;
+    if (p.ks_shift > 0) return launch_conv_impl<128, 128, 2, 2, 2, F16, 8, false, X3, true, true>(p, s, rec);
+    switch (f.tile) {
+    SBBSEG_CONV_TILE(kTile256x256, 256, 256, 2, 4, 2, 8, false)
+    SBBSEG_CONV_TILE(kTile512x128, 512, 128, 4, 2, 2, 8, false)
+    SBBSEG_CONV_TILE(kTile128x128, 128, 128, 2, 2, 2, 8, false)
+    SBBSEG_CONV_TILE(kTile256x64, 256, 64, 4, 1, 2, 8, false)
+    SBBSEG_CONV_TILE(kTile256x32, 256, 32, 4, 1, 2, 8, false)
     }
-    // Residual layers (the expand convs that `expand_reduce` does not take: the last block of stages 3 / 4, stage 5) on the 256 x 256 tile when
-    // the launch still gives every CU a block: the pixel operand is re-read by half as many channel tiles; the residual is then read in the
-    // epilogue (add_split8) instead of being prefetched -- same arithmetic.  Round 5: 0.61 -> 0.56, 0.39 -> 0.35, 0.27 -> 0.25 ms per 160
-    // patches (profiles/r05_experiments.md section 12).  SBBSEG_X3_RES256_MINK=0 switches it off.
-    static const int kres256 = getenv("SBBSEG_X3_RES256_MINK") ? atoi(getenv("SBBSEG_X3_RES256_MINK")) : 256;
-    if (p.variant == 0 && bc == 128 && p.residual && kres256 > 0 && p.cout % 256 == 0 && p.Ktot >= kres256 &&
-        (long)p.n_cls * ((p.M + 255) / 256) * (p.cout / 256) >= 200)
-        return launch_conv_t<256, 256, 2, 4, 2, true, 8, false, true>(p, s, rec);
-    if (p.variant == 0 && bc == 128 && !p.residual) {          // the long-K decoder launches: same 8-wave tiles as the plain modes
-        const long t256 = (long)p.n_cls * ((p.M + 255) / 256) * (p.cout / 256);
-        const long t512 = (long)p.n_cls * ((p.M + 511) / 512) * ((p.cout + 127) / 128);
-        static const int k512 = getenv("SBBSEG_X3_T512_MINK") ? atoi(getenv("SBBSEG_X3_T512_MINK")) : 2048;      // A/B knobs
-        // (768 since round 5: the projection-shortcut merge at the head of stage 3 -- 128 + 256 -> 512 channels at 56 x 56, K = 384 channels -- takes
-        //  the 256 x 256 tile too: 0.79 -> 0.68 ms per 160 patches; nothing else has a K between 768 and 1024)
-        static const int k256 = getenv("SBBSEG_X3_T256_MINK") ? atoi(getenv("SBBSEG_X3_T256_MINK")) : 768;
-        if (p.cout % 256 == 0 && p.Ktot >= k256 && t256 >= 200) return launch_conv_t<256, 256, 2, 4, 2, true, 8, false, true>(p, s, rec);
-        if (p.Ktot >= k512 && t512 >= 200) return launch_conv_t<512, 128, 4, 2, 2, true, 8, false, true>(p, s, rec);
-    }
-    // (launches of less than one round of tiles -- one patch, the border model's whole-image forward -- cost the latency of their K-steps'
-    // loads, ~1.4 us a step; 3- and 4-stage rings of the 128 x 128 tile were probed there and LOST, 3.57 vs 2.67 ms per one-patch forward:
-    // the deeper rings run the plain gather, whose address arithmetic outweighs the extra loads in flight; profiles/r04_experiments.md section 12)
-    if (bc == 128) return launch_conv_t<128, 128, 2, 2, 2, true, 8, false, true>(p, s, rec);
-    if (bc == 64) return launch_conv_t<256, 64, 4, 1, 2, true, 8, false, true>(p, s, rec);
-    return launch_conv_t<256, 32, 4, 1, 2, true, 8, false, true>(p, s, rec);
+    return hipErrorInvalidValue;
 }
+#undef SBBSEG_CONV_TILE
 
 // Second half of a split-K launch: partial sums of the 2^ks_shift splits added in split order, then the conv's epilogue -- scale / shift,
 // residual, ReLU, store -- on 8 channels of one pixel per thread.  MODE 0 = split mode ([32 hi][32 lo] channel groups), 1 = fp16, 2 = bf16.
@@ -1364,19 +1322,17 @@ hipError_t launch_splitk_finish(const float* ws, int splits, long split_elems, l
     return hipGetLastError();
 }
 
-hipError_t launch_conv(const ConvParams& p0, int precision, hipStream_t s, LaunchRec* rec)
+// the launch of conv_choice.h's chosen form (kF32 handles: conv_naive_f32, whatever the form)
+hipError_t launch_conv(const ConvParams& p, const ConvForm& form, int precision, hipStream_t s, LaunchRec* rec)
 {
-    if (precision == kF16X3) return launch_conv_x3(p0, s, rec);
-    static const bool split_issue = !(getenv("SBBSEG_SPLIT_ISSUE") && getenv("SBBSEG_SPLIT_ISSUE")[0] == '0');      // A/B (plain 16-bit modes)
-    ConvParams p = p0;
-    if (!split_issue) p.variant_flags |= 8;
+    if (precision == kF16X3) return launch_conv_form_x3(p, form, s, rec);
     if (precision == kF32) {
         const long total = (long)p.M * (p.cout / 4);
         launch_rec(rec, SBBSEG_LAUNCH_CONV_NAIVE_F32, 256, 4, 1, (int)((total + 255) / 256), (int)((total + 255) / 256), 0, 0, p.residual != nullptr);
         hipLaunchKernelGGL(conv_naive_f32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
         return hipGetLastError();
     }
-    return precision == kF16 ? launch_conv_16<true>(p, s, rec) : launch_conv_16<false>(p, s, rec);
+    return precision == kF16 ? launch_conv_form_16<true>(p, form, s, rec) : launch_conv_form_16<false>(p, form, s, rec);
 }
 
 }  // namespace sbbseg
