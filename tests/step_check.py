@@ -37,7 +37,10 @@ on absolute values; K = sum over sources of kh * kw * channels, the number of pr
     rounding) or a product and a sum (two): the two-rounding form is assumed everywhere.  In the split mode the residual is
     ``hi + lo`` added in fp32 first (exact: 22 significant bits), then to the value (``add_split8``): one rounding, as modelled.
   * ReLU and the saturation to +-65504 of the fp16 formats (``pack_f16x2`` / ``split_f32``) are 1-Lipschitz: the error passes
-    through; the reference saturates too.
+    through; the reference saturates too.  On top of the bound, at the extremes (tests/gained_nets.py): an element whose float64
+    value in front of the clip lies beyond +-65504 by more than its own bound cannot have been inside the range in correct
+    arithmetic, so its stored value must be exactly +-65504 with that sign -- in the split mode hi + lo, that is lo = 0
+    (``sat_bad``, which ``failed`` counts; ``n_sat`` / ``n_sub`` say how much of a step sits at the clip / below 2^-14).
   * one output rounding, ``u * |v| + sub``: u = 2^-11 (f16), 2^-8 (bf16), 2^-21 (split: hi = f16(v), lo = f16(v - hi) leaves at
     most 2^-11 * 2^-11 |v|; 2^-21 is the figure ``test_ingest_forms`` holds the format to), 2^-24 (f32: the fp32 store is exact, the
     term covers nothing and costs nothing); sub = 2^-25, half the spacing of fp16 subnormals, for the fp16 formats (the rounding
@@ -60,6 +63,8 @@ U32 = 2.0 ** -24
 U_OUT = {"f16": 2.0 ** -11, "bf16": 2.0 ** -8, "f16x3": 2.0 ** -21, "f32": 2.0 ** -24}
 SUBNORMAL = {"f16": 2.0 ** -25, "bf16": 0.0, "f16x3": 2.0 ** -25, "f32": 0.0}
 F16_MAX = 65504.0
+F16_MIN_NORMAL = 2.0 ** -14
+F16_MIN_SUBNORMAL = 2.0 ** -24
 SATURATING = ("f16", "f16x3")
 _PARITY_TAPS = {(0, 0): (0, 0), (0, 1): (1, 2), (1, 0): (0, 1), (1, 1): (2, 2)}      # [parity][t] -> first, last tap summed (wpack.h `taps`)
 
@@ -235,10 +240,11 @@ def _conv_outputs(s, vals, precision, weff, extra_adds=0):
         S = S + source_conv64(np.abs(a), np.abs(w), g, s.out_h, s.out_w)
     n_add = step_K(s) * (3 if split else 1) + extra_adds
     acc = n_add * 2.0 ** -23 * S + (2.0 ** -21 * S if split else 0.0)
-    ref, bound = {}, {}
+    ref, bound, pre = {}, {}, {}
     if s.raw_out >= 0:
         v, e = _mul(y, acc, np.asarray(s.raw_scale, np.float64))
         v, e = _add(v, e, np.asarray(s.raw_shift, np.float64))
+        pre["raw_out"] = v
         ref["raw_out"], bound["raw_out"] = _store(precision, v, e)
     v, e = _mul(y, acc, np.asarray(s.scale, np.float64))
     v, e = _add(v, e, np.asarray(s.shift, np.float64))
@@ -247,10 +253,11 @@ def _conv_outputs(s, vals, precision, weff, extra_adds=0):
     if s.relu:
         v = np.maximum(v, 0.0)
     if s.out >= 0:
+        pre["out"] = v
         ref["out"], bound["out"] = _store(precision, v, e)
     if s.head is not None:
         ref["logits"], bound["logits"] = _head(s.head, v, e)
-    return ref, bound
+    return ref, bound, pre
 
 
 def _maxpool64(x, k, stride):
@@ -259,8 +266,14 @@ def _maxpool64(x, k, stride):
 
 
 def step_reference(plan, step, vals, precision, extra_adds=0):
-    """(ref, bound): dicts of float64 arrays keyed by the outputs the step has -- "out", "raw_out" (on the step's own output grid,
-    see `placed`) and "logits" ([n, out_h, out_w, classes] of a head, fused or not).  `extra_adds`: further fp32 additions of partial
+    """step_reference_pre without the values before the clip."""
+    return step_reference_pre(plan, step, vals, precision, extra_adds)[:2]
+
+
+def step_reference_pre(plan, step, vals, precision, extra_adds=0):
+    """(ref, bound, pre): dicts of float64 arrays keyed by the outputs the step has -- "out", "raw_out" (on the step's own output grid,
+    see `placed`) and "logits" ([n, out_h, out_w, classes] of a head, fused or not); `pre` holds, for the stored outputs, the float64 value in
+    front of the saturation to +-65504 (equal to `ref` where nothing clips, and in the formats that do not saturate).  `extra_adds`: further fp32 additions of partial
     sums on top of the K (3 K) of the contraction -- ``splits - 1`` for a conv launched split-K (module docstring); convs only."""
     assert extra_adds == 0 or step.kind == "conv", (step.name, step.kind, extra_adds)
     if step.kind == "conv":
@@ -272,10 +285,10 @@ def step_reference(plan, step, vals, precision, extra_adds=0):
         lg = np.zeros((n, step.out_h, step.out_w, step.head.classes))
         bd = np.zeros_like(lg)
         for q, c in enumerate(classes):
-            r, b = _conv_outputs(c, vals, precision, [flat[q], flat[4]])
+            r, b, _ = _conv_outputs(c, vals, precision, [flat[q], flat[4]])
             placed(lg, c)[...] = r["logits"]
             placed(bd, c)[...] = b["logits"]
-        return {"logits": lg}, {"logits": bd}
+        return {"logits": lg}, {"logits": bd}, {}
     if step.kind == "maxpool":
         x = np.asarray(vals[step.src], np.float64)
         e = np.zeros_like(x)
@@ -284,16 +297,16 @@ def step_reference(plan, step, vals, precision, extra_adds=0):
             x, e = _add(x, e, np.asarray(step.pre_shift, np.float64))
             if step.pre_relu:
                 x = np.maximum(x, 0.0)
-            v, e = _maxpool64(x, step.k, step.stride), _maxpool64(e, step.k, step.stride)
-            v, e = _store(precision, v, e)
+            p, e = _maxpool64(x, step.k, step.stride), _maxpool64(e, step.k, step.stride)
+            v, e = _store(precision, p, e)
         else:
-            v = _maxpool64(x, step.k, step.stride)
+            p = v = _maxpool64(x, step.k, step.stride)
             e = np.zeros_like(v)
-        return {"out": v}, {"out": e}
+        return {"out": v}, {"out": e}, {"out": p}
     if step.kind == "head":
         z = np.asarray(vals[step.src], np.float64)
         lg, e = _head(step, z, np.zeros_like(z))
-        return {"logits": lg}, {"logits": e}
+        return {"logits": lg}, {"logits": e}, {}
     raise ValueError(step.kind)
 
 
@@ -348,11 +361,17 @@ def check_step(plan, step, vals, precision, probs=None, mask=None, extra_adds=0)
       rms       rms of err / bound;  ref_absmax  largest |ref| (0: the step proves nothing)
       abs_err, old_rel   max |err| and max |err| / max |ref| (the range-relative criterion of the per-layer tests)
       label_bad labels (argmax of probs) that differ from the float64 argmax where the top-2 logit margin exceeds 2 d; n_decided
-      p_err     max |probs - softmax64(ref logits)|"""
-    ref, bound = step_reference(plan, step, vals, precision, extra_adds)
+      p_err     max |probs - softmax64(ref logits)|
+    The extremes of the fp16 formats (f16, f16x3; all zero in the others), over the stored outputs:
+      n_sat     reference elements at the clip (|value before the clip| >= 65504); n_beyond / n_beyond_neg: those strictly beyond it / below -65504
+      sat_bad   elements whose value before the clip exceeds 65504 in magnitude by more than their own bound while the stored value is not
+                exactly +-65504 with that sign (split mode: hi + lo, so lo must be 0) -- inf, a one-sided clamp, a lo half left over
+      n_sub     nonzero reference elements below 2^-14 in magnitude; n_sub_held: those of them at or above 2^-24; n_nonzero"""
+    ref, bound, pre = step_reference_pre(plan, step, vals, precision, extra_adds)
     got = step_got(plan, step, vals)
     rep = dict(name=step.name, kind=step.kind, K=step_K(step), worst=0.0, index=None, n_over=0, n_nan=0, n_inf=0, n_ref_bad=0,
-               rms=0.0, ref_absmax=0.0, abs_err=0.0, old_rel=0.0, label_bad=0, n_decided=0, p_err=None, n_elem=0)
+               rms=0.0, ref_absmax=0.0, abs_err=0.0, old_rel=0.0, label_bad=0, n_decided=0, p_err=None, n_elem=0,
+               n_sat=0, sat_bad=0, n_sub=0, n_beyond=0, n_beyond_neg=0, n_sub_held=0, n_nonzero=0)
     sq = 0.0
     for key, g in got.items():
         r, b = ref[key], bound[key]
@@ -370,6 +389,17 @@ def check_step(plan, step, vals, precision, probs=None, mask=None, extra_adds=0)
             ratio = np.where(err > 0, err / b, 0.0)                       # b == 0 < err -> inf
         rep["n_over"] += int((err > b).sum())
         rep["n_elem"] += int(ok.sum())
+        if precision in SATURATING:
+            p = np.where(ref_ok, pre[key], 0.0)
+            rep["n_sat"] += int((np.abs(p) >= F16_MAX).sum())
+            rep["n_beyond"] += int((np.abs(p) > F16_MAX).sum())
+            rep["n_beyond_neg"] += int((p < -F16_MAX).sum())
+            # beyond the range by more than the element's own bound: correct arithmetic cannot have kept it inside, so the store saturates
+            rep["sat_bad"] += int(((np.abs(p) - F16_MAX > b) & ref_ok & (g != np.sign(p) * F16_MAX)).sum())
+            a = np.abs(np.where(ref_ok, r, 0.0))
+            rep["n_nonzero"] += int((a > 0).sum())
+            rep["n_sub"] += int(((a > 0) & (a < F16_MIN_NORMAL)).sum())
+            rep["n_sub_held"] += int(((a >= F16_MIN_SUBNORMAL) & (a < F16_MIN_NORMAL)).sum())
         sq += float(np.square(np.where(np.isfinite(ratio), ratio, 0.0)).sum())
         rmax = float(np.abs(np.where(ref_ok, r, 0.0)).max()) if r.size else 0.0
         rep["ref_absmax"] = max(rep["ref_absmax"], rmax)
@@ -400,5 +430,6 @@ def check_step(plan, step, vals, precision, probs=None, mask=None, extra_adds=0)
 
 
 def failed(rep):
-    """True when a report breaks the per-step contract (over the bound, non-finite output, undecidable reference, wrong label)."""
-    return bool(rep["n_over"] or rep["n_nan"] or rep["n_inf"] or rep["n_ref_bad"] or rep["label_bad"] or not rep["ref_absmax"] > 0)
+    """True when a report breaks the per-step contract (over the bound, non-finite output, undecidable reference, wrong label, a value
+    beyond the fp16 range not stored as +-65504)."""
+    return bool(rep["n_over"] or rep["n_nan"] or rep["n_inf"] or rep["n_ref_bad"] or rep["label_bad"] or rep["sat_bad"] or not rep["ref_absmax"] > 0)

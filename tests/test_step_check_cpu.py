@@ -3,7 +3,7 @@
 A numpy stand-in for the device runs small plans step by step: operands quantised as the host code quantises them, products
 accumulated in FLOAT32 in K-chunks of 16 or 32 walked in a shuffled (seeded) order, epilogue in float32, outputs rounded to the
 storage format.  (1) Correct arithmetic stays inside the derived bound in all four precisions; (2) each of thirteen one-line kernel
-defects, injected into the stand-in, puts the step it was injected into over the bound in f16 and f16x3 -- and the range-relative
+defects (and of five more at the extremes of the fp16 formats, below), injected into the stand-in, puts the step it was injected into over the bound in f16 and f16x3 -- and the range-relative
 criterion of the per-layer tests (``TOL_LAYER_REL``) is evaluated on the same tensor to show what it lets through.
 
 Split-K (the whole-image branch's one-patch launches, csrc/forward.hip launch_op): ``StandIn.conv(splits=...)`` deals the K-chunks to
@@ -14,7 +14,11 @@ tests/small_plans.py run clean through the same stand-in.
 Fused stage-2 blocks (csrc/bottleneck.hip under conv variant bit 26, tests/test_gpu_steps_blocks.py): ``StandIn.block`` runs a triple as one
 launch -- a on the halo, b from it, c with the residual, intermediates rounded to storage, the inner a and b stored.  Defects 14 to 16 are
 defects of that path; each must be reported in the phase it belongs to and in no other, and the whole-block range-relative criterion that
-held these kernels before (4e-3 / 3e-2 of the three convs' output) is printed beside it: it lets 14 and 16 through."""
+held these kernels before (4e-3 / 3e-2 of the three convs' output) is printed beside it: it lets 14 and 16 through.
+
+The extremes (tests/gained_nets.py): the same net with every activation times 2^15, 2^16 or 2^-17 runs clean through the stand-in -- values
+beyond +-65504 stored as +-65504, results below 2^-14 as fp16 subnormals -- and defects 17 to 21 (a store to inf, a one-sided clamp, a lo
+half taken from the unclamped value, results and inputs below 2^-14 flushed to zero) are each reported on such a net."""
 import copy
 import functools
 import zlib
@@ -25,7 +29,7 @@ import pytest
 import step_check as sc
 from plan_interp import make_input_forms
 from small_plans import SMALL_PLANS, assert_odd_geometries, small_net, small_plan
-from sbb_textline_detection_amd.keras_graph import parse_model_config
+from sbb_textline_detection_amd.keras_graph import parse_model_config, resnet50_unet_config
 from sbb_textline_detection_amd.planner import build_plan
 from sbb_textline_detection_amd.synthetic import synthetic_page
 from tools.synth_model import calibrated_model
@@ -82,6 +86,32 @@ class StandIn:
     def __init__(self, precision, seed=0):
         self.precision, self.seed = precision, seed
 
+    def _store(self, v32, defect=None):
+        """fp32 values -> what the step stores (sc.round_storage), or what one of the defects of the extremes (17 to 20) stores instead."""
+        prec = self.precision
+        v32 = np.asarray(v32, np.float32)
+        if defect not in (17, 18, 19, 20) or prec not in sc.SATURATING:
+            return sc.round_storage(prec, v32)
+        with np.errstate(over="ignore"):
+            cvt = lambda a: np.asarray(a, np.float32).astype(np.float16).astype(np.float32)     # the bare conversion: RNE, inf beyond the range
+            if defect == 17:
+                v = np.maximum(v32, -sc.F16_MAX)                         # the upper clamp missing: +inf instead of 65504
+            elif defect == 18:
+                v = np.minimum(v32, sc.F16_MAX)                          # fminf only, as behind a ReLU -- in a step that has none: -inf
+            else:
+                v = np.clip(v32, -sc.F16_MAX, sc.F16_MAX)
+            hi = cvt(v)
+            if defect == 20:
+                hi = np.where(np.abs(hi) < sc.F16_MIN_NORMAL, np.float32(0), hi)      # a result below 2^-14 flushed to zero
+            if prec == "f16":
+                return hi
+            if defect == 19:
+                v = v32                                                  # lo from the UNclamped value: not 0 at saturation
+            lo = np.where(np.isfinite(hi), sc._f16(v - np.where(np.isfinite(hi), hi, 0)), np.float32(0))
+            if defect == 20:
+                lo = np.where(np.abs(lo) < sc.F16_MIN_NORMAL, np.float32(0), lo)
+            return hi + lo
+
     def _accumulate(self, A, W, rng, drop=None, splits=1, skip_tail=None):
         """float32 sum over K in shuffled chunks; A, W lists of operand planes multiplied pairwise (split: hi*hi, hi*lo, lo*hi).
         splits > 1 (split-K): the chunks are dealt to `splits` contiguous ranges, each summed in fp32 on its own (shuffled inside the
@@ -131,6 +161,8 @@ class StandIn:
         tap = ((g0.kh // 2) * g0.kw + g0.kw // 2) * g0.channels           # the centre tap of source 0
         px = np.arange(A.shape[0])
         ox, oy, on = px % s.out_w, (px // s.out_w) % s.out_h, px // (s.out_w * s.out_h)
+        if defect == 21:
+            A = np.where(np.abs(A) < sc.F16_MIN_NORMAL, np.float32(0), A)   # a stored fp16 subnormal (split: a value whose hi half is one) read as zero
         if defect == 1:
             A = A.copy()
             A[ox == s.out_w - 1, tap:tap + g0.channels] = 0              # one tap skipped, last output column
@@ -157,7 +189,7 @@ class StandIn:
         out = {}
         shape = (n, s.out_h, s.out_w, s.cout)
         if s.raw_out >= 0:
-            out["raw_out"] = sc.round_storage(prec, acc * (f32(s.raw_scale) / np.float32(pre)) + f32(s.raw_shift)).reshape(shape)
+            out["raw_out"] = self._store(acc * (f32(s.raw_scale) / np.float32(pre)) + f32(s.raw_shift), defect).reshape(shape)
         res = f32(sc.placed(vals[s.residual], s)).reshape(-1, s.cout) if s.residual >= 0 else None
         if defect == 3:
             z = (acc + res * np.float32(pre)) * scale + shift            # residual added before `* scale`
@@ -177,7 +209,7 @@ class StandIn:
                 z[:, 1] = keep                                           # ReLU not applied to one channel
         z = f32(z)
         if s.out >= 0 or s.head is None:
-            o = sc.round_storage(prec, z)
+            o = self._store(z, defect)
             if defect == 8:                                              # channels 16..31 of the ragged last pixel tile from the tile before
                 m0 = (o.shape[0] // PIXEL_TILE) * PIXEL_TILE
                 o = o.copy()
@@ -435,7 +467,15 @@ DEFECTS = {
     14: "fused block: a packed through bf16 before b reads it, in the f16 mode",
     15: "fused block: out-of-image halo of a = ReLU(shift) instead of zero (x padded instead of a)",
     16: "fused block: the residual added after y was rounded to storage, then rounded again",
+    17: "extremes: a store that overflows to +inf instead of 65504 (the upper clamp missing)",
+    18: "extremes: a clamp on the positive side only, in a step without ReLU (-inf below -65504)",
+    19: "extremes: a split store that takes hi from the clamped value and lo from the unclamped one (lo not 0 at saturation)",
+    20: "extremes: an output (or a lo half) below 2^-14 flushed to zero",
+    21: "extremes: a subnormal fp16 input read as zero",
 }
+# defects of the extremes -> injected on the hottest (True) or the coldest (False) gained net of tests/gained_nets.py; see
+# test_injected_extreme_defect_is_reported.  19 exists in the split mode only: the plain mode has no lo half.
+EXTREME_DEFECTS = {17: True, 18: True, 19: True, 20: False, 21: False}
 # defects of the fused stage-2 block path (StandIn.block) -> the phase ("abc" index) the per-phase check must report it in: the phase that
 # packs the wrong number (14: a, 16: c), or for the halo -- whose copies of a are not stored -- the phase that reads it (15: b)
 BLOCK_DEFECTS = {14: 0, 15: 1, 16: 2}
@@ -464,7 +504,7 @@ _INVISIBLE = {(5, "longest_k", "f16"): "0.107", (5, "longest_k", "f16x3"): "0.03
               (10, "longest_k", "f16x3"): "2.2e-05 (the same: error 0 on that channel)"}
 _CASES = [pytest.param(d, w, p, marks=[pytest.mark.xfail(strict=True, reason=f"worst err / bound {_INVISIBLE[(d, w, p)]}: below the bound at K = 13312")]
                        if (d, w, p) in _INVISIBLE else [])
-          for d in sorted(DEFECTS) if d not in BLOCK_DEFECTS for w in ("first", "longest_k") for p in ("f16", "f16x3")]
+          for d in sorted(DEFECTS) if d not in BLOCK_DEFECTS and d not in EXTREME_DEFECTS for w in ("first", "longest_k") for p in ("f16", "f16x3")]
 
 
 @pytest.mark.parametrize("defect,where,precision", _CASES)
@@ -486,6 +526,76 @@ def test_injected_defect_is_reported(defect, where, precision):
           f"{rep['n_over']} elements over; caught-by-new {sc.failed(rep)}; caught-by-old {old_caught} "
           f"(max|err| / max|ref| {rep['old_rel']:.3g} vs {TOL_LAYER_REL[precision]})")
     assert sc.failed(rep) and rep["n_over"] > 0, (DEFECTS[defect], step.name, rep)
+
+
+# ------------------------------------------------------------------------------------------------ the extremes of the fp16 formats
+@functools.lru_cache(maxsize=None)
+def _gained_run(precision, g):
+    """_clean_run of the c2_64x96 net gained by g (tests/gained_nets.py): (plan, vals, probs, [report per step])."""
+    from gained_nets import gained
+    classes, h, w, _ = MODELS["c2_64x96"]
+    cfg = resnet50_unet_config(classes, h, w)                            # (the config _net's calibrated_model built its graph from)
+    graph, weights, x = _net("c2_64x96")
+    plan = build_plan(graph, gained(cfg, weights, g), fuse_head=True, fuse_tail=True)
+    dev = StandIn(precision, seed=11)
+    vals, probs = _fresh(plan, precision, x)
+    for s in plan.steps:
+        dev.run_step(plan, s, vals, probs)
+    return plan, vals, probs, [sc.check_step(plan, s, vals, precision, probs=probs) for s in plan.steps]
+
+
+def _extreme_gains():
+    from gained_nets import COLD_GAINS, HOT_GAINS
+    return HOT_GAINS + COLD_GAINS
+
+
+@pytest.mark.parametrize("precision", ["f16", "f16x3"])
+@pytest.mark.parametrize("g", _extreme_gains(), ids=lambda g: f"gain{int(np.log2(g))}")
+def test_correct_arithmetic_stays_inside_the_bound_at_the_extremes(g, precision):
+    """The clean stand-in on every hot and cold variant: inside the unchanged bound, every value beyond the range stored as +-65504 (split:
+    lo = 0), and the variant really is at the extreme it is named for."""
+    plan, _, _, reports = _gained_run(precision, g)
+    for s, r in zip(plan.steps, reports):
+        assert not sc.failed(r) and r["sat_bad"] == 0, (s.name, r)
+    from gained_nets import stores_fp16
+    stored = [r for s, r in zip(plan.steps, reports) if stores_fp16(s)]
+    print(f"\n[stand-in c2_64x96 {precision} gain 2^{int(np.log2(g))}] worst err / bound {max(r['worst'] for r in reports):.3f}, "
+          f"n_sat {sum(r['n_sat'] for r in stored)}, n_sub {sum(r['n_sub'] for r in stored)} of {sum(r['n_elem'] for r in stored)} stored elements")
+    if g > 1:
+        assert all(r["n_sat"] > 0 for r in stored)
+    else:
+        assert all(r["n_sub"] > 0 for r in stored) and all(r["n_sat"] == 0 for r in stored)
+
+
+def _applies_extreme(plan, s, defect):
+    """First-step rule of the defects of the extremes: 17, 19, 20 the first step that stores in the activation format; 18 the first that
+    stores what no ReLU precedes; 21 the first conv that multiplies a stored activation (no input form)."""
+    if s.kind != "conv":
+        return False
+    if defect == 18:
+        return s.raw_out >= 0 or (s.out >= 0 and not s.relu)
+    if defect == 21:
+        return s.out >= 0 and all(plan.tensors[g.tensor].kind == "act" for g in s.srcs)
+    return s.out >= 0 or s.raw_out >= 0
+
+
+@pytest.mark.parametrize("defect,precision", [(d, p) for d in sorted(EXTREME_DEFECTS) for p in ("f16", "f16x3") if (d, p) != (19, "f16")])
+def test_injected_extreme_defect_is_reported(defect, precision):
+    """Each defect on the hottest / coldest gained net, in the first step of the plan it can occur in, on the clean run's stored inputs."""
+    from gained_nets import COLD_GAINS, HOT_GAINS
+    g = max(HOT_GAINS) if EXTREME_DEFECTS[defect] else min(COLD_GAINS)
+    plan, clean_vals, clean_probs, _ = _gained_run(precision, g)
+    step = next(s for s in plan.steps if _applies_extreme(plan, s, defect))
+    vals = {k: v.copy() for k, v in clean_vals.items()}
+    StandIn(precision, seed=11).run_step(plan, step, vals, clean_probs.copy(), defect=defect)
+    rep = sc.check_step(plan, step, vals, precision)
+    print(f"\n[defect {defect} {precision} gain 2^{int(np.log2(g))}] {DEFECTS[defect]} -> step {step.name}: worst err / bound {rep['worst']:.3g}, {rep['n_over']} over, "
+          f"{rep['n_inf']} inf, sat_bad {rep['sat_bad']} of n_sat {rep['n_sat']}, n_sub {rep['n_sub']}; caught {sc.failed(rep)}")
+    assert sc.failed(rep), (DEFECTS[defect], step.name, rep)
+    if EXTREME_DEFECTS[defect]:
+        assert rep["sat_bad"] > 0 and rep["n_sat"] > 0, rep               # reported as what it is, not only as a large error
+    else:
+        assert rep["n_over"] > 0 and rep["n_sub"] > 0, rep
 
 
 # ------------------------------------------------------------------------------------------------ fused stage-2 blocks

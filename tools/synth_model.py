@@ -28,10 +28,11 @@ from sbb_textline_detection_amd.synthetic import synthetic_page  # noqa: E402
 from sbb_textline_detection_amd.weights import save_sbbw, synthetic_weights  # noqa: E402
 
 
-def forward_torch(graph, weights, x_nhwc, dtype=torch.float32, calibrate_bn=False):
+def forward_torch(graph, weights, x_nhwc, dtype=torch.float32, calibrate_bn=False, taps=None):
     """fp32/fp64 forward of a parsed Keras graph with torch-CPU ops (NCHW inside).
     With ``calibrate_bn`` the BN moving statistics in ``weights`` are overwritten in place by the
-    batch statistics of each BN's input before it is applied."""
+    batch statistics of each BN's input before it is applied.  ``taps``: a dict that receives
+    every node's output (NCHW numpy, in ``dtype``) under the node's name."""
     vals = {}
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype)
     for n in graph.nodes:
@@ -88,6 +89,8 @@ def forward_torch(graph, weights, x_nhwc, dtype=torch.float32, calibrate_bn=Fals
         else:
             raise NotImplementedError(n.op)
         vals[n.name] = y
+        if taps is not None:
+            taps[n.name] = y.numpy()
     return vals[graph.output_name].permute(0, 2, 3, 1).contiguous().to(torch.float32).numpy()
 
 
